@@ -2,6 +2,7 @@
 """Benchmark of the SDformerFlow forward hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--neuron lif|psn] [--no-cpu] [--inflight F] [--replicas R] [--eager]
+                    [--dump-outputs DIR]
     python bench.py --train [--local-batch B] ...      (BASELINE configs[3], the training step; not the default workload)
 
 One "step" = one forward of MS_SpikingformerFlowNet_en4 over one synthetic 1 x 10 x 2 x 288 x 384 event
@@ -423,6 +424,12 @@ class InFlight:
         for j, m in self._plan(n):
             self._issue(j, m)
 
+    def last_outputs(self, n):
+        """What the caller of the last launch sequence of run(n) received: {"flow<i>": (m, 2, H_i, W_i) fp32 on the host}, m samples."""
+        torch.cuda.synchronize()
+        j, m = self._plan(n)[-1]
+        return {f"flow{i}": f.detach().float().cpu().numpy() for i, f in enumerate(self.slots[(j, m)][1]["flow"])}
+
     def verify(self):
         """Every sample of every slot equals the plain single-stream batch-1 forward of its voxel, bit for bit."""
         torch.cuda.synchronize()
@@ -440,6 +447,25 @@ class InFlight:
     def release(self):
         self.slots.clear()
         self._voxels.clear()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write every array as outdir/<name>.npy (float32 / float64).  Above `limit` bytes in all, each array is replaced by the same
+    fixed seeded sample of its flattened elements (sorted indices from numpy's PCG64 seeded by `seed`), so that two builds compare
+    element for element."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrays.items():
+        if total > limit:
+            keep = max(1, int(v.size * limit // total))
+            idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(v.size, keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(outdir, k + ".npy"), v)
 
 
 def inflight_rate(model, dev, F_, R, steps, warmup=6):
@@ -970,11 +996,18 @@ def main():
                     help="16-bit weight planes of the spike GEMMs / convolutions: 2 = fp16 hi+lo (22 significand bits, the default "
                          "parity mode), 3 = bf16 hi+mid+lo (the fp32 weight exactly), 1 = one bf16 plane (BASELINE configs[1]'s "
                          "stated bf16 precision; a separately labelled throughput line, never the parity mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the flow maps of the last launch sequence the timed region issued (its last step "
+                         "among them) as DIR/flow<i>.npy, fp32; inputs are seeded, so two builds compare output for output")
     ap.add_argument("--plumbing", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--plan", default=None, help=argparse.SUPPRESS)       # diagnostic: the timed steps' dealing as "stream:samples,..."
     args = ap.parse_args()
     if args.inflight < 1 or args.replicas < 1:
         ap.error("--inflight and --replicas must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.train or args.plumbing):
+        ap.error("--dump-outputs covers the forward benchmark (not --train / --plumbing)")
     if args.steps is None:
         args.steps = 10 if args.train else 300
     if args.warmup is None:
@@ -1026,6 +1059,7 @@ def main():
         fl.run(args.steps)                                       # EXACTLY --steps forwards of one sample each
         barrier()
         dt_local = time.perf_counter() - t0
+        dumped = fl.last_outputs(args.steps) if args.dump_outputs else None      # (outside the timed region; the loops below overwrite it)
         # the same loop over >= 96 samples when the contract's --steps is shorter (a 20-step region is 30 ms: VERDICT r3); reported
         # beside `value`, which stays the contract's EXACTLY --steps
         dt_long = dt_local
@@ -1049,6 +1083,8 @@ def main():
 
     if rank == 0:
         check_ranks(ranks, world, shared_ok=os.environ.get("SDF_DIST_BACKEND", "nccl") != "nccl")
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         gemm, neuron = time_dominant_kernels(model, R=args.replicas)
         blocks = time_swin_blocks(model, chunk, args.replicas)
         by_time = time_by_entry_point(model, chunk)

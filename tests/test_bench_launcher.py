@@ -113,3 +113,46 @@ def test_inflight_plan_deals_exactly_n_samples_evenly():
                 share = [sum(m for j, m in plan if j == s) for s in range(F_)]
                 assert max(share) - min(share) <= 1                      # evenly over the streams
                 assert all(sum(1 for j, m in plan if j == s and m < R) <= 1 for s in range(F_))     # at most one remainder graph per stream
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_limit(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): every array as DIR/<name>.npy in fp32 / fp64, whole while the total fits the limit;
+    above it every array shrinks to the same seeded sample of its elements - the same indices run after run - and the total fits."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    g = np.random.Generator(np.random.PCG64(5))
+    arrays = {"flow0": g.standard_normal((3, 2, 36, 48)).astype(np.float32), "flow1": g.standard_normal((3, 2, 72, 96)),
+              "half": g.standard_normal((4, 5)).astype(np.float16)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype in (np.float32, np.float64) and got.shape == v.shape and np.array_equal(got, v.astype(got.dtype))
+    limit = 20000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    total = 0
+    for k, v in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b) and 0 < a.size < v.size
+        assert np.isin(a, v.reshape(-1).astype(a.dtype)).all()                   # elements of the array, not something derived
+        total += a.nbytes
+    assert total <= limit
+
+
+def test_dump_takes_the_last_launch_sequence_of_the_timed_run(monkeypatch):
+    """bench.InFlight.last_outputs(n): the flows held by the slot of the LAST (stream, samples) entry run(n) issues - the arrays the
+    caller of that launch sequence received, on the host in fp32."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    fl = bench.InFlight.__new__(bench.InFlight)
+    fl.F, fl.R = 2, 10
+    fl.slots = {(j, m): [None, {"flow": [torch.full((m, 2, 3, 4), 10.0 * j + m), torch.full((m, 2, 6, 8), -(10.0 * j + m))]}, None]
+                for j in (0, 1) for m in (1, 2, 3, 10)}
+    for n, (j, m) in ((20, (1, 10)), (23, (1, 1)), (25, (1, 2)), (26, (1, 3)), (1, (0, 1))):
+        assert fl._plan(n)[-1] == (j, m)
+        out = fl.last_outputs(n)
+        assert sorted(out) == ["flow0", "flow1"] and out["flow0"].dtype.name == "float32"
+        assert out["flow0"].shape == (m, 2, 3, 4) and (out["flow0"] == 10.0 * j + m).all() and (out["flow1"] == -(10.0 * j + m)).all()

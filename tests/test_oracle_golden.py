@@ -113,7 +113,7 @@ def test_slice_table_matches_reference(tag):
     assert torch.equal(O.scatter_slices(y, B, D, H, W, ws, ss), x)
     Dp, Hp, Wp = -(-D // ws[0]) * ws[0], -(-H // ws[1]) * ws[1], -(-W // ws[2]) * ws[2]
     m = O.compute_mask(Dp, Hp, Wp, ws, ss)
-    assert float(m.sum()) == float(g[f"{tag}_mask_sum"])
+    assert float(m.double().sum()) == float(g[f"{tag}_mask_sum"])     # exact (a float32 sum's rounding follows the host's reduction order)
     if tag != "s0":
         assert np.array_equal(m.numpy().astype(np.int8), g[f"{tag}_mask"])
 

@@ -2,12 +2,15 @@
 tensors do (the library path: the gloo tests and the plumbing dry run use it - the HIP wrappers themselves refuse CPU tensors), and that
 the ctypes descriptors have the layout include/sdformerflow_hip.h declares."""
 import ctypes as C
+import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from sdformerflow_amd import hip, train
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_which_shapes_the_weight_gradient_kernels_take():
@@ -35,7 +38,7 @@ def test_cpu_tensors_take_the_library_path():
 
 
 def test_descriptor_layouts_match_the_header():
-    hdr = open(hip.HEADER_PATH if hasattr(hip, "HEADER_PATH") else "include/sdformerflow_hip.h").read()
+    hdr = open(os.path.join(ROOT, "include", "sdformerflow_hip.h")).read()
     for name, cls, fields in (("SdfLinearDwDesc", hip.LinearDwDesc, ["dy", "x", "dw", "partial", "M", "N", "K", "nsplit", "cv_C", "cv_Wp"]),
                               ("SdfLinearTrainDesc", hip.LinearTrainDesc, ["a", "w", "bias", "out", "M", "N", "K", "mode", "cv_C", "cv_Wp"])):
         body = hdr[hdr.index("typedef struct " + name):hdr.index("} " + name + ";")]
