@@ -684,6 +684,37 @@ typedef struct SdfWinAttnDesc {
 
 int sdf_win_attn_fwd(const SdfWinAttnDesc* d, void* stream);
 
+/* ---- backward of the SDF_ATTN_ANN core of sdf_win_attn_fwd (training of the ANN model) -------------------------------------
+ * Per window b and head g: q^ = q / max(|q|, 1e-12), k^ likewise, S = q^ k^T * scale[g] + bias[g] (+ mask[b % nW]),
+ * P = softmax(S), O = P v.  Given dout = dL/dO (rows, C) through the same row map (D = rowsum(dO o O) is formed as
+ * rowsum(P o dP) from the recomputed P, so the forward's output is not an input):
+ *   dqkv (rows, 3C): dL/d(q | k | v) of every real row (written through row_map; each real row lies in exactly one window);
+ *   d_pad (3C): the summed dq | dk | dv of all padding tokens (they read pad_qkv: part of the qkv bias gradient);
+ *   d_scale (nH) = sum dS o (q^ k^T);  d_bias (nH, N, N) = sum over windows of dS.
+ * qkv, row_map, pad_qkv, scale, bias, mask as in SdfWinAttnDesc (ANN mode; row_map NULL = window-major rows, d_pad may then be
+ * NULL).  head_dim 32, N <= 192, any nH; SDF_E_SHAPE otherwise.  Exact fp32 MFMA products.  The cross-window sums go through
+ * `workspace` (sdf_win_attn_ann_bwd_workspace_bytes(B_, nH, N) bytes, 256-byte aligned, caller-owned) in a fixed order: two
+ * calls give bit-equal results. */
+typedef struct SdfWinAttnBwdDesc {
+  const float* qkv;         /* (rows, 3C) */
+  const int32_t* row_map;   /* (B_*N) or NULL */
+  const float* pad_qkv;     /* (3C), required with row_map */
+  const float* dout;        /* (rows, C) */
+  const float* scale;       /* (nH) */
+  const float* bias;        /* (nH,N,N) */
+  const float* mask;        /* (nW,N,N) or NULL */
+  float* dqkv;              /* (rows, 3C) */
+  float* d_pad;             /* (3C), required with row_map */
+  float* d_scale;           /* (nH) */
+  float* d_bias;            /* (nH,N,N) */
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t B_, nW, nH, N, hd;
+} SdfWinAttnBwdDesc;
+
+int64_t sdf_win_attn_ann_bwd_workspace_bytes(int B_, int nH, int N);   /* 0 for an unsupported shape */
+int sdf_win_attn_ann_bwd(const SdfWinAttnBwdDesc* d, void* stream);
+
 /* ---- the attention half of an ANN video-swin block as one launch (BASELINE config 3, first stage) -----------------
  * Replaces `SwinTransformerBlock3D.forward_part1` + the shortcut (reference models/STSwinNet/swin_transformer3D_v2.py:272-310, :331)
  * with `WindowAttention3D.forward` (:169-205) inside:

@@ -108,6 +108,11 @@ class PatchEmbedLocal(nn.Module):
                 y = hip.dense_conv3x3_strided(a, self._packed_proj(), self.proj.bias.detach().float(), st[0], T)
                 return y.view(B, T, *y.shape[1:]).permute(0, 4, 1, 2, 3)
             y = self.proj(a.permute(0, 3, 1, 2)).contiguous()
+        elif self.training:
+            # one temporal chunk at a time, as the reference runs it (PatchEmbed.py:180-185): the BatchNorm batch statistics and running
+            # averages are per chunk, not over all T x B images
+            xs = x.view(T, B, *x.shape[1:])
+            return torch.stack([self.proj(self.residual_encoding(self.head(xs[t]))) for t in range(T)], dim=2)
         else:
             y = self.proj(self.residual_encoding(self.head(x)))
         return y.view(T, B, *y.shape[1:]).permute(1, 2, 0, 3, 4)

@@ -2,7 +2,10 @@
 `STT_encoder` :14-138, `STT_MultiResUNet` :140-283, `STTFlowNet` :309-481, `STTFlowNet_4en` :486-497.
 The window-attention core (section 8 row a10) is this framework's fused HIP kernel; the dense glue around it
 (LayerNorm, Linear, GELU, fp32 convolutions, bilinear upsampling) is library work through torch on the GPU.
-Forward-only: the modules refuse training mode and CPU tensors (no fallback path)."""
+Training mode on GPU tensors runs the same modules under autograd (train.py `train_step`): the attention core through
+`autograd.WinAttnAnnFunction` (HIP forward and backward), the dense glue and batch-statistics BatchNorm through the library
+branches, DropPath as the reference builds it.  CPU tensors are refused in both modes (no fallback path)."""
+import contextlib
 import os
 
 import torch
@@ -205,8 +208,6 @@ class STTFlowNet(nn.Module):
         return x
 
     def forward(self, event_voxel, event_cnt=None, log=False):
-        if self.training:
-            raise NotImplementedError("forward-only (SURVEY.md section 8f row 3 covers the backward kernels)")
         if self.encoding == "voxel":
             x = event_voxel
         elif self.encoding == "cnt":
@@ -214,10 +215,13 @@ class STTFlowNet(nn.Module):
         else:
             raise AttributeError("Model error: Incorrect input encoding.")
         if not x.is_cuda:
+            if self.training:
+                raise NotImplementedError("training runs on the GPU only: the attention backward is a HIP kernel (no CPU fallback)")
             raise hip.SdfError("STTFlowNet runs on the GPU only (no CPU fallback)")
         if log:
             raise NotImplementedError("attention-score logging is analysis tooling outside the forward path")
-        with torch.no_grad():
+        # training: under autograd (train.train_step); eval: no graph, the fused inference kernels
+        with contextlib.nullcontext() if self.training else torch.no_grad():
             if x.size(1) != self.num_bins:                     # DSEC double-chunk input: last block of chunk 1 + chunk 2
                 c1, c2 = x[:, :self.num_bins], x[:, self.num_bins:]
                 if self.norm_input:

@@ -2,7 +2,10 @@
 `window_partition` :37-49, `window_reverse` :52-65, `get_window_size` :68-81, `compute_mask` :409-421 and the cosine
 `WindowAttention3D` :87-205, whose score / bias / mask / softmax / .V core runs in one fused MFMA kernel
 (csrc/win_attn.hip) and whose projections - like the Mlp's - run on this framework's Linear kernel (csrc/dense_linear.hip:
-two fp16 planes per operand, bias / GELU / shortcut add in the epilogue; `SDF_DENSE_LINEAR=0` keeps the library GEMMs)."""
+two fp16 planes per operand, bias / GELU / shortcut add in the epilogue; `SDF_DENSE_LINEAR=0` keeps the library GEMMs).
+Training mode (GPU): LayerNorm / Linear / GELU are library autograd, the attention core is `autograd.WinAttnAnnFunction`
+(forward csrc/win_attn.hip, backward csrc/win_attn_bwd.hip; `SDF_ANN_ATTN_BWD=0`: a plain torch composition, for A/B runs),
+and stochastic depth (DropPath) applies to both residual branches as the reference builds it (:313, :329)."""
 import math
 import os
 from functools import lru_cache
@@ -121,13 +124,31 @@ class WindowAttention3D(nn.Module):
 
     def _bias_and_scale(self):
         """(position bias (nH, N, N), clamped exp logit scale (nH,)): functions of the parameters alone, so in eval they are computed
-        once per parameter version instead of once per forward (ten cpb_mlp evaluations per config-3 forward otherwise)."""
+        once per parameter version instead of once per forward (ten cpb_mlp evaluations per config-3 forward otherwise).  In training
+        they are computed afresh under autograd on every call and not cached (logit_scale and cpb_mlp receive their gradients)."""
+        if self.training:
+            return self.position_bias(), torch.clamp(self.logit_scale, max=math.log(1.0 / 0.01)).exp().reshape(-1)
         ps = list(self.cpb_mlp.parameters()) + [self.logit_scale]
         stamp = tuple((p.data_ptr(), p._version) for p in ps)
-        if self.training or getattr(self, "_bs_stamp", None) != stamp:
+        if getattr(self, "_bs_stamp", None) != stamp:
             scale = torch.clamp(self.logit_scale, max=math.log(1.0 / 0.01)).exp().reshape(-1).contiguous()
             self._bs, self._bs_stamp = (self.position_bias(), scale), stamp
         return self._bs
+
+    def forward_train_rows(self, y2, row_map, B_, mask):
+        """Training form of `forward_rows` (no shortcut): proj(attention(qkv(y2))) on un-partitioned rows y2 (rows, C) under autograd.
+        The core is `WinAttnAnnFunction` (HIP forward and backward); a padding token reads the qkv bias, so its gradient reaches
+        `qkv.bias` through the Function's `pad_qkv` input.  `SDF_ANN_ATTN_BWD=0`: the same attention as a torch composition."""
+        qkv = F.linear(y2, self.qkv.weight, self.qkv.bias)
+        pad = self.qkv.bias if self.qkv.bias is not None else torch.zeros(3 * self.dim, device=y2.device)
+        bias, scale = self._bias_and_scale()
+        N = self.window_size[0] * self.window_size[1] * self.window_size[2]
+        if hip.sw("SDF_ANN_ATTN_BWD", "1") == "0":
+            o = attention_rows_torch(qkv, row_map, B_, N, pad, scale, bias, mask, self.num_heads)
+        else:
+            from ..autograd import WinAttnAnnFunction
+            o = WinAttnAnnFunction.apply(qkv, scale, bias, pad, row_map, B_, N, mask, self.num_heads)
+        return F.linear(o, self.proj.weight, self.proj.bias)
 
     def forward(self, x, mask=None):
         if self.training:
@@ -166,6 +187,31 @@ class WindowAttention3D(nn.Module):
             return linear_rows(self.proj, o, False, resid)
 
 
+def attention_rows_torch(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH):
+    """The core of `WinAttnAnnFunction` as a torch composition (reference :176-202 after the pad / roll / partition that the row map
+    encodes): the A/B path of `SDF_ANN_ATTN_BWD=0`.  It keeps the (B_, nH, N, N) scores and probabilities for autograd."""
+    rows, C3 = qkv.shape
+    Cc = C3 // 3
+    idx = row_map.long()
+    real = idx >= 0
+    win = torch.where(real[:, None], qkv[idx.clamp(min=0)], pad_qkv.view(1, C3))          # (B_*N, 3C), padding tokens read the pad row
+    q, k, v = win.view(B_, N, 3, nH, Cc // nH).permute(2, 0, 3, 1, 4)
+    attn = F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-2, -1)
+    attn = attn * scale.view(1, nH, 1, 1) + bias.unsqueeze(0)
+    if mask is not None:
+        nW = mask.shape[0]
+        attn = (attn.view(B_ // nW, nW, nH, N, N) + mask.view(1, nW, 1, N, N)).view(B_, nH, N, N)
+    o = (torch.softmax(attn, dim=-1) @ v).transpose(1, 2).reshape(B_ * N, Cc)
+    out = qkv.new_zeros((rows, Cc))
+    return out.index_copy(0, idx[real], o[real])
+
+
+def drop_path(x, p, training):
+    """timm's per-sample stochastic depth (the reference's DropPath): keep a sample with probability 1 - p, scaled by 1 / (1 - p)."""
+    from ..train import _drop_path
+    return _drop_path(x, p, training)
+
+
 class Mlp(nn.Module):
     """fc1 -> GELU -> fc2 (reference :15-34; dropout is identity in eval)."""
 
@@ -187,9 +233,10 @@ class SwinTransformerBlock3D(nn.Module):
     Input and output (B,D,H,W,C)."""
 
     def __init__(self, dim, num_heads, window_size=(2, 7, 7), shift_size=(0, 0, 0), mlp_ratio=4.0, qkv_bias=True,
-                 pretrained_window_size=(0, 0, 0)):
+                 pretrained_window_size=(0, 0, 0), drop_path=0.0):
         super().__init__()
         self.dim, self.num_heads = dim, num_heads
+        self.drop_path = float(drop_path)                  # stochastic depth of both residual branches (training only)
         self.window_size, self.shift_size = tuple(window_size), tuple(shift_size)
         self.norm1 = nn.LayerNorm(dim)
         self.attn = WindowAttention3D(dim, self.window_size, pretrained_window_size, num_heads, qkv_bias=qkv_bias)
@@ -198,6 +245,29 @@ class SwinTransformerBlock3D(nn.Module):
 
     _maps = {}             # (B, D, H, W, window, shift, device) -> device row map, shared by the blocks of a process; LRU-bounded
     _MAPS_MAX = 32
+
+    @staticmethod
+    def _row_map(B, D, H, W, ws, ss, device):
+        """(row map, B_) of pad + roll + window partition (hip.window_slice_map), cached per geometry."""
+        key = (B, D, H, W, ws, ss, str(device))
+        maps = SwinTransformerBlock3D._maps
+        if key not in maps:
+            while len(maps) >= SwinTransformerBlock3D._MAPS_MAX:      # bounded: evaluation sweeps over many input sizes
+                maps.pop(next(iter(maps)))                          # must not grow GPU memory without limit (oldest first)
+            maps[key] = hip.window_slice_map(B, D, H, W, ws, ss, device)
+        else:
+            maps[key] = maps.pop(key)                               # most recently used last
+        return maps[key]
+
+    def forward_train(self, x, mask):
+        """Training mode: x + DropPath(proj(attention(norm1(x)))), then x + DropPath(mlp(norm2(x))) (reference :315-336) under autograd;
+        the window partition stays inside the attention kernels (row map), nothing is padded, rolled or partitioned in memory."""
+        B, D, H, W, C = x.shape
+        ws, ss = get_window_size((D, H, W), self.window_size, self.shift_size)
+        row_map, B_ = self._row_map(B, D, H, W, tuple(ws), tuple(ss), x.device)
+        a = self.attn.forward_train_rows(self.norm1(x).reshape(-1, C), row_map, B_, mask).view(B, D, H, W, C)
+        x = x + drop_path(a, self.drop_path, True)
+        return x + drop_path(self.mlp(self.norm2(x)), self.drop_path, True)
 
     def forward(self, x, mask_matrix=None):
         """forward_part1 + forward_part2 (reference :272-313).  The reference pads, rolls and partitions LN(x) into windows and
@@ -212,15 +282,17 @@ class SwinTransformerBlock3D(nn.Module):
             # the nominal window, to the smaller scores (:190, RuntimeError); the same input is refused here, not mis-addressed
             raise RuntimeError(f"feature map {(D, H, W)} is smaller than the window {self.window_size}: the relative position bias of "
                                "WindowAttention3D is defined for the nominal window only (reference swin_transformer3D_v2.py:184-190)")
-        materialise = hip.sw("SDF_ATTN_MATERIALISE") == "1" or self.training
+        Dp, Hp, Wp = D + (-D) % ws[0], H + (-H) % ws[1], W + (-W) % ws[2]
+        shifted = any(s > 0 for s in ss)
+        mask = (mask_matrix if mask_matrix is not None else compute_mask(Dp, Hp, Wp, ws, ss, x.device)) if shifted else None
+        if self.training:
+            return self.forward_train(x, None if mask is None else mask.contiguous())
+        materialise = hip.sw("SDF_ATTN_MATERIALISE") == "1"
         # first stage (C = 96, three heads, 162-token windows): LayerNorm -> qkv -> attention -> proj -> + x is ONE launch that reads x
         # through the slice map (csrc/ann_block.hip); elsewhere the norm runs here and forward_rows takes its output
         fused = (not materialise and x.is_cuda and x.dtype == torch.float32 and self.norm1.elementwise_affine and self.norm1.bias is not None
                  and hip.ann_attn_block_supported(C, self.num_heads, ws[0] * ws[1] * ws[2]) and x.numel() * 4 < 1 << 31)
         y = None if fused else layer_norm(self.norm1, x)
-        Dp, Hp, Wp = D + (-D) % ws[0], H + (-H) % ws[1], W + (-W) % ws[2]
-        shifted = any(s > 0 for s in ss)
-        mask = (mask_matrix if mask_matrix is not None else compute_mask(Dp, Hp, Wp, ws, ss, x.device)) if shifted else None
         if materialise:
             y = F.pad(y, (0, 0, 0, Wp - W, 0, Hp - H, 0, Dp - D))
             if shifted:
@@ -231,15 +303,7 @@ class SwinTransformerBlock3D(nn.Module):
                 a = torch.roll(a, shifts=ss, dims=(1, 2, 3))
             x = x + a[:, :D, :H, :W]
         else:
-            key = (B, D, H, W, ws, ss, str(x.device))
-            maps = SwinTransformerBlock3D._maps
-            if key not in maps:
-                while len(maps) >= SwinTransformerBlock3D._MAPS_MAX:      # bounded: evaluation sweeps over many input sizes
-                    maps.pop(next(iter(maps)))                          # must not grow GPU memory without limit (oldest first)
-                maps[key] = hip.window_slice_map(B, D, H, W, ws, ss, x.device)
-            else:
-                maps[key] = maps.pop(key)                               # most recently used last
-            row_map, B_ = maps[key]
+            row_map, B_ = self._row_map(B, D, H, W, ws, ss, x.device)
             x = self.attn.forward_rows(y.reshape(-1, C) if y is not None else None, row_map, B_, None if mask is None else mask.contiguous(),
                                        x.reshape(-1, C), norm=self.norm1).view(B, D, H, W, C)
         # first stage (C = 96, hidden 384): LayerNorm -> fc1 -> GELU -> fc2 -> + x is one launch, the hidden activations stay in registers
@@ -278,16 +342,17 @@ class PatchMerging(nn.Module):
 
 class Swin_BasicLayer(nn.Module):
     """One stage (reference :424-512): `depth` blocks alternating plain / shifted windows, then the optional merge.
-    forward((B,D,H,W,C)) -> (stage output, merged output)."""
+    forward((B,D,H,W,C)) -> (stage output, merged output).  `drop_path`: one stochastic-depth rate per block, or one for all."""
 
     def __init__(self, dim, depth, num_heads, window_size, mlp_ratio=4.0, qkv_bias=True, downsample=None,
-                 pretrained_window_size=(0, 0, 0)):
+                 pretrained_window_size=(0, 0, 0), drop_path=0.0):
         super().__init__()
         self.window_size = tuple(window_size)
         self.shift_size = tuple(i // 2 for i in window_size)
         self.swin_blocks = nn.ModuleList([
             SwinTransformerBlock3D(dim, num_heads, self.window_size, (0, 0, 0) if i % 2 == 0 else self.shift_size, mlp_ratio,
-                                   qkv_bias, pretrained_window_size) for i in range(depth)])
+                                   qkv_bias, pretrained_window_size, drop_path[i] if isinstance(drop_path, (list, tuple)) else drop_path)
+            for i in range(depth)])
         self.downsample = downsample(dim) if downsample is not None else None
 
     def forward(self, x):
@@ -298,17 +363,20 @@ class Swin_BasicLayer(nn.Module):
 
 class SwinTransformer3D_v2(nn.Module):
     """Backbone (reference :538-763): patch embedding -> stages; every stage output goes through its own LayerNorm
-    `norm{i}` and is returned channel-first (B,C,D,h,w)."""
+    `norm{i}` and is returned channel-first (B,C,D,h,w).  Stochastic depth rises linearly from 0 to `drop_path_rate` over the
+    blocks (reference :611, :629; STSwinNet.py:95 hard-wires 0.2)."""
 
     def __init__(self, patch_embed, embed_dim, depths, num_heads, window_size, mlp_ratio=4.0, qkv_bias=True,
-                 out_indices=(0, 1, 2), pretrained_window_size=(0, 0, 0)):
+                 out_indices=(0, 1, 2), pretrained_window_size=(0, 0, 0), drop_path_rate=0.2):
         super().__init__()
         self.patch_embed = patch_embed
         self.num_layers, self.out_indices = len(depths), tuple(out_indices)
         self.num_features = [embed_dim * 2 ** i for i in range(self.num_layers)]
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths))]
         self.layers = nn.ModuleList([
             Swin_BasicLayer(self.num_features[i], depths[i], num_heads[i], window_size, mlp_ratio, qkv_bias,
-                            PatchMerging if i < self.num_layers - 1 else None, pretrained_window_size)
+                            PatchMerging if i < self.num_layers - 1 else None, pretrained_window_size,
+                            dpr[sum(depths[:i]):sum(depths[:i + 1])])
             for i in range(self.num_layers)])
         for i in self.out_indices:
             self.add_module(f"norm{i}", nn.LayerNorm(self.num_features[i]))

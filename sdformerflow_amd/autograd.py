@@ -292,3 +292,26 @@ class SpikeLinearFunction(torch.autograd.Function):
         gw = g2.t() @ xu8.float() if ctx.needs_input_grad[1] else None
         gb = g2.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return gx, gw, gb, None
+
+
+class WinAttnAnnFunction(torch.autograd.Function):
+    """The cosine window attention core of the ANN WindowAttention3D with the window partition inside the kernels (reference
+    models/STSwinNet/swin_transformer3D_v2.py:176-202): forward `hip.win_attn_ann_windowed` (csrc/win_attn.hip), backward
+    `hip.win_attn_ann_bwd` (csrc/win_attn_bwd.hip).  Gradients for qkv (rows, 3C), scale (nH), bias (nH, N, N) and pad_qkv (3C:
+    the padding tokens read it - pass the qkv Linear's bias); scale = exp(clamp(logit_scale)) and bias = 16 sigmoid(cpb_mlp(...))
+    stay torch autograd upstream.  Saves its inputs only (the backward recomputes the scores); no (N, N) tensor outlives a call."""
+
+    @staticmethod
+    def forward(ctx, qkv, scale, bias, pad_qkv, row_map, B_, N, mask, nH):
+        qkv, scale, bias, pad = qkv.contiguous(), scale.contiguous(), bias.contiguous(), pad_qkv.contiguous()
+        out = hip.win_attn_ann_windowed(qkv, row_map, B_, N, pad, scale, bias, mask, nH)
+        ctx.save_for_backward(qkv, scale, bias, pad)
+        ctx.cfg = (row_map, B_, N, mask, nH)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, scale, bias, pad = ctx.saved_tensors
+        row_map, B_, N, mask, nH = ctx.cfg
+        dqkv, d_pad, d_scale, d_bias = hip.win_attn_ann_bwd(qkv, row_map, B_, N, pad, scale, bias, mask, nH, dout.contiguous())
+        return dqkv, d_scale, d_bias, d_pad, None, None, None, None, None

@@ -29,7 +29,8 @@ EXPORTS = ("sdf_version", "sdf_switches_reload", "sdf_launch_log", "sdf_launch_l
            "sdf_rows_gather_fwd", "sdf_rows_scatter_fwd",
            "sdf_split_weight_i8x3", "sdf_bn_train_fwd", "sdf_bn_train_bwd", "sdf_bn_train_workspace_bytes", "sdf_bn_train_nchw_fwd", "sdf_bn_train_nchw_bwd",
            "sdf_dense_conv3x3_fwd", "sdf_pack_planes", "sdf_unpack_planes", "sdf_pack_planes_up2", "sdf_pack_planes_zero_up2", "sdf_dense_linear_fwd", "sdf_layer_norm_fwd",
-           "sdf_linear_dw_fwd", "sdf_linear_dw_splits", "sdf_ringed_rows_fwd", "sdf_linear_train_fwd", "sdf_unring_rows_fwd")
+           "sdf_linear_dw_fwd", "sdf_linear_dw_splits", "sdf_ringed_rows_fwd", "sdf_linear_train_fwd", "sdf_unring_rows_fwd",
+           "sdf_win_attn_ann_bwd", "sdf_win_attn_ann_bwd_workspace_bytes")
 
 
 class SdfError(RuntimeError):
@@ -139,6 +140,13 @@ class WinAttnDesc(C.Structure):
                 ("B_", C.c_int32), ("nW", C.c_int32), ("nH", C.c_int32), ("N", C.c_int32), ("hd", C.c_int32),
                 ("Tq", C.c_int32), ("N1", C.c_int32),
                 ("scale", C.c_void_p), ("bias", C.c_void_p), ("mask", C.c_void_p), ("row_map", C.c_void_p), ("pad_qkv", C.c_void_p)]
+
+
+class WinAttnBwdDesc(C.Structure):
+    _fields_ = [("qkv", C.c_void_p), ("row_map", C.c_void_p), ("pad_qkv", C.c_void_p), ("dout", C.c_void_p),
+                ("scale", C.c_void_p), ("bias", C.c_void_p), ("mask", C.c_void_p), ("dqkv", C.c_void_p), ("d_pad", C.c_void_p),
+                ("d_scale", C.c_void_p), ("d_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("B_", C.c_int32), ("nW", C.c_int32), ("nH", C.c_int32), ("N", C.c_int32), ("hd", C.c_int32)]
 
 
 class AnnMlpBlockDesc(C.Structure):
@@ -280,6 +288,7 @@ def lib():
         _lib.sdf_ms_mlp_workspace_bytes.restype = C.c_int64
         _lib.sdf_bn_train_workspace_bytes.restype = C.c_int64
         _lib.sdf_qk_gate_bwd_workspace_bytes.restype = C.c_int64
+        _lib.sdf_win_attn_ann_bwd_workspace_bytes.restype = C.c_int64
     return _lib
 
 
@@ -674,6 +683,8 @@ def window_slice_map(B, D, H, W, ws, ss, device):
     """sdf_window_slice_map: the int32 gather table of pad + roll + window_partition_v2, built on the device.
     Returns (map (B_*Wd*Wh*Ww,), B_)."""
     Wd, Wh, Ww = ws
+    if torch.device(device).type != "cuda":
+        raise SdfError("window_slice_map builds the map on the GPU (no CPU fallback)")
     B_ = B * -(-D // Wd) * -(-H // Wh) * -(-W // Ww)
     m = torch.empty((B_ * Wd * Wh * Ww,), dtype=torch.int32, device=device)
     nw = C.c_int64(0)
@@ -1041,6 +1052,28 @@ def win_attn_ann_windowed(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH):
     d.row_map, d.pad_qkv = _ptr(row_map, torch.int32), _ptr(pad_qkv, torch.float32)
     _check(lib().sdf_win_attn_fwd(C.byref(d), _stream()), "sdf_win_attn_fwd")
     return out
+
+
+def win_attn_ann_bwd(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout):
+    """Backward of `win_attn_ann_windowed` (sdf_win_attn_ann_bwd): qkv (rows, 3C), row_map (B_*N,) int32, pad_qkv (3C), scale (nH),
+    bias (nH, N, N), mask (nW, N, N) or None as the forward took them; dout = dL/d(output) (rows, C).  -> (dqkv (rows, 3C), d_pad (3C), d_scale (nH), d_bias (nH, N, N)); deterministic (fixed-order window sums)."""
+    rows, C3 = qkv.shape
+    dev = qkv.device
+    dqkv = torch.empty_like(qkv)                                 # every real row lies in exactly one window: all of it is written
+    d_pad = torch.empty((C3,), dtype=torch.float32, device=dev)
+    d_scale = torch.empty((nH,), dtype=torch.float32, device=dev)
+    d_bias = torch.empty((nH, N, N), dtype=torch.float32, device=dev)
+    nbytes = lib().sdf_win_attn_ann_bwd_workspace_bytes(C.c_int(B_), C.c_int(nH), C.c_int(N))
+    ws = torch.empty((max(nbytes, 256) // 4,), dtype=torch.float32, device=dev)
+    d = WinAttnBwdDesc()
+    d.qkv, d.row_map, d.pad_qkv = _ptr(qkv, torch.float32), _ptr(row_map, torch.int32), _ptr(pad_qkv, torch.float32)
+    d.dout = _ptr(dout, torch.float32)
+    d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
+    d.dqkv, d.d_pad, d.d_scale, d.d_bias = _ptr(dqkv), _ptr(d_pad), _ptr(d_scale), _ptr(d_bias)
+    d.workspace, d.workspace_bytes = _ptr(ws), nbytes
+    d.B_, d.nW, d.nH, d.N, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, N, C3 // 3 // nH
+    _check(lib().sdf_win_attn_ann_bwd(C.byref(d), _stream()), "sdf_win_attn_ann_bwd")
+    return dqkv, d_pad, d_scale, d_bias
 
 
 def ann_attn_block_supported(Cc, nH, N):

@@ -395,17 +395,29 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
     `amp`: the reference trains under `torch.cuda.amp.autocast` with fp16 + GradScaler (`optimizer.use_amp: true`,
     :248, :314-331); here the same regions run under bf16 autocast (no scaler needed) - spikes are exact in bf16, the
     membranes / neuron kernels, BatchNorm statistics, the loss and the optimiser stay fp32.
+    An STTFlowNet (the ANN family, `clip_grad=None` as its config has it) trains through its own train-mode forward,
+    `model(chunk, None)["flow"]`, in fp32.
     `forward_fn(model, chunk) -> flows` replaces the HIP train-mode forward (the CPU dry run of the N > 1 plumbing, bench.py --train
     --plumbing: everything else in this function is the code the GPU ranks run)."""
     from .spikingjelly_compat import functional
+    from .STSwinNet.STSwinNet import STTFlowNet
+    ann = isinstance(model, STTFlowNet)             # the ANN family (train_flow_parallel_supervised.py): model(voxel, cnt)["flow"]
+    if ann and amp:
+        raise NotImplementedError("the ANN model trains in fp32 (configs/train_DSEC_supervised_STT_voxel.yml: use_amp False)")
     model.train()
-    functional.reset_net(model)
+    if not ann:
+        functional.reset_net(model)
     if buckets is not None:
         buckets.begin(dist, world)
     else:
         optimizer.zero_grad(set_to_none=True)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-        flows = forward_train(model, chunk) if forward_fn is None else forward_fn(model, chunk)
+        if forward_fn is not None:
+            flows = forward_fn(model, chunk)
+        elif ann:
+            flows = model(chunk, None)["flow"]
+        else:
+            flows = forward_train(model, chunk)
     n_valid = global_valid_count(mask, dist, world)
     # local mean over B_local of err_i / n_global, times 1 / world from the gradient average = the gathered-batch mean
     loss = flow_loss_supervised([f.float() for f in flows], label, mask, flow_scaling, lambda_mod, n_valid=n_valid)
