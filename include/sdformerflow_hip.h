@@ -63,7 +63,7 @@ int sdf_launch_log_read(SdfLaunchRecord* out, int max_records);
  *   h = v + (x_t - v)/tau ; s = (h - v_th >= 0) ; v = h - s*v_th (soft) | (1-s)*h + s*v_reset
  *   tau > 1: spikingjelly LIFNode.  0 < tau < 1 (every forward entry point and descriptor that carries a neuron): the
  *   multiplicative charge h = v + (x_t - v)*tau of ParametricLIFNode, tau = sigmoid(w) (reference Spiking_modules.py:75-82).
- *   tau <= 0 or tau == 1: SDF_E_SHAPE.  The backward entry points take tau > 1 only.
+ *   tau <= 0 or tau == 1: SDF_E_SHAPE.  The backward entry points take tau > 1 only (PLIF: sdf_plif_bwd, below).
  * v starts at 0 (soft) or v_reset (hard).  `v_last` (fp32, N) receives the final membrane or is NULL.
  */
 int sdf_lif_fwd(const float* x, void* spike, float* v_last, int T, int64_t N, float tau, float v_th,
@@ -99,6 +99,21 @@ int64_t sdf_psn_bwd_workspace_bytes(int T, int64_t N);
 int sdf_psn_bwd(const float* x, const float* W, const float* b, const float* grad_spike, float* grad_x, float* grad_W,
                 float* grad_b, float* grad_h, void* workspace, int64_t workspace_bytes, int T, int64_t N, int surrogate,
                 float alpha, void* stream);
+
+/* Training path of ParametricLIFNode (spikingjelly; the reference's `neuron_type: plif`, Spiking_modules.py:75-82): the
+ * multiplier k = sigmoid(w) is ONE fp32 in device memory (`plif_k`, the caller's sigmoid on the same stream), so a train step
+ * reads nothing back to the host.  Forward: sdf_lif_fwd's arithmetic with tau = k (h = v + d * k, d = x - v or
+ * x - (v - v_reset)), fp32 spikes, the same spikes eval mode gives for the same k.  Backward: sdf_lif_bwd's BPTT with
+ *   gx_t = gh_t * k ;  gv_{t-1} = gh_t - gh_t * k ;  grad_k = sum_t sum_n gh_t * d_t      (k = 0.5: LIF tau = 2 bit for bit)
+ * grad_k (one fp32) is reduced lane -> wave -> workgroup -> per-workgroup partials in `workspace`
+ * (sdf_plif_bwd_workspace_bytes(T, N) = 4 * ceil(N / 1024) bytes, caller-owned) -> one fixed-order finish: no atomics, two calls
+ * give bit-equal results.  Same shapes, T set and ATan surrogate as sdf_lif_bwd; soft / hard reset, any v_reset, detach_reset 0 / 1. */
+int sdf_plif_fwd(const float* x, const float* plif_k, float* spike, int T, int64_t N, float v_th, int soft_reset, float v_reset,
+                 void* stream);
+int64_t sdf_plif_bwd_workspace_bytes(int T, int64_t N);
+int sdf_plif_bwd(const float* x, const float* plif_k, const float* grad_spike, float* grad_x, float* grad_k, void* workspace,
+                 int64_t workspace_bytes, int T, int64_t N, float v_th, int soft_reset, float v_reset, int detach_reset,
+                 int surrogate, float alpha, void* stream);
 
 /* Batch-statistics BatchNorm over the last dim of a channel-last (R, C) fp32 buffer, forward and backward (training form of
  * the SpikingNormLayer "BN": spikingjelly layer.BatchNorm2d multi-step -> nn.BatchNorm2d on the view the reference makes with
@@ -140,6 +155,16 @@ int sdf_qk_gate_bwd(const float* q, const float* k, const float* grad_e, float* 
                     int kind, float tau, float v_th, int soft_reset, float v_reset, int detach_reset, int surrogate, float alpha,
                     const float* psn_w, const float* psn_b, float* grad_psn_w, float* grad_psn_b, void* workspace,
                     int64_t workspace_bytes, void* stream);
+/* The same gate with a PLIF SN2_q (ParametricLIFNode, the gate `Spiking_neuron` builds for `neuron_type: plif`, reference
+ * Spiking_swin_transformer3D.py:636): the multiplicative charge with k = sigmoid(w) read from `plif_k` (one fp32, device memory).
+ * The backward also returns grad_plif_k = sum over (t, row, head) of gh * d, reduced through `workspace`
+ * (sdf_qk_gate_plif_bwd_workspace_bytes(Tq, rows, C) = 4 * ceil(rows * C / 1024) bytes) in a fixed order: bit-reproducible. */
+int sdf_qk_gate_plif_f32_fwd(const float* q, const float* k, float* e, const float* plif_k, int Tq, int64_t rows, int C, float v_th,
+                             int soft_reset, float v_reset, void* stream);
+int64_t sdf_qk_gate_plif_bwd_workspace_bytes(int Tq, int64_t rows, int C);
+int sdf_qk_gate_plif_bwd(const float* q, const float* k, const float* grad_e, float* grad_q, float* grad_k, const float* plif_k,
+                         float* grad_plif_k, void* workspace, int64_t workspace_bytes, int Tq, int64_t rows, int C, float v_th,
+                         int soft_reset, float v_reset, int detach_reset, int surrogate, float alpha, void* stream);
 
 /* General neuron launch: strided / gathered input, fused eval-BatchNorm and additive prologue.
  * Replaces the reference idiom  SN( BN( y.permute(..) ).permute(..) [+ positional_encoding] )

@@ -96,9 +96,15 @@ class ParametricLIFNode(LIFNode):
             raise hip.SdfError(f"ParametricLIFNode: sigmoid(w) = {k} is not inside (0, 1)")
         return k
 
+    def k(self):
+        """sigmoid(w) as a device tensor, differentiable to w (the training path; `tau` reads it back to the host)."""
+        return torch.sigmoid(self.w.float())
+
     def forward(self, x_seq):
-        if torch.is_grad_enabled() and (x_seq.requires_grad or self.training):
-            raise NotImplementedError("ParametricLIFNode: the gradient (to x and to w) is not built; inference only")
+        if torch.is_grad_enabled() and (x_seq.requires_grad or self.training):     # training path: HIP forward + BPTT, dL/dw
+            from ..autograd import PLIFFunction
+            return PLIFFunction.apply(x_seq, self.k(), self.v_threshold, self.v_reset, self.detach_reset,
+                                      getattr(self.surrogate_function, "alpha", 2.0))
         return super().forward(x_seq)
 
     def extra_repr(self):

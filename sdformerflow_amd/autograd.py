@@ -32,6 +32,28 @@ class LIFFunction(torch.autograd.Function):
         return gx.to(ctx.in_dtype), None, None, None, None, None, None
 
 
+class PLIFFunction(torch.autograd.Function):
+    """Multi-step ParametricLIFNode over dim 0: spikes = PLIF(x; k); (dL/dx, dL/dk) by BPTT with the ATan surrogate (reference:
+    autograd through spikingjelly's ParametricLIFNode as Spiking_modules.py:75-82 builds it).  `k` = sigmoid(w) as a device tensor:
+    autograd carries dL/dk on to w, and no kernel argument is read back to the host."""
+
+    @staticmethod
+    def forward(ctx, x, k, v_th, v_reset, detach_reset, alpha):
+        ctx.in_dtype = x.dtype
+        x = x.float().contiguous()                  # under bf16 autocast the producer hands over bf16: the membrane is fp32
+        kf = k.detach().float().reshape(1).contiguous()
+        ctx.save_for_backward(x, kf)
+        ctx.cfg = (v_th, v_reset, detach_reset, alpha, k.shape, k.dtype)
+        return hip.plif_fwd(x, kf, v_th, v_reset)
+
+    @staticmethod
+    def backward(ctx, grad_spike):
+        x, kf = ctx.saved_tensors
+        v_th, v_reset, detach_reset, alpha, kshape, kdtype = ctx.cfg
+        gx, gk = hip.plif_bwd(x, kf, grad_spike.float(), v_th, v_reset, detach_reset, alpha)
+        return gx.to(ctx.in_dtype), gk.view(kshape).to(kdtype), None, None, None, None
+
+
 class PSNFunction(torch.autograd.Function):
     """Parallel spiking neuron over dim 0: spikes = (b + W x >= 0); (dL/dx, dL/dW, dL/db) with the ATan surrogate
     (reference PSN.forward, Spiking_submodules.py:207-211)."""
@@ -75,6 +97,27 @@ class QKGateFunction(torch.autograd.Function):
         gq, gk, gW, gb = hip.qk_gate_bwd(q, k, grad_e.float(), p, detach_reset, alpha)
         return (gq.to(ctx.in_dtype), gk.to(ctx.in_dtype), gW, None if gb is None else gb.view(bshape),
                 None, None, None, None, None, None)
+
+
+class QKGatePLIFFunction(torch.autograd.Function):
+    """The token gate with a PLIF SN2_q (ParametricLIFNode): e = k * PLIF(head sums of q; plif_k), plif_k = sigmoid(w) as a
+    device tensor; the backward launch also returns dL/d plif_k (fixed-order reduction)."""
+
+    @staticmethod
+    def forward(ctx, q, k, plif_k, v_th, v_reset, detach_reset, alpha):
+        ctx.in_dtype = q.dtype
+        q, k = q.float().contiguous(), k.float().contiguous()
+        pk = plif_k.detach().float().reshape(1).contiguous()
+        ctx.save_for_backward(q, k, pk)
+        ctx.cfg = (v_th, v_reset, detach_reset, alpha, plif_k.shape, plif_k.dtype)
+        return hip.qk_gate_plif_f32(q, k, pk, v_th, v_reset)
+
+    @staticmethod
+    def backward(ctx, grad_e):
+        q, k, pk = ctx.saved_tensors
+        v_th, v_reset, detach_reset, alpha, kshape, kdtype = ctx.cfg
+        gq, gk, gpk = hip.qk_gate_plif_bwd(q, k, grad_e.float(), pk, v_th, v_reset, detach_reset, alpha)
+        return gq.to(ctx.in_dtype), gk.to(ctx.in_dtype), gpk.view(kshape).to(kdtype), None, None, None, None
 
 
 class BatchNormLastFunction(torch.autograd.Function):

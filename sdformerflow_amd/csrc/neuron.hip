@@ -378,4 +378,56 @@ extern "C" int sdf_psn_fwd(const float* x, const float* W, const float* b, void*
   return sdf_neuron_fwd(&d, stream);
 }
 
+namespace {
+
+// Training-path PLIF forward: the multiplier k = sigmoid(w) is read from device memory (one fp32 scalar, written by the caller's
+// sigmoid on the same stream), so a train step needs no host read-back per neuron.  Arithmetic = lif_charge with inv_tau = k.
+template <int TT>
+__global__ __launch_bounds__(256) void plif_fwd_kernel(const float* x, const float* kp, float* spike, int64_t N, float v_th,
+                                                       int soft_reset, float v_reset) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q * 4 >= N) return;
+  const int64_t e = q * 4;
+  float4 xv[TT];
+#pragma unroll
+  for (int t = 0; t < TT; ++t) xv[t] = load4(x + (int64_t)t * N + e);
+  const float k = *kp;
+  const bool soft = soft_reset != 0, reset0 = soft || v_reset == 0.f;
+  const float v0 = soft ? 0.f : v_reset;
+  float4 v = make_float4(v0, v0, v0, v0);
+#pragma unroll
+  for (int t = 0; t < TT; ++t) {
+    float4 h, s;
+    h.x = lif_charge(v.x, xv[t].x, __builtin_inff(), k, v_reset, reset0);
+    h.y = lif_charge(v.y, xv[t].y, __builtin_inff(), k, v_reset, reset0);
+    h.z = lif_charge(v.z, xv[t].z, __builtin_inff(), k, v_reset, reset0);
+    h.w = lif_charge(v.w, xv[t].w, __builtin_inff(), k, v_reset, reset0);
+    s.x = fire_reset(v.x, h.x, v_th, v_reset, soft);
+    s.y = fire_reset(v.y, h.y, v_th, v_reset, soft);
+    s.z = fire_reset(v.z, h.z, v_th, v_reset, soft);
+    s.w = fire_reset(v.w, h.w, v_th, v_reset, soft);
+    *reinterpret_cast<float4*>(spike + (int64_t)t * N + e) = s;
+  }
+}
+
+}  // namespace
+
+extern "C" int sdf_plif_fwd(const float* x, const float* plif_k, float* spike, int T, int64_t N, float v_th, int soft_reset,
+                            float v_reset, void* stream) {
+  if (!x || !plif_k || !spike) return SDF_E_NULL;
+  if (N < 4 || N % 4) return SDF_E_SHAPE;
+  if (!sdf_aligned(x, 16) || !sdf_aligned(spike, 16) || !sdf_aligned(plif_k, 4)) return SDF_E_ALIGN;
+  if (soft_reset) v_reset = 0.f;
+  dim3 grid((unsigned)((N / 4 + 255) / 256)), block(256);
+  hipStream_t s = sdf_stream(stream);
+#define SDF_T_CASE(TT) case TT: SDF_LAUNCH(plif_fwd_kernel<TT>, grid, block, 0, s, x, plif_k, spike, N, v_th, soft_reset, v_reset); break;
+  switch (T) {
+    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
+    default: return SDF_E_SHAPE;
+  }
+#undef SDF_T_CASE
+  SDF_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int sdf_version(void) { return SDF_VERSION; }

@@ -230,6 +230,77 @@ __global__ __launch_bounds__(256) void psn_bwd_finish_kernel(const float* partia
   }
 }
 
+// PLIF (spikingjelly ParametricLIFNode, h = v + d * k with k = sigmoid(w) read from device memory): lif_bwd_kernel's streaming
+// shape and BPTT with gx = gh * k, gv = gh - gh * k (k = 0.5 is LIF tau = 2 bit for bit), plus dL/dk = sum_t sum_i gh_t * d_t,
+// d_t the charge difference the forward used, kept beside h_t (167 VGPRs at T = 10, 3 waves per SIMD; lif_bwd: 128, 4).
+// dL/dk: per lane over its steps and neurons -> wave butterfly -> workgroup (LDS) -> one partial per workgroup ->
+// psn_bwd_finish_kernel (fixed order).
+template <int TT>
+__global__ __launch_bounds__(256) void plif_bwd_kernel(BwdParams P, const float* kp) {
+  __shared__ float red[4];
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = q * 4 < P.N;
+  const int64_t e = live ? q * 4 : P.N - 4;                    // lanes past the end re-read the last quad and add nothing
+  const float k = *kp;
+  float4 xv[TT], gv_[TT];
+#pragma unroll
+  for (int t = 0; t < TT; ++t) xv[t] = ld4(P.x + (int64_t)t * P.N + e);
+#pragma unroll
+  for (int t = 0; t < TT; ++t) gv_[t] = ld4(P.gs + (int64_t)t * P.N + e);
+  const bool soft = P.soft != 0, reset0 = soft || P.v_reset == 0.f;
+  const float v0 = soft ? 0.f : P.v_reset;
+  float hx[TT][4], dx[TT][4];
+  {
+    float v[4] = {v0, v0, v0, v0};
+#pragma unroll
+    for (int t = 0; t < TT; ++t) {
+      const float xs[4] = {xv[t].x, xv[t].y, xv[t].z, xv[t].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float d = reset0 ? (xs[j] - v[j]) : (xs[j] - (v[j] - P.v_reset));
+        dx[t][j] = d;
+        const float h = v[j] + d * k;
+        const float s = (h - P.v_th >= 0.f) ? 1.f : 0.f;
+        v[j] = soft ? (h - s * P.v_th) : ((1.f - s) * h + s * P.v_reset);
+        hx[t][j] = h;
+      }
+    }
+  }
+  float gv[4] = {0.f, 0.f, 0.f, 0.f};
+  float acc = 0.f;
+#pragma unroll
+  for (int t = TT - 1; t >= 0; --t) {
+    const float gs[4] = {gv_[t].x, gv_[t].y, gv_[t].z, gv_[t].w};
+    float gx[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float h = hx[t][j], u = h - P.v_th;
+      const float s = (u >= 0.f) ? 1.f : 0.f;
+      float gspike = gs[j];
+      float gh;
+      if (soft) {
+        if (!P.detach) gspike = gspike + (-(gv[j] * P.v_th));
+        gh = gv[j] + sg_atan(u, gspike, P.c_atan, P.half_alpha);
+      } else {
+        if (!P.detach) gspike = gspike + (gv[j] * P.v_reset + (-(gv[j] * h)));
+        gh = gv[j] * (1.f - s) + sg_atan(u, gspike, P.c_atan, P.half_alpha);
+      }
+      const float qd = gh * k;
+      gx[j] = qd;
+      gv[j] = gh - qd;
+      acc = __builtin_fmaf(gh, dx[t][j], acc);
+    }
+    if (live) st4(P.gx + (int64_t)t * P.N + e, make_float4(gx[0], gx[1], gx[2], gx[3]));
+  }
+  if (!live) acc = 0.f;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) P.partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 int psn_vec(int T, bool reduce) { return (reduce && T >= 8) ? 2 : 4; }
 
 int psn_blocks(int T, int64_t N, bool reduce) {
@@ -311,5 +382,42 @@ extern "C" int sdf_psn_bwd(const float* x, const float* W, const float* b, const
     SDF_LAUNCH(psn_bwd_finish_kernel, dim3(nacc), dim3(256), 0, s, P.partial, nblk, nacc, T, grad_W, grad_b);
     SDF_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+extern "C" int64_t sdf_plif_bwd_workspace_bytes(int T, int64_t N) {
+  if (T < 1 || N < 4) return 0;
+  return (N / 4 + 255) / 256 * (int64_t)sizeof(float);          // one fp32 partial of dL/dk per workgroup
+}
+
+extern "C" int sdf_plif_bwd(const float* x, const float* plif_k, const float* grad_spike, float* grad_x, float* grad_k,
+                            void* workspace, int64_t workspace_bytes, int T, int64_t N, float v_th, int soft_reset, float v_reset,
+                            int detach_reset, int surrogate, float alpha, void* stream) {
+  if (!x || !plif_k || !grad_spike || !grad_x || !grad_k || !workspace) return SDF_E_NULL;
+  if (N < 4 || N % 4) return SDF_E_SHAPE;
+  if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_DTYPE;
+  if (T != 1 && T != 2 && T != 4 && T != 5 && T != 8 && T != 10 && T != 16 && T != 20) return SDF_E_SHAPE;
+  if (workspace_bytes < sdf_plif_bwd_workspace_bytes(T, N)) return SDF_E_SHAPE;
+  if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16) || !sdf_aligned(plif_k, 4) ||
+      !sdf_aligned(grad_k, 4) || !sdf_aligned(workspace, 4))
+    return SDF_E_ALIGN;
+  BwdParams P = {};
+  P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = SDF_LIF; P.soft = soft_reset; P.detach = detach_reset;
+  P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
+  P.c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
+  P.half_alpha = (float)((double)alpha / 2);
+  P.partial = reinterpret_cast<float*>(workspace);
+  const int nblk = (int)((N / 4 + 255) / 256);
+  dim3 grid((unsigned)nblk), block(256);
+  hipStream_t s = sdf_stream(stream);
+#define SDF_T_CASE(TT) case TT: SDF_LAUNCH(plif_bwd_kernel<TT>, grid, block, 0, s, P, plif_k); break;
+  switch (T) {
+    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
+    default: return SDF_E_SHAPE;
+  }
+#undef SDF_T_CASE
+  SDF_LAUNCH_CHECK();
+  SDF_LAUNCH(psn_bwd_finish_kernel, dim3(1), dim3(256), 0, s, P.partial, nblk, 1, 0, (float*)nullptr, grad_k);
+  SDF_LAUNCH_CHECK();
   return 0;
 }

@@ -1,6 +1,6 @@
 // Training-path token gate of Spiking_QK_WindowAttention3D (reference Spiking_swin_transformer3D.py:687-694) on fp32 spike
 // tensors, forward and backward ("backward kernels for ... QK-attention"):
-//   s[t,row,g] = sum_{d<32} q[t,row,g*32+d]          A = SN2_q(s) over the T' attention steps (LIF / IF)
+//   s[t,row,g] = sum_{d<32} q[t,row,g*32+d]          A = SN2_q(s) over the T' attention steps (LIF / IF / PSN / PLIF)
 //   e[t,row,c] = k[t,row,c] * A[t,row,c/32]
 // backward, given dL/de:
 //   gk[t,row,c] = ge[t,row,c] * A[t,row,c/32]        gA[t,row,g] = sum_{d<32} ge * k
@@ -21,7 +21,8 @@ struct GateTrainParams {
   int kind, soft, detach;
   float tau, inv_tau, v_th, v_reset, c_atan, half_alpha;
   const float* psn_w; const float* psn_b;   // PSN gate: (T', T') and (T')
-  float* partial;                           // PSN backward: [nblk][T'*T' + T'] partial sums of dW | db
+  float* partial;                           // PSN backward: [nblk][T'*T' + T'] partial sums of dW | db; PLIF: [nblk] of dL/dk
+  const float* plif_k;                      // PLIF gate: the multiplier k = sigmoid(w), one fp32 in device memory
 };
 
 __device__ __forceinline__ float sum8(float v) {          // over the 8 lanes of one (row, head)
@@ -59,7 +60,23 @@ __device__ __forceinline__ void gate_neuron(const GateTrainParams& P, const floa
   }
 }
 
-template <int TQ, bool BWD>
+// PLIF gate (spikingjelly ParametricLIFNode): the LIF recurrence with the multiplicative charge h = v + d * k; keeps the charge
+// differences d_t for dL/dk
+template <int TQ>
+__device__ __forceinline__ void gate_neuron_plif(const GateTrainParams& P, float k, const float (&s)[TQ], float (&h)[TQ], float (&A)[TQ],
+                                                 float (&d)[TQ]) {
+  const bool soft = P.soft != 0, reset0 = soft || P.v_reset == 0.f;
+  float v = soft ? 0.f : P.v_reset;
+#pragma unroll
+  for (int t = 0; t < TQ; ++t) {
+    d[t] = reset0 ? (s[t] - v) : (s[t] - (v - P.v_reset));
+    h[t] = v + d[t] * k;
+    A[t] = (h[t] - P.v_th >= 0.f) ? 1.f : 0.f;
+    v = soft ? (h[t] - A[t] * P.v_th) : ((1.f - A[t]) * h[t] + A[t] * P.v_reset);
+  }
+}
+
+template <int TQ, bool BWD, bool PLIF = false>
 __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;     // lane i owns channels 4 (i % 8) .. +3 of (row, head) i / 8
   const int64_t pairs = P.rows * P.G;
@@ -67,7 +84,8 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
   const int64_t off = live ? i * 4 : 0;                          // ((row*G + g)*32 + 4*(i%8)) == row*C + g*32 + 4*(i%8)
   const int64_t step = P.rows * (int64_t)P.C;
   float4 qv[TQ], kv[TQ], gv[TQ];
-  float s[TQ], h[TQ], A[TQ];
+  float s[TQ], h[TQ], A[TQ], dch[TQ];
+  const float kp = PLIF ? *P.plif_k : 0.f;
 #pragma unroll
   for (int t = 0; t < TQ; ++t) {
     qv[t] = live ? *reinterpret_cast<const float4*>(P.q + t * step + off) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -76,7 +94,8 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
   }
 #pragma unroll
   for (int t = 0; t < TQ; ++t) s[t] = sum8((qv[t].x + qv[t].y) + (qv[t].z + qv[t].w));      // spikes: an exact integer 0..32
-  gate_neuron<TQ>(P, s, h, A);
+  if (PLIF) gate_neuron_plif<TQ>(P, kp, s, h, A, dch);
+  else gate_neuron<TQ>(P, s, h, A);
   if (!BWD) {
     if (live) {
 #pragma unroll
@@ -139,7 +158,7 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
   }
   // BPTT through the gate neuron (the recurrence of neuron_bwd.hip on the TQ head sums)
   const bool soft = P.soft != 0;
-  float gvm = 0.f;
+  float gvm = 0.f, acc = 0.f;
 #pragma unroll
   for (int t = TQ - 1; t >= 0; --t) {
     const float u = h[t] - P.v_th;
@@ -152,7 +171,12 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
       if (!P.detach) gsp = gsp + (gvm * P.v_reset + (-(gvm * h[t])));
       gh = gvm * (1.f - A[t]) + ((1.f / y) * P.half_alpha) * gsp;
     }
-    if (P.kind == SDF_IF) {
+    if (PLIF) {                                                  // h = v + d * k: gd = gh * k, dL/dk += gh * d
+      const float qd = gh * kp;
+      gs[t] = qd;
+      gvm = gh - qd;
+      acc = __builtin_fmaf(gh, dch[t], acc);
+    } else if (P.kind == SDF_IF) {
       gs[t] = gh;
       gvm = gh;
     } else {
@@ -167,6 +191,15 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
       *reinterpret_cast<float4*>(P.gq + t * step + off) = make_float4(gs[t], gs[t], gs[t], gs[t]);
       *reinterpret_cast<float4*>(P.gk + t * step + off) = make_float4(gv[t].x * A[t], gv[t].y * A[t], gv[t].z * A[t], gv[t].w * A[t]);
     }
+  }
+  if (PLIF) {                                                    // dL/dk: one lane per (row, head) -> wave -> workgroup -> partial
+    __shared__ float red1[4];
+    acc = (live && (threadIdx.x & 7) == 0) ? acc : 0.f;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) red1[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) P.partial[blockIdx.x] = (red1[0] + red1[1]) + (red1[2] + red1[3]);
   }
 }
 
@@ -198,14 +231,14 @@ __global__ __launch_bounds__(256) void gate_finish_kernel(const float* partial, 
   }
 }
 
-template <bool BWD>
+template <bool BWD, bool PLIF = false>
 int launch(const GateTrainParams& P, int Tq, hipStream_t s) {
   const int64_t lanes = P.rows * P.G * 8;
   dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
   switch (Tq) {
-    case 1: SDF_LAUNCH((qk_gate_train_kernel<1, BWD>), grid, block, 0, s, P); break;
-    case 2: SDF_LAUNCH((qk_gate_train_kernel<2, BWD>), grid, block, 0, s, P); break;
-    case 4: SDF_LAUNCH((qk_gate_train_kernel<4, BWD>), grid, block, 0, s, P); break;
+    case 1: SDF_LAUNCH((qk_gate_train_kernel<1, BWD, PLIF>), grid, block, 0, s, P); break;
+    case 2: SDF_LAUNCH((qk_gate_train_kernel<2, BWD, PLIF>), grid, block, 0, s, P); break;
+    case 4: SDF_LAUNCH((qk_gate_train_kernel<4, BWD, PLIF>), grid, block, 0, s, P); break;
     default: return SDF_E_SHAPE;
   }
   SDF_LAUNCH_CHECK();
@@ -256,6 +289,50 @@ extern "C" int sdf_qk_gate_bwd(const float* q, const float* k, const float* grad
   const int64_t nblk = (rows * (C / 32) * 8 + 255) / 256;
   const int nacc = Tq * Tq + Tq;
   SDF_LAUNCH(gate_finish_kernel, dim3(nacc), dim3(256), 0, sdf_stream(stream), P.partial, nblk, nacc, Tq, grad_psn_w, grad_psn_b);
+  SDF_LAUNCH_CHECK();
+  return 0;
+}
+
+// PLIF gate (the multiplier k = sigmoid(w) by device pointer, no host read-back): forward, and backward with dL/dk reduced
+// lane -> wave -> workgroup -> per-workgroup partial -> fixed-order finish, like the PSN gate's dW / db
+extern "C" int sdf_qk_gate_plif_f32_fwd(const float* q, const float* k, float* e, const float* plif_k, int Tq, int64_t rows, int C,
+                                        float v_th, int soft_reset, float v_reset, void* stream) {
+  if (!q || !k || !e || !plif_k) return SDF_E_NULL;
+  if (!sdf_aligned(q, 16) || !sdf_aligned(k, 16) || !sdf_aligned(e, 16) || !sdf_aligned(plif_k, 4)) return SDF_E_ALIGN;
+  GateTrainParams P = {};
+  const int rc = fill(P, rows, C, SDF_LIF, 2.f, v_th, soft_reset, v_reset);
+  if (rc) return rc;
+  P.q = q; P.k = k; P.e = e; P.plif_k = plif_k;
+  return launch<false, true>(P, Tq, sdf_stream(stream));
+}
+
+extern "C" int64_t sdf_qk_gate_plif_bwd_workspace_bytes(int Tq, int64_t rows, int C) {
+  if (Tq < 1 || rows < 1 || C < 32) return 0;
+  return (rows * (C / 32) * 8 + 255) / 256 * (int64_t)sizeof(float);     // one fp32 partial of dL/dk per workgroup
+}
+
+extern "C" int sdf_qk_gate_plif_bwd(const float* q, const float* k, const float* grad_e, float* grad_q, float* grad_k,
+                                    const float* plif_k, float* grad_plif_k, void* workspace, int64_t workspace_bytes, int Tq,
+                                    int64_t rows, int C, float v_th, int soft_reset, float v_reset, int detach_reset, int surrogate,
+                                    float alpha, void* stream) {
+  if (!q || !k || !grad_e || !grad_q || !grad_k || !plif_k || !grad_plif_k || !workspace) return SDF_E_NULL;
+  if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_DTYPE;
+  if (Tq != 1 && Tq != 2 && Tq != 4) return SDF_E_SHAPE;
+  GateTrainParams P = {};
+  const int rc = fill(P, rows, C, SDF_LIF, 2.f, v_th, soft_reset, v_reset);
+  if (rc) return rc;
+  if (workspace_bytes < sdf_qk_gate_plif_bwd_workspace_bytes(Tq, rows, C)) return SDF_E_SHAPE;
+  if (!sdf_aligned(q, 16) || !sdf_aligned(k, 16) || !sdf_aligned(grad_e, 16) || !sdf_aligned(grad_q, 16) || !sdf_aligned(grad_k, 16) ||
+      !sdf_aligned(plif_k, 4) || !sdf_aligned(grad_plif_k, 4) || !sdf_aligned(workspace, 4))
+    return SDF_E_ALIGN;
+  P.q = q; P.k = k; P.ge = grad_e; P.gq = grad_q; P.gk = grad_k; P.detach = detach_reset; P.plif_k = plif_k;
+  P.partial = reinterpret_cast<float*>(workspace);
+  P.c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
+  P.half_alpha = (float)((double)alpha / 2);
+  const int rc2 = launch<true, true>(P, Tq, sdf_stream(stream));
+  if (rc2) return rc2;
+  const int64_t nblk = (rows * (C / 32) * 8 + 255) / 256;
+  SDF_LAUNCH(gate_finish_kernel, dim3(1), dim3(256), 0, sdf_stream(stream), P.partial, nblk, 1, 0, (float*)nullptr, grad_plif_k);
   SDF_LAUNCH_CHECK();
   return 0;
 }

@@ -30,7 +30,9 @@ EXPORTS = ("sdf_version", "sdf_switches_reload", "sdf_launch_log", "sdf_launch_l
            "sdf_split_weight_i8x3", "sdf_bn_train_fwd", "sdf_bn_train_bwd", "sdf_bn_train_workspace_bytes", "sdf_bn_train_nchw_fwd", "sdf_bn_train_nchw_bwd",
            "sdf_dense_conv3x3_fwd", "sdf_pack_planes", "sdf_unpack_planes", "sdf_pack_planes_up2", "sdf_pack_planes_zero_up2", "sdf_dense_linear_fwd", "sdf_layer_norm_fwd",
            "sdf_linear_dw_fwd", "sdf_linear_dw_splits", "sdf_ringed_rows_fwd", "sdf_linear_train_fwd", "sdf_unring_rows_fwd",
-           "sdf_win_attn_ann_bwd", "sdf_win_attn_ann_bwd_workspace_bytes")
+           "sdf_win_attn_ann_bwd", "sdf_win_attn_ann_bwd_workspace_bytes",
+           "sdf_plif_fwd", "sdf_plif_bwd", "sdf_plif_bwd_workspace_bytes", "sdf_qk_gate_plif_f32_fwd", "sdf_qk_gate_plif_bwd",
+           "sdf_qk_gate_plif_bwd_workspace_bytes")
 
 
 class SdfError(RuntimeError):
@@ -289,6 +291,8 @@ def lib():
         _lib.sdf_bn_train_workspace_bytes.restype = C.c_int64
         _lib.sdf_qk_gate_bwd_workspace_bytes.restype = C.c_int64
         _lib.sdf_win_attn_ann_bwd_workspace_bytes.restype = C.c_int64
+        _lib.sdf_plif_bwd_workspace_bytes.restype = C.c_int64
+        _lib.sdf_qk_gate_plif_bwd_workspace_bytes.restype = C.c_int64
     return _lib
 
 
@@ -419,6 +423,42 @@ def lif_bwd(x, grad_spike, tau=2.0, v_th=1.0, v_reset=None, detach_reset=True, a
                            C.c_int(1 if detach_reset else 0), C.c_int(0), C.c_float(alpha), _stream())
     _check(rc, "sdf_lif_bwd")
     return gx
+
+
+def plif_fwd(x, k, v_th=1.0, v_reset=None):
+    """Multi-step ParametricLIFNode over dim 0 for the training path (sdf_plif_fwd): fp32 spikes; `k` = sigmoid(w), a one-element
+    fp32 DEVICE tensor (read by the kernel, never by the host)."""
+    (x,), info = _pad4(x)
+    if info is not None:
+        return _unpad4(plif_fwd(x, k, v_th, v_reset), info)
+    T, N = x.shape[0], x[0].numel()
+    out = torch.empty_like(x)
+    rc = lib().sdf_plif_fwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(out)),
+                            C.c_int(T), C.c_int64(N), C.c_float(v_th), C.c_int(1 if v_reset is None else 0),
+                            C.c_float(0.0 if v_reset is None else v_reset), _stream())
+    _check(rc, "sdf_plif_fwd")
+    return out
+
+
+def plif_bwd(x, k, grad_spike, v_th=1.0, v_reset=None, detach_reset=True, alpha=2.0):
+    """BPTT through the multi-step ParametricLIFNode (sdf_plif_bwd): (dL/dx, dL/dk), dL/dk a one-element fp32 tensor reduced in a
+    fixed order (no atomics); ATan surrogate.  Padded columns (x = 0, dL/ds = 0) add nothing to dL/dk."""
+    (x, g), info = _pad4(x, grad_spike)
+    if info is not None:
+        gx, gk = plif_bwd(x, k, g, v_th, v_reset, detach_reset, alpha)
+        return _unpad4(gx, info), gk
+    T, N = x.shape[0], x[0].numel()
+    gx = torch.empty_like(x)
+    gk = torch.empty((1,), dtype=torch.float32, device=x.device)
+    nbytes = lib().sdf_plif_bwd_workspace_bytes(C.c_int(T), C.c_int64(N))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
+    rc = lib().sdf_plif_bwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(g, torch.float32)),
+                            C.c_void_p(_ptr(gx)), C.c_void_p(_ptr(gk)), C.c_void_p(_ptr(ws)), C.c_int64(nbytes), C.c_int(T),
+                            C.c_int64(N), C.c_float(v_th), C.c_int(1 if v_reset is None else 0),
+                            C.c_float(0.0 if v_reset is None else v_reset), C.c_int(1 if detach_reset else 0), C.c_int(0),
+                            C.c_float(alpha), _stream())
+    _check(rc, "sdf_plif_bwd")
+    return gx, gk
 
 
 def psn_bwd(x, W, b, grad_spike, alpha=2.0, need_param_grads=True):
@@ -1025,6 +1065,37 @@ def qk_gate_bwd(q, k, grad_e, p: NeuronParams, detach_reset=True, alpha=2.0):
                                C.c_void_p(_ptr(gW)), C.c_void_p(_ptr(gb)), C.c_void_p(_ptr(ws)), C.c_int64(nbytes), _stream())
     _check(rc, "sdf_qk_gate_bwd")
     return gq, gk, gW, gb
+
+
+def qk_gate_plif_f32(q, k, plif_k, v_th=1.0, v_reset=None):
+    """sdf_qk_gate_plif_f32_fwd: the token gate with a PLIF SN2_q; `plif_k` = sigmoid(w), a one-element fp32 device tensor."""
+    q, k = q.contiguous(), k.contiguous()
+    Tq, Cc = q.shape[0], q.shape[-1]
+    e = torch.empty_like(k)
+    rc = lib().sdf_qk_gate_plif_f32_fwd(C.c_void_p(_ptr(q, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(e)),
+                                        C.c_void_p(_ptr(plif_k, torch.float32)), C.c_int(Tq), C.c_int64(q[0].numel() // Cc), C.c_int(Cc),
+                                        C.c_float(v_th), C.c_int(1 if v_reset is None else 0),
+                                        C.c_float(0.0 if v_reset is None else v_reset), _stream())
+    _check(rc, "sdf_qk_gate_plif_f32_fwd")
+    return e
+
+
+def qk_gate_plif_bwd(q, k, grad_e, plif_k, v_th=1.0, v_reset=None, detach_reset=True, alpha=2.0):
+    """sdf_qk_gate_plif_bwd: (dL/dq, dL/dk, dL/d plif_k) of the PLIF token gate; the last one-element, fixed-order reduced."""
+    q, k, g = q.contiguous(), k.contiguous(), grad_e.contiguous()
+    Tq, Cc = q.shape[0], q.shape[-1]
+    rows = q[0].numel() // Cc
+    gq, gk = torch.empty_like(q), torch.empty_like(k)
+    gpk = torch.empty((1,), dtype=torch.float32, device=q.device)
+    nbytes = lib().sdf_qk_gate_plif_bwd_workspace_bytes(C.c_int(Tq), C.c_int64(rows), C.c_int(Cc))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=q.device)
+    rc = lib().sdf_qk_gate_plif_bwd(C.c_void_p(_ptr(q, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(g, torch.float32)),
+                                    C.c_void_p(_ptr(gq)), C.c_void_p(_ptr(gk)), C.c_void_p(_ptr(plif_k, torch.float32)), C.c_void_p(_ptr(gpk)),
+                                    C.c_void_p(_ptr(ws)), C.c_int64(nbytes), C.c_int(Tq), C.c_int64(rows), C.c_int(Cc), C.c_float(v_th),
+                                    C.c_int(1 if v_reset is None else 0), C.c_float(0.0 if v_reset is None else v_reset),
+                                    C.c_int(1 if detach_reset else 0), C.c_int(0), C.c_float(alpha), _stream())
+    _check(rc, "sdf_qk_gate_plif_bwd")
+    return gq, gk, gpk
 
 
 def affine_resid(x, alpha, beta, Cch, inner, resid=None, out=None):

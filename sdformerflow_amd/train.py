@@ -29,6 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
+from .STSwinNet_SNN.Spiking_submodules import ParametricLIFNode
 
 
 # ---------------------------------------------------------------------------------------------- layers
@@ -173,7 +174,10 @@ def qk_attention(x, attn):
     if hd == 32 and Tq in (1, 2, 4):                                    # token gate, forward and backward one HIP launch each
         from .autograd import QKGateFunction
         alpha = getattr(gate.surrogate_function, "alpha", 2.0)
-        if gate.kind == "psn":
+        if isinstance(gate, ParametricLIFNode):                          # (its `kind` stays "lif": the inference engine reads that)
+            from .autograd import QKGatePLIFFunction
+            e = QKGatePLIFFunction.apply(q, k, gate.k(), gate.v_threshold, gate.v_reset, gate.detach_reset, alpha)
+        elif gate.kind == "psn":
             e = QKGateFunction.apply(q, k, gate.weight, gate.bias, "psn", 2.0, 0.0, None, True, alpha)
         else:
             e = QKGateFunction.apply(q, k, None, None, gate.kind, gate.tau, gate.v_threshold, gate.v_reset, gate.detach_reset, alpha)
