@@ -1,7 +1,9 @@
 """ctypes binding of libsdformerflow_hip.so (the C ABI declared in include/sdformerflow_hip.h).
 
 PyTorch is plumbing here: it owns device memory and the stream; every compute call goes through the
-C ABI with raw pointers.  There is NO CPU fallback: if the library is missing or a tensor is not on
+C ABI with raw pointers.  `SIGNATURES` declares the return and argument types of every entry point, so
+call sites pass plain Python ints, floats, pointers (`_ptr`, `None`) and descriptors (`C.byref(desc)`
+or an array of them).  There is NO CPU fallback: if the library is missing or a tensor is not on
 the GPU the call raises.
 """
 from __future__ import annotations
@@ -19,20 +21,6 @@ LIB_PATH = os.environ.get("SDF_HIP_LIB") or os.path.join(_HERE, "csrc", "libsdfo
 SDF_F32, SDF_U8 = 0, 1
 SDF_LIF, SDF_PSN, SDF_IF = 0, 1, 2
 KIND = {"lif": SDF_LIF, "psn": SDF_PSN, "if": SDF_IF}
-
-VOID_EXPORTS = ("sdf_switches_reload", "sdf_launch_log")       # the entry points that return nothing
-EXPORTS = ("sdf_version", "sdf_switches_reload", "sdf_launch_log", "sdf_launch_log_read", "sdf_lif_fwd", "sdf_psn_fwd", "sdf_neuron_fwd", "sdf_spike_gemm_fwd",
-           "sdf_split_weight_bf16", "sdf_split_weight_f16x2", "sdf_qk_gate_fwd", "sdf_qk_gate_strided_fwd", "sdf_affine_resid_fwd", "sdf_win_attn_fwd", "sdf_ann_attn_block_fwd", "sdf_ann_attn_block_supported", "sdf_ann_mlp_block_fwd", "sdf_ann_mlp_block_supported", "sdf_spike_conv2d_fwd", "sdf_spike_deconv3x3s2_fwd", "sdf_head_conv_sn_fwd",
-           "sdf_flow_out_fwd", "sdf_deconv_col2im_fwd", "sdf_lif_bwd", "sdf_psn_bwd", "sdf_psn_bwd_workspace_bytes",
-           "sdf_window_slice_map", "sdf_window_zsrc_map", "sdf_qk_attn_fwd", "sdf_qk_attn_is_wide", "sdf_ms_mlp_is_wide", "sdf_ms_patch_merge_fwd", "sdf_tile_weight_i8x3", "sdf_spike_conv2d_multi_fwd", "sdf_qk_attn_workspace_bytes", "sdf_spike_gemm_bn_fwd",
-           "sdf_ms_mlp_fwd", "sdf_ms_mlp_workspace_bytes", "sdf_pred_head_fwd", "sdf_pointwise_conv_f32_fwd", "sdf_neuron_multi_fwd", "sdf_qk_gate_f32_fwd", "sdf_qk_gate_bwd", "sdf_qk_gate_bwd_workspace_bytes",
-           "sdf_rows_gather_fwd", "sdf_rows_scatter_fwd",
-           "sdf_split_weight_i8x3", "sdf_bn_train_fwd", "sdf_bn_train_bwd", "sdf_bn_train_workspace_bytes", "sdf_bn_train_nchw_fwd", "sdf_bn_train_nchw_bwd",
-           "sdf_dense_conv3x3_fwd", "sdf_pack_planes", "sdf_unpack_planes", "sdf_pack_planes_up2", "sdf_pack_planes_zero_up2", "sdf_dense_linear_fwd", "sdf_layer_norm_fwd",
-           "sdf_linear_dw_fwd", "sdf_linear_dw_splits", "sdf_ringed_rows_fwd", "sdf_linear_train_fwd", "sdf_unring_rows_fwd",
-           "sdf_win_attn_ann_bwd", "sdf_win_attn_ann_bwd_workspace_bytes",
-           "sdf_plif_fwd", "sdf_plif_bwd", "sdf_plif_bwd_workspace_bytes", "sdf_qk_gate_plif_f32_fwd", "sdf_qk_gate_plif_bwd",
-           "sdf_qk_gate_plif_bwd_workspace_bytes")
 
 
 class SdfError(RuntimeError):
@@ -194,6 +182,125 @@ class LinearTrainDesc(C.Structure):
                 ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("mode", C.c_int32), ("cv_C", C.c_int32), ("cv_Wp", C.c_int32)]
 
 
+class LaunchRecord(C.Structure):
+    _fields_ = [("kernel", C.c_char * 192), ("workgroups", C.c_uint32), ("threads", C.c_uint32), ("lds_bytes", C.c_uint32), ("us", C.c_float)]
+
+
+class NeuronCfg(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("tau", C.c_float), ("v_th", C.c_float), ("v_reset", C.c_float),
+                ("soft_reset", C.c_int32), ("psn_w", C.c_void_p), ("psn_b", C.c_void_p)]
+
+
+class QkAttnDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("slice_map", C.c_void_p), ("B_", C.c_int64), ("x_rows", C.c_int64),
+                ("Tq", C.c_int32), ("N1", C.c_int32), ("C", C.c_int32), ("nH", C.c_int32), ("nsplit", C.c_int32),
+                ("qk_planes", C.c_void_p), ("qk_alpha", C.c_void_p), ("qk_beta", C.c_void_p), ("qk_add", C.c_void_p),
+                ("qk_acc_scale", C.c_float),
+                ("q_planes", C.c_void_p), ("q_alpha", C.c_void_p), ("q_beta", C.c_void_p), ("q_acc_scale", C.c_float),
+                ("k_planes", C.c_void_p), ("k_alpha", C.c_void_p), ("k_beta", C.c_void_p), ("k_add", C.c_void_p),
+                ("k_acc_scale", C.c_float),
+                ("p_planes", C.c_void_p), ("p_bias", C.c_void_p), ("p_alpha", C.c_void_p), ("p_beta", C.c_void_p),
+                ("p_acc_scale", C.c_float),
+                ("sn_proj", NeuronCfg), ("sn_q", NeuronCfg), ("sn_k", NeuronCfg), ("sn2_q", NeuronCfg),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("gemm_workspace", C.c_void_p), ("gemm_workspace_bytes", C.c_int64), ("flags", C.c_int32),
+                ("x_src", C.c_void_p), ("xB", C.c_int32), ("xD", C.c_int32), ("xHW", C.c_int64), ("emit_s1", C.c_void_p),
+                ("emit_sn", NeuronCfg),
+                ("qk_digits", C.c_void_p), ("qk_cscale", C.c_void_p), ("q_digits", C.c_void_p), ("q_cscale", C.c_void_p),
+                ("k_digits", C.c_void_p), ("k_cscale", C.c_void_p), ("p_digits", C.c_void_p), ("p_cscale", C.c_void_p),
+                ("rep_windows", C.c_int32)]
+
+
+class MsMlpDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("B", C.c_int32), ("D", C.c_int32), ("HW", C.c_int64), ("C", C.c_int32), ("Ch", C.c_int32),
+                ("nsplit", C.c_int32),
+                ("fc1_planes", C.c_void_p), ("fc1_alpha", C.c_void_p), ("fc1_beta", C.c_void_p), ("fc1_acc_scale", C.c_float),
+                ("fc2_planes", C.c_void_p), ("fc2_alpha", C.c_void_p), ("fc2_beta", C.c_void_p), ("fc2_acc_scale", C.c_float),
+                ("sn1", NeuronCfg), ("sn2", NeuronCfg),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("gemm_workspace", C.c_void_p), ("gemm_workspace_bytes", C.c_int64), ("flags", C.c_int32), ("s1_in", C.c_void_p),
+                ("fc1_digits", C.c_void_p), ("fc1_cscale", C.c_void_p), ("fc2_digits", C.c_void_p), ("fc2_cscale", C.c_void_p),
+                ("emit_next", C.c_void_p), ("emit_sn", NeuronCfg), ("fc2_tiled", C.c_void_p)]
+
+
+class MsMergeDesc(C.Structure):
+    _fields_ = [("spikes", C.c_void_p), ("digits", C.c_void_p), ("cscale", C.c_void_p), ("alpha", C.c_void_p), ("beta", C.c_void_p),
+                ("out", C.c_void_p), ("B", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+                ("N", C.c_int32)]
+
+
+class PointwiseConvDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("imgs", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("Cin", C.c_int32), ("N", C.c_int32), ("stride", C.c_int32), ("OH", C.c_int32), ("OW", C.c_int32)]
+
+
+class PredHeadDesc(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("B", C.c_int32), ("D", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("Cin", C.c_int32),
+                ("sn_pred", NeuronCfg), ("wgt", C.c_void_p), ("bias", C.c_void_p), ("pred", C.c_void_p), ("flow", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("next_spikes", C.c_void_p), ("next_ld", C.c_int32), ("next_z_off", C.c_int32),
+                ("next_pred_off", C.c_int32), ("next_zero_off", C.c_int32), ("next_zero_len", C.c_int32), ("sn_next", NeuronCfg),
+                ("keep_spikes", C.c_void_p)]
+
+
+# The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
+# plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
+# still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
+_i, _i64, _f, _p, _P = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.POINTER
+SIGNATURES = {
+    "sdf_version": (_i, ()), "sdf_switches_reload": (None, ()),
+    "sdf_launch_log": (None, (_i,)), "sdf_launch_log_read": (_i, (_P(LaunchRecord), _i)),
+    "sdf_lif_fwd": (_i, (_p, _p, _p, _i, _i64, _f, _f, _i, _f, _i, _p)),
+    "sdf_psn_fwd": (_i, (_p, _p, _p, _p, _i, _i64, _i, _p)),
+    "sdf_lif_bwd": (_i, (_p, _p, _p, _i, _i64, _i, _f, _f, _i, _f, _i, _i, _f, _p)),
+    "sdf_psn_bwd_workspace_bytes": (_i64, (_i, _i64)),
+    "sdf_psn_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i, _f, _p)),
+    "sdf_plif_fwd": (_i, (_p, _p, _p, _i, _i64, _f, _i, _f, _p)), "sdf_plif_bwd_workspace_bytes": (_i64, (_i, _i64)),
+    "sdf_plif_bwd": (_i, (_p, _p, _p, _p, _p, _p, _i64, _i, _i64, _f, _i, _f, _i, _i, _f, _p)),
+    "sdf_bn_train_workspace_bytes": (_i64, (_i64, _i)),
+    "sdf_bn_train_fwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _f, _f, _p, _i64, _p)),
+    "sdf_bn_train_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p)),
+    "sdf_bn_train_nchw_fwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _f, _f, _p, _i64, _p)),
+    "sdf_bn_train_nchw_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _p, _i64, _p)),
+    "sdf_qk_gate_f32_fwd": (_i, (_p, _p, _p, _i, _i64, _i, _i, _f, _f, _i, _f, _p, _p, _p)),
+    "sdf_qk_gate_bwd_workspace_bytes": (_i64, (_i, _i64, _i)),
+    "sdf_qk_gate_bwd": (_i, (_p, _p, _p, _p, _p, _i, _i64, _i, _i, _f, _f, _i, _f, _i, _i, _f, _p, _p, _p, _p, _p, _i64, _p)),
+    "sdf_qk_gate_plif_f32_fwd": (_i, (_p, _p, _p, _p, _i, _i64, _i, _f, _i, _f, _p)),
+    "sdf_qk_gate_plif_bwd_workspace_bytes": (_i64, (_i, _i64, _i)),
+    "sdf_qk_gate_plif_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i, _f, _i, _f, _i, _i, _f, _p)),
+    "sdf_neuron_fwd": (_i, (_P(NeuronDesc), _p)), "sdf_neuron_multi_fwd": (_i, (_P(NeuronDesc), _i, _p)),
+    "sdf_split_weight_i8x3": (_i, (_p, _p, _p, _i, _i, _p)), "sdf_tile_weight_i8x3": (_i, (_p, _p, _i, _i, _p)),
+    "sdf_spike_gemm_fwd": (_i, (_P(SpikeGemmDesc), _p)),
+    "sdf_spike_gemm_bn_fwd": (_i, (_p, _p, _i, _f, _p, _p, _p, _i64, _i, _i, _p)),
+    "sdf_window_slice_map": (_i, (_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p)),
+    "sdf_rows_gather_fwd": (_i, (_p, _p, _p, _i64, _i, _p)), "sdf_rows_scatter_fwd": (_i, (_p, _p, _p, _i64, _i, _p)),
+    "sdf_window_zsrc_map": (_i, (_p, _i64, _i, _i, _i, _p, _p)), "sdf_qk_attn_workspace_bytes": (_i64, (_i64, _i, _i, _i)),
+    "sdf_qk_attn_fwd": (_i, (_P(QkAttnDesc), _p)), "sdf_qk_attn_is_wide": (_i, (_P(QkAttnDesc),)),
+    "sdf_ms_mlp_workspace_bytes": (_i64, (_i64, _i, _i)), "sdf_ms_mlp_fwd": (_i, (_P(MsMlpDesc), _p)),
+    "sdf_ms_mlp_is_wide": (_i, (_P(MsMlpDesc),)),
+    "sdf_ms_patch_merge_fwd": (_i, (_P(MsMergeDesc), _p)), "sdf_spike_deconv3x3s2_fwd": (_i, (_P(SpikeDeconvDesc), _p)),
+    "sdf_spike_conv2d_fwd": (_i, (_P(SpikeConvDesc), _p)), "sdf_spike_conv2d_multi_fwd": (_i, (_P(SpikeConvDesc), _i, _p)),
+    "sdf_split_weight_bf16": (_i, (_p, _p, _i64, _i, _p)), "sdf_split_weight_f16x2": (_i, (_p, _p, _i64, _f, _p)),
+    "sdf_qk_gate_fwd": (_i, (_p, _p, _p, _i, _i64, _i, _i, _f, _f, _f, _i, _p, _p, _p)),
+    "sdf_qk_gate_strided_fwd": (_i, (_p, _p, _p, _i, _i64, _i, _i64, _i64, _i, _f, _f, _f, _i, _p, _p, _p)),
+    "sdf_head_conv_sn_fwd": (_i, (_P(HeadConvDesc), _p)), "sdf_pointwise_conv_f32_fwd": (_i, (_P(PointwiseConvDesc), _p)),
+    "sdf_deconv_col2im_fwd": (_i, (_p, _p, _p, _p, _i, _i, _i, _i, _p)),
+    "sdf_flow_out_fwd": (_i, (_p, _p, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _p)),
+    "sdf_pred_head_fwd": (_i, (_P(PredHeadDesc), _p)), "sdf_affine_resid_fwd": (_i, (_p, _p, _p, _p, _p, _i64, _i, _i64, _p)),
+    "sdf_win_attn_fwd": (_i, (_P(WinAttnDesc), _p)),
+    "sdf_win_attn_ann_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_ann_bwd": (_i, (_P(WinAttnBwdDesc), _p)),
+    "sdf_ann_attn_block_supported": (_i, (_i, _i, _i)), "sdf_ann_attn_block_fwd": (_i, (_P(AnnAttnBlockDesc), _p)),
+    "sdf_ann_mlp_block_supported": (_i, (_i, _i)), "sdf_ann_mlp_block_fwd": (_i, (_P(AnnMlpBlockDesc), _p)),
+    "sdf_dense_conv3x3_fwd": (_i, (_P(DenseConvDesc), _p)),
+    "sdf_pack_planes": (_i, (_p, _p, _i, _i, _i, _i, _p)), "sdf_unpack_planes": (_i, (_p, _p, _i, _i, _i, _i, _p)),
+    "sdf_pack_planes_up2": (_i, (_p, _p, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _i, _p)),
+    "sdf_pack_planes_zero_up2": (_i, (_p, _p, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _i, _p)),
+    "sdf_dense_linear_fwd": (_i, (_P(DenseLinearDesc), _p)),
+    "sdf_linear_dw_splits": (_i, (_i64, _i, _i, _i)), "sdf_linear_dw_fwd": (_i, (_P(LinearDwDesc), _p)),
+    "sdf_ringed_rows_fwd": (_i, (_p, _p, _i, _i, _i, _i, _p)), "sdf_unring_rows_fwd": (_i, (_p, _p, _p, _i, _i, _i, _i, _p)),
+    "sdf_linear_train_fwd": (_i, (_P(LinearTrainDesc), _p)), "sdf_layer_norm_fwd": (_i, (_p, _p, _p, _p, _i64, _i, _f, _p)),
+}
+
+
 _lib = None
 _PROF = None            # bench.py's per-call profile: a list of (entry point, note, start event, end event) while profile_calls() is active
 _NOTE = {}
@@ -249,25 +356,21 @@ class profile_calls:
         return self._rows
 
 
-class LaunchRecord(C.Structure):
-    _fields_ = [("kernel", C.c_char * 192), ("workgroups", C.c_uint32), ("threads", C.c_uint32), ("lds_bytes", C.c_uint32), ("us", C.c_float)]
-
-
 class launch_log:
     """`with hip.launch_log() as log:` - every kernel launch the library makes inside is timed with HIP events on its own stream
     (sdf_launch_log); afterwards `log.rows` = [(kernel name, workgroups, threads per workgroup, dynamic LDS bytes, microseconds)] in
     launch order.  workgroups x microseconds / 256 = the launch's chip time.  Eager launches only (not under graph capture)."""
 
     def __enter__(self):
-        lib().sdf_launch_log(C.c_int(1))
+        lib().sdf_launch_log(1)
         return self
 
     def __exit__(self, *exc):
         c = _lib
-        c.sdf_launch_log(C.c_int(0))
-        n = c.sdf_launch_log_read(None, C.c_int(0))
+        c.sdf_launch_log(0)
+        n = c.sdf_launch_log_read(None, 0)
         buf = (LaunchRecord * max(n, 1))()
-        c.sdf_launch_log_read(buf, C.c_int(n))
+        c.sdf_launch_log_read(buf, n)
         self.rows = [(buf[i].kernel.decode(errors="replace"), int(buf[i].workgroups), int(buf[i].threads), int(buf[i].lds_bytes), float(buf[i].us))
                      for i in range(n)]
 
@@ -281,18 +384,11 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise SdfError(f"{LIB_PATH} not built - run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(sdformerflow_amd/csrc/build.sh); there is no CPU fallback")
-        _lib = C.CDLL(LIB_PATH)
-        _lib.sdf_version.restype = C.c_int
-        for name in EXPORTS[1:]:
-            getattr(_lib, name).restype = None if name in VOID_EXPORTS else C.c_int
-        _lib.sdf_psn_bwd_workspace_bytes.restype = C.c_int64
-        _lib.sdf_qk_attn_workspace_bytes.restype = C.c_int64
-        _lib.sdf_ms_mlp_workspace_bytes.restype = C.c_int64
-        _lib.sdf_bn_train_workspace_bytes.restype = C.c_int64
-        _lib.sdf_qk_gate_bwd_workspace_bytes.restype = C.c_int64
-        _lib.sdf_win_attn_ann_bwd_workspace_bytes.restype = C.c_int64
-        _lib.sdf_plif_bwd_workspace_bytes.restype = C.c_int64
-        _lib.sdf_qk_gate_plif_bwd_workspace_bytes.restype = C.c_int64
+        cdll = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in SIGNATURES.items():
+            f = getattr(cdll, name)
+            f.restype, f.argtypes = restype, argtypes
+        _lib = cdll
     return _lib
 
 
@@ -316,7 +412,12 @@ def _ptr(t, dtype=None):
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _reset(v_reset):
+    """(soft_reset, v_reset) as the C ABI takes them for a neuron's v_reset (None: soft reset)."""
+    return (1, 0.0) if v_reset is None else (0, float(v_reset))
 
 
 _WS = {}
@@ -360,8 +461,7 @@ def _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, row
     d.alpha, d.beta, d.C, d.inner = _ptr(alpha, torch.float32), _ptr(beta, torch.float32), Cch, inner
     d.add, d.add_st, d.add_period = _ptr(add, torch.float32), add_st, add_period
     d.tau, d.v_th = p.tau, p.v_th
-    d.v_reset = 0.0 if p.v_reset is None else float(p.v_reset)
-    d.soft_reset = 1 if p.v_reset is None else 0
+    d.soft_reset, d.v_reset = _reset(p.v_reset)
     d.psn_w, d.psn_b = _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32)
     return d
 
@@ -378,7 +478,7 @@ def neuron_fwd(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, rowma
 def neuron_multi_fwd(calls):
     """sdf_neuron_multi_fwd: `calls` = argument tuples of neuron_fwd; one launch when they share T and are at most six."""
     descs = (NeuronDesc * len(calls))(*[_neuron_desc(*c) for c in calls])
-    _check(lib().sdf_neuron_multi_fwd(descs, C.c_int(len(calls)), _stream()), "sdf_neuron_multi_fwd")
+    _check(lib().sdf_neuron_multi_fwd(descs, len(calls), _stream()), "sdf_neuron_multi_fwd")
 
 
 def _pad4(*ts):
@@ -402,10 +502,8 @@ def lif_fwd(x, tau=2.0, v_th=1.0, v_reset=None, out_dtype=torch.float32, return_
     T, N = x.shape[0], x[0].numel()
     out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     v = torch.empty(x.shape[1:], dtype=torch.float32, device=x.device) if return_v else None
-    rc = lib().sdf_lif_fwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(out)), C.c_void_p(_ptr(v)),
-                           C.c_int(T), C.c_int64(N), C.c_float(tau), C.c_float(v_th),
-                           C.c_int(1 if v_reset is None else 0), C.c_float(0.0 if v_reset is None else v_reset),
-                           C.c_int(SDF_F32 if out_dtype == torch.float32 else SDF_U8), _stream())
+    rc = lib().sdf_lif_fwd(_ptr(x, torch.float32), _ptr(out), _ptr(v), T, N, tau, v_th, *_reset(v_reset),
+                           SDF_F32 if out_dtype == torch.float32 else SDF_U8, _stream())
     _check(rc, "sdf_lif_fwd")
     return (out, v) if return_v else out
 
@@ -417,10 +515,8 @@ def lif_bwd(x, grad_spike, tau=2.0, v_th=1.0, v_reset=None, detach_reset=True, a
         return _unpad4(lif_bwd(x, g, tau, v_th, v_reset, detach_reset, alpha, kind), info)
     T, N = x.shape[0], x[0].numel()
     gx = torch.empty_like(x)
-    rc = lib().sdf_lif_bwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(g, torch.float32)), C.c_void_p(_ptr(gx)),
-                           C.c_int(T), C.c_int64(N), C.c_int(KIND[kind]), C.c_float(tau), C.c_float(v_th),
-                           C.c_int(1 if v_reset is None else 0), C.c_float(0.0 if v_reset is None else v_reset),
-                           C.c_int(1 if detach_reset else 0), C.c_int(0), C.c_float(alpha), _stream())
+    rc = lib().sdf_lif_bwd(_ptr(x, torch.float32), _ptr(g, torch.float32), _ptr(gx), T, N, KIND[kind], tau, v_th, *_reset(v_reset),
+                           1 if detach_reset else 0, 0, alpha, _stream())
     _check(rc, "sdf_lif_bwd")
     return gx
 
@@ -433,9 +529,7 @@ def plif_fwd(x, k, v_th=1.0, v_reset=None):
         return _unpad4(plif_fwd(x, k, v_th, v_reset), info)
     T, N = x.shape[0], x[0].numel()
     out = torch.empty_like(x)
-    rc = lib().sdf_plif_fwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(out)),
-                            C.c_int(T), C.c_int64(N), C.c_float(v_th), C.c_int(1 if v_reset is None else 0),
-                            C.c_float(0.0 if v_reset is None else v_reset), _stream())
+    rc = lib().sdf_plif_fwd(_ptr(x, torch.float32), _ptr(k, torch.float32), _ptr(out), T, N, v_th, *_reset(v_reset), _stream())
     _check(rc, "sdf_plif_fwd")
     return out
 
@@ -450,13 +544,10 @@ def plif_bwd(x, k, grad_spike, v_th=1.0, v_reset=None, detach_reset=True, alpha=
     T, N = x.shape[0], x[0].numel()
     gx = torch.empty_like(x)
     gk = torch.empty((1,), dtype=torch.float32, device=x.device)
-    nbytes = lib().sdf_plif_bwd_workspace_bytes(C.c_int(T), C.c_int64(N))
+    nbytes = lib().sdf_plif_bwd_workspace_bytes(T, N)
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
-    rc = lib().sdf_plif_bwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(g, torch.float32)),
-                            C.c_void_p(_ptr(gx)), C.c_void_p(_ptr(gk)), C.c_void_p(_ptr(ws)), C.c_int64(nbytes), C.c_int(T),
-                            C.c_int64(N), C.c_float(v_th), C.c_int(1 if v_reset is None else 0),
-                            C.c_float(0.0 if v_reset is None else v_reset), C.c_int(1 if detach_reset else 0), C.c_int(0),
-                            C.c_float(alpha), _stream())
+    rc = lib().sdf_plif_bwd(_ptr(x, torch.float32), _ptr(k, torch.float32), _ptr(g, torch.float32), _ptr(gx), _ptr(gk), _ptr(ws),
+                            nbytes, T, N, v_th, *_reset(v_reset), 1 if detach_reset else 0, 0, alpha, _stream())
     _check(rc, "sdf_plif_bwd")
     return gx, gk
 
@@ -474,13 +565,10 @@ def psn_bwd(x, W, b, grad_spike, alpha=2.0, need_param_grads=True):
     gW = torch.empty((T, T), dtype=torch.float32, device=x.device) if fused else None
     gb = torch.empty((T,), dtype=torch.float32, device=x.device) if fused else None
     gh = torch.empty_like(x) if (need_param_grads and not fused) else None
-    nbytes = lib().sdf_psn_bwd_workspace_bytes(C.c_int(T), C.c_int64(N)) if fused else 0
+    nbytes = lib().sdf_psn_bwd_workspace_bytes(T, N) if fused else 0
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device) if fused else None
-    rc = lib().sdf_psn_bwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(W.contiguous(), torch.float32)),
-                           C.c_void_p(_ptr(b.contiguous().view(-1), torch.float32)), C.c_void_p(_ptr(g, torch.float32)),
-                           C.c_void_p(_ptr(gx)), C.c_void_p(_ptr(gW)), C.c_void_p(_ptr(gb)), C.c_void_p(_ptr(gh)),
-                           C.c_void_p(_ptr(ws)), C.c_int64(nbytes), C.c_int(T), C.c_int64(N), C.c_int(0), C.c_float(alpha),
-                           _stream())
+    rc = lib().sdf_psn_bwd(_ptr(x, torch.float32), _ptr(W.contiguous(), torch.float32), _ptr(b.contiguous().view(-1), torch.float32),
+                           _ptr(g, torch.float32), _ptr(gx), _ptr(gW), _ptr(gb), _ptr(gh), _ptr(ws), nbytes, T, N, 0, alpha, _stream())
     _check(rc, "sdf_psn_bwd")
     if gh is not None:
         gW, gb = gh.view(T, -1) @ x.view(T, -1).t(), gh.view(T, -1).sum(1)
@@ -492,10 +580,8 @@ def psn_fwd(x, W, b, out_dtype=torch.float32):
     x = x.contiguous()
     T, N = x.shape[0], x[0].numel()
     out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    rc = lib().sdf_psn_fwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(W.contiguous(), torch.float32)),
-                           C.c_void_p(_ptr(b.contiguous().view(-1), torch.float32)), C.c_void_p(_ptr(out)),
-                           C.c_int(T), C.c_int64(N), C.c_int(SDF_F32 if out_dtype == torch.float32 else SDF_U8),
-                           _stream())
+    rc = lib().sdf_psn_fwd(_ptr(x, torch.float32), _ptr(W.contiguous(), torch.float32), _ptr(b.contiguous().view(-1), torch.float32),
+                           _ptr(out), T, N, SDF_F32 if out_dtype == torch.float32 else SDF_U8, _stream())
     _check(rc, "sdf_psn_fwd")
     return out
 
@@ -512,12 +598,11 @@ def split_weight(W, nsplit=3):
         mx = float(W.detach().abs().max())
         scale = 2.0 ** (14 - math.floor(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 1.0
         scale = min(max(scale, 2.0 ** -100), 2.0 ** 100)
-        _check(lib().sdf_split_weight_f16x2(C.c_void_p(_ptr(W, torch.float32)), C.c_void_p(planes.data_ptr()),
-                                            C.c_int64(W.numel()), C.c_float(scale), _stream()), "sdf_split_weight_f16x2")
+        _check(lib().sdf_split_weight_f16x2(_ptr(W, torch.float32), planes.data_ptr(), W.numel(), scale, _stream()),
+               "sdf_split_weight_f16x2")
         planes.sdf_acc_scale = 1.0 / scale
         return planes
-    _check(lib().sdf_split_weight_bf16(C.c_void_p(_ptr(W, torch.float32)), C.c_void_p(planes.data_ptr()),
-                                       C.c_int64(W.numel()), C.c_int(nsplit), _stream()), "sdf_split_weight_bf16")
+    _check(lib().sdf_split_weight_bf16(_ptr(W, torch.float32), planes.data_ptr(), W.numel(), nsplit, _stream()), "sdf_split_weight_bf16")
     return planes
 
 
@@ -533,8 +618,8 @@ def split_weight_i8x3(W):
     N, K = W.shape
     planes = torch.empty((3, N, K), dtype=torch.int8, device=W.device)
     scale = torch.empty((N,), dtype=torch.float32, device=W.device)
-    _check(lib().sdf_split_weight_i8x3(C.c_void_p(_ptr(W, torch.float32)), C.c_void_p(planes.data_ptr()), C.c_void_p(scale.data_ptr()),
-                                       C.c_int(N), C.c_int(K), _stream()), "sdf_split_weight_i8x3")
+    _check(lib().sdf_split_weight_i8x3(_ptr(W, torch.float32), planes.data_ptr(), scale.data_ptr(), N, K, _stream()),
+           "sdf_split_weight_i8x3")
     planes.sdf_col_scale = scale
     return planes
 
@@ -576,8 +661,7 @@ def tile_weight_i8x3(planes):
     the shape (3, N, K); attribute `sdf_tiled`): what the small-M convolution streams at full rate (csrc/ms_smallm.hip)."""
     _, N, K = planes.shape
     tiled = torch.empty_like(planes)
-    _check(lib().sdf_tile_weight_i8x3(C.c_void_p(_ptr(planes, torch.int8)), C.c_void_p(tiled.data_ptr()), C.c_int(N), C.c_int(K), _stream()),
-           "sdf_tile_weight_i8x3")
+    _check(lib().sdf_tile_weight_i8x3(_ptr(planes, torch.int8), tiled.data_ptr(), N, K, _stream()), "sdf_tile_weight_i8x3")
     tiled.sdf_col_scale = planes.sdf_col_scale
     tiled.sdf_tiled = True
     return tiled
@@ -661,7 +745,7 @@ def spike_gemm_sn(A, Wp, out_spike, N, K, T, pos_count, pos_inner, pos_ostride, 
     d.lda, d.ldo, d.nsplit, d.acc_scale = (K if lda is None else lda), N, Wp.shape[0], _acc_scale(Wp)
     d.alpha, d.beta = _ptr(alpha, torch.float32), _ptr(beta, torch.float32)
     d.sn_T, d.sn_kind, d.tau, d.v_th = T, KIND[p.kind], p.tau, p.v_th
-    d.v_reset, d.soft_reset = (0.0 if p.v_reset is None else float(p.v_reset)), (1 if p.v_reset is None else 0)
+    d.soft_reset, d.v_reset = _reset(p.v_reset)
     d.psn_w, d.psn_b = _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32)
     d.pos_count, d.pos_inner, d.pos_ostride, d.t_stride = pos_count, pos_inner, pos_ostride, t_stride
     d.add, d.add_prows = _ptr(add, torch.float32), add_prows
@@ -673,41 +757,12 @@ def spike_gemm_sn(A, Wp, out_spike, N, K, T, pos_count, pos_inner, pos_ostride, 
 def qk_gate(q, k, e, Tq, rows, Cch, p: NeuronParams, ldq=None, ldk=None):
     """sdf_qk_gate_strided_fwd on u8 spike tensors laid out (Tq, rows, C); q / k rows may be ldq / ldk bytes apart
     (the halves of a fused q|k GEMM output)."""
-    rc = lib().sdf_qk_gate_strided_fwd(C.c_void_p(_ptr(q, torch.uint8)), C.c_void_p(_ptr(k, torch.uint8)),
-                               C.c_void_p(_ptr(e, torch.uint8)), C.c_int(Tq), C.c_int64(rows), C.c_int(Cch),
-                               C.c_int64(Cch if ldq is None else ldq), C.c_int64(Cch if ldk is None else ldk),
-                               C.c_int(KIND[p.kind]), C.c_float(p.tau), C.c_float(p.v_th),
-                               C.c_float(0.0 if p.v_reset is None else p.v_reset),
-                               C.c_int(1 if p.v_reset is None else 0),
-                               C.c_void_p(_ptr(p.psn_w, torch.float32)), C.c_void_p(_ptr(p.psn_b, torch.float32)),
-                               _stream())
+    soft_reset, v_reset = _reset(p.v_reset)
+    rc = lib().sdf_qk_gate_strided_fwd(_ptr(q, torch.uint8), _ptr(k, torch.uint8), _ptr(e, torch.uint8), Tq, rows, Cch,
+                                       Cch if ldq is None else ldq, Cch if ldk is None else ldk, KIND[p.kind], p.tau, p.v_th,
+                                       v_reset, soft_reset, _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32), _stream())
     _check(rc, "sdf_qk_gate_strided_fwd")
     return e
-
-
-class NeuronCfg(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("tau", C.c_float), ("v_th", C.c_float), ("v_reset", C.c_float),
-                ("soft_reset", C.c_int32), ("psn_w", C.c_void_p), ("psn_b", C.c_void_p)]
-
-
-class QkAttnDesc(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("slice_map", C.c_void_p), ("B_", C.c_int64), ("x_rows", C.c_int64),
-                ("Tq", C.c_int32), ("N1", C.c_int32), ("C", C.c_int32), ("nH", C.c_int32), ("nsplit", C.c_int32),
-                ("qk_planes", C.c_void_p), ("qk_alpha", C.c_void_p), ("qk_beta", C.c_void_p), ("qk_add", C.c_void_p),
-                ("qk_acc_scale", C.c_float),
-                ("q_planes", C.c_void_p), ("q_alpha", C.c_void_p), ("q_beta", C.c_void_p), ("q_acc_scale", C.c_float),
-                ("k_planes", C.c_void_p), ("k_alpha", C.c_void_p), ("k_beta", C.c_void_p), ("k_add", C.c_void_p),
-                ("k_acc_scale", C.c_float),
-                ("p_planes", C.c_void_p), ("p_bias", C.c_void_p), ("p_alpha", C.c_void_p), ("p_beta", C.c_void_p),
-                ("p_acc_scale", C.c_float),
-                ("sn_proj", NeuronCfg), ("sn_q", NeuronCfg), ("sn_k", NeuronCfg), ("sn2_q", NeuronCfg),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-                ("gemm_workspace", C.c_void_p), ("gemm_workspace_bytes", C.c_int64), ("flags", C.c_int32),
-                ("x_src", C.c_void_p), ("xB", C.c_int32), ("xD", C.c_int32), ("xHW", C.c_int64), ("emit_s1", C.c_void_p),
-                ("emit_sn", NeuronCfg),
-                ("qk_digits", C.c_void_p), ("qk_cscale", C.c_void_p), ("q_digits", C.c_void_p), ("q_cscale", C.c_void_p),
-                ("k_digits", C.c_void_p), ("k_cscale", C.c_void_p), ("p_digits", C.c_void_p), ("p_cscale", C.c_void_p),
-                ("rep_windows", C.c_int32)]
 
 
 SDF_QK_KEEP_SPIKES, SDF_QK_FOUR_LAUNCHES, SDF_QK_NARROW = 1, 2, 4
@@ -715,7 +770,7 @@ SDF_QK_KEEP_SPIKES, SDF_QK_FOUR_LAUNCHES, SDF_QK_NARROW = 1, 2, 4
 
 def _ncfg(c, p: NeuronParams):
     c.kind, c.tau, c.v_th = KIND[p.kind], p.tau, p.v_th
-    c.v_reset, c.soft_reset = (0.0 if p.v_reset is None else float(p.v_reset)), (1 if p.v_reset is None else 0)
+    c.soft_reset, c.v_reset = _reset(p.v_reset)
     c.psn_w, c.psn_b = _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32)
 
 
@@ -728,9 +783,8 @@ def window_slice_map(B, D, H, W, ws, ss, device):
     B_ = B * -(-D // Wd) * -(-H // Wh) * -(-W // Ww)
     m = torch.empty((B_ * Wd * Wh * Ww,), dtype=torch.int32, device=device)
     nw = C.c_int64(0)
-    _check(lib().sdf_window_slice_map(C.c_void_p(m.data_ptr()), C.c_int(B), C.c_int(D), C.c_int(H), C.c_int(W), C.c_int(Wd),
-                                      C.c_int(Wh), C.c_int(Ww), C.c_int(ss[0]), C.c_int(ss[1]), C.c_int(ss[2]), C.byref(nw),
-                                      _stream()), "sdf_window_slice_map")
+    _check(lib().sdf_window_slice_map(m.data_ptr(), B, D, H, W, Wd, Wh, Ww, ss[0], ss[1], ss[2], C.byref(nw), _stream()),
+           "sdf_window_slice_map")
     assert nw.value == B_
     return m, B_
 
@@ -774,8 +828,7 @@ def window_zsrc_map(slice_map, B_, Tq, N1, nH, x_rows):
     """sdf_window_zsrc_map: per row of x the byte offset of its gated spikes in E behind the reference's head scramble - what the
     wide-stage projection (csrc/ms_wide.hip) gathers its operand through.  int32 (x_rows,)."""
     z = torch.zeros((x_rows,), dtype=torch.int32, device=slice_map.device)
-    _check(lib().sdf_window_zsrc_map(C.c_void_p(slice_map.data_ptr()), C.c_int64(B_), C.c_int(Tq), C.c_int(N1), C.c_int(nH),
-                                     C.c_void_p(z.data_ptr()), _stream()), "sdf_window_zsrc_map")
+    _check(lib().sdf_window_zsrc_map(slice_map.data_ptr(), B_, Tq, N1, nH, z.data_ptr(), _stream()), "sdf_window_zsrc_map")
     return z
 
 
@@ -804,7 +857,7 @@ def qk_attn(x, slice_map, B_, Tq, N1, nH, p_lin, sn_proj, sn_q, sn_k, sn2_q, qk=
     d.p_acc_scale = _acc_scale(p_lin.Wp)
     for c, p in ((d.sn_proj, sn_proj), (d.sn_q, sn_q), (d.sn_k, sn_k), (d.sn2_q, sn2_q)):
         _ncfg(c, p)
-    nbytes = lib().sdf_qk_attn_workspace_bytes(C.c_int64(B_), C.c_int(Tq), C.c_int(N1), C.c_int(Cc))
+    nbytes = lib().sdf_qk_attn_workspace_bytes(B_, Tq, N1, Cc)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)          # intermediates: caller-owned, caching allocator
     d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
     gws = workspace(x.device)
@@ -838,31 +891,13 @@ def qk_attn(x, slice_map, B_, Tq, N1, nH, p_lin, sn_proj, sn_q, sn_k, sn2_q, qk=
     return x
 
 
-class MsMlpDesc(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("B", C.c_int32), ("D", C.c_int32), ("HW", C.c_int64), ("C", C.c_int32), ("Ch", C.c_int32),
-                ("nsplit", C.c_int32),
-                ("fc1_planes", C.c_void_p), ("fc1_alpha", C.c_void_p), ("fc1_beta", C.c_void_p), ("fc1_acc_scale", C.c_float),
-                ("fc2_planes", C.c_void_p), ("fc2_alpha", C.c_void_p), ("fc2_beta", C.c_void_p), ("fc2_acc_scale", C.c_float),
-                ("sn1", NeuronCfg), ("sn2", NeuronCfg),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-                ("gemm_workspace", C.c_void_p), ("gemm_workspace_bytes", C.c_int64), ("flags", C.c_int32), ("s1_in", C.c_void_p),
-                ("fc1_digits", C.c_void_p), ("fc1_cscale", C.c_void_p), ("fc2_digits", C.c_void_p), ("fc2_cscale", C.c_void_p),
-                ("emit_next", C.c_void_p), ("emit_sn", NeuronCfg), ("fc2_tiled", C.c_void_p)]
-
-
-class MsMergeDesc(C.Structure):
-    _fields_ = [("spikes", C.c_void_p), ("digits", C.c_void_p), ("cscale", C.c_void_p), ("alpha", C.c_void_p), ("beta", C.c_void_p),
-                ("out", C.c_void_p), ("B", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
-                ("N", C.c_int32)]
-
-
 MLP_KEEP_SPIKES, MLP_THREE_LAUNCHES, MLP_NARROW = 1, 2, 4
 
 
 def ms_mlp_workspace(x, Ch):
     """The caller-owned workspace of ms_mlp for x (B,D,H,W,C): u8, SN1's spikes [tokens][C] at its head (what qk_attn's `emit` fills)."""
     B, D, H, W, Cc = x.shape
-    nbytes = lib().sdf_ms_mlp_workspace_bytes(C.c_int64(B * D * H * W), C.c_int(Cc), C.c_int(Ch))
+    nbytes = lib().sdf_ms_mlp_workspace_bytes(B * D * H * W, Cc, Ch)
     return torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
 
 
@@ -956,13 +991,11 @@ def bn_train_fwd(x2, weight, bias, running_mean, running_var, momentum, eps):
     R, Cc = x2.shape
     y = torch.empty_like(x2)
     mean, invstd = torch.empty(Cc, dtype=torch.float32, device=x2.device), torch.empty(Cc, dtype=torch.float32, device=x2.device)
-    nbytes = lib().sdf_bn_train_workspace_bytes(C.c_int64(R), C.c_int(Cc))
+    nbytes = lib().sdf_bn_train_workspace_bytes(R, Cc)
     ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x2.device)
-    rc = lib().sdf_bn_train_fwd(C.c_void_p(_ptr(x2, torch.float32)), C.c_void_p(_ptr(weight, torch.float32)),
-                                C.c_void_p(_ptr(bias, torch.float32)), C.c_void_p(_ptr(y)), C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(invstd)),
-                                C.c_void_p(_ptr(running_mean, torch.float32)), C.c_void_p(_ptr(running_var, torch.float32)),
-                                C.c_int64(R), C.c_int(Cc), C.c_float(eps), C.c_float(momentum), C.c_void_p(ws.data_ptr()),
-                                C.c_int64(nbytes), _stream())
+    rc = lib().sdf_bn_train_fwd(_ptr(x2, torch.float32), _ptr(weight, torch.float32), _ptr(bias, torch.float32), _ptr(y), _ptr(mean),
+                                _ptr(invstd), _ptr(running_mean, torch.float32), _ptr(running_var, torch.float32), R, Cc, eps, momentum,
+                                ws.data_ptr(), nbytes, _stream())
     _check(rc, "sdf_bn_train_fwd")
     return y, mean, invstd
 
@@ -972,12 +1005,10 @@ def bn_train_bwd(x2, grad_y, weight, mean, invstd):
     R, Cc = x2.shape
     gx = torch.empty_like(x2)
     gw, gb = torch.empty(Cc, dtype=torch.float32, device=x2.device), torch.empty(Cc, dtype=torch.float32, device=x2.device)
-    nbytes = lib().sdf_bn_train_workspace_bytes(C.c_int64(R), C.c_int(Cc))
+    nbytes = lib().sdf_bn_train_workspace_bytes(R, Cc)
     ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x2.device)
-    rc = lib().sdf_bn_train_bwd(C.c_void_p(_ptr(x2, torch.float32)), C.c_void_p(_ptr(grad_y, torch.float32)),
-                                C.c_void_p(_ptr(weight, torch.float32)), C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(invstd)),
-                                C.c_void_p(_ptr(gx)), C.c_void_p(_ptr(gw)), C.c_void_p(_ptr(gb)), C.c_int64(R), C.c_int(Cc),
-                                C.c_void_p(ws.data_ptr()), C.c_int64(nbytes), _stream())
+    rc = lib().sdf_bn_train_bwd(_ptr(x2, torch.float32), _ptr(grad_y, torch.float32), _ptr(weight, torch.float32), _ptr(mean),
+                                _ptr(invstd), _ptr(gx), _ptr(gw), _ptr(gb), R, Cc, ws.data_ptr(), nbytes, _stream())
     _check(rc, "sdf_bn_train_bwd")
     return gx, gw, gb
 
@@ -991,13 +1022,11 @@ def bn_train_nchw_fwd(x, weight, bias, running_mean, running_var, momentum, eps)
     N, Cc, H, W = x.shape
     y = torch.empty_like(x)
     mean, invstd = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
-    nbytes = lib().sdf_bn_train_workspace_bytes(C.c_int64(N * H * W), C.c_int((Cc + 3) // 4 * 4))
+    nbytes = lib().sdf_bn_train_workspace_bytes(N * H * W, (Cc + 3) // 4 * 4)
     ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
-    rc = lib().sdf_bn_train_nchw_fwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(weight, torch.float32)),
-                                     C.c_void_p(_ptr(bias, torch.float32)), C.c_void_p(_ptr(y)), C.c_void_p(_ptr(mean)),
-                                     C.c_void_p(_ptr(invstd)), C.c_void_p(_ptr(running_mean, torch.float32)),
-                                     C.c_void_p(_ptr(running_var, torch.float32)), C.c_int64(N), C.c_int(Cc), C.c_int(H * W),
-                                     C.c_float(eps), C.c_float(momentum), C.c_void_p(ws.data_ptr()), C.c_int64(nbytes), _stream())
+    rc = lib().sdf_bn_train_nchw_fwd(_ptr(x, torch.float32), _ptr(weight, torch.float32), _ptr(bias, torch.float32), _ptr(y),
+                                     _ptr(mean), _ptr(invstd), _ptr(running_mean, torch.float32), _ptr(running_var, torch.float32),
+                                     N, Cc, H * W, eps, momentum, ws.data_ptr(), nbytes, _stream())
     _check(rc, "sdf_bn_train_nchw_fwd")
     return y, mean, invstd
 
@@ -1006,12 +1035,10 @@ def bn_train_nchw_bwd(x, grad_y, weight, mean, invstd):
     N, Cc, H, W = x.shape
     gx = torch.empty_like(x)
     gw, gb = torch.empty(Cc, dtype=torch.float32, device=x.device), torch.empty(Cc, dtype=torch.float32, device=x.device)
-    nbytes = lib().sdf_bn_train_workspace_bytes(C.c_int64(N * H * W), C.c_int((Cc + 3) // 4 * 4))
+    nbytes = lib().sdf_bn_train_workspace_bytes(N * H * W, (Cc + 3) // 4 * 4)
     ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
-    rc = lib().sdf_bn_train_nchw_bwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(grad_y, torch.float32)),
-                                     C.c_void_p(_ptr(weight, torch.float32)), C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(invstd)),
-                                     C.c_void_p(_ptr(gx)), C.c_void_p(_ptr(gw)), C.c_void_p(_ptr(gb)), C.c_int64(N), C.c_int(Cc),
-                                     C.c_int(H * W), C.c_void_p(ws.data_ptr()), C.c_int64(nbytes), _stream())
+    rc = lib().sdf_bn_train_nchw_bwd(_ptr(x, torch.float32), _ptr(grad_y, torch.float32), _ptr(weight, torch.float32), _ptr(mean),
+                                     _ptr(invstd), _ptr(gx), _ptr(gw), _ptr(gb), N, Cc, H * W, ws.data_ptr(), nbytes, _stream())
     _check(rc, "sdf_bn_train_nchw_bwd")
     return gx, gw, gb
 
@@ -1019,16 +1046,16 @@ def bn_train_nchw_bwd(x, grad_y, weight, mean, invstd):
 def rows_gather(x2, row_map):
     """sdf_rows_gather_fwd: (rows, C) fp32 -> (len(map), C), zero rows where the map is negative."""
     out = torch.empty((row_map.numel(), x2.shape[1]), dtype=torch.float32, device=x2.device)
-    _check(lib().sdf_rows_gather_fwd(C.c_void_p(_ptr(x2, torch.float32)), C.c_void_p(_ptr(row_map, torch.int32)), C.c_void_p(_ptr(out)),
-                                     C.c_int64(row_map.numel()), C.c_int(x2.shape[1]), _stream()), "sdf_rows_gather_fwd")
+    _check(lib().sdf_rows_gather_fwd(_ptr(x2, torch.float32), _ptr(row_map, torch.int32), _ptr(out),
+                                     row_map.numel(), x2.shape[1], _stream()), "sdf_rows_gather_fwd")
     return out
 
 
 def rows_scatter(y2, row_map, rows):
     """sdf_rows_scatter_fwd: (len(map), C) fp32 -> (rows, C): out[map[i]] = y2[i]; rows nobody names are zero."""
     out = torch.zeros((rows, y2.shape[1]), dtype=torch.float32, device=y2.device)
-    _check(lib().sdf_rows_scatter_fwd(C.c_void_p(_ptr(y2, torch.float32)), C.c_void_p(_ptr(row_map, torch.int32)), C.c_void_p(_ptr(out)),
-                                      C.c_int64(row_map.numel()), C.c_int(y2.shape[1]), _stream()), "sdf_rows_scatter_fwd")
+    _check(lib().sdf_rows_scatter_fwd(_ptr(y2, torch.float32), _ptr(row_map, torch.int32), _ptr(out),
+                                      row_map.numel(), y2.shape[1], _stream()), "sdf_rows_scatter_fwd")
     return out
 
 
@@ -1037,11 +1064,8 @@ def qk_gate_f32(q, k, p: NeuronParams):
     q, k = q.contiguous(), k.contiguous()
     Tq, Cc = q.shape[0], q.shape[-1]
     e = torch.empty_like(k)
-    rc = lib().sdf_qk_gate_f32_fwd(C.c_void_p(_ptr(q, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(e)),
-                                   C.c_int(Tq), C.c_int64(q[0].numel() // Cc), C.c_int(Cc), C.c_int(KIND[p.kind]), C.c_float(p.tau),
-                                   C.c_float(p.v_th), C.c_int(1 if p.v_reset is None else 0),
-                                   C.c_float(0.0 if p.v_reset is None else p.v_reset), C.c_void_p(_ptr(p.psn_w, torch.float32)),
-                                   C.c_void_p(_ptr(p.psn_b, torch.float32)), _stream())
+    rc = lib().sdf_qk_gate_f32_fwd(_ptr(q, torch.float32), _ptr(k, torch.float32), _ptr(e), Tq, q[0].numel() // Cc, Cc, KIND[p.kind],
+                                   p.tau, p.v_th, *_reset(p.v_reset), _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32), _stream())
     _check(rc, "sdf_qk_gate_f32_fwd")
     return e
 
@@ -1055,14 +1079,11 @@ def qk_gate_bwd(q, k, grad_e, p: NeuronParams, detach_reset=True, alpha=2.0):
     psn = p.kind == "psn"
     gW = torch.empty((Tq, Tq), dtype=torch.float32, device=q.device) if psn else None
     gb = torch.empty((Tq,), dtype=torch.float32, device=q.device) if psn else None
-    nbytes = lib().sdf_qk_gate_bwd_workspace_bytes(C.c_int(Tq), C.c_int64(rows), C.c_int(Cc)) if psn else 0
+    nbytes = lib().sdf_qk_gate_bwd_workspace_bytes(Tq, rows, Cc) if psn else 0
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=q.device) if psn else None
-    rc = lib().sdf_qk_gate_bwd(C.c_void_p(_ptr(q, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(g, torch.float32)),
-                               C.c_void_p(_ptr(gq)), C.c_void_p(_ptr(gk)), C.c_int(Tq), C.c_int64(rows), C.c_int(Cc),
-                               C.c_int(KIND[p.kind]), C.c_float(p.tau), C.c_float(p.v_th), C.c_int(1 if p.v_reset is None else 0),
-                               C.c_float(0.0 if p.v_reset is None else p.v_reset), C.c_int(1 if detach_reset else 0), C.c_int(0),
-                               C.c_float(alpha), C.c_void_p(_ptr(p.psn_w, torch.float32)), C.c_void_p(_ptr(p.psn_b, torch.float32)),
-                               C.c_void_p(_ptr(gW)), C.c_void_p(_ptr(gb)), C.c_void_p(_ptr(ws)), C.c_int64(nbytes), _stream())
+    rc = lib().sdf_qk_gate_bwd(_ptr(q, torch.float32), _ptr(k, torch.float32), _ptr(g, torch.float32), _ptr(gq), _ptr(gk), Tq, rows, Cc,
+                               KIND[p.kind], p.tau, p.v_th, *_reset(p.v_reset), 1 if detach_reset else 0, 0, alpha,
+                               _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32), _ptr(gW), _ptr(gb), _ptr(ws), nbytes, _stream())
     _check(rc, "sdf_qk_gate_bwd")
     return gq, gk, gW, gb
 
@@ -1072,10 +1093,8 @@ def qk_gate_plif_f32(q, k, plif_k, v_th=1.0, v_reset=None):
     q, k = q.contiguous(), k.contiguous()
     Tq, Cc = q.shape[0], q.shape[-1]
     e = torch.empty_like(k)
-    rc = lib().sdf_qk_gate_plif_f32_fwd(C.c_void_p(_ptr(q, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(e)),
-                                        C.c_void_p(_ptr(plif_k, torch.float32)), C.c_int(Tq), C.c_int64(q[0].numel() // Cc), C.c_int(Cc),
-                                        C.c_float(v_th), C.c_int(1 if v_reset is None else 0),
-                                        C.c_float(0.0 if v_reset is None else v_reset), _stream())
+    rc = lib().sdf_qk_gate_plif_f32_fwd(_ptr(q, torch.float32), _ptr(k, torch.float32), _ptr(e), _ptr(plif_k, torch.float32), Tq,
+                                        q[0].numel() // Cc, Cc, v_th, *_reset(v_reset), _stream())
     _check(rc, "sdf_qk_gate_plif_f32_fwd")
     return e
 
@@ -1087,13 +1106,11 @@ def qk_gate_plif_bwd(q, k, grad_e, plif_k, v_th=1.0, v_reset=None, detach_reset=
     rows = q[0].numel() // Cc
     gq, gk = torch.empty_like(q), torch.empty_like(k)
     gpk = torch.empty((1,), dtype=torch.float32, device=q.device)
-    nbytes = lib().sdf_qk_gate_plif_bwd_workspace_bytes(C.c_int(Tq), C.c_int64(rows), C.c_int(Cc))
+    nbytes = lib().sdf_qk_gate_plif_bwd_workspace_bytes(Tq, rows, Cc)
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=q.device)
-    rc = lib().sdf_qk_gate_plif_bwd(C.c_void_p(_ptr(q, torch.float32)), C.c_void_p(_ptr(k, torch.float32)), C.c_void_p(_ptr(g, torch.float32)),
-                                    C.c_void_p(_ptr(gq)), C.c_void_p(_ptr(gk)), C.c_void_p(_ptr(plif_k, torch.float32)), C.c_void_p(_ptr(gpk)),
-                                    C.c_void_p(_ptr(ws)), C.c_int64(nbytes), C.c_int(Tq), C.c_int64(rows), C.c_int(Cc), C.c_float(v_th),
-                                    C.c_int(1 if v_reset is None else 0), C.c_float(0.0 if v_reset is None else v_reset),
-                                    C.c_int(1 if detach_reset else 0), C.c_int(0), C.c_float(alpha), _stream())
+    rc = lib().sdf_qk_gate_plif_bwd(_ptr(q, torch.float32), _ptr(k, torch.float32), _ptr(g, torch.float32), _ptr(gq), _ptr(gk),
+                                    _ptr(plif_k, torch.float32), _ptr(gpk), _ptr(ws), nbytes, Tq, rows, Cc, v_th, *_reset(v_reset),
+                                    1 if detach_reset else 0, 0, alpha, _stream())
     _check(rc, "sdf_qk_gate_plif_bwd")
     return gq, gk, gpk
 
@@ -1102,10 +1119,8 @@ def affine_resid(x, alpha, beta, Cch, inner, resid=None, out=None):
     """out = fmaf(x, alpha[c], beta[c]) (+ resid) with c = (i // inner) % C (sdf_affine_resid_fwd)."""
     if out is None:
         out = torch.empty_like(x)
-    rc = lib().sdf_affine_resid_fwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(alpha, torch.float32)),
-                                    C.c_void_p(_ptr(beta, torch.float32)), C.c_void_p(_ptr(resid, torch.float32)),
-                                    C.c_void_p(_ptr(out, torch.float32)), C.c_int64(x.numel()), C.c_int(Cch),
-                                    C.c_int64(inner), _stream())
+    rc = lib().sdf_affine_resid_fwd(_ptr(x, torch.float32), _ptr(alpha, torch.float32), _ptr(beta, torch.float32),
+                                    _ptr(resid, torch.float32), _ptr(out, torch.float32), x.numel(), Cch, inner, _stream())
     _check(rc, "sdf_affine_resid_fwd")
     return out
 
@@ -1134,7 +1149,7 @@ def win_attn_ann_bwd(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout):
     d_pad = torch.empty((C3,), dtype=torch.float32, device=dev)
     d_scale = torch.empty((nH,), dtype=torch.float32, device=dev)
     d_bias = torch.empty((nH, N, N), dtype=torch.float32, device=dev)
-    nbytes = lib().sdf_win_attn_ann_bwd_workspace_bytes(C.c_int(B_), C.c_int(nH), C.c_int(N))
+    nbytes = lib().sdf_win_attn_ann_bwd_workspace_bytes(B_, nH, N)
     ws = torch.empty((max(nbytes, 256) // 4,), dtype=torch.float32, device=dev)
     d = WinAttnBwdDesc()
     d.qkv, d.row_map, d.pad_qkv = _ptr(qkv, torch.float32), _ptr(row_map, torch.int32), _ptr(pad_qkv, torch.float32)
@@ -1264,8 +1279,7 @@ def pack_planes(x):
     x = x.contiguous()
     imgs, Cc, H, W = x.shape
     planes = torch.empty((imgs, -(-Cc // 16), H, W, 32), dtype=torch.float16, device=x.device)
-    _check(lib().sdf_pack_planes(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(planes.data_ptr()), C.c_int(imgs), C.c_int(Cc),
-                                 C.c_int(H), C.c_int(W), _stream()), "sdf_pack_planes")
+    _check(lib().sdf_pack_planes(_ptr(x, torch.float32), planes.data_ptr(), imgs, Cc, H, W, _stream()), "sdf_pack_planes")
     return planes
 
 
@@ -1273,8 +1287,7 @@ def unpack_planes(planes, Cc):
     """activation planes -> (imgs, Cc, H, W) fp32 (sdf_unpack_planes)."""
     imgs, nch, H, W, _ = planes.shape
     x = torch.empty((imgs, Cc, H, W), dtype=torch.float32, device=planes.device)
-    _check(lib().sdf_unpack_planes(C.c_void_p(_ptr(planes, torch.float16)), C.c_void_p(x.data_ptr()), C.c_int(imgs), C.c_int(Cc),
-                                   C.c_int(H), C.c_int(W), _stream()), "sdf_unpack_planes")
+    _check(lib().sdf_unpack_planes(_ptr(planes, torch.float16), x.data_ptr(), imgs, Cc, H, W, _stream()), "sdf_unpack_planes")
     return x
 
 
@@ -1288,9 +1301,8 @@ def pack_planes_up2(x, planes=None, rec0=0):
     if tuple(planes.shape[2:]) != (2 * h, 2 * w, 32) or planes.shape[0] != imgs or not planes.is_contiguous():
         raise SdfError("planes must be a contiguous (imgs, R, 2h, 2w, 32) tensor")
     sn, sc, sh, sw = x.stride()
-    _check(lib().sdf_pack_planes_up2(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(planes, torch.float16)), C.c_int(imgs),
-                                     C.c_int(Cc), C.c_int(h), C.c_int(w), C.c_int64(sn), C.c_int64(sc), C.c_int64(sh), C.c_int64(sw),
-                                     C.c_int(rec0), C.c_int(planes.shape[1]), _stream()), "sdf_pack_planes_up2")
+    _check(lib().sdf_pack_planes_up2(_ptr(x, torch.float32), _ptr(planes, torch.float16), imgs, Cc, h, w, sn, sc, sh, sw, rec0,
+                                     planes.shape[1], _stream()), "sdf_pack_planes_up2")
     return planes
 
 
@@ -1302,9 +1314,8 @@ def pack_planes_zero_up2(x, planes, rec0=0):
     if tuple(planes.shape[2:]) != (2 * h, 2 * w, 32) or planes.shape[0] != imgs or not planes.is_contiguous():
         raise SdfError("planes must be a contiguous (imgs, R, 2h, 2w, 32) tensor")
     sn, sc, sh, sw_ = x.stride()
-    _check(lib().sdf_pack_planes_zero_up2(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(planes, torch.float16)), C.c_int(imgs),
-                                          C.c_int(Cc), C.c_int(h), C.c_int(w), C.c_int64(sn), C.c_int64(sc), C.c_int64(sh), C.c_int64(sw_),
-                                          C.c_int(rec0), C.c_int(planes.shape[1]), _stream()), "sdf_pack_planes_zero_up2")
+    _check(lib().sdf_pack_planes_zero_up2(_ptr(x, torch.float32), _ptr(planes, torch.float16), imgs, Cc, h, w, sn, sc, sh, sw_, rec0,
+                                          planes.shape[1], _stream()), "sdf_pack_planes_zero_up2")
     return planes
 
 
@@ -1459,7 +1470,7 @@ def linear_dw(dy, x, conv_wp=0):
     K = 9 * Cx if conv_wp else Cx
     if x.shape[0] != M or not dy.is_contiguous() or not x.is_contiguous():
         raise SdfError("linear_dw needs contiguous (M, N) and (M, K) operands")
-    ns = lib().sdf_linear_dw_splits(C.c_int64(M), C.c_int(N), C.c_int(K), C.c_int(Cx if conv_wp else 0))
+    ns = lib().sdf_linear_dw_splits(M, N, K, Cx if conv_wp else 0)
     if ns < 1:
         raise SdfError(f"sdf_linear_dw_fwd: unsupported shape M={M} N={N} K={K} (N and K must be multiples of 96)")
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
@@ -1483,8 +1494,7 @@ def ringed_rows(t):
     if not t.is_contiguous():
         raise SdfError("ringed rows need a contiguous (imgs, C, H, W) tensor")
     out = torch.empty((imgs * (H + 2) * (W + 2), Cc), dtype=torch.float32, device=t.device)
-    _check(lib().sdf_ringed_rows_fwd(C.c_void_p(_ptr(t, torch.float32)), C.c_void_p(out.data_ptr()), C.c_int(imgs), C.c_int(Cc), C.c_int(H),
-                                     C.c_int(W), _stream()), "sdf_ringed_rows_fwd")
+    _check(lib().sdf_ringed_rows_fwd(_ptr(t, torch.float32), out.data_ptr(), imgs, Cc, H, W, _stream()), "sdf_ringed_rows_fwd")
     return out
 
 
@@ -1493,8 +1503,8 @@ def unring_rows(rows, imgs, Cc, H, W, bias=None):
     if tuple(rows.shape) != (imgs * (H + 2) * (W + 2), Cc) or not rows.is_contiguous():
         raise SdfError("unring_rows: shape does not match the ringed grid")
     out = torch.empty((imgs, Cc, H, W), dtype=torch.float32, device=rows.device)
-    _check(lib().sdf_unring_rows_fwd(C.c_void_p(_ptr(rows, torch.float32)), C.c_void_p(_ptr(bias, torch.float32)), C.c_void_p(out.data_ptr()),
-                                     C.c_int(imgs), C.c_int(Cc), C.c_int(H), C.c_int(W), _stream()), "sdf_unring_rows_fwd")
+    _check(lib().sdf_unring_rows_fwd(_ptr(rows, torch.float32), _ptr(bias, torch.float32), out.data_ptr(),
+                                     imgs, Cc, H, W, _stream()), "sdf_unring_rows_fwd")
     return out
 
 
@@ -1529,9 +1539,8 @@ def layer_norm(x, gamma, beta, eps):
     if not x.is_contiguous():
         raise SdfError("layer_norm needs a contiguous tensor")
     out = torch.empty_like(x)
-    _check(lib().sdf_layer_norm_fwd(C.c_void_p(_ptr(x, torch.float32)), C.c_void_p(_ptr(gamma, torch.float32)), C.c_void_p(_ptr(beta, torch.float32)),
-                                    C.c_void_p(out.data_ptr()), C.c_int64(x.numel() // Cc), C.c_int(Cc), C.c_float(eps), _stream()),
-           "sdf_layer_norm_fwd")
+    _check(lib().sdf_layer_norm_fwd(_ptr(x, torch.float32), _ptr(gamma, torch.float32), _ptr(beta, torch.float32), out.data_ptr(),
+                                    x.numel() // Cc, Cc, eps, _stream()), "sdf_layer_norm_fwd")
     return out
 
 
@@ -1587,7 +1596,7 @@ def spike_conv2d_multi(x, classes, imgs, H, W, Cin, OH, OW, out, alpha=None, bet
         C.memmove(C.byref(arr, i * C.sizeof(SpikeConvDesc)), C.byref(d), C.sizeof(SpikeConvDesc))
         flop += 2 * d.g.M * d.g.N * d.g.K
     _note(flop=flop, shape=(int(arr[0].g.M), int(arr[0].g.N), len(classes)))
-    _check(lib().sdf_spike_conv2d_multi_fwd(arr, C.c_int(len(classes)), _stream()), "sdf_spike_conv2d_multi_fwd")
+    _check(lib().sdf_spike_conv2d_multi_fwd(arr, len(classes), _stream()), "sdf_spike_conv2d_multi_fwd")
     return out
 
 
@@ -1611,7 +1620,7 @@ def _conv_desc(x, Wp, imgs, H, W, Cin, OH, OW, KH, KW, stride, dy, dx, out, out_
         g.out_spike = _ptr(out_spike, torch.uint8)
         g.out = _ptr(out, torch.float32)                          # optional membrane output (pre-activation + resid)
         g.sn_T, g.sn_kind, g.tau, g.v_th = sn_T, KIND[sn.kind], sn.tau, sn.v_th
-        g.v_reset, g.soft_reset = (0.0 if sn.v_reset is None else float(sn.v_reset)), (1 if sn.v_reset is None else 0)
+        g.soft_reset, g.v_reset = _reset(sn.v_reset)
         g.psn_w, g.psn_b = _ptr(sn.psn_w, torch.float32), _ptr(sn.psn_b, torch.float32)
         g.pos_count, g.pos_inner, g.pos_ostride, g.t_stride = pos
     else:
@@ -1649,7 +1658,7 @@ def head_conv_sn(x, w, B, T, H, W, p: NeuronParams, alpha=None, beta=None, voxel
     d.alpha, d.beta = _ptr(alpha, torch.float32), _ptr(beta, torch.float32)
     d.B, d.T, d.H, d.W, d.Cin, d.Cout = B, T, H, W, Cin, Cout
     d.sn_kind, d.tau, d.v_th = KIND[p.kind], p.tau, p.v_th
-    d.v_reset, d.soft_reset = (0.0 if p.v_reset is None else float(p.v_reset)), (1 if p.v_reset is None else 0)
+    d.soft_reset, d.v_reset = _reset(p.v_reset)
     d.psn_w, d.psn_b = _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32)
     _check(lib().sdf_head_conv_sn_fwd(C.byref(d), _stream()), "sdf_head_conv_sn_fwd")
     return out
@@ -1661,15 +1670,9 @@ def flow_out(pred, H, W, scale_y, scale_x):
     if pred.stride(4) != 1 or pred.stride(2) != w * pred.stride(3) or pred.stride(1) != h * pred.stride(2) or pred.stride(0) != D * pred.stride(1):
         raise SdfError("flow_out needs a (B,D,h,w,C) view of a dense (rows, ldp) buffer")
     out = torch.empty((B, Cc, H, W), dtype=torch.float32, device=pred.device)
-    _check(lib().sdf_flow_out_fwd(C.c_void_p(_ptr(pred, torch.float32)), C.c_void_p(out.data_ptr()), C.c_int(B), C.c_int(D), C.c_int(h),
-                                  C.c_int(w), C.c_int64(pred.stride(3)), C.c_int(Cc), C.c_int(H), C.c_int(W), C.c_float(scale_y),
-                                  C.c_float(scale_x), _stream()), "sdf_flow_out_fwd")
+    _check(lib().sdf_flow_out_fwd(_ptr(pred, torch.float32), out.data_ptr(), B, D, h, w, pred.stride(3), Cc, H, W, scale_y, scale_x,
+                                  _stream()), "sdf_flow_out_fwd")
     return out
-
-
-class PointwiseConvDesc(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("imgs", C.c_int32), ("H", C.c_int32),
-                ("W", C.c_int32), ("Cin", C.c_int32), ("N", C.c_int32), ("stride", C.c_int32), ("OH", C.c_int32), ("OW", C.c_int32)]
 
 
 def pointwise_conv_supported(Cin, N):
@@ -1689,14 +1692,6 @@ def pointwise_conv_f32(x, w, stride, bias=None):
     d.imgs, d.H, d.W, d.Cin, d.N, d.stride, d.OH, d.OW = imgs, H, W, Cin, N, stride, OH, OW
     _check(lib().sdf_pointwise_conv_f32_fwd(C.byref(d), _stream()), "sdf_pointwise_conv_f32_fwd")
     return out
-
-
-class PredHeadDesc(C.Structure):
-    _fields_ = [("z", C.c_void_p), ("B", C.c_int32), ("D", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("Cin", C.c_int32),
-                ("sn_pred", NeuronCfg), ("wgt", C.c_void_p), ("bias", C.c_void_p), ("pred", C.c_void_p), ("flow", C.c_void_p),
-                ("H", C.c_int32), ("W", C.c_int32), ("next_spikes", C.c_void_p), ("next_ld", C.c_int32), ("next_z_off", C.c_int32),
-                ("next_pred_off", C.c_int32), ("next_zero_off", C.c_int32), ("next_zero_len", C.c_int32), ("sn_next", NeuronCfg),
-                ("keep_spikes", C.c_void_p)]
 
 
 def pred_head_supported(D, Cin, H, W, h, w, sn, sn_next=None):
@@ -1784,7 +1779,6 @@ def deconv_col2im(Y, imgs, H, W, Cout, alpha=None, beta=None, out=None):
     """sdf_deconv_col2im_fwd: Y (imgs*H*W, 9*Cout) fp32 per-tap products -> (imgs, 2H, 2W, Cout) fp32, BN fused."""
     if out is None:
         out = torch.empty((imgs, 2 * H, 2 * W, Cout), dtype=torch.float32, device=Y.device)
-    _check(lib().sdf_deconv_col2im_fwd(C.c_void_p(_ptr(Y, torch.float32)), C.c_void_p(_ptr(alpha, torch.float32)),
-                                       C.c_void_p(_ptr(beta, torch.float32)), C.c_void_p(_ptr(out, torch.float32)), C.c_int(imgs),
-                                       C.c_int(H), C.c_int(W), C.c_int(Cout), _stream()), "sdf_deconv_col2im_fwd")
+    _check(lib().sdf_deconv_col2im_fwd(_ptr(Y, torch.float32), _ptr(alpha, torch.float32), _ptr(beta, torch.float32),
+                                       _ptr(out, torch.float32), imgs, H, W, Cout, _stream()), "sdf_deconv_col2im_fwd")
     return out

@@ -1,33 +1,82 @@
-"""CPU-side checks of the C ABI: the library loads and exports every symbol the header declares."""
-import ctypes
+"""CPU-side checks of the C ABI: the binding's signature table and descriptor mirrors match the header, the library loads and
+exports every symbol the header declares, and its argument checks return before any launch."""
+import ctypes as C
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# C scalar types of the header -> ctypes (every pointer is c_void_p, or POINTER(<mirror>) for a descriptor parameter)
+CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "float": C.c_float,
+          "char": C.c_char}
 
 
-def declared_symbols():
+def header():
+    """include/sdformerflow_hip.h without its comments."""
     src = open(os.path.join(ROOT, "include", "sdformerflow_hip.h")).read()
-    return sorted(set(re.findall(r"^(?:int|int64_t|void) (sdf_\w+)\(", src, flags=re.M)))
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
 
 
-def test_header_declares_the_expected_entry_points():
+def declared_prototypes():
+    """{entry point: (restype, argtypes)} of every prototype in the header, in header order, typed as hip.SIGNATURES types them."""
     from sdformerflow_amd import hip
-    assert set(declared_symbols()) == set(hip.EXPORTS)
+
+    def param(decl):
+        if "*" not in decl:
+            return CTYPES[decl.replace("const ", "").split()[0]]
+        desc = re.search(r"\bSdf(\w+)\s*\*", decl)
+        return C.POINTER(getattr(hip, desc.group(1))) if desc else C.c_void_p
+    return {name: (None if ret == "void" else CTYPES[ret], tuple(param(d) for d in params.split(",") if d.strip() not in ("", "void")))
+            for ret, name, params in re.findall(r"^(int|int64_t|void) (sdf_\w+)\(([^)]*)\);", header(), flags=re.M)}
 
 
-def test_library_exports_every_declared_symbol():
+def declared_structs():
+    """{X: [(member, ctypes type), ...]} of every `typedef struct SdfX { ... } SdfX;` in the header."""
+    from sdformerflow_amd import hip
+    structs = {}
+    for name, body in re.findall(r"typedef struct Sdf(\w+) \{(.*?)\} Sdf\1;", header(), flags=re.S):
+        members = []
+        for decl in body.split(";")[:-1]:                        # "const float* x", "int64_t nb, ni", "int32_t dy[3], dx[3]"
+            base, declarators = re.fullmatch(r"\s*(?:const\s+)?(\w+)(.*)", decl, flags=re.S).groups()
+            for d in declarators.split(","):
+                ptr, member, n = re.fullmatch(r"\s*(\*?)\s*(\w+)(?:\[(\d+)\])?\s*", d).groups()
+                t = C.c_void_p if ptr else getattr(hip, base[3:]) if base.startswith("Sdf") else CTYPES[base]
+                members.append((member, t * int(n) if n else t))
+        structs[name] = members
+    return structs
+
+
+def loaded_lib():
     from sdformerflow_amd import hip
     if not os.path.exists(hip.LIB_PATH):
         import __graft_entry__ as g
         g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in declared_symbols():
-        assert hasattr(lib, name), name
-    lib.sdf_version.restype = ctypes.c_int
-    assert lib.sdf_version() == 107            # host-only call, no GPU needed
+    return hip.lib()
+
+
+def test_binding_matches_the_header():
+    """The binding is the header's contract, checked once for everything: hip.SIGNATURES - what lib() declares to ctypes - lists the
+    header's prototypes in header order, each with its return and parameter types, and every Structure mirror has its header
+    struct's members in order, with ctypes types of the same size and kind."""
+    from sdformerflow_amd import hip
+    hdr = header()
+    protos = declared_prototypes()
+    assert len(protos) == len(re.findall(r"\bsdf_\w+\(", hdr))        # (no prototype the pattern above misses)
+    assert list(hip.SIGNATURES) == list(protos)
+    for name, sig in protos.items():
+        assert hip.SIGNATURES[name] == sig, name
+    structs = declared_structs()
+    assert len(structs) == hdr.count("typedef struct")
+    for name, members in structs.items():
+        assert getattr(hip, name)._fields_ == members, name
+
+
+def test_library_exports_every_declared_symbol():
+    L = loaded_lib()                           # (binds every entry point of hip.SIGNATURES: a missing symbol raises here)
+    for name in declared_prototypes():
+        assert hasattr(L, name), name
+    assert L.sdf_version() == 107              # host-only call, no GPU needed
 
 
 def test_switches_are_read_once_and_reloaded_on_request(monkeypatch):
@@ -65,14 +114,8 @@ def test_product_refuses_cpu_tensors():
 def test_argument_errors_are_reported_before_any_launch():
     """Error behaviour of the C ABI (include/sdformerflow_hip.h: negative = argument error, checked before launch - so
     these calls never touch the dummy pointers and need no GPU): NULL, shape, selector and alignment codes."""
-    import ctypes as C
     from sdformerflow_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = C.CDLL(hip.LIB_PATH)
-    for name in hip.EXPORTS[1:]:
-        getattr(lib, name).restype = None if name in hip.VOID_EXPORTS else C.c_int
+    lib = loaded_lib()
     p, odd = C.c_void_p(0x10000), C.c_void_p(0x10004)
     E_NULL, E_SHAPE, E_DTYPE, E_ALIGN = -1, -2, -3, -4
     lif = lambda x, out, T, N, dt=0: lib.sdf_lif_fwd(x, out, None, C.c_int(T), C.c_int64(N), C.c_float(2.0), C.c_float(0.1),
@@ -96,7 +139,6 @@ def test_argument_errors_are_reported_before_any_launch():
                                                  C.c_int(0), C.c_float(2.0), None)
     assert psn(p, None, p, 10) == E_NULL                        # dW without db
     assert psn(p, p, p, 20) == E_SHAPE                          # in-kernel dW / db reduction only for T <= 10
-    lib.sdf_psn_bwd_workspace_bytes.restype = C.c_int64
     assert lib.sdf_psn_bwd_workspace_bytes(C.c_int(10), C.c_int64(1 << 20)) == 512 * 110 * 4
     assert lib.sdf_psn_bwd_workspace_bytes(C.c_int(20), C.c_int64(1 << 20)) == 0
     d = hip.WinAttnDesc()
@@ -148,7 +190,6 @@ def test_argument_errors_are_reported_before_any_launch():
     assert lib.sdf_qk_attn_fwd(C.byref(q), None) == E_SHAPE     # C must be nH * 32
     q.C, q.workspace_bytes = 96, 16
     assert lib.sdf_qk_attn_fwd(C.byref(q), None) == E_SHAPE     # workspace smaller than sdf_qk_attn_workspace_bytes
-    lib.sdf_qk_attn_workspace_bytes.restype = C.c_int64
     # E (padded to 256 bytes), q | k (padded), and the slice spikes of the wide-stage form (round 4)
     assert lib.sdf_qk_attn_workspace_bytes(C.c_int64(4), C.c_int(2), C.c_int(81), C.c_int(96)) == 62208 + 2 * 62208 + 62208
     # wide-stage additions (round 4): the inverse slice map, and the host-only "will this run wide" queries
@@ -192,7 +233,7 @@ def test_argument_errors_are_reported_before_any_launch():
     mg.D, mg.C = 10, 80
     assert lib.sdf_ms_patch_merge_fwd(C.byref(mg), None) == E_SHAPE          # C in steps of 32 up to 192, of 64 beyond
     assert lib.sdf_spike_conv2d_multi_fwd(None, 4, None) == E_NULL
-    assert lib.sdf_spike_conv2d_multi_fwd(q16, 0, None) == E_SHAPE
+    assert lib.sdf_spike_conv2d_multi_fwd((hip.SpikeConvDesc * 1)(), 0, None) == E_SHAPE
     g5 = hip.SpikeGemmDesc()
     g5.A, g5.Wp, g5.out, g5.col_scale = 0x10000, 0x10000, 0x10000, 0x10000
     g5.M, g5.N, g5.K, g5.lda, g5.ldo, g5.nsplit = 12, 64, 128, 128, 64, hip.PLANES_I8X3_TILED
