@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the SDformerFlow forward hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--neuron lif|psn] [--no-cpu] [--inflight F] [--replicas R] [--eager]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--neuron lif|psn] [--inflight F] [--replicas R] [--eager]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-config3] [--no-sides]]
     python bench.py --train [--local-batch B] ...      (BASELINE configs[3], the training step; not the default workload)
 
 One "step" = one forward of MS_SpikingformerFlowNet_en4 over one synthetic 1 x 10 x 2 x 288 x 384 event
@@ -13,14 +13,17 @@ data-path collective, value = N*K / max-over-ranks(time).
 
 Every rank keeps F (default 2) HIP streams busy, each replaying the HIP graph of ONE launch sequence that carries R (default 10)
 independent batch-1 forwards of different voxels (`model.forward_replicas`: every sample keeps the reference's batch-1
-semantics - a batch of R would couple the samples - and its flow maps are asserted bit-equal to a separate forward in this
-run; `--eager` launches kernel by kernel instead): the layers of a batch-1 forward are too small to fill 256 CUs one
+semantics - a batch of R would couple the samples - and its flow maps are asserted bit-equal to a separate forward by
+--full; `--eager` launches kernel by kernel instead): the layers of a batch-1 forward are too small to fill 256 CUs one
 kernel at a time and spend a fixed few microseconds per launch on cold operands and weight staging, R samples share both.
-A step is still one whole forward of one sample; the K timed steps are dealt evenly to the streams (class InFlight).  The
-single-stream latency of a plain forward is reported next to the throughput.
+A step is still one whole forward of one sample; the K timed steps are dealt evenly to the streams (class InFlight).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant own kernel, timed live with HIP events on the
-launch stream) and `cpu_baseline` (the CPU oracle = port of the reference, timed on this box's host cores).
+A plain run does only what the headline needs: it sets up (model, graphs of the launch sequences), warms up, times the K steps,
+writes --dump-outputs and prints ONE JSON line on rank 0 (`value`, `ms_per_step`, the configuration).  `--full` adds, after the
+timed region: the single-stream latency, the same loop over >= 96 steps and for ~2 s, the bit-equality check of every in-flight
+sample, `roofline` (dominant own kernel, timed live with HIP events on the launch stream) with its per-kernel and per-entry-point
+tables, the swin stages' GEMM fraction, configs[2], the side measurements and `cpu_baseline` (the CPU oracle = port of the
+reference, timed on this box's host cores).
 """
 import argparse
 import json
@@ -985,9 +988,14 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 300 forwards / 10 training steps)")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--neuron", default="lif", choices=["lif", "psn"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-config3", action="store_true", help="skip the BASELINE configs[2] (ANN, batch 8) side measurement")
-    ap.add_argument("--no-sides", action="store_true", help="skip the other side measurements (weight-plane modes, PSN, configs[3] / [4])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures and checks: single-stream latency, the >= 96-step and "
+                         "~2 s loops, the bit-equality of every in-flight sample with a plain forward, rooflines, the per-kernel and per-entry-"
+                         "point tables, the swin stages, configs[2], the side measurements and the CPU baseline (minutes; a plain run "
+                         "sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-config3", action="store_true", help="--full: skip the BASELINE configs[2] (ANN, batch 8) side measurement")
+    ap.add_argument("--no-sides", action="store_true", help="--full: skip the other side measurements (weight-plane modes, PSN, configs[3] / [4])")
     ap.add_argument("--inflight", type=int, default=2, help="HIP streams per GPU, each replaying its own graph")
     ap.add_argument("--replicas", type=int, default=10, help="independent batch-1 forwards carried by ONE launch sequence (model.forward_replicas: "
                                                             "bit-equal to separate forwards); 1 = one sample per launch sequence")
@@ -1008,6 +1016,8 @@ def main():
         ap.error("--steps must be >= 1")
     if args.dump_outputs and (args.train or args.plumbing):
         ap.error("--dump-outputs covers the forward benchmark (not --train / --plumbing)")
+    if args.full and (args.train or args.plumbing):
+        ap.error("--full covers the forward benchmark (not --train / --plumbing)")
     if args.steps is None:
         args.steps = 10 if args.train else 300
     if args.warmup is None:
@@ -1035,20 +1045,21 @@ def main():
         torch.cuda.synchronize()
 
     with torch.no_grad():
-        # single-stream latency of one forward (reported beside the throughput; not part of the timed region)
         for _ in range(5):                                       # first calls: library algorithm search, allocator growth
             model(chunk)
         torch.cuda.synchronize()
-        lat = []
-        for _ in range(9):
-            t0 = time.perf_counter()
-            model(chunk)
-            torch.cuda.synchronize()
-            lat.append((time.perf_counter() - t0) * 1e3)
-        latency_ms = sorted(lat)[len(lat) // 2]                      # median of 9 synchronous forwards
+        if args.full:
+            # single-stream latency of one forward (reported beside the throughput; not part of the timed region)
+            lat = []
+            for _ in range(9):
+                t0 = time.perf_counter()
+                model(chunk)
+                torch.cuda.synchronize()
+                lat.append((time.perf_counter() - t0) * 1e3)
+            latency_ms = sorted(lat)[len(lat) // 2]                  # median of 9 synchronous forwards
 
         # F streams, each replaying its own HIP graph of one launch sequence over R independent samples (class InFlight)
-        long_steps = max(args.steps, 96)
+        long_steps = max(args.steps, 96) if args.full else args.steps
         fl = InFlight(model, dev, F_, args.replicas, eager=args.eager)
         if args.plan:
             fl.plan_override = [tuple(int(v) for v in p.split(":")) for p in args.plan.split(",")]
@@ -1060,24 +1071,25 @@ def main():
         barrier()
         dt_local = time.perf_counter() - t0
         dumped = fl.last_outputs(args.steps) if args.dump_outputs else None      # (outside the timed region; the loops below overwrite it)
-        # the same loop over >= 96 samples when the contract's --steps is shorter (a 20-step region is 30 ms: VERDICT r3); reported
-        # beside `value`, which stays the contract's EXACTLY --steps
-        dt_long = dt_local
-        if long_steps > args.steps:
+        if args.full:
+            # the same loop over >= 96 samples when the contract's --steps is shorter (a 20-step region is 30 ms: VERDICT r3); reported
+            # beside `value`, which stays the contract's EXACTLY --steps
+            dt_long = dt_local
+            if long_steps > args.steps:
+                barrier()
+                t0 = time.perf_counter()
+                fl.run(long_steps)
+                barrier()
+                dt_long = time.perf_counter() - t0
+            # the sustained rate: the same loop for about two seconds (the chip's clock under a load of seconds is lower than in a burst
+            # of a few hundred milliseconds: DVFS) - reported beside `value`, never instead of it
+            n_sus = max(F_ * args.replicas, int(2.0 * long_steps / dt_long) // (F_ * args.replicas) * (F_ * args.replicas))
             barrier()
             t0 = time.perf_counter()
-            fl.run(long_steps)
+            fl.run(n_sus)
             barrier()
-            dt_long = time.perf_counter() - t0
-        # the sustained rate: the same loop for about two seconds (the chip's clock under a load of seconds is lower than in a burst
-        # of a few hundred milliseconds: MI355X_MICROARCH.md, DVFS) - reported beside `value`, never instead of it
-        n_sus = max(F_ * args.replicas, int(2.0 * long_steps / dt_long) // (F_ * args.replicas) * (F_ * args.replicas))
-        barrier()
-        t0 = time.perf_counter()
-        fl.run(n_sus)
-        barrier()
-        dt_sus = time.perf_counter() - t0
-        fl.verify()                                              # every in-flight sample == the plain forward of its voxel, bit for bit
+            dt_sus = time.perf_counter() - t0
+            fl.verify()                                          # every in-flight sample == the plain forward of its voxel, bit for bit
     dt = max_over_ranks(dt_local, dev, dist)
     ranks = gather_ranks(rank_record(rank, dev, args.steps, dt_local), dist, td)
 
@@ -1085,17 +1097,6 @@ def main():
         check_ranks(ranks, world, shared_ok=os.environ.get("SDF_DIST_BACKEND", "nccl") != "nccl")
         if dumped is not None:
             dump_outputs(args.dump_outputs, dumped)
-        gemm, neuron = time_dominant_kernels(model, R=args.replicas)
-        blocks = time_swin_blocks(model, chunk, args.replicas)
-        by_time = time_by_entry_point(model, chunk)
-        gemm["by_time"] = by_time["rows"]
-        gemm["by_time_note"] = by_time["note"]
-        gemm["calls_per_forward"] = by_time["calls_per_forward"]
-        gemm["largest_share"] = by_time["rows"][0]["entry_point"] + " " + str(by_time["rows"][0]["shape"])
-        try:
-            gemm["by_kernel"] = time_by_kernel(model, args.replicas)
-        except Exception as e:                                     # (diagnostic: never takes the line down)
-            gemm["by_kernel"] = {"error": repr(e)[:300]}
         planes_txt = {1: "ONE bf16 weight plane (8 significand bits; throughput mode at BASELINE configs[1]'s stated precision, NOT the "
                          "parity mode)",
                       2: "2 fp16 weight planes hi+lo (22 of fp32's 24 significand bits; the default parity mode)",
@@ -1103,11 +1104,6 @@ def main():
         res = {
             "metric": "event-frames/sec fwd (1x10x2x288x384)", "value": whole_job_rate(world, args.steps, dt), "unit": "samples/s",
             "n_gpus": world, "world_size": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "value_over_90_steps": {"steps": long_steps, "samples_per_s_this_rank": long_steps / dt_long, "ms_per_step": dt_long / long_steps * 1e3},
-            "value_sustained": {"steps": n_sus, "seconds": dt_sus, "samples_per_s_this_rank": n_sus / dt_sus, "ms_per_step": dt_sus / n_sus * 1e3,
-                                "note": "the same timed loop run for ~2 s: the clock the chip holds under seconds of this load is lower than in the "
-                                        "contract's short region"},
-            "latency_ms_single_stream": latency_ms,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": {1: "bf16", 2: "f16x2", 3: "f32"}[args.planes], "data": "synthetic",
             "dtype_note": "binary u8 spikes x " + planes_txt + ", fp32 accumulate on the 16-bit MFMA pipe; membranes, BN, neurons fp32",
@@ -1115,37 +1111,56 @@ def main():
                                    "voxel, neuron=" + args.neuron + f"; a step = one forward of one sample; {args.inflight} HIP streams per GPU, each "
                                    f"{'launching' if args.eager else 'replaying the HIP graph of'} one launch sequence that carries {args.replicas} "
                                    "independent batch-1 forwards of different voxels (replicas: every flow map bit-equal to a separate batch-1 "
-                                   "forward, asserted in this run); one process per GPU",
+                                   "forward, " + ("asserted in this run" if args.full else "asserted by --full runs") + "); one process per GPU",
                        "in_flight": args.inflight, "replicas_per_launch": args.replicas, "samples_in_flight": args.inflight * args.replicas,
                        "hip_graph": not args.eager, "weight_planes": args.planes},
             "ranks": ranks,
-            "roofline": gemm, "roofline_neuron": neuron,
-            "attention_gemm_roofline_frac": blocks["frac"], "attention_gemm": blocks,
         }
-        if not args.no_config3 and world == 1:
-            res["config3_ann"] = time_config3()
-        if not args.no_sides and world == 1 and args.planes == 2 and args.neuron == "lif":
-            # the headline's graphs, static inputs and outputs are released first (their memory pools would stay beside the side runs),
-            # and no side run can take the headline down: each is wrapped, the line is printed whatever happens
-            fl.release()
-            del model, fl
-            torch.cuda.empty_cache()
+        if args.full:
+            gemm, neuron = time_dominant_kernels(model, R=args.replicas)
+            blocks = time_swin_blocks(model, chunk, args.replicas)
+            by_time = time_by_entry_point(model, chunk)
+            gemm["by_time"] = by_time["rows"]
+            gemm["by_time_note"] = by_time["note"]
+            gemm["calls_per_forward"] = by_time["calls_per_forward"]
+            gemm["largest_share"] = by_time["rows"][0]["entry_point"] + " " + str(by_time["rows"][0]["shape"])
             try:
-                res["side_measurements"] = side_measurements(args, dev)
-            except Exception as e:
-                res["side_measurements"] = {"error": repr(e)[:300]}
-        if not args.no_cpu and world == 1:
-            res["cpu_baseline"] = cpu_baseline(args.neuron, sd, chunk_cpu)
-            res["gpu_over_cpu"] = res["value"] / res["cpu_baseline"]["value"]
-        # the numbers a reader needs again as the LAST key: the driver's record keeps the tail of this (long) line
-        sm = res.get("side_measurements", {}) if isinstance(res.get("side_measurements"), dict) else {}
-        res["headline_summary"] = {
-            "value": res["value"], "unit": res["unit"], "steps": args.steps, "value_over_90_steps": res["value_over_90_steps"],
-            "value_sustained_2s": res["value_sustained"]["samples_per_s_this_rank"],
-            "latency_ms_single_stream": latency_ms, "roofline_frac": gemm.get("frac"), "attention_gemm_roofline_frac": blocks["frac"],
-            "swin_stages_ms": blocks.get("swin_stages_ms"), "neuron_psn_samples_per_s": (sm.get("neuron_psn") or {}).get("samples_per_s"),
-            "one_sample_per_launch_three_streams_samples_per_s": (sm.get("one_sample_per_launch_three_streams") or {}).get("samples_per_s"),
-            "cpu_baseline_samples_per_s": (res.get("cpu_baseline") or {}).get("value")}
+                gemm["by_kernel"] = time_by_kernel(model, args.replicas)
+            except Exception as e:                                 # (diagnostic: never takes the line down)
+                gemm["by_kernel"] = {"error": repr(e)[:300]}
+            res.update({
+                "value_over_90_steps": {"steps": long_steps, "samples_per_s_this_rank": long_steps / dt_long, "ms_per_step": dt_long / long_steps * 1e3},
+                "value_sustained": {"steps": n_sus, "seconds": dt_sus, "samples_per_s_this_rank": n_sus / dt_sus, "ms_per_step": dt_sus / n_sus * 1e3,
+                                    "note": "the same timed loop run for ~2 s: the clock the chip holds under seconds of this load is lower than in the "
+                                            "contract's short region"},
+                "latency_ms_single_stream": latency_ms,
+                "roofline": gemm, "roofline_neuron": neuron,
+                "attention_gemm_roofline_frac": blocks["frac"], "attention_gemm": blocks,
+            })
+            if not args.no_config3 and world == 1:
+                res["config3_ann"] = time_config3()
+            if not args.no_sides and world == 1 and args.planes == 2 and args.neuron == "lif":
+                # the headline's graphs, static inputs and outputs are released first (their memory pools would stay beside the side runs),
+                # and no side run can take the headline down: each is wrapped, the line is printed whatever happens
+                fl.release()
+                del model, fl
+                torch.cuda.empty_cache()
+                try:
+                    res["side_measurements"] = side_measurements(args, dev)
+                except Exception as e:
+                    res["side_measurements"] = {"error": repr(e)[:300]}
+            if not args.no_cpu and world == 1:
+                res["cpu_baseline"] = cpu_baseline(args.neuron, sd, chunk_cpu)
+                res["gpu_over_cpu"] = res["value"] / res["cpu_baseline"]["value"]
+            # the numbers a reader needs again as the LAST key: a record that keeps only the tail of this (long) line has them
+            sm = res.get("side_measurements", {}) if isinstance(res.get("side_measurements"), dict) else {}
+            res["headline_summary"] = {
+                "value": res["value"], "unit": res["unit"], "steps": args.steps, "value_over_90_steps": res["value_over_90_steps"],
+                "value_sustained_2s": res["value_sustained"]["samples_per_s_this_rank"],
+                "latency_ms_single_stream": latency_ms, "roofline_frac": gemm.get("frac"), "attention_gemm_roofline_frac": blocks["frac"],
+                "swin_stages_ms": blocks.get("swin_stages_ms"), "neuron_psn_samples_per_s": (sm.get("neuron_psn") or {}).get("samples_per_s"),
+                "one_sample_per_launch_three_streams_samples_per_s": (sm.get("one_sample_per_launch_three_streams") or {}).get("samples_per_s"),
+                "cpu_baseline_samples_per_s": (res.get("cpu_baseline") or {}).get("value")}
         print(json.dumps(res))
     if dist:
         td.barrier()

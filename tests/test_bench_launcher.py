@@ -51,6 +51,16 @@ def test_flag_that_disagrees_with_the_joined_ranks_is_refused():
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
+def test_full_is_an_option_of_the_forward_benchmark_only():
+    """`--full` (everything beside the headline) is offered, and refused with the training step or the dry run: no line, non-zero exit."""
+    out = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 0 and "--full" in out.stdout
+    for args in (["--full", "--plumbing"], ["--full", "--train", "--plumbing"]):
+        out = _run(["--steps", "5"] + args)
+        assert out.returncode != 0 and "--full" in out.stderr
+        assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
 def test_launcher_refuses_more_ranks_than_gpus_on_the_real_backend():
     """Without the gloo test backend the launcher checks the visible device count BEFORE starting anything (this container
     has no GPU): exit 2, no line."""

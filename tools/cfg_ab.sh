@@ -4,5 +4,5 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print("%8.1f samples/s 
 VAR=$1; shift
 for c in "$@"; do
   echo -n "$VAR=$c : "
-  if [ $c = none ]; then python3 bench.py --no-cpu --no-sides --no-config3 2>/dev/null | python3 -c "$pick"; else env $VAR=$c python3 bench.py --no-cpu --no-sides --no-config3 2>/dev/null | python3 -c "$pick"; fi
+  if [ $c = none ]; then python3 bench.py --full --no-cpu --no-sides --no-config3 2>/dev/null | python3 -c "$pick"; else env $VAR=$c python3 bench.py --full --no-cpu --no-sides --no-config3 2>/dev/null | python3 -c "$pick"; fi
 done

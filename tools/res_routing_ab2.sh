@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:?run on the GPU box}" || exit 1
 run() {
   local label=$1; shift
-  local v=$(env "$@" python bench.py --no-config3 --no-cpu --no-sides 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f samples/s, latency %.3f ms, swin stages %.3f ms' % (d['value'], d['latency_ms_single_stream'], d['attention_gemm']['swin_stages_ms']))")
+  local v=$(env "$@" python bench.py --full --no-config3 --no-cpu --no-sides 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.1f samples/s, latency %.3f ms, swin stages %.3f ms' % (d['value'], d['latency_ms_single_stream'], d['attention_gemm']['swin_stages_ms']))")
   echo "$label: $v"
 }
 for rep in 1 2; do
