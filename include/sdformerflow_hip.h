@@ -740,6 +740,36 @@ typedef struct SdfWinAttnBwdDesc {
 int64_t sdf_win_attn_ann_bwd_workspace_bytes(int B_, int nH, int N);   /* 0 for an unsupported shape */
 int sdf_win_attn_ann_bwd(const SdfWinAttnBwdDesc* d, void* stream);
 
+/* ---- backward of the SDF_ATTN_SEW core of sdf_win_attn_fwd (training of the SEW model family) ------------------------------
+ * Per window b and head g: A = scale[g] Q K^T + bias[g] (+ mask[b % nW]), O = A V, no softmax; Q, K, V the raw head view
+ * (B_, nH, N, 32) of the (T', B_, N1, C) u8 spike buffers, O leaving through the (B_,nH,T',N1,hd) -> (T',B_,N1,C) scramble.
+ * Given dout = dL/dO in that scrambled (T', B_, N1, C) layout:
+ *   dq = scale dO (V^T K),  dk = scale V (dO^T Q),  dv = scale K (Q^T dO) + (bias[g] + mask)^T dO   (fp32, raw head view of q / k / v);
+ *   d_bias (nH, N, N) = sum over windows of dO V^T.  The mask gets no gradient.
+ * head_dim 32, N = Tq * N1 <= 192, any nH; SDF_E_SHAPE otherwise.  fp32 FMA on the vector ALU (spikes exact, dO and the 32 x 32
+ * Gram matrices fp32).  d_bias goes through fixed-order split-K partials in `workspace`
+ * (sdf_win_attn_sew_bwd_workspace_bytes(B_, nH, N) bytes, 256-byte aligned, caller-owned): no atomics, two calls give bit-equal
+ * results. */
+typedef struct SdfWinAttnSewBwdDesc {
+  const uint8_t* q;         /* (T', B_, N1, C) spikes */
+  const uint8_t* k;
+  const uint8_t* v;
+  const float* dout;        /* (T', B_, N1, C) */
+  const float* scale;       /* (nH) */
+  const float* bias;        /* (nH,N,N) */
+  const float* mask;        /* (nW,N,N) or NULL */
+  float* dq;                /* (T', B_, N1, C) each */
+  float* dk;
+  float* dv;
+  float* d_bias;            /* (nH,N,N) */
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t B_, nW, nH, Tq, N1, hd;
+} SdfWinAttnSewBwdDesc;
+
+int64_t sdf_win_attn_sew_bwd_workspace_bytes(int B_, int nH, int N);   /* 0 for an unsupported shape */
+int sdf_win_attn_sew_bwd(const SdfWinAttnSewBwdDesc* d, void* stream);
+
 /* ---- the attention half of an ANN video-swin block as one launch (BASELINE config 3, first stage) -----------------
  * Replaces `SwinTransformerBlock3D.forward_part1` + the shortcut (reference models/STSwinNet/swin_transformer3D_v2.py:272-310, :331)
  * with `WindowAttention3D.forward` (:169-205) inside:

@@ -253,7 +253,7 @@ class MS_SpikingformerFlowNet_en4(MS_SpikingformerFlowNet):
 
 class SpikingformerFlowNet(MS_SpikingformerFlowNet):
     """SEW-shortcut SDformerFlow, 3 encoders (reference Spiking_STSwinNet.py:254-311): the stream between blocks carries sums
-    of spikes.  Inference runs on `engine_sew.SEWFlowEngine`; training of this family is not built."""
+    of spikes.  Inference runs on `engine_sew.SEWFlowEngine`; training on `train.forward_train_sew`."""
     num_en = 3
     unet_type = Spikingformer_MultiResUNet
 
@@ -262,8 +262,9 @@ class SpikingformerFlowNet(MS_SpikingformerFlowNet):
         return SEWFlowEngine(self)
 
     def forward(self, x, log=False):
-        if self.training:
-            raise NotImplementedError("the SEW family is forward-only here (the training path covers the shipped MS models)")
+        if self.training:                     # train-mode forward under autograd (the SEW attention backward: csrc/win_attn_sew_bwd.hip)
+            from ..train import forward_train_sew
+            return {"flow": forward_train_sew(self, x), "attn": None}
         if log:
             raise NotImplementedError("SEW attention maps (B_, nH, N, N) live in registers of the fused window-attention kernel and "
                                       "are never materialised; log=True is built for the MS (QK token-gate) family")

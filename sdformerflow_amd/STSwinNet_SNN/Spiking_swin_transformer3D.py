@@ -127,7 +127,8 @@ class Spiking_BN_WindowAttention3D(nn.Module):
         from .. import hip
         from ..engine import bn_affine, _np
         if self.training:
-            raise NotImplementedError("forward-only")
+            raise NotImplementedError("Spiking_BN_WindowAttention3D.forward: inference only at module level (training goes through the "
+                                      "model: sdformerflow_amd.train.forward_train_sew)")
         with torch.no_grad():
             Tq, B_, Wh, Ww, C = x.shape
             N1, dev, nsplit = Wh * Ww, x.device, 2

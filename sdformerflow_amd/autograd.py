@@ -358,3 +358,29 @@ class WinAttnAnnFunction(torch.autograd.Function):
         row_map, B_, N, mask, nH = ctx.cfg
         dqkv, d_pad, d_scale, d_bias = hip.win_attn_ann_bwd(qkv, row_map, B_, N, pad, scale, bias, mask, nH, dout.contiguous())
         return dqkv, d_scale, d_bias, d_pad, None, None, None, None, None
+
+
+class WinAttnSewFunction(torch.autograd.Function):
+    """The softmax-free core of the SEW Spiking_BN_WindowAttention3D (reference Spiking_swin_transformer3D.py:320-363): q, k, v
+    (T', B_, N1, C) spikes in the reference's raw head view, bias (nH, N, N) = table[index[:N, :N]] (autograd carries its gradient on to
+    the table), scale (nH), mask (nW, N, N) or None -> (T', B_, N1, C) fp32 through the reference's scramble.  Forward
+    `hip.win_attn_sew` on the spikes as bytes (exact), backward `hip.win_attn_sew_bwd` (csrc/win_attn_sew_bwd.hip).  Saves the three
+    byte tensors and the bias; no (N, N) tensor per window exists in either direction.  fp32 under autocast too."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, scale, mask, nH):
+        Tq, B_, N1, _ = q.shape
+        qu, ku, vu = (t.detach().to(torch.uint8).contiguous() for t in (q, k, v))
+        b = bias.detach().float().contiguous()
+        out = hip.win_attn_sew(qu, ku, vu, scale, b, mask, nH, Tq, B_, N1)
+        ctx.save_for_backward(qu, ku, vu, b)
+        ctx.cfg = (scale, mask, nH, q.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qu, ku, vu, b = ctx.saved_tensors
+        scale, mask, nH, dtype = ctx.cfg
+        Tq, B_, N1, _ = qu.shape
+        dq, dk, dv, d_bias = hip.win_attn_sew_bwd(qu, ku, vu, scale, b, mask, nH, Tq, B_, N1, dout.float().contiguous())
+        return dq.to(dtype), dk.to(dtype), dv.to(dtype), d_bias, None, None, None

@@ -139,6 +139,13 @@ class WinAttnBwdDesc(C.Structure):
                 ("B_", C.c_int32), ("nW", C.c_int32), ("nH", C.c_int32), ("N", C.c_int32), ("hd", C.c_int32)]
 
 
+class WinAttnSewBwdDesc(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("dout", C.c_void_p), ("scale", C.c_void_p),
+                ("bias", C.c_void_p), ("mask", C.c_void_p), ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p),
+                ("d_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("B_", C.c_int32), ("nW", C.c_int32), ("nH", C.c_int32), ("Tq", C.c_int32), ("N1", C.c_int32), ("hd", C.c_int32)]
+
+
 class AnnMlpBlockDesc(C.Structure):
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int64), ("C", C.c_int32), ("Ch", C.c_int32),
                 ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("ln_eps", C.c_float), ("w1", C.c_void_p), ("b1", C.c_void_p),
@@ -288,6 +295,7 @@ SIGNATURES = {
     "sdf_pred_head_fwd": (_i, (_P(PredHeadDesc), _p)), "sdf_affine_resid_fwd": (_i, (_p, _p, _p, _p, _p, _i64, _i, _i64, _p)),
     "sdf_win_attn_fwd": (_i, (_P(WinAttnDesc), _p)),
     "sdf_win_attn_ann_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_ann_bwd": (_i, (_P(WinAttnBwdDesc), _p)),
+    "sdf_win_attn_sew_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_sew_bwd": (_i, (_P(WinAttnSewBwdDesc), _p)),
     "sdf_ann_attn_block_supported": (_i, (_i, _i, _i)), "sdf_ann_attn_block_fwd": (_i, (_P(AnnAttnBlockDesc), _p)),
     "sdf_ann_mlp_block_supported": (_i, (_i, _i)), "sdf_ann_mlp_block_fwd": (_i, (_P(AnnMlpBlockDesc), _p)),
     "sdf_dense_conv3x3_fwd": (_i, (_P(DenseConvDesc), _p)),
@@ -1270,6 +1278,26 @@ def win_attn_sew(q, k, v, scale, bias, mask, nH, Tq, B_, N1):
     d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
     _check(lib().sdf_win_attn_fwd(C.byref(d), _stream()), "sdf_win_attn_fwd")
     return out
+
+
+def win_attn_sew_bwd(q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout):
+    """Backward of `win_attn_sew` (sdf_win_attn_sew_bwd): q, k, v u8 (T',B_,N1,C), scale (nH), bias (nH,N,N), mask (nW,N,N) or None as
+    the forward took them; dout = dL/d(output) (T',B_,N1,C) fp32.  -> (dq, dk, dv (T',B_,N1,C) fp32, d_bias (nH,N,N)); deterministic
+    (fixed-order split-K sum over windows for d_bias)."""
+    Cc, N = q.shape[-1], Tq * N1
+    dev = q.device
+    dq, dk, dv = (torch.empty((Tq, B_, N1, Cc), dtype=torch.float32, device=dev) for _ in range(3))
+    d_bias = torch.empty((nH, N, N), dtype=torch.float32, device=dev)
+    nbytes = lib().sdf_win_attn_sew_bwd_workspace_bytes(B_, nH, N)
+    ws = torch.empty((max(nbytes, 256) // 4,), dtype=torch.float32, device=dev)
+    d = WinAttnSewBwdDesc()
+    d.q, d.k, d.v, d.dout = _ptr(q, torch.uint8), _ptr(k, torch.uint8), _ptr(v, torch.uint8), _ptr(dout, torch.float32)
+    d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
+    d.dq, d.dk, d.dv, d.d_bias = _ptr(dq), _ptr(dk), _ptr(dv), _ptr(d_bias)
+    d.workspace, d.workspace_bytes = _ptr(ws), nbytes
+    d.B_, d.nW, d.nH, d.Tq, d.N1, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, Tq, N1, Cc // nH
+    _check(lib().sdf_win_attn_sew_bwd(C.byref(d), _stream()), "sdf_win_attn_sew_bwd")
+    return dq, dk, dv, d_bias
 
 
 # ---- dense 3x3 convolution of real-valued activations (ANN patch embedding; csrc/dense_conv_wres.hip) ----

@@ -191,16 +191,22 @@ def qk_attention(x, attn):
 _SLICE_MAPS = {}
 
 
-def ssa(x, blk):
-    """Window partition -> attention -> window reverse, both as row moves through the int32 slice map (built on the device,
-    cached per shape): no materialised pad / roll / permute / crop in either direction of autograd."""
-    from .autograd import WindowGatherFunction, WindowScatterFunction
+def _slice_map(x, blk):
+    """(window size, shift, int32 slice map, B_) of block `blk` on x (B, D, H, W, C): the map is built on the device, cached per shape."""
     B, D, H, W, C = x.shape
     (Wd, Wh, Ww), ss = get_window_size((D, H, W), blk.window_size, blk.shift_size)
     key = (B, D, H, W, Wd, Wh, Ww, ss, str(x.device))
     if key not in _SLICE_MAPS:
         _SLICE_MAPS[key] = hip.window_slice_map(B, D, H, W, (Wd, Wh, Ww), ss, x.device)
-    row_map, B_ = _SLICE_MAPS[key]
+    return (Wd, Wh, Ww), ss, *_SLICE_MAPS[key]
+
+
+def ssa(x, blk):
+    """Window partition -> attention -> window reverse, both as row moves through the int32 slice map (built on the device,
+    cached per shape): no materialised pad / roll / permute / crop in either direction of autograd."""
+    from .autograd import WindowGatherFunction, WindowScatterFunction
+    B, D, H, W, C = x.shape
+    (Wd, Wh, Ww), ss, row_map, B_ = _slice_map(x, blk)
     xw = WindowGatherFunction.apply(x, row_map)                          # (Wd * B_ * Wh * Ww, C): step t' of window b' is slice t' B_ + b'
     y = qk_attention(xw.view(Wd, B_, Wh * Ww, C), blk.attn)
     return WindowScatterFunction.apply(y.reshape(-1, C), row_map, (B, D, H, W, C))
@@ -261,6 +267,127 @@ def forward_train(model, x):
         z = F.conv_transpose2d(s.flatten(0, 1), dc.weight, dc.bias, stride=2, padding=dc.kernel_size[0] // 2, output_padding=1)
         y = _bn_ch2(z.view(T, B, *z.shape[1:]), dec.norm_layer.norm_layer)
         preds.append(_conv_seq(pr.sn(y), pr.conv[0], padding=0))
+    flows = []
+    for f in preds:
+        f = f.sum(0)
+        flows.append(F.interpolate(f, scale_factor=(H / f.shape[-2], W / f.shape[-1])))
+    return flows
+
+
+# ---------------------------------------------------------------------------------------------- SEW family (SpikingformerFlowNet)
+# The stream between SEW blocks carries SUMS of spikes (reference Spiking_STSwinNet.py:254-311).  Every layer that reads it (q / k / v,
+# fc1, the merge reduction, the res-block's first convolution, the decoders) and the real-valued attention output (proj) take library
+# products: the hand-written spike products keep the top 16 bits of the activation and would truncate them.  Only the layers a neuron
+# feeds (fc2, the res-block's second convolution) take the spike products.
+def sew_attention_core_torch(q, k, v, scale, bias, mask, nH):
+    """The core of `autograd.WinAttnSewFunction` as a torch composition (reference Spiking_swin_transformer3D.py:320-363), fp32: the A/B
+    path of SDF_SEW_ATTN_BWD=0.  It keeps the (B_, nH, N, N) scores for autograd."""
+    Tq, B_, N1, Cc = q.shape
+    N, hd = Tq * N1, Cc // nH
+    with torch.autocast("cuda", enabled=False):
+        qh, kh, vh = (t.float().reshape(B_, nH, N, hd) for t in (q, k, v))
+        a = (qh * scale.float().view(1, nH, 1, 1)) @ kh.transpose(-2, -1) + bias.float().unsqueeze(0)
+        if mask is not None:
+            nW = mask.shape[0]
+            a = (a.view(B_ // nW, nW, nH, N, N) + mask.float().view(1, nW, 1, N, N)).view(B_, nH, N, N)
+        o = a @ vh
+    return o.reshape(B_, nH, Tq, N1, hd).permute(2, 0, 3, 1, 4).reshape(Tq, B_, N1, Cc)
+
+
+def sew_attention(xw, attn, mask):
+    """`Spiking_BN_WindowAttention3D.forward` in training (reference :300-370): xw (T', B_, N1, C) window slices of the SEW stream ->
+    (T', B_, N1, C) spikes.  q / k / v = SN(BN(Linear)); the core is `autograd.WinAttnSewFunction` (HIP both ways; SDF_SEW_ATTN_BWD=0:
+    the torch composition); the relative-position bias is the table gathered under autograd; proj (with bias) -> BN -> SN."""
+    Tq, B_, N1, Cc = xw.shape
+    nH, N = attn.num_heads, Tq * N1
+    q, k, v = (getattr(attn, f"sn_{n}")(_bn_last(_linear(xw, getattr(attn, f"linear_{n}"), spikes=False), getattr(attn, f"bn_{n}").norm_layer))
+               for n in ("q", "k", "v"))
+    bias = attn.relative_position_bias_table[attn.relative_position_index[:N, :N].reshape(-1)].reshape(N, N, nH).permute(2, 0, 1)
+    scale = torch.full((nH,), float(attn.scale), dtype=torch.float32, device=xw.device)
+    if hip.sw("SDF_SEW_ATTN_BWD", "1") == "0":
+        z = sew_attention_core_torch(q, k, v, scale, bias, mask, nH)
+    else:
+        from .autograd import WinAttnSewFunction
+        z = WinAttnSewFunction.apply(q, k, v, bias.float(), scale, mask, nH)
+    return attn.proj_sn(_bn_last(_linear(z, attn.proj, spikes=False), attn.proj_bn.norm_layer))
+
+
+def sew_ssa(x, blk):
+    """`Spiking_SwinTransformerBlock3D.SSA` around the SEW attention (Spiking_swin_transformer3D.py:781-821) through the slice map; the
+    shift mask of the padded grid is passed whenever the block is shifted (:799-801, layer forward :1070-1076)."""
+    from .autograd import WindowGatherFunction, WindowScatterFunction
+    from .STSwinNet.swin_transformer3D_v2 import compute_mask
+    B, D, H, W, C = x.shape
+    ws, ss, row_map, B_ = _slice_map(x, blk)
+    mask = None
+    if any(s > 0 for s in ss):
+        mask = compute_mask(-(-D // ws[0]) * ws[0], -(-H // ws[1]) * ws[1], -(-W // ws[2]) * ws[2], ws, ss, x.device).contiguous()
+    xw = WindowGatherFunction.apply(x, row_map)
+    y = sew_attention(xw.view(ws[0], B_, ws[1] * ws[2], C), blk.attn, mask)
+    return WindowScatterFunction.apply(y.reshape(-1, C), row_map, (B, D, H, W, C))
+
+
+def sew_mlp(x, mlp):
+    """`Spiking_Mlp.forward` (:147-162): fc1 -> BN -> SN -> fc2 -> BN -> SN on (T, B, H, W, C)."""
+    h = mlp.sn1(_bn_last(_linear(x, mlp.fc1, spikes=False), mlp.bn1.norm_layer))
+    return mlp.sn2(_bn_last(_linear(h, mlp.fc2), mlp.bn2.norm_layer))
+
+
+def sew_block(x, blk, training=True):
+    """`Spiking_SwinTransformerBlock3D.forward`, cnf ADD (:824-847): DropPath on the SSA branch, as the MS block."""
+    x = _drop_path(sew_ssa(x, blk), blk.drop_path_rate, training) + x
+    return sew_mlp(x.permute(1, 0, 2, 3, 4).contiguous(), blk.mlp).permute(1, 0, 2, 3, 4) + x
+
+
+def sew_patch_merge(x, pm):
+    """`SpikingPatchMerging.forward` (:914-934): 2x2 gather -> Linear -> BN -> SN."""
+    B, D, H, W, C = x.shape
+    if H % 2 or W % 2:
+        x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
+    x = torch.cat([x[:, :, 0::2, 0::2], x[:, :, 1::2, 0::2], x[:, :, 0::2, 1::2], x[:, :, 1::2, 1::2]], -1)
+    y = _bn_last(_linear(x.permute(1, 0, 2, 3, 4).contiguous(), pm.reduction, spikes=False), pm.norm.norm_layer)
+    return pm.sn(y).permute(1, 0, 2, 3, 4)
+
+
+def sew_resblock(x, rb):
+    """`SEWResBlock.forward`, connect ADD (Spiking_modules.py:852-878): conv-BN-SN-conv-BN-SN + identity on (T, B, C, H, W)."""
+    y = rb.sn1(_bn_ch2(_conv_seq(x, rb.conv1[0]), rb.norm1.norm_layer))
+    y = rb.sn2(_bn_ch2(_conv_seq(y, rb.conv2[0], spikes=True), rb.norm2.norm_layer))
+    return y + x
+
+
+def forward_train_sew(model, x):
+    """`SpikingformerFlowNet.forward` in train mode (Spiking_STSwinNet.py:278-305, :161-182): (B, bins, 2, H, W) on the GPU -> list of
+    flow maps (B, 2, H, W), differentiable; BN running statistics are updated.  Same patch embedding as the MS models; SEW blocks,
+    SEW patch merging, SEW res-blocks, decoders ConvT 3x3 s2 -> BN -> SN (no neuron in front), plain 1x1 predictions."""
+    if not x.is_cuda:
+        raise hip.SdfError("the training path runs on the GPU only (no CPU fallback)")
+    H, W = x.shape[-2:]
+    unet = model.sttmultires_unet
+    sw = unet.encoders.swin3d
+    y = patch_embed(x.float(), sw.patch_embed).permute(1, 0, 3, 4, 2).contiguous()          # (B, D, h, w, C)
+    blocks = []
+    for i, layer in enumerate(sw.layers):
+        for blk in layer.swin_blocks:
+            y = sew_block(y, blk, model.training)
+        if i in sw.out_indices:
+            blocks.append(y.permute(1, 0, 4, 2, 3).contiguous())                            # (D, B, C, h, w)
+        if layer.downsample is not None:
+            y = sew_patch_merge(y, layer.downsample)
+    y = blocks[-1]
+    for rb in unet.resblocks:
+        y = sew_resblock(y, rb)
+    preds, E = [], len(blocks)
+    for i in range(E):
+        y = skip_concat_ch(y, blocks[E - i - 1])
+        if i > 0:
+            y = skip_concat_ch(preds[-1], y)
+        dec, pr = unet.decoders[i], unet.preds[i]
+        T, B = y.shape[:2]
+        dc = dec.deconv[0]
+        z = F.conv_transpose2d(y.flatten(0, 1), dc.weight, dc.bias, stride=2, padding=dc.kernel_size[0] // 2, output_padding=1)
+        y = dec.sn(_bn_ch2(z.view(T, B, *z.shape[1:]), dec.norm_layer.norm_layer))
+        preds.append(_conv_seq(y, pr.conv[0], padding=0))
     flows = []
     for f in preds:
         f = f.sum(0)
@@ -400,11 +527,12 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
     :248, :314-331); here the same regions run under bf16 autocast (no scaler needed) - spikes are exact in bf16, the
     membranes / neuron kernels, BatchNorm statistics, the loss and the optimiser stay fp32.
     An STTFlowNet (the ANN family, `clip_grad=None` as its config has it) trains through its own train-mode forward,
-    `model(chunk, None)["flow"]`, in fp32.
+    `model(chunk, None)["flow"]`, in fp32; a SpikingformerFlowNet (the SEW family) through `forward_train_sew`.
     `forward_fn(model, chunk) -> flows` replaces the HIP train-mode forward (the CPU dry run of the N > 1 plumbing, bench.py --train
     --plumbing: everything else in this function is the code the GPU ranks run)."""
     from .spikingjelly_compat import functional
     from .STSwinNet.STSwinNet import STTFlowNet
+    from .STSwinNet_SNN.Spiking_STSwinNet import SpikingformerFlowNet
     ann = isinstance(model, STTFlowNet)             # the ANN family (train_flow_parallel_supervised.py): model(voxel, cnt)["flow"]
     if ann and amp:
         raise NotImplementedError("the ANN model trains in fp32 (configs/train_DSEC_supervised_STT_voxel.yml: use_amp False)")
@@ -420,6 +548,8 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
             flows = forward_fn(model, chunk)
         elif ann:
             flows = model(chunk, None)["flow"]
+        elif isinstance(model, SpikingformerFlowNet):
+            flows = forward_train_sew(model, chunk)
         else:
             flows = forward_train(model, chunk)
     n_valid = global_valid_count(mask, dist, world)
