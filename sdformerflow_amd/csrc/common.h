@@ -24,6 +24,11 @@ static inline float sdf_inv_tau(int kind, float tau) {
   int ex;
   return frexpf(tau, &ex) == 0.5f ? 1.0f / tau : 0.f;
 }
+// constants of the ATan surrogate (neuron_step.h sg_atan), formed in double and rounded once
+static inline void sdf_atan_consts(float alpha, float& c_atan, float& half_alpha) {
+  c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
+  half_alpha = (float)((double)alpha / 2);
+}
 static inline bool sdf_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // Dynamic LDS above 64 KiB needs an opt-in (hipFuncSetAttribute) per kernel function AND per device.  `done` = one bit per device

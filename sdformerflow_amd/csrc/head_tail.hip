@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void h
               fire = h - v_th >= 0.f;
               vm = fire ? h - v_th : h;
             } else {
-              float h;
+              float h;                                                  // neuron_step.h's neuron_charge + fire_reset, written out: the calls change this kernel's registers
               if (is_if) h = vm + xv;
               else {
                 const float dl = reset0 ? (xv - vm) : (xv - (vm - v_reset));

@@ -10,6 +10,7 @@
 // rounded IEEE fp32 op - this file is compiled with -ffp-contract=off - and the only fused
 // operations are the explicit fmaf() of the BN prologue and of the PSN chain.
 #include "common.h"
+#include "neuron_step.h"
 
 namespace {
 
@@ -24,18 +25,6 @@ __device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_ca
 
 template <int KIND>
 struct Step;  // charge/fire/reset of one time step on a 4-vector
-
-__device__ __forceinline__ float lif_charge(float v, float x, float tau, float inv_tau, float v_reset, bool reset0) {
-  float d = reset0 ? (x - v) : (x - (v - v_reset));
-  float q = (inv_tau != 0.f) ? d * inv_tau : d / tau;   // power-of-two tau: multiplication is exact
-  return v + q;
-}
-
-__device__ __forceinline__ float fire_reset(float& v, float h, float v_th, float v_reset, bool soft) {
-  float s = (h - v_th >= 0.f) ? 1.f : 0.f;
-  v = soft ? (h - s * v_th) : ((1.f - s) * h + s * v_reset);
-  return s;
-}
 
 __device__ __forceinline__ void store_spikes(const NeuronParams& P, int64_t ooff, float4 s) {
   if (P.d.out_dtype == SDF_F32) {
@@ -130,20 +119,16 @@ __device__ __forceinline__ void neuron_body(const NeuronParams& P, int64_t q) {
       return;
     }
     const bool soft = P.d.soft_reset != 0;
-    const bool reset0 = soft || P.d.v_reset == 0.f;
+    const bool reset0 = soft || P.d.v_reset == 0.f, is_if = P.d.kind == SDF_IF;
     const float v0 = soft ? 0.f : P.d.v_reset;
     float4 v = make_float4(v0, v0, v0, v0);
 #pragma unroll
     for (int t = 0; t < TT; ++t) {
       float4 h, s;
-      if (P.d.kind == SDF_IF) {
-        h.x = v.x + xv[t].x; h.y = v.y + xv[t].y; h.z = v.z + xv[t].z; h.w = v.w + xv[t].w;
-      } else {
-        h.x = lif_charge(v.x, xv[t].x, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-        h.y = lif_charge(v.y, xv[t].y, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-        h.z = lif_charge(v.z, xv[t].z, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-        h.w = lif_charge(v.w, xv[t].w, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-      }
+      h.x = neuron_charge(is_if, v.x, xv[t].x, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+      h.y = neuron_charge(is_if, v.y, xv[t].y, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+      h.z = neuron_charge(is_if, v.z, xv[t].z, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+      h.w = neuron_charge(is_if, v.w, xv[t].w, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
       s.x = fire_reset(v.x, h.x, P.d.v_th, P.d.v_reset, soft);
       s.y = fire_reset(v.y, h.y, P.d.v_th, P.d.v_reset, soft);
       s.z = fire_reset(v.z, h.z, P.d.v_th, P.d.v_reset, soft);
@@ -154,7 +139,7 @@ __device__ __forceinline__ void neuron_body(const NeuronParams& P, int64_t q) {
   } else {
     // runtime T: sequential neurons only (PSN with an unlisted T is rejected on the host)
     const bool soft = P.d.soft_reset != 0;
-    const bool reset0 = soft || P.d.v_reset == 0.f;
+    const bool reset0 = soft || P.d.v_reset == 0.f, is_if = P.d.kind == SDF_IF;
     const float v0 = soft ? 0.f : P.d.v_reset;
     float4 v = make_float4(v0, v0, v0, v0);
     const float* p = x_addr(P, 0, e, b, r, xrep);
@@ -167,14 +152,10 @@ __device__ __forceinline__ void neuron_body(const NeuronParams& P, int64_t q) {
       }
       x = prologue(P, x, t, r, al, be);
       float4 h, s;
-      if (P.d.kind == SDF_IF) {
-        h.x = v.x + x.x; h.y = v.y + x.y; h.z = v.z + x.z; h.w = v.w + x.w;
-      } else {
-        h.x = lif_charge(v.x, x.x, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-        h.y = lif_charge(v.y, x.y, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-        h.z = lif_charge(v.z, x.z, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-        h.w = lif_charge(v.w, x.w, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
-      }
+      h.x = neuron_charge(is_if, v.x, x.x, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+      h.y = neuron_charge(is_if, v.y, x.y, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+      h.z = neuron_charge(is_if, v.z, x.z, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+      h.w = neuron_charge(is_if, v.w, x.w, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
       s.x = fire_reset(v.x, h.x, P.d.v_th, P.d.v_reset, soft);
       s.y = fire_reset(v.y, h.y, P.d.v_th, P.d.v_reset, soft);
       s.z = fire_reset(v.z, h.z, P.d.v_th, P.d.v_reset, soft);
@@ -237,7 +218,7 @@ __global__ __launch_bounds__(256) void neuron_scalar_kernel(const float* __restr
   float v = soft ? 0.f : v_reset;
   for (int t = 0; t < T; ++t) {
     const float xt = x[(int64_t)t * N + n];
-    const float h = kind == SDF_IF ? v + xt : lif_charge(v, xt, tau, inv_tau, v_reset, reset0);
+    const float h = neuron_charge(kind == SDF_IF, v, xt, tau, inv_tau, v_reset, reset0);
     put(t, fire_reset(v, h, v_th, v_reset, soft));
   }
   if (v_last) v_last[n] = v;
@@ -381,7 +362,8 @@ extern "C" int sdf_psn_fwd(const float* x, const float* W, const float* b, void*
 namespace {
 
 // Training-path PLIF forward: the multiplier k = sigmoid(w) is read from device memory (one fp32 scalar, written by the caller's
-// sigmoid on the same stream), so a train step needs no host read-back per neuron.  Arithmetic = lif_charge with inv_tau = k.
+// sigmoid on the same stream), so a train step needs no host read-back per neuron.  Arithmetic = lif_charge with inv_tau = k
+// (plif_charge's single multiply costs this kernel a register, and a wave per SIMD at T = 16).
 template <int TT>
 __global__ __launch_bounds__(256) void plif_fwd_kernel(const float* x, const float* kp, float* spike, int64_t N, float v_th,
                                                        int soft_reset, float v_reset) {

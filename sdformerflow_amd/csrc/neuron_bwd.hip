@@ -16,6 +16,7 @@
 // workgroup (LDS) -> per-workgroup partials in the caller's workspace, summed in a fixed order by a second tiny kernel
 // (deterministic, no atomics).
 #include "common.h"
+#include "neuron_step.h"
 
 namespace {
 
@@ -31,23 +32,23 @@ struct BwdParams {
   const float* b;
   float* partial;                  // [nblk][T*T + T]
   float* gh_out;                   // optional (T, N)
+  const float* plif_k;             // PLIF: the multiplier k = sigmoid(w), one fp32 in device memory
 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
-// torch: alpha / 2 / (1 + (pi / 2 * alpha * u).pow(2)) * g   ==   ((1 + t*t).reciprocal() * (alpha/2)) * g
-__device__ __forceinline__ float sg_atan(float u, float g, float c, float ha) {
-  const float t = c * u;
-  const float y = 1.f + t * t;
-  return ((1.f / y) * ha) * g;
-}
-
-template <int TT>
+// LIF / IF, and PLIF (spikingjelly ParametricLIFNode, h = v + d * k with k = sigmoid(w) read from device memory): the same
+// streaming shape and BPTT with gx = gh * k, gv = gh - gh * k (k = 0.5 is LIF tau = 2 bit for bit), plus dL/dk = sum_t sum_i gh_t * d_t,
+// d_t the charge difference the forward used, kept beside h_t (167 VGPRs at T = 10, 3 waves per SIMD; LIF: 128, 4).
+// dL/dk: per lane over its steps and neurons -> wave butterfly -> workgroup (LDS) -> one partial per workgroup ->
+// psn_bwd_finish_kernel (fixed order).
+template <int TT, bool PLIF>
 __global__ __launch_bounds__(256) void lif_bwd_kernel(BwdParams P) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (q * 4 >= P.N) return;
-  const int64_t e = q * 4;
+  const bool live = q * 4 < P.N;
+  if (!PLIF && !live) return;
+  const int64_t e = live ? q * 4 : P.N - 4;                    // PLIF: lanes past the end re-read the last quad and add nothing
   float4 xv[TT], gv_[TT];
 #pragma unroll
   for (int t = 0; t < TT; ++t) xv[t] = ld4(P.x + (int64_t)t * P.N + e);
@@ -55,7 +56,9 @@ __global__ __launch_bounds__(256) void lif_bwd_kernel(BwdParams P) {
   for (int t = 0; t < TT; ++t) gv_[t] = ld4(P.gs + (int64_t)t * P.N + e);
   const bool soft = P.soft != 0, reset0 = soft || P.v_reset == 0.f, is_if = P.kind == SDF_IF;
   const float v0 = soft ? 0.f : P.v_reset;
+  const float k = PLIF ? *P.plif_k : 0.f;
   float hx[TT][4];                                             // membrane before fire, per step and neuron
+  float dx[PLIF ? TT : 1][4];
   {
     float v[4] = {v0, v0, v0, v0};
 #pragma unroll
@@ -64,46 +67,41 @@ __global__ __launch_bounds__(256) void lif_bwd_kernel(BwdParams P) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float h;
-        if (is_if) {
-          h = v[j] + xs[j];
-        } else {
-          const float d = reset0 ? (xs[j] - v[j]) : (xs[j] - (v[j] - P.v_reset));
-          h = v[j] + ((P.inv_tau != 0.f) ? d * P.inv_tau : d / P.tau);
-        }
-        const float s = (h - P.v_th >= 0.f) ? 1.f : 0.f;
-        v[j] = soft ? (h - s * P.v_th) : ((1.f - s) * h + s * P.v_reset);
+        if constexpr (PLIF) h = plif_charge(v[j], xs[j], k, P.v_reset, reset0, dx[t][j]);
+        else h = neuron_charge(is_if, v[j], xs[j], P.tau, P.inv_tau, P.v_reset, reset0);
+        fire_reset(v[j], h, P.v_th, P.v_reset, soft);
         hx[t][j] = h;
       }
     }
   }
   float gv[4] = {0.f, 0.f, 0.f, 0.f};                          // dL/dv_t flowing back from step t+1 (v_T is unused)
+  float acc = 0.f;
 #pragma unroll
   for (int t = TT - 1; t >= 0; --t) {
     const float gs[4] = {gv_[t].x, gv_[t].y, gv_[t].z, gv_[t].w};
     float gx[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float h = hx[t][j], u = h - P.v_th;
-      const float s = (u >= 0.f) ? 1.f : 0.f;
-      float gspike = gs[j];                                    // dL/ds_t, plus the reset path unless it is detached
-      float gh;
-      if (soft) {                                              // v_t = h - s * v_th
-        if (!P.detach) gspike = gspike + (-(gv[j] * P.v_th));
-        gh = gv[j] + sg_atan(u, gspike, P.c_atan, P.half_alpha);
-      } else {                                                 // v_t = (1 - s) * h + s * v_reset
-        if (!P.detach) gspike = gspike + (gv[j] * P.v_reset + (-(gv[j] * h)));
-        gh = gv[j] * (1.f - s) + sg_atan(u, gspike, P.c_atan, P.half_alpha);
-      }
-      if (is_if) {                                             // h = v + x
-        gx[j] = gh;
-        gv[j] = gh;
-      } else {                                                 // h = v + (x - v) / tau  (v_reset is a constant)
-        const float qd = (P.inv_tau != 0.f) ? gh * P.inv_tau : gh / P.tau;
-        gx[j] = qd;
-        gv[j] = gh - qd;
+      const float h = hx[t][j];
+      const float gh = bptt_gh(gv[j], gs[j], h, spike_of(h, P.v_th), P.v_th, P.v_reset, soft, P.detach != 0, P.c_atan, P.half_alpha);
+      if constexpr (PLIF) {
+        plif_charge_bwd(gh, k, gx[j], gv[j]);
+        acc = __builtin_fmaf(gh, dx[t][j], acc);
+      } else {
+        neuron_charge_bwd(is_if, gh, P.tau, P.inv_tau, gx[j], gv[j]);
       }
     }
-    st4(P.gx + (int64_t)t * P.N + e, make_float4(gx[0], gx[1], gx[2], gx[3]));
+    if (live) st4(P.gx + (int64_t)t * P.N + e, make_float4(gx[0], gx[1], gx[2], gx[3]));
+  }
+  if constexpr (PLIF) {
+    __shared__ float red[4];
+    if (!live) acc = 0.f;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) P.partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
   }
 }
 
@@ -230,77 +228,6 @@ __global__ __launch_bounds__(256) void psn_bwd_finish_kernel(const float* partia
   }
 }
 
-// PLIF (spikingjelly ParametricLIFNode, h = v + d * k with k = sigmoid(w) read from device memory): lif_bwd_kernel's streaming
-// shape and BPTT with gx = gh * k, gv = gh - gh * k (k = 0.5 is LIF tau = 2 bit for bit), plus dL/dk = sum_t sum_i gh_t * d_t,
-// d_t the charge difference the forward used, kept beside h_t (167 VGPRs at T = 10, 3 waves per SIMD; lif_bwd: 128, 4).
-// dL/dk: per lane over its steps and neurons -> wave butterfly -> workgroup (LDS) -> one partial per workgroup ->
-// psn_bwd_finish_kernel (fixed order).
-template <int TT>
-__global__ __launch_bounds__(256) void plif_bwd_kernel(BwdParams P, const float* kp) {
-  __shared__ float red[4];
-  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = q * 4 < P.N;
-  const int64_t e = live ? q * 4 : P.N - 4;                    // lanes past the end re-read the last quad and add nothing
-  const float k = *kp;
-  float4 xv[TT], gv_[TT];
-#pragma unroll
-  for (int t = 0; t < TT; ++t) xv[t] = ld4(P.x + (int64_t)t * P.N + e);
-#pragma unroll
-  for (int t = 0; t < TT; ++t) gv_[t] = ld4(P.gs + (int64_t)t * P.N + e);
-  const bool soft = P.soft != 0, reset0 = soft || P.v_reset == 0.f;
-  const float v0 = soft ? 0.f : P.v_reset;
-  float hx[TT][4], dx[TT][4];
-  {
-    float v[4] = {v0, v0, v0, v0};
-#pragma unroll
-    for (int t = 0; t < TT; ++t) {
-      const float xs[4] = {xv[t].x, xv[t].y, xv[t].z, xv[t].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float d = reset0 ? (xs[j] - v[j]) : (xs[j] - (v[j] - P.v_reset));
-        dx[t][j] = d;
-        const float h = v[j] + d * k;
-        const float s = (h - P.v_th >= 0.f) ? 1.f : 0.f;
-        v[j] = soft ? (h - s * P.v_th) : ((1.f - s) * h + s * P.v_reset);
-        hx[t][j] = h;
-      }
-    }
-  }
-  float gv[4] = {0.f, 0.f, 0.f, 0.f};
-  float acc = 0.f;
-#pragma unroll
-  for (int t = TT - 1; t >= 0; --t) {
-    const float gs[4] = {gv_[t].x, gv_[t].y, gv_[t].z, gv_[t].w};
-    float gx[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float h = hx[t][j], u = h - P.v_th;
-      const float s = (u >= 0.f) ? 1.f : 0.f;
-      float gspike = gs[j];
-      float gh;
-      if (soft) {
-        if (!P.detach) gspike = gspike + (-(gv[j] * P.v_th));
-        gh = gv[j] + sg_atan(u, gspike, P.c_atan, P.half_alpha);
-      } else {
-        if (!P.detach) gspike = gspike + (gv[j] * P.v_reset + (-(gv[j] * h)));
-        gh = gv[j] * (1.f - s) + sg_atan(u, gspike, P.c_atan, P.half_alpha);
-      }
-      const float qd = gh * k;
-      gx[j] = qd;
-      gv[j] = gh - qd;
-      acc = __builtin_fmaf(gh, dx[t][j], acc);
-    }
-    if (live) st4(P.gx + (int64_t)t * P.N + e, make_float4(gx[0], gx[1], gx[2], gx[3]));
-  }
-  if (!live) acc = 0.f;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) P.partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 int psn_vec(int T, bool reduce) { return (reduce && T >= 8) ? 2 : 4; }
 
 int psn_blocks(int T, int64_t N, bool reduce) {
@@ -322,13 +249,11 @@ extern "C" int sdf_lif_bwd(const float* x, const float* grad_spike, float* grad_
   BwdParams P = {};
   P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = kind; P.soft = soft_reset; P.detach = detach_reset;
   P.tau = tau; P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
-  int ex;
-  P.inv_tau = (kind == SDF_LIF && frexpf(tau, &ex) == 0.5f) ? 1.0f / tau : 0.f;
-  P.c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
-  P.half_alpha = (float)((double)alpha / 2);
+  P.inv_tau = sdf_inv_tau(kind, tau);
+  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   dim3 grid((unsigned)((N / 4 + 255) / 256)), block(256);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH(lif_bwd_kernel<TT>, grid, block, 0, s, P); break;
+#define SDF_T_CASE(TT) case TT: SDF_LAUNCH((lif_bwd_kernel<TT, false>), grid, block, 0, s, P); break;
   switch (T) {
     SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
     default: return SDF_E_SHAPE;
@@ -358,8 +283,7 @@ extern "C" int sdf_psn_bwd(const float* x, const float* W, const float* b, const
   BwdParams P = {};
   P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.W = W; P.b = b;
   P.partial = reinterpret_cast<float*>(workspace); P.gh_out = grad_h;
-  P.c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
-  P.half_alpha = (float)((double)alpha / 2);
+  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   const int nblk = psn_blocks(T, N, reduce);
   dim3 grid((unsigned)nblk), block(256);
   hipStream_t s = sdf_stream(stream);
@@ -404,13 +328,12 @@ extern "C" int sdf_plif_bwd(const float* x, const float* plif_k, const float* gr
   BwdParams P = {};
   P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = SDF_LIF; P.soft = soft_reset; P.detach = detach_reset;
   P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
-  P.c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
-  P.half_alpha = (float)((double)alpha / 2);
-  P.partial = reinterpret_cast<float*>(workspace);
+  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
+  P.partial = reinterpret_cast<float*>(workspace); P.plif_k = plif_k;
   const int nblk = (int)((N / 4 + 255) / 256);
   dim3 grid((unsigned)nblk), block(256);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH(plif_bwd_kernel<TT>, grid, block, 0, s, P, plif_k); break;
+#define SDF_T_CASE(TT) case TT: SDF_LAUNCH((lif_bwd_kernel<TT, true>), grid, block, 0, s, P); break;
   switch (T) {
     SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
     default: return SDF_E_SHAPE;

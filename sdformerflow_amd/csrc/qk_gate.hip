@@ -5,6 +5,7 @@
 // One lane per (row, 32-channel group): 32 B of q and k per step, all byte traffic.
 // Compiled with -ffp-contract=off (LIF ops are separately rounded; PSN uses explicit fmaf).
 #include "common.h"
+#include "neuron_step.h"
 
 namespace {
 constexpr int TQ_MAX = 4;
@@ -59,16 +60,8 @@ __global__ __launch_bounds__(256) void qk_gate_kernel(GateParams P) {
 #pragma unroll
     for (int t = 0; t < TQ_MAX; ++t) {
       if (t < P.Tq) {
-        float h;
-        if (P.kind == SDF_IF) {
-          h = v + a[t];
-        } else {
-          float dlt = reset0 ? (a[t] - v) : (a[t] - (v - P.v_reset));
-          h = v + ((P.inv_tau != 0.f) ? dlt * P.inv_tau : dlt / P.tau);
-        }
-        float s = (h - P.v_th >= 0.f) ? 1.f : 0.f;
-        v = soft ? (h - s * P.v_th) : ((1.f - s) * h + s * P.v_reset);
-        gate[t] = s;
+        const float h = neuron_charge(P.kind == SDF_IF, v, a[t], P.tau, P.inv_tau, P.v_reset, reset0);
+        gate[t] = fire_reset(v, h, P.v_th, P.v_reset, soft);
       }
     }
   }

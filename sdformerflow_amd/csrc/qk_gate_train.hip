@@ -11,6 +11,7 @@
 // carry gradients (the inference kernel of qk_gate.hip moves bytes).  PSN gates carry a learnable T' x T' matrix and bias: their
 // gradients are reduced wave -> workgroup -> per-workgroup partials -> fixed-order finish (deterministic, no atomics).
 #include "common.h"
+#include "neuron_step.h"
 
 namespace {
 
@@ -32,14 +33,16 @@ __device__ __forceinline__ float sum8(float v) {          // over the 8 lanes of
   return v;
 }
 
-template <int TQ>
-__device__ __forceinline__ void gate_neuron(const GateTrainParams& P, const float (&s)[TQ], float (&h)[TQ], float (&A)[TQ]) {
-  if (P.kind == SDF_PSN) {                                       // h = b + W s (the forward kernel's fma chain), A = (h >= 0)
+// PLIF (spikingjelly ParametricLIFNode): the multiplicative charge h = v + d * k; keeps the charge differences d_t for dL/dk
+template <int TQ, bool PLIF>
+__device__ __forceinline__ void gate_neuron(const GateTrainParams& P, float k, const float (&s)[TQ], float (&h)[TQ], float (&A)[TQ],
+                                            float (&d)[TQ]) {
+  if (!PLIF && P.kind == SDF_PSN) {                              // h = b + W s (the forward kernel's fma chain), A = (h >= 0)
 #pragma unroll
     for (int t = 0; t < TQ; ++t) {
       float hh = P.psn_b[t];
 #pragma unroll
-      for (int k = 0; k < TQ; ++k) hh = __builtin_fmaf(P.psn_w[t * TQ + k], s[k], hh);
+      for (int kk = 0; kk < TQ; ++kk) hh = __builtin_fmaf(P.psn_w[t * TQ + kk], s[kk], hh);
       h[t] = hh;
       A[t] = hh >= 0.f ? 1.f : 0.f;
     }
@@ -49,30 +52,9 @@ __device__ __forceinline__ void gate_neuron(const GateTrainParams& P, const floa
   float v = soft ? 0.f : P.v_reset;
 #pragma unroll
   for (int t = 0; t < TQ; ++t) {
-    if (P.kind == SDF_IF) {
-      h[t] = v + s[t];
-    } else {
-      const float d = reset0 ? (s[t] - v) : (s[t] - (v - P.v_reset));
-      h[t] = v + ((P.inv_tau != 0.f) ? d * P.inv_tau : d / P.tau);
-    }
-    A[t] = (h[t] - P.v_th >= 0.f) ? 1.f : 0.f;
-    v = soft ? (h[t] - A[t] * P.v_th) : ((1.f - A[t]) * h[t] + A[t] * P.v_reset);
-  }
-}
-
-// PLIF gate (spikingjelly ParametricLIFNode): the LIF recurrence with the multiplicative charge h = v + d * k; keeps the charge
-// differences d_t for dL/dk
-template <int TQ>
-__device__ __forceinline__ void gate_neuron_plif(const GateTrainParams& P, float k, const float (&s)[TQ], float (&h)[TQ], float (&A)[TQ],
-                                                 float (&d)[TQ]) {
-  const bool soft = P.soft != 0, reset0 = soft || P.v_reset == 0.f;
-  float v = soft ? 0.f : P.v_reset;
-#pragma unroll
-  for (int t = 0; t < TQ; ++t) {
-    d[t] = reset0 ? (s[t] - v) : (s[t] - (v - P.v_reset));
-    h[t] = v + d[t] * k;
-    A[t] = (h[t] - P.v_th >= 0.f) ? 1.f : 0.f;
-    v = soft ? (h[t] - A[t] * P.v_th) : ((1.f - A[t]) * h[t] + A[t] * P.v_reset);
+    if constexpr (PLIF) h[t] = plif_charge(v, s[t], k, P.v_reset, reset0, d[t]);
+    else h[t] = neuron_charge(P.kind == SDF_IF, v, s[t], P.tau, P.inv_tau, P.v_reset, reset0);
+    A[t] = fire_reset(v, h[t], P.v_th, P.v_reset, soft);
   }
 }
 
@@ -94,8 +76,7 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
   }
 #pragma unroll
   for (int t = 0; t < TQ; ++t) s[t] = sum8((qv[t].x + qv[t].y) + (qv[t].z + qv[t].w));      // spikes: an exact integer 0..32
-  if (PLIF) gate_neuron_plif<TQ>(P, kp, s, h, A, dch);
-  else gate_neuron<TQ>(P, s, h, A);
+  gate_neuron<TQ, PLIF>(P, kp, s, h, A, dch);
   if (!BWD) {
     if (live) {
 #pragma unroll
@@ -112,10 +93,7 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
     // gh = gA * g'(h);  gs_k = sum_t W[t][k] gh_t;  dW[t][k] += gh_t s_k, db[t] += gh_t over all (row, head) pairs
     float gh[TQ];
 #pragma unroll
-    for (int t = 0; t < TQ; ++t) {
-      const float tt = P.c_atan * h[t], y = 1.f + tt * tt;
-      gh[t] = ((1.f / y) * P.half_alpha) * gA[t];
-    }
+    for (int t = 0; t < TQ; ++t) gh[t] = sg_atan(h[t], gA[t], P.c_atan, P.half_alpha);
 #pragma unroll
     for (int k = 0; k < TQ; ++k) {
       float g = 0.f;
@@ -156,33 +134,17 @@ __global__ __launch_bounds__(256) void qk_gate_train_kernel(GateTrainParams P) {
       P.partial[(int64_t)blockIdx.x * NACC + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
     return;
   }
-  // BPTT through the gate neuron (the recurrence of neuron_bwd.hip on the TQ head sums)
+  // BPTT through the gate neuron on the TQ head sums
   const bool soft = P.soft != 0;
   float gvm = 0.f, acc = 0.f;
 #pragma unroll
   for (int t = TQ - 1; t >= 0; --t) {
-    const float u = h[t] - P.v_th;
-    float gsp = gA[t], gh;
-    const float tt = P.c_atan * u, y = 1.f + tt * tt;
-    if (soft) {
-      if (!P.detach) gsp = gsp + (-(gvm * P.v_th));
-      gh = gvm + ((1.f / y) * P.half_alpha) * gsp;
-    } else {
-      if (!P.detach) gsp = gsp + (gvm * P.v_reset + (-(gvm * h[t])));
-      gh = gvm * (1.f - A[t]) + ((1.f / y) * P.half_alpha) * gsp;
-    }
-    if (PLIF) {                                                  // h = v + d * k: gd = gh * k, dL/dk += gh * d
-      const float qd = gh * kp;
-      gs[t] = qd;
-      gvm = gh - qd;
+    const float gh = bptt_gh(gvm, gA[t], h[t], A[t], P.v_th, P.v_reset, soft, P.detach != 0, P.c_atan, P.half_alpha);
+    if (PLIF) {                                                  // dL/dk += gh * d
+      plif_charge_bwd(gh, kp, gs[t], gvm);
       acc = __builtin_fmaf(gh, dch[t], acc);
-    } else if (P.kind == SDF_IF) {
-      gs[t] = gh;
-      gvm = gh;
     } else {
-      const float qd = (P.inv_tau != 0.f) ? gh * P.inv_tau : gh / P.tau;
-      gs[t] = qd;
-      gvm = gh - qd;
+      neuron_charge_bwd(P.kind == SDF_IF, gh, P.tau, P.inv_tau, gs[t], gvm);
     }
   }
   if (live) {
@@ -209,8 +171,7 @@ int fill(GateTrainParams& P, int64_t rows, int C, int kind, float tau, float v_t
   if (kind == SDF_LIF && !(tau > 1.f)) return SDF_E_SHAPE;
   P.rows = rows; P.C = C; P.G = C / 32; P.kind = kind; P.soft = soft_reset; P.tau = tau; P.v_th = v_th;
   P.v_reset = soft_reset ? 0.f : v_reset;
-  int ex;
-  P.inv_tau = (kind == SDF_LIF && frexpf(tau, &ex) == 0.5f) ? 1.0f / tau : 0.f;
+  P.inv_tau = sdf_inv_tau(kind, tau);
   return 0;
 }
 
@@ -282,8 +243,7 @@ extern "C" int sdf_qk_gate_bwd(const float* q, const float* k, const float* grad
   if (rc) return rc;
   P.q = q; P.k = k; P.ge = grad_e; P.gq = grad_q; P.gk = grad_k; P.detach = detach_reset;
   P.psn_w = psn_w; P.psn_b = psn_b; P.partial = reinterpret_cast<float*>(workspace);
-  P.c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
-  P.half_alpha = (float)((double)alpha / 2);
+  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   const int rc2 = launch<true>(P, Tq, sdf_stream(stream));
   if (rc2 || kind != SDF_PSN) return rc2;
   const int64_t nblk = (rows * (C / 32) * 8 + 255) / 256;
@@ -327,8 +287,7 @@ extern "C" int sdf_qk_gate_plif_bwd(const float* q, const float* k, const float*
     return SDF_E_ALIGN;
   P.q = q; P.k = k; P.ge = grad_e; P.gq = grad_q; P.gk = grad_k; P.detach = detach_reset; P.plif_k = plif_k;
   P.partial = reinterpret_cast<float*>(workspace);
-  P.c_atan = (float)(3.14159265358979323846 / 2 * (double)alpha);
-  P.half_alpha = (float)((double)alpha / 2);
+  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   const int rc2 = launch<true, true>(P, Tq, sdf_stream(stream));
   if (rc2) return rc2;
   const int64_t nblk = (rows * (C / 32) * 8 + 255) / 256;

@@ -353,15 +353,8 @@ __global__ __launch_bounds__(512) void spike_conv_wres_kernel(GemmParams P) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               float& vm = vmem[q4 * 4 + j];
-              float hcur;
-              if (d.sn_kind == SDF_IF) {
-                hcur = vm + xs[j];
-              } else {
-                const float dl = (soft || d.v_reset == 0.f) ? (xs[j] - vm) : (xs[j] - (vm - d.v_reset));
-                hcur = vm + ((P.inv_tau != 0.f) ? dl * P.inv_tau : dl / d.tau);
-              }
-              const float s = (hcur - d.v_th >= 0.f) ? 1.f : 0.f;
-              vm = soft ? (hcur - s * d.v_th) : ((1.f - s) * hcur + s * d.v_reset);
+              const float hcur = neuron_charge(d.sn_kind == SDF_IF, vm, xs[j], d.tau, P.inv_tau, d.v_reset, soft || d.v_reset == 0.f);
+              const float s = fire_reset(vm, hcur, d.v_th, d.v_reset, soft);
               pk |= ((__float_as_uint(s) >> 29) & 1u) << (8 * j);     // 1.0f has bit 29 set
             }
             __builtin_amdgcn_raw_buffer_store_b32(pk, sp_rs, rowg[q4] != INV ? rowg[q4] * (uint32_t)N + (uint32_t)(n0 + 4 * qd) : INV, 0, 0);
@@ -797,15 +790,8 @@ __global__ __launch_bounds__(256 * NGRP) void spike_conv_wres_i8_kernel(GemmPara
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                   float& vm = vmem[rb * 16 + q4 * 4 + j];
-                  float hcur;
-                  if (d.sn_kind == SDF_IF) {
-                    hcur = vm + xs[j];
-                  } else {
-                    const float dl = (soft || d.v_reset == 0.f) ? (xs[j] - vm) : (xs[j] - (vm - d.v_reset));
-                    hcur = vm + ((P.inv_tau != 0.f) ? dl * P.inv_tau : dl / d.tau);
-                  }
-                  const float sp = (hcur - d.v_th >= 0.f) ? 1.f : 0.f;
-                  vm = soft ? (hcur - sp * d.v_th) : ((1.f - sp) * hcur + sp * d.v_reset);
+                  const float hcur = neuron_charge(d.sn_kind == SDF_IF, vm, xs[j], d.tau, P.inv_tau, d.v_reset, soft || d.v_reset == 0.f);
+                  const float sp = fire_reset(vm, hcur, d.v_th, d.v_reset, soft);
                   pk |= ((__float_as_uint(sp) >> 29) & 1u) << (8 * j);
                 }
               }

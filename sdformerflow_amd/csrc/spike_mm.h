@@ -1,6 +1,7 @@
 // Shared definitions of the spike matrix-multiply kernels (spike_gemm.hip, spike_mm_pp.hip, spike_splitk.hip).
 #pragma once
 #include "common.h"
+#include "neuron_step.h"
 #include <math.h>
 
 namespace sdfmm {
@@ -66,7 +67,7 @@ __device__ __forceinline__ bf16x8 expand_spikes(uint2 v) {
 }
 
 
-// LIF / IF recurrence over the T pre-activations a lane holds (same separately-rounded op sequence as neuron.hip).
+// LIF / IF recurrence over the T pre-activations a lane holds (neuron_step.h).
 // All flags are wave-uniform; the shipped configuration (LIF, soft reset, power-of-two tau) gets a branch-free body.
 template <int T>
 __device__ __forceinline__ void lif_steps(const float (&xs)[T], float (&sp)[T], int kind, bool soft, float v_reset, float v_th,
@@ -74,13 +75,10 @@ __device__ __forceinline__ void lif_steps(const float (&xs)[T], float (&sp)[T], 
   if (kind == SDF_LIF && soft && inv_tau != 0.f) {
     float v = 0.f;
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
-      const float hcur = v + (xs[t] - v) * inv_tau;
-      sp[t] = (hcur - v_th >= 0.f) ? 1.f : 0.f;
-      v = hcur - sp[t] * v_th;
-    }
+    for (int t = 0; t < T; ++t) sp[t] = lif_step_fast(v, xs[t], inv_tau, v_th);
     return;
   }
+  // neuron_step.h's neuron_charge + fire_reset, written out: the calls move a register between the files of a T = 20 wide kernel
   const bool reset0 = soft || v_reset == 0.f;
   float v = soft ? 0.f : v_reset;
 #pragma unroll
