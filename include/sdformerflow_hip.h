@@ -952,6 +952,57 @@ int sdf_linear_train_fwd(const SdfLinearTrainDesc* d, void* stream);
  * `norm1` / `norm2` of the blocks :231-233, `PatchMerging.norm` :356, the per-stage output norms :622-624).  C % 4 == 0, C <= 2048. */
 int sdf_layer_norm_fwd(const float* x, const float* gamma, const float* beta, float* out, int64_t rows, int C, float eps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Raw event lists -> voxel grid: the front end the model's input comes from when the data is not preprocessed.
+ * Replaces: VoxelGrid.convert_CHW / convert_CHW_polarities (reference DSEC_dataloader/event_representations.py:241-313), optionally with
+ * rectify_events (:20-28) in front and the input preparation of the evaluation loop behind (eval_DSEC_flow_SNN.py:179-217: centre crop,
+ * polarity split, min-max over the non-zeros, spike threshold).  Semantics are the reference's, quirks included:
+ *   t_norm = (C - 1) (t - t[0]) / (t[N-1] - t[0])  fp32, multiply then divide;  x0, y0, t0 = truncation toward zero;
+ *   the 8 corners (x0 | x0+1, y0 | y0+1, t0 | t0+1), kept iff inside [0, W) x [0, H) x [0, C);
+ *   weight (2p - 1) (1 - |xc - x|) (1 - |yc - y|) (1 - |tc - t_norm|), three fp32 products in that order (negative for x in (-1, 0));
+ *   a cell's sum is formed in the order of the reference's CPU put_: corner passes x outer / y middle / t inner, list order inside a pass.
+ * No float atomics: results are bit-identical from run to run and do not depend on how the lists are batched.
+ *
+ * B event lists lie back to back in x, y, t, p (n_events in all); `offsets` is a HOST array of B + 1 positions (NULL: B == 1).  A list
+ * is in time order; an empty list gives a zero grid.  A list with t[last] == t[first] has no t_norm (the reference returns NaN): pass
+ * the HOST array t_range = {t_first, t_last} per list and the call is refused with SDF_E_SHAPE before any launch; with t_range NULL it
+ * is not detected and that list's events add nothing.
+ * xy_dtype 0: x, y fp32 (already rectified, possibly fractional).  1 / 2: int32 / uint16 sensor coordinates, looked up in
+ * rectify_map (map_h, map_w, 2) fp32 as x, y <- map[y, x]; an event outside the map adds nothing.
+ * crop_h, crop_w > 0: only the centre window (crop_h, crop_w) of the (H, W) grid is computed and written; 0, 0: the whole grid.
+ * mode 0: out = the signed grid (B, C, h, w).
+ * mode 1: out = the model's input (B, C, 2, h, w): relu(v) | relu(-v); norm 1 = min-max over the non-zero elements of the whole output;
+ *         use_spike_th: > spike_th -> 1, < spike_th -> 0 (sdformerflow_amd.harness.prepare_chunk).  norm / use_spike_th: mode 1 only.
+ * mode 2: out = convert_CHW_polarities (B, C, 2, h, w): unsigned weights of the p == 1 | p == 0 events.
+ *
+ * Two calls with the caller's stable sort between them (the sort is plumbing: any stable sort of int32 keys):
+ *   sdf_event_voxel_keys_fwd    writes keys[n_events] (the event's base-cell key; events that touch no output cell sort last)
+ *   caller                      keys_sorted, order = stable ascending sort of keys (order: int64 positions into the event arrays)
+ *   sdf_event_voxel_gather_fwd  out, from keys_sorted, order and the workspace the first call filled
+ * workspace: sdf_event_voxel_workspace_bytes(...) bytes, 16-byte aligned, the same for both calls (0: refused geometry). */
+typedef struct SdfEventVoxelDesc {
+  const void* x;
+  const void* y;
+  const float* t;
+  const float* p;
+  const float* rectify_map;
+  const int64_t* offsets;
+  const float* t_range;
+  int32_t* keys;
+  const int32_t* keys_sorted;
+  const int64_t* order;
+  void* out;
+  void* workspace;
+  int64_t workspace_bytes, n_events;
+  int32_t B, C, H, W, crop_h, crop_w, map_h, map_w;
+  int32_t xy_dtype, mode, norm, use_spike_th;
+  float spike_th;
+} SdfEventVoxelDesc;
+
+int64_t sdf_event_voxel_workspace_bytes(int64_t n_events, int B, int C, int H, int W, int crop_h, int crop_w);
+int sdf_event_voxel_keys_fwd(const SdfEventVoxelDesc* d, void* stream);
+int sdf_event_voxel_gather_fwd(const SdfEventVoxelDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

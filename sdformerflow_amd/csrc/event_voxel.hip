@@ -1,0 +1,325 @@
+// Raw event lists -> voxel grid (the front end of "events in, flow out"), gfx950.
+//
+// Replaces the reference's VoxelGrid.convert_CHW / convert_CHW_polarities (DSEC_dataloader/event_representations.py:241-313: eight
+// put_(accumulate=True) passes over the event list) and, fused behind it, what the evaluation loop does to the grid before the model
+// sees it (eval_DSEC_flow_SNN.py:179-217: centre crop, polarity split, min-max over the non-zeros, spike threshold).
+//
+// No float atomics.  A cell's sum is formed by ONE lane in the order the reference's CPU put_ forms it: the eight corner passes in
+// their order (x outer, y middle, t inner), events in list order inside a pass.  The order is made available by a stable sort of the
+// events by the integer key of their BASE cell (x0, y0, t0): the run of base cell (X - dx, Y - dy, c - dt) in the sorted list is
+// exactly the events pass (dx, dy, dt) adds to cell (c, Y, X), in list order.  The sort itself is the caller's (sdf_event_voxel_keys_fwd
+// writes the keys, the caller sorts them stably, sdf_event_voxel_gather_fwd takes the sorted keys and the permutation); nothing here
+// depends on how the events are split over workgroups, so two runs - or two different batchings - give the same bits.
+//
+// Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | runs + permute | gather | [finish].
+#include "common.h"
+
+namespace {
+
+constexpr int kLongRun = 48;     // runs at least this long are summed by their lane with the whole wave fetching and weighting for it
+
+struct EvGeom {
+  int32_t B, C, h, w, ox, oy;    // output window (h, w) at offset (oy, ox) inside the (H, W) sensor grid
+  int32_t KT;                    // number of keys = B (C + 1) (h + 1) (w + 1); KT itself = "touches no output cell"
+};
+
+__device__ __forceinline__ int ev_key(const EvGeom& g, int b, int kt, int ky, int kx) {
+  return ((b * (g.C + 1) + kt) * (g.h + 1) + ky) * (g.w + 1) + kx;
+}
+
+// XY: 0 = fp32 coordinates as given, 1 = int32 sensor coordinates through the rectify map, 2 = uint16 likewise
+template <int XY>
+__global__ __launch_bounds__(256) void ev_keys_kernel(const void* __restrict__ xs, const void* __restrict__ ys, const float* __restrict__ t,
+                                                      const float* __restrict__ p, const float* __restrict__ map, int map_h, int map_w,
+                                                      int64_t i0, int n, int b, EvGeom g, int* __restrict__ keys, float4* __restrict__ rec) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t e = i0 + i;
+  float x, y;
+  bool ok = true;
+  if (XY == 0) {
+    x = static_cast<const float*>(xs)[e];
+    y = static_cast<const float*>(ys)[e];
+  } else {
+    int xi, yi;
+    if (XY == 1) {
+      xi = static_cast<const int32_t*>(xs)[e];
+      yi = static_cast<const int32_t*>(ys)[e];
+    } else {
+      xi = static_cast<const uint16_t*>(xs)[e];
+      yi = static_cast<const uint16_t*>(ys)[e];
+    }
+    ok = xi >= 0 && xi < map_w && yi >= 0 && yi < map_h;        // (the reference asserts this; here such an event adds nothing)
+    const int64_t m = ok ? ((int64_t)yi * map_w + xi) * 2 : 0;
+    x = map[m];
+    y = map[m + 1];
+  }
+  // t_norm = (C - 1) (t - t[0]) / (t[N-1] - t[0]): multiply, then divide, each rounded to fp32 (event_representations.py:255)
+  const float t_first = t[i0], t_last = t[i0 + n - 1];
+  const float tn = ((float)(g.C - 1) * (t[e] - t_first)) / (t_last - t_first);
+  // float range first (NaN fails every comparison), so that the truncations below are exact
+  ok = ok && x > (float)(g.ox - 2) && x < (float)(g.ox + g.w + 1) && y > (float)(g.oy - 2) && y < (float)(g.oy + g.h + 1) &&
+       tn > -2.f && tn < (float)(g.C + 1);
+  int key = g.KT;
+  if (ok) {
+    const int kx = (int)x - g.ox + 1, ky = (int)y - g.oy + 1, kt = (int)tn + 1;      // .int(): truncation toward zero
+    if (kx >= 0 && kx <= g.w && ky >= 0 && ky <= g.h && kt >= 0 && kt <= g.C) key = ev_key(g, b, kt, ky, kx);
+  }
+  keys[e] = key;
+  rec[e] = make_float4(x, y, tn, p[e]);
+}
+
+// sorted position i: the event's record moves to its sorted place, and the first / last position of a key's run go to the run table
+__global__ __launch_bounds__(256) void ev_runs_kernel(const int* __restrict__ ks, const int64_t* __restrict__ order,
+                                                      const float4* __restrict__ rec, int n, int KT, float4* __restrict__ rec_s,
+                                                      int2* __restrict__ tab) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int k = ks[i];
+  if (k < 0 || k >= KT) return;
+  const int64_t e = order[i];
+  if (e < 0 || e >= n) return;
+  rec_s[i] = rec[e];
+  if (i == 0 || ks[i - 1] != k) tab[k].x = i;
+  if (i == n - 1 || ks[i + 1] != k) tab[k].y = i + 1;
+}
+
+// weight of an event for the corner at (xc, yc, tc): three fp32 products in the reference's order, nothing contracted
+template <int MODE>
+__device__ __forceinline__ void ev_add(const float4 r, float xc, float yc, float tc, float& acc, float& acc2) {
+  const float wx = 1.f - fabsf(xc - r.x), wy = 1.f - fabsf(yc - r.y), wt = 1.f - fabsf(tc - r.z);
+  if (MODE == 2) {
+    const float wgt = (wx * wy) * wt;
+    if (r.w == 1.f) acc += wgt;
+    if (r.w == 0.f) acc2 += wgt;
+  } else {
+    acc += (((2.f * r.w - 1.f) * wx) * wy) * wt;
+  }
+}
+
+// relu as ATen's device clamp_min forms it: NaN stays, else fmaxf(v, 0) = v_max_f32, which orders -0 below +0: relu(-0) = +0
+__device__ __forceinline__ float ev_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
+// MODE 0: signed grid (B, C, h, w).  1: relu(v) | relu(-v) as (B, C, 2, h, w) (+ min / max of the non-zeros into mm when asked).
+// 2: convert_CHW_polarities, unsigned weights of the p == 1 | p == 0 events as (B, C, 2, h, w).
+template <int MODE>
+__global__ __launch_bounds__(256) void ev_gather_kernel(const int2* __restrict__ tab, const float4* __restrict__ rec, float* __restrict__ out,
+                                                        unsigned* __restrict__ mm, EvGeom g, int want_minmax) {
+  const int64_t total = (int64_t)g.B * g.C * g.h * g.w;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool active = idx < total;
+  const int64_t cell = active ? idx : 0;
+  const int lane = threadIdx.x & 63;
+  const int xx = (int)(cell % g.w), yy = (int)((cell / g.w) % g.h);
+  const int c = (int)((cell / ((int64_t)g.w * g.h)) % g.C), b = (int)(cell / ((int64_t)g.w * g.h * g.C));
+  const float xc = (float)(xx + g.ox), yc = (float)(yy + g.oy), tc = (float)c;
+  float acc = 0.f, acc2 = 0.f;
+#pragma unroll 1
+  for (int pass = 0; pass < 8; ++pass) {
+    const int dx = pass >> 2, dy = (pass >> 1) & 1, dt = pass & 1;      // x outer, y middle, t inner
+    int2 r = make_int2(0, 0);
+    if (active) r = tab[ev_key(g, b, c - dt + 1, yy - dy + 1, xx - dx + 1)];
+    const bool is_long = r.y - r.x >= kLongRun;
+    if (!is_long)
+      for (int i = r.x; i < r.y; ++i) ev_add<MODE>(rec[i], xc, yc, tc, acc, acc2);
+    unsigned long long todo = __ballot(is_long);
+    while (todo) {                                                       // (wave-uniform)
+      const int L = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int s = __shfl(r.x, L), e = __shfl(r.y, L);
+      const float lxc = __shfl(xc, L), lyc = __shfl(yc, L), ltc = __shfl(tc, L);
+      for (int base = s; base < e; base += 64) {
+        float w1 = 0.f, w2 = 0.f;
+        if (base + lane < e) ev_add<MODE>(rec[base + lane], lxc, lyc, ltc, w1, w2);      // 0 + w = w: lane j holds event j's term
+        const int cnt = min(64, e - base);
+        for (int j = 0; j < cnt; ++j) {
+          const float a1 = __shfl(w1, j);
+          if (lane == L) acc += a1;                                      // (adding a skipped event's + 0 leaves acc as it is)
+          if (MODE == 2) {
+            const float a2 = __shfl(w2, j);
+            if (lane == L) acc2 += a2;
+          }
+        }
+      }
+    }
+  }
+  const int64_t hw = (int64_t)g.h * g.w, plane = (int64_t)yy * g.w + xx, bc = (int64_t)b * g.C + c;
+  if (MODE == 0) {
+    if (active) out[idx] = acc;
+    return;
+  }
+  float o1 = acc, o2 = acc2;
+  if (MODE == 1) {
+    o1 = ev_relu(acc);
+    o2 = ev_relu(-acc);
+  }
+  if (active) {
+    out[(bc * 2) * hw + plane] = o1;
+    out[(bc * 2 + 1) * hw + plane] = o2;
+  }
+  if (MODE == 1 && want_minmax) {
+    // non-zero values here are positive floats, which order as their bit patterns: integer min / max, any arrival order
+    unsigned lo = 0xffffffffu, hi = 0u;
+    if (active && o1 != 0.f) lo = hi = __float_as_uint(o1);
+    if (active && o2 != 0.f) {
+      lo = min(lo, __float_as_uint(o2));
+      hi = max(hi, __float_as_uint(o2));
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
+      hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
+    }
+    if (lane == 0 && hi != 0u) {
+      atomicMin(&mm[0], lo);
+      atomicMax(&mm[1], hi);
+    }
+  }
+}
+
+// harness.prepare_chunk's tail on output 1, in place: (v - lo) / (hi - lo) on the non-zeros when there are any and lo != hi; then the
+// spike threshold (> th: 1, < th: 0, == th: kept)
+__global__ __launch_bounds__(256) void ev_finish_kernel(float* __restrict__ out, int64_t n, const unsigned* __restrict__ mm, int want_minmax,
+                                                        int want_th, float th) {
+  const unsigned lob = mm[0], hib = mm[1];
+  const float lo = __uint_as_float(lob), hi = __uint_as_float(hib);
+  const bool norm = want_minmax && hib != 0u && lob != hib;
+  const float span = hi - lo;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float v = out[i];
+    if (norm && v != 0.f) v = (v - lo) / span;
+    if (want_th) v = v > th ? 1.f : (v < th ? 0.f : v);
+    out[i] = v;
+  }
+}
+
+inline int64_t pad256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+struct EvPlan {
+  EvGeom g;
+  int64_t off_rec, off_rec_s, off_tab, off_mm, bytes;
+};
+
+// geometry and workspace layout; false = SDF_E_SHAPE
+bool ev_plan(int64_t n, int B, int C, int H, int W, int crop_h, int crop_w, EvPlan& pl) {
+  if (n < 0 || n >= (1ll << 31) - 64 || B < 1 || C < 1 || H < 1 || W < 1 || crop_h < 0 || crop_w < 0 || crop_h > H || crop_w > W) return false;
+  if ((crop_h == 0) != (crop_w == 0)) return false;
+  EvGeom& g = pl.g;
+  g.B = B;
+  g.C = C;
+  g.h = crop_h ? crop_h : H;
+  g.w = crop_w ? crop_w : W;
+  g.oy = (H - g.h) / 2;            // harness.center_crop
+  g.ox = (W - g.w) / 2;
+  const int64_t KT = (int64_t)B * (C + 1) * (g.h + 1) * (g.w + 1);
+  if (KT >= (1ll << 31) - 1 || (int64_t)B * C * 2 * g.h * g.w >= (1ll << 40)) return false;
+  g.KT = (int)KT;
+  pl.off_rec = 0;
+  pl.off_rec_s = pl.off_rec + pad256(n * 16);
+  pl.off_tab = pl.off_rec_s + pad256(n * 16);
+  pl.off_mm = pl.off_tab + pad256(KT * 8);
+  pl.bytes = pl.off_mm + 256;
+  return true;
+}
+
+int ev_check(const SdfEventVoxelDesc* d, EvPlan& pl, const int64_t*& offs, int64_t* own) {
+  if (!d) return SDF_E_NULL;
+  if (!ev_plan(d->n_events, d->B, d->C, d->H, d->W, d->crop_h, d->crop_w, pl)) return SDF_E_SHAPE;
+  if (d->mode < 0 || d->mode > 2 || d->norm < 0 || d->norm > 1 || d->xy_dtype < 0 || d->xy_dtype > 2) return SDF_E_DTYPE;
+  if (d->mode != 1 && (d->norm || d->use_spike_th)) return SDF_E_DTYPE;          // normalisation and threshold belong to the model-input form
+  if (!d->workspace || !d->out) return SDF_E_NULL;
+  if (d->workspace_bytes < pl.bytes) return SDF_E_SHAPE;
+  if (!sdf_aligned(d->workspace, 16) || !sdf_aligned(d->out, 4)) return SDF_E_ALIGN;
+  offs = d->offsets;
+  if (!offs) {
+    if (d->B != 1) return SDF_E_NULL;
+    own[0] = 0;
+    own[1] = d->n_events;
+    offs = own;
+  }
+  if (offs[0] != 0 || offs[d->B] != d->n_events) return SDF_E_SHAPE;
+  for (int b = 0; b < d->B; ++b)
+    if (offs[b + 1] < offs[b]) return SDF_E_SHAPE;
+  if (d->t_range)
+    for (int b = 0; b < d->B; ++b)                                       // a list whose first and last time are equal has no t_norm
+      if (offs[b + 1] > offs[b] && !(d->t_range[2 * b + 1] != d->t_range[2 * b])) return SDF_E_SHAPE;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t sdf_event_voxel_workspace_bytes(int64_t n_events, int B, int C, int H, int W, int crop_h, int crop_w) {
+  EvPlan pl;
+  return ev_plan(n_events, B, C, H, W, crop_h, crop_w, pl) ? pl.bytes : 0;
+}
+
+extern "C" int sdf_event_voxel_keys_fwd(const SdfEventVoxelDesc* d, void* stream) {
+  EvPlan pl;
+  const int64_t* offs;
+  int64_t own[2];
+  if (int rc = ev_check(d, pl, offs, own)) return rc;
+  if (d->n_events == 0) return 0;
+  if (!d->x || !d->y || !d->t || !d->p || !d->keys) return SDF_E_NULL;
+  if (d->xy_dtype != 0 && (!d->rectify_map || d->map_h < 1 || d->map_w < 1)) return d->rectify_map ? SDF_E_SHAPE : SDF_E_NULL;
+  if (d->xy_dtype == 0 && d->rectify_map) return SDF_E_DTYPE;            // the map is indexed by integer sensor coordinates
+  if (!sdf_aligned(d->x, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->y, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->t, 4) ||
+      !sdf_aligned(d->p, 4) || !sdf_aligned(d->keys, 4) || (d->rectify_map && !sdf_aligned(d->rectify_map, 4)))
+    return SDF_E_ALIGN;
+  hipStream_t s = sdf_stream(stream);
+  float4* rec = reinterpret_cast<float4*>(static_cast<char*>(d->workspace) + pl.off_rec);
+  for (int b = 0; b < d->B; ++b) {
+    const int64_t i0 = offs[b];
+    const int n = (int)(offs[b + 1] - i0);
+    if (n == 0) continue;
+    const dim3 grid((n + 255) / 256), block(256);
+#define EV_KEYS(XY) \
+  SDF_LAUNCH(ev_keys_kernel<XY>, grid, block, 0, s, d->x, d->y, d->t, d->p, d->rectify_map, d->map_h, d->map_w, i0, n, b, pl.g, d->keys, rec)
+    if (d->xy_dtype == 0) EV_KEYS(0);
+    else if (d->xy_dtype == 1) EV_KEYS(1);
+    else EV_KEYS(2);
+#undef EV_KEYS
+    SDF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int sdf_event_voxel_gather_fwd(const SdfEventVoxelDesc* d, void* stream) {
+  EvPlan pl;
+  const int64_t* offs;
+  int64_t own[2];
+  if (int rc = ev_check(d, pl, offs, own)) return rc;
+  const int n = (int)d->n_events;
+  if (n && (!d->keys_sorted || !d->order)) return SDF_E_NULL;
+  if (n && (!sdf_aligned(d->keys_sorted, 4) || !sdf_aligned(d->order, 8))) return SDF_E_ALIGN;
+  hipStream_t s = sdf_stream(stream);
+  char* ws = static_cast<char*>(d->workspace);
+  const float4* rec = reinterpret_cast<const float4*>(ws + pl.off_rec);
+  float4* rec_s = reinterpret_cast<float4*>(ws + pl.off_rec_s);
+  int2* tab = reinterpret_cast<int2*>(ws + pl.off_tab);
+  unsigned* mm = reinterpret_cast<unsigned*>(ws + pl.off_mm);
+  const EvGeom& g = pl.g;
+  hipError_t e = hipMemsetAsync(tab, 0, (size_t)g.KT * 8, s);           // every run empty
+  if (e != hipSuccess) return (int)e;
+  if (d->norm) {
+    e = hipMemsetAsync(mm, 0xff, 4, s);                                  // min over nothing
+    if (e == hipSuccess) e = hipMemsetAsync(mm + 1, 0, 4, s);            // max over nothing: "no non-zero element"
+    if (e != hipSuccess) return (int)e;
+  }
+  if (n) {
+    SDF_LAUNCH(ev_runs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d->keys_sorted, d->order, rec, n, g.KT, rec_s, tab);
+    SDF_LAUNCH_CHECK();
+  }
+  const int64_t cells = (int64_t)g.B * g.C * g.h * g.w;
+  const dim3 grid((unsigned)((cells + 255) / 256)), block(256);
+  float* out = static_cast<float*>(d->out);
+  if (d->mode == 0) SDF_LAUNCH(ev_gather_kernel<0>, grid, block, 0, s, tab, rec_s, out, mm, g, 0);
+  else if (d->mode == 1) SDF_LAUNCH(ev_gather_kernel<1>, grid, block, 0, s, tab, rec_s, out, mm, g, d->norm);
+  else SDF_LAUNCH(ev_gather_kernel<2>, grid, block, 0, s, tab, rec_s, out, mm, g, 0);
+  SDF_LAUNCH_CHECK();
+  if (d->mode == 1 && (d->norm || d->use_spike_th)) {
+    const int64_t nout = cells * 2;
+    const unsigned blocks = (unsigned)((nout + 255) / 256 < 2048 ? (nout + 255) / 256 : 2048);
+    SDF_LAUNCH(ev_finish_kernel, dim3(blocks), block, 0, s, out, nout, mm, d->norm, d->use_spike_th, d->spike_th);
+    SDF_LAUNCH_CHECK();
+  }
+  return 0;
+}

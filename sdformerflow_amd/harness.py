@@ -35,22 +35,79 @@ def prepare_chunk(voxel, norm_input="minmax", spike_th=None, polarity=True):
     return chunk
 
 
+def event_times(ts):
+    """Integer sensor timestamps -> the fp32 times the voxeliser takes, as the reference's preprocessing forms them
+    (DSEC_dataset_preprocess.py:185-186): (t - t[0]) in integers, to fp32, divided by the last.  Floating times pass as fp32."""
+    if ts.is_floating_point() or ts.numel() == 0:
+        return ts.to(torch.float32)
+    t = (ts - ts[0]).to(torch.float32)
+    return t / t[-1]
+
+
+def events_to_chunk(events, bins, sensor_size, crop, norm_input, spike_th, rectify_map=None):
+    """Raw events -> network input (B, bins, 2, h, w) in one HIP launch sequence (hip.event_voxel): voxel grid with the reference's
+    semantics (event_representations.py:248-277), centre crop, polarity split, normalisation and spike threshold as
+    prepare_chunk(center_crop(grid)) gives them, bit for bit.  `events`: a dict of device tensors 'x', 'y', 'p' and 't' (or 'ts'), or a
+    list of B such dicts (one batch; min-max runs over the whole batch tensor, as prepare_chunk does).  x, y: fp32, or integer sensor
+    coordinates with `rectify_map` (H_s, W_s, 2).  norm_input "std" runs prepare_chunk's own code on the un-normalised output."""
+    from . import hip
+    lists = [events] if isinstance(events, dict) else list(events)
+    cols = {k: [] for k in "xytp"}
+    offsets = [0]
+    for ev in lists:
+        t = ev["t"] if "t" in ev else ev["ts"]
+        for a in (ev["x"], ev["y"], t, ev["p"]):
+            if not a.is_cuda:
+                raise hip.SdfError("HIP path needs device tensors (no CPU fallback)")
+        x, y = ev["x"], ev["y"]
+        if rectify_map is not None and x.dtype not in (torch.int32, torch.uint16):
+            x, y = x.to(torch.int32), y.to(torch.int32)
+        elif rectify_map is None:
+            x, y = x.to(torch.float32), y.to(torch.float32)
+        for k, a in zip("xytp", (x, y, event_times(t), ev["p"].to(torch.float32))):
+            cols[k].append(a.reshape(-1))
+        offsets.append(offsets[-1] + cols["t"][-1].numel())
+    x, y, t, p = (c[0] if len(c) == 1 else torch.cat(c) for c in (cols[k] for k in "xytp"))
+    fused = norm_input if norm_input == "minmax" else None
+    chunk = hip.event_voxel(x, y, t, p, bins, tuple(sensor_size), offsets=offsets, crop=tuple(crop) if crop else None, mode="split",
+                            norm=fused, spike_th=spike_th if norm_input != "std" else None, rectify_map=rectify_map)
+    if norm_input == "std":
+        chunk = prepare_chunk(chunk, "std", spike_th, polarity=False)
+    return chunk
+
+
 def evaluate(model, samples, config, device="cuda"):
     """Run `model` over an iterable of (chunk (B,bins,H,W), mask (B,H,W), label (B,2,H,W)) like
-    valid_test does and return the running-mean metrics dict (AEE, PE1-3, outliers) (:253-271, :283-305)."""
+    valid_test does and return the running-mean metrics dict (AEE, PE1-3, outliers) (:253-271, :283-305).
+    `chunk` may also be the raw event dict {'ts', 'x', 'y', 'p'} DSECDatasetLite yields when data.preprocessed is false (one sample;
+    mask (H,W), label (2,H,W)): it goes through events_to_chunk at loader.resolution / model.num_bins, on the device only."""
     from .loss.flow_supervised import AEE
     from .spikingjelly_compat import functional
     crop = config["loader"].get("crop")
     tot = {"AEE": 0.0, "PE1": 0.0, "PE2": 0.0, "PE3": 0.0, "outliers": 0.0}
     it = 0
     for chunk, mask, label in samples:
+        if isinstance(chunk, dict):
+            if not config["loader"].get("polarity", True):
+                raise ValueError("the event path builds the two-polarity input (loader.polarity: true)")
+            ev = {k: v.to(device) for k, v in chunk.items()}
+            x = events_to_chunk(ev, config["model"]["num_bins"], config["loader"]["resolution"], crop,
+                                config["model"].get("norm_input"), config["data"].get("spike_th"))
+            if label.dim() == 3:
+                label, mask = label.unsqueeze(0), mask.unsqueeze(0)
+            chunk = None
         functional.reset_net(model)
-        chunk, label = chunk.to(device, torch.float32), label.to(device, torch.float32)
+        label = label.to(device, torch.float32)
         mask = mask.to(device).unsqueeze(1).float()
+        if chunk is not None:
+            chunk = chunk.to(device, torch.float32)
         if crop:
-            chunk, label, mask = (center_crop(t, crop) for t in (chunk, label, mask))
-        x = prepare_chunk(chunk, config["model"].get("norm_input"), config["data"].get("spike_th"),
-                          config["loader"].get("polarity", True))
+            label, mask = center_crop(label, crop), center_crop(mask, crop)
+        if chunk is not None:
+            if crop:
+                chunk = center_crop(chunk, crop)
+            x = prepare_chunk(chunk, config["model"].get("norm_input"), config["data"].get("spike_th"),
+                              config["loader"].get("polarity", True))
         with torch.no_grad():
             pred = model(x)["flow"][-1]
         if config["metrics"].get("mask_events"):

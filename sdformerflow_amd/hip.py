@@ -249,6 +249,15 @@ class PredHeadDesc(C.Structure):
                 ("keep_spikes", C.c_void_p)]
 
 
+class EventVoxelDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("t", C.c_void_p), ("p", C.c_void_p), ("rectify_map", C.c_void_p),
+                ("offsets", C.c_void_p), ("t_range", C.c_void_p), ("keys", C.c_void_p), ("keys_sorted", C.c_void_p), ("order", C.c_void_p),
+                ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("n_events", C.c_int64),
+                ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32),
+                ("map_h", C.c_int32), ("map_w", C.c_int32), ("xy_dtype", C.c_int32), ("mode", C.c_int32), ("norm", C.c_int32),
+                ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
+
+
 # The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
 # plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
 # still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
@@ -306,6 +315,8 @@ SIGNATURES = {
     "sdf_linear_dw_splits": (_i, (_i64, _i, _i, _i)), "sdf_linear_dw_fwd": (_i, (_P(LinearDwDesc), _p)),
     "sdf_ringed_rows_fwd": (_i, (_p, _p, _i, _i, _i, _i, _p)), "sdf_unring_rows_fwd": (_i, (_p, _p, _p, _i, _i, _i, _i, _p)),
     "sdf_linear_train_fwd": (_i, (_P(LinearTrainDesc), _p)), "sdf_layer_norm_fwd": (_i, (_p, _p, _p, _p, _i64, _i, _f, _p)),
+    "sdf_event_voxel_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i)),
+    "sdf_event_voxel_keys_fwd": (_i, (_P(EventVoxelDesc), _p)), "sdf_event_voxel_gather_fwd": (_i, (_P(EventVoxelDesc), _p)),
 }
 
 
@@ -1809,4 +1820,82 @@ def deconv_col2im(Y, imgs, H, W, Cout, alpha=None, beta=None, out=None):
         out = torch.empty((imgs, 2 * H, 2 * W, Cout), dtype=torch.float32, device=Y.device)
     _check(lib().sdf_deconv_col2im_fwd(_ptr(Y, torch.float32), _ptr(alpha, torch.float32), _ptr(beta, torch.float32),
                                        _ptr(out, torch.float32), imgs, H, W, Cout, _stream()), "sdf_deconv_col2im_fwd")
+    return out
+
+
+EVENT_VOXEL_MODES = {"signed": 0, "split": 1, "polarities": 2}
+_EV_WS = {}
+
+
+def event_voxel(x, y, t, p, bins, sensor_size, offsets=None, crop=None, mode="signed", norm=None, spike_th=None, rectify_map=None,
+                check=True, out=None):
+    """Raw event lists -> voxel grid on the GPU (sdf_event_voxel_keys_fwd | stable sort | sdf_event_voxel_gather_fwd), with the semantics
+    and the per-cell summation order of the reference's VoxelGrid on the CPU (DSEC_dataloader/event_representations.py:241-313): the
+    result is bit-identical from run to run and independent of how lists are batched.
+
+    x, y: fp32 (rectified, possibly fractional) - or int32 / uint16 sensor coordinates with `rectify_map` (H_s, W_s, 2) fp32, looked up
+    as x, y <- map[y, x].  t, p: fp32, each list in time order.  `offsets`: B + 1 host ints cutting the arrays into B lists (None: one
+    list).  `sensor_size` (H, W); `crop` (h, w): only the centre window is computed.
+    mode "signed": (B, bins, h, w) | "split": the model's input (B, bins, 2, h, w) = relu(v) | relu(-v), with norm "minmax" / spike_th as
+    harness.prepare_chunk applies them | "polarities": convert_CHW_polarities (B, bins, 2, h, w).
+    A non-empty list whose first and last time are equal raises SdfError (`check` reads the two times back: one small copy; False
+    skips it, and such a list then adds nothing)."""
+    for a in (x, y, t, p):
+        _ptr(a)                                                          # (CPU tensors are refused, as everywhere)
+    n = int(t.numel())
+    if not (x.numel() == y.numel() == p.numel() == n and x.dim() == y.dim() == t.dim() == p.dim() == 1):
+        raise SdfError("event_voxel: x, y, t, p are 1-D arrays of one length")
+    if mode not in EVENT_VOXEL_MODES or norm not in (None, "minmax"):
+        raise SdfError(f"event_voxel: unknown mode {mode!r} / norm {norm!r} (norm 'std' is harness.prepare_chunk's, on the un-normalised output)")
+    offs = [0, n] if offsets is None else [int(o) for o in offsets]
+    B, (H, W) = len(offs) - 1, sensor_size
+    h, w = crop if crop else (H, W)
+    dev = t.device
+    d = EventVoxelDesc()
+    if x.dtype != y.dtype:
+        raise SdfError("event_voxel: x and y differ in dtype")
+    xy = {torch.float32: 0, torch.int32: 1, torch.uint16: 2}.get(x.dtype)
+    if xy is None:
+        raise SdfError(f"event_voxel: x, y are fp32, or int32 / uint16 with a rectify_map, not {x.dtype}")
+    x, y, t, p = x.contiguous(), y.contiguous(), t.contiguous(), p.contiguous()
+    d.x, d.y, d.t, d.p, d.xy_dtype = x.data_ptr(), y.data_ptr(), _ptr(t, torch.float32), _ptr(p, torch.float32), xy
+    if rectify_map is not None:
+        if rectify_map.dim() != 3 or rectify_map.shape[2] != 2:
+            raise SdfError("event_voxel: rectify_map is (H_s, W_s, 2)")
+        rectify_map = rectify_map.contiguous()
+        d.rectify_map, d.map_h, d.map_w = _ptr(rectify_map, torch.float32), rectify_map.shape[0], rectify_map.shape[1]
+    host_offs = (C.c_int64 * (B + 1))(*offs)
+    d.offsets, d.n_events = C.addressof(host_offs), n
+    d.B, d.C, d.H, d.W, d.crop_h, d.crop_w = B, bins, H, W, (h if crop else 0), (w if crop else 0)
+    d.mode, d.norm = EVENT_VOXEL_MODES[mode], int(norm == "minmax")
+    d.use_spike_th, d.spike_th = int(spike_th is not None), float(spike_th or 0.0)
+    if check and n:
+        ends = [i for b in range(B) if offs[b + 1] > offs[b] for i in (offs[b], offs[b + 1] - 1)]
+        if any(i < 0 or i >= n for i in ends):
+            raise SdfError("event_voxel: offsets outside the event arrays")
+        got = iter(t[torch.tensor(ends, device=dev, dtype=torch.long)].tolist())
+        flat = [v for b in range(B) for v in ((next(got), next(got)) if offs[b + 1] > offs[b] else (0.0, 1.0))]
+        host_range = (C.c_float * (2 * B))(*flat)
+        d.t_range = C.addressof(host_range)
+    need = lib().sdf_event_voxel_workspace_bytes(n, B, bins, H, W, d.crop_h, d.crop_w)
+    if need <= 0:
+        raise SdfError(f"event_voxel: geometry refused (B {B}, bins {bins}, sensor {H} x {W}, crop {crop}, {n} events)", rc=E_SHAPE)
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    if key not in _EV_WS or _EV_WS[key].numel() < need:
+        _EV_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _EV_WS[key]
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    shape = (B, bins, h, w) if mode == "signed" else (B, bins, 2, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise SdfError(f"event_voxel: out must be a contiguous {shape} tensor")
+    d.out = _ptr(out, torch.float32)
+    keys = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    d.keys = keys.data_ptr()
+    _check(lib().sdf_event_voxel_keys_fwd(C.byref(d), _stream()), "sdf_event_voxel_keys_fwd")
+    if n:
+        keys_sorted, order = torch.sort(keys, stable=True)               # plumbing: any stable sort serves
+        d.keys_sorted, d.order = keys_sorted.data_ptr(), order.data_ptr()
+    _check(lib().sdf_event_voxel_gather_fwd(C.byref(d), _stream()), "sdf_event_voxel_gather_fwd")
     return out
