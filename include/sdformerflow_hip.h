@@ -1003,6 +1003,61 @@ int64_t sdf_event_voxel_workspace_bytes(int64_t n_events, int B, int C, int H, i
 int sdf_event_voxel_keys_fwd(const SdfEventVoxelDesc* d, void* stream);
 int sdf_event_voxel_gather_fwd(const SdfEventVoxelDesc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Raw event lists -> the time-bilinear voxel grid of the MVSEC / MDR loaders, and the model's input behind it.
+ * Replaces: EventSequence(..., timestamp_multiplier, convert_to_relative=True) + EventSequenceToVoxelGrid_Pytorch (reference
+ * MDR_dataloader/loader_utils.py:344-389, 421-577) and the input preparation of eval_MV_flow_SNN.py:162-219 (old | new along the bins,
+ * polarity split, min-max over the non-zeros, spike threshold, event mask).  Semantics are the reference's, per list:
+ *   ts = t * t_scale - (t * t_scale)[0];  deltaT = ts[last] (1.0 if that is 0);  tn = (nb - 1) * ts / deltaT, all float64, multiply
+ *   then divide;  tis = floor(tn);  dts = fp32(tn - tis);  x, y truncated to integers;  pol = p with 0 -> -1;
+ *   left pass: grid[tis, y, x] += pol * (1 - dts) for 0 <= tis < nb;  right pass: grid[tis + 1, y, x] += pol * dts for tis + 1 < nb;
+ *   a cell sums its left-pass events in list order, then its right-pass events in list order, in fp32 (index_add_ on the CPU);
+ *   normalize: over the non-zero cells of the list's WHOLE (nb, H, W) grid, v <- (v - mean) / std (unbiased std; v - mean when std is
+ *   not > 0; nothing without a non-zero cell).  mean and std are fp64 sums combined in a fixed order, the quotient is formed in fp64
+ *   and rounded once.
+ * No float atomics: results are bit-identical from run to run and do not depend on how the lists are batched.
+ * Unlike the reference: an event with x outside [0, W) or y outside [0, H) adds nothing (the reference writes into a neighbouring row
+ * or bin, or raises); a list whose times are all equal goes to bin 0 with weight pol (its deltaT = 1.0 rule); an empty list gives zeros.
+ *
+ * n_lists event lists lie back to back in x, y, t, p (n_events in all, each list in time order); `offsets` is a HOST array of
+ * n_lists + 1 positions.  t is float64; `t_scale` is a HOST pointer to the float64 multiplier (NULL: 1.0).  xy_dtype 0 / 1 / 2: x, y
+ * fp32 / int32 / uint16.  crop_h, crop_w > 0: only the window (crop_h, crop_w) at (crop_oy, crop_ox) is written - and, without
+ * normalize, computed; 0, 0 (origin 0, 0): the whole grid.
+ * mode 0: out = the signed volumes (n_lists, nb, h, w).
+ * mode 1: out = the model's input (n_lists / lists_per_sample, lists_per_sample * nb, 2, h, w): the lists of a sample (old, new) one
+ *         after the other along the bins, relu(v) | relu(-v); norm 1 = min-max over the non-zero elements of the whole output;
+ *         use_spike_th: > spike_th -> 1, < spike_th -> 0; event_mask (may be NULL): (samples, 1, h, w) fp32, 1 where any element of the
+ *         pixel is non-zero.  lists_per_sample 1 | 2; norm / use_spike_th / event_mask / lists_per_sample 2: mode 1 only.
+ * mode 2: out = the pol=False form (n_lists, nb, 2, h, w): unsigned weights of the pol == 1 | pol == -1 events.
+ *
+ * Two calls with the caller's stable sort between them, as for sdf_event_voxel_*:
+ *   sdf_event_voxel_tb_keys_fwd    writes keys[n_events]
+ *   caller                         keys_sorted, order = stable ascending sort of keys (order: int64 positions into the event arrays)
+ *   sdf_event_voxel_tb_gather_fwd  out (and event_mask)
+ * workspace: sdf_event_voxel_tb_workspace_bytes(...) bytes, 16-byte aligned, the same for both calls (0: refused geometry). */
+typedef struct SdfEventVoxelTbDesc {
+  const void* x;
+  const void* y;
+  const double* t;
+  const double* t_scale;
+  const float* p;
+  const int64_t* offsets;
+  int32_t* keys;
+  const int32_t* keys_sorted;
+  const int64_t* order;
+  void* out;
+  float* event_mask;
+  void* workspace;
+  int64_t workspace_bytes, n_events;
+  int32_t n_lists, lists_per_sample, nb, H, W, crop_h, crop_w, crop_oy, crop_ox;
+  int32_t xy_dtype, normalize, mode, norm, use_spike_th;
+  float spike_th;
+} SdfEventVoxelTbDesc;
+
+int64_t sdf_event_voxel_tb_workspace_bytes(int64_t n_events, int n_lists, int nb, int H, int W, int crop_h, int crop_w, int crop_oy, int crop_ox, int normalize);
+int sdf_event_voxel_tb_keys_fwd(const SdfEventVoxelTbDesc* d, void* stream);
+int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

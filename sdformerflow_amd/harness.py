@@ -76,6 +76,112 @@ def events_to_chunk(events, bins, sensor_size, crop, norm_input, spike_th, recti
     return chunk
 
 
+def center_crop_origin(size, crop):
+    """torchvision.transforms.CenterCrop's origin, int(round((H - h) / 2.0)) per axis: (2, 45) for 260 x 346 cropped to 256 x 256."""
+    return tuple(int(round((s - c) / 2.0)) for s, c in zip(size, crop))
+
+
+def event_pairs_to_chunk(pairs, num_frames, sensor_size, crop, norm_input, spike_th, crop_origin=None, want_event_mask=False,
+                         timestamp_multiplier=1e6, normalize=True, num_chunks=2):
+    """Raw (old, new) event lists -> network input (B, 2 num_frames, 2, h, w) in one HIP launch sequence (hip.event_voxel_tb): per list
+    the reference's EventSequence(..., timestamp_multiplier, convert_to_relative=True) and EventSequenceToVoxelGrid_Pytorch
+    (MDR_dataloader/loader_utils.py:344-389, 421-577) with its per-list normalisation, the crop window (h, w) at `crop_origin` (default
+    torchvision CenterCrop's), then eval_MV_flow_SNN.py:162-213: old | new along the bins, polarity split, normalisation, spike
+    threshold - as prepare_chunk(cat(old, new)) gives them, bit for bit.  `pairs`: one (events_old, events_new) pair or a list of B of
+    them (min-max runs over the whole batch tensor); each a dict of device tensors 'ts' (or 't', float64), 'x', 'y', 'p'.
+    `want_event_mask`: also returns the loop's event mask (:217-219) as fp32 (B, 1, h, w).  norm_input "std" runs prepare_chunk's own
+    code on the un-normalised output.  num_chunks 1: only the new list of each pair is used (B, num_frames, 2, h, w)."""
+    from . import hip
+    if isinstance(pairs, tuple) and len(pairs) == 2 and isinstance(pairs[0], dict):
+        pairs = [pairs]
+    cols = {k: [] for k in "xytp"}
+    offsets = [0]
+    for pair in pairs:
+        for ev in (pair if num_chunks == 2 else pair[1:]):
+            t = ev["ts"] if "ts" in ev else ev["t"]
+            x, y, p = ev["x"], ev["y"], ev["p"]
+            for a in (x, y, t, p):
+                if not a.is_cuda:
+                    raise hip.SdfError("HIP path needs device tensors (no CPU fallback)")
+            if x.dtype not in (torch.float32, torch.int32, torch.uint16) or y.dtype != x.dtype:
+                x, y = x.to(torch.int32), y.to(torch.int32)                 # (.long(): truncation toward zero)
+            for k, a in zip("xytp", (x, y, t.to(torch.float64), p.to(torch.float32))):
+                cols[k].append(a.reshape(-1))
+            offsets.append(offsets[-1] + cols["t"][-1].numel())
+    x, y, t, p = (c[0] if len(c) == 1 else torch.cat(c) for c in (cols[k] for k in "xytp"))
+    fused = norm_input != "std"
+    out = hip.event_voxel_tb(x, y, t, p, num_frames, tuple(sensor_size), offsets=offsets, t_scale=timestamp_multiplier,
+                             crop=tuple(crop) if crop else None, crop_origin=crop_origin, normalize=normalize, mode="split",
+                             lists_per_sample=num_chunks, norm="minmax" if norm_input == "minmax" else None,
+                             spike_th=spike_th if fused else None, want_event_mask=want_event_mask and fused)
+    if fused:
+        return out
+    chunk = prepare_chunk(out, "std", spike_th, polarity=False)
+    return (chunk, chunk.sum(1).sum(1, keepdim=True).bool().float()) if want_event_mask else chunk
+
+
+def evaluate_mv(model, samples, config, device="cuda"):
+    """The model-facing loop of eval_MV_flow_SNN.py:157-249 over an iterable of sample dicts, either the reference loader's
+    ('event_volume_old', 'event_volume_new' (B, num_frames, h, w), 'flow' (B, 2, h, w), 'valid' (B, h, w)) or the raw form
+    ('events_old', 'events_new': event dicts, or lists of B of them; 'flow', 'valid' at the sensor's or the crop's size, with or without
+    the batch dim), which goes through event_pairs_to_chunk at loader.resolution / loader.crop / data.num_frames on the device only.
+    Honours data.num_chunks, loader.polarity, model.norm_input, data.spike_th and metrics.mask_events; returns the running means of
+    metrics.name: AEE (with PE1-3 and outliers) and AAE."""
+    from .loss import flow_supervised
+    from .spikingjelly_compat import functional
+    names = config["metrics"].get("name", ["AEE", "AAE"])
+    chunks = config["data"].get("num_chunks", 2)
+    polarity = config["loader"].get("polarity", True)
+    norm_input, spike_th = config["model"].get("norm_input"), config["data"].get("spike_th")
+    mask_events = config["metrics"].get("mask_events")
+    tot = {k: 0.0 for n in names for k in ((n, "PE1", "PE2", "PE3", "outliers") if n == "AEE" else (n,))}
+    it = 0
+    for data in samples:
+        functional.reset_net(model)
+        label = data["flow"].to(device, torch.float32)
+        mask = data["valid"].to(device, torch.float32)
+        if label.dim() == 3:
+            label, mask = label.unsqueeze(0), mask.unsqueeze(0)
+        mask = mask.unsqueeze(1)
+        event_mask = None
+        if "events_new" in data:
+            if not polarity:
+                raise ValueError("the event path builds the two-polarity input (loader.polarity: true)")
+            old, new = data["events_old"], data["events_new"]
+            pairs = [(old, new)] if isinstance(new, dict) else list(zip(old, new))
+            pairs = [tuple({k: v.to(device) for k, v in ev.items()} for ev in pair) for pair in pairs]
+            size, crop = tuple(config["loader"]["resolution"]), config["loader"].get("crop")
+            x = event_pairs_to_chunk(pairs, config["data"]["num_frames"], size, crop, norm_input, spike_th,
+                                     want_event_mask=bool(mask_events), num_chunks=chunks)
+            if mask_events:
+                x, event_mask = x
+            if crop and tuple(label.shape[-2:]) == size:
+                oy, ox = center_crop_origin(size, crop)
+                label, mask = label[..., oy:oy + crop[0], ox:ox + crop[1]], mask[..., oy:oy + crop[0], ox:ox + crop[1]]
+        else:
+            chunk = data["event_volume_new"].to(device, torch.float32)
+            if chunks == 2:
+                chunk = torch.cat((data["event_volume_old"].to(device, torch.float32), chunk), dim=1)
+            x = prepare_chunk(chunk, norm_input, spike_th, polarity)
+            if mask_events:
+                event_mask = x.sum(1).sum(1, keepdim=True).bool() if polarity else x.sum(1, keepdim=True).bool()
+        with torch.no_grad():
+            pred = model(x)["flow"][-1]
+        if mask_events:
+            mask = mask * event_mask
+        results = {n: getattr(flow_supervised, n)(pred, label, mask, config["metrics"]["flow_scaling"])() for n in names}
+        for b in range(pred.shape[0]):
+            it += 1
+            for n, m in results.items():
+                if n == "AEE":
+                    tot["AEE"] += float(m[0][b])
+                    for key, v in zip(("PE1", "PE2", "PE3", "outliers"), m[1:]):
+                        tot[key] += float(v.reshape(-1)[b] if v.numel() > 1 else v)
+                else:
+                    tot[n] += float(m[0].reshape(-1)[b] if m[0].numel() > 1 else m[0])
+    return {k: v / max(it, 1) for k, v in tot.items()}
+
+
 def evaluate(model, samples, config, device="cuda"):
     """Run `model` over an iterable of (chunk (B,bins,H,W), mask (B,H,W), label (B,2,H,W)) like
     valid_test does and return the running-mean metrics dict (AEE, PE1-3, outliers) (:253-271, :283-305).

@@ -258,6 +258,15 @@ class EventVoxelDesc(C.Structure):
                 ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
 
 
+class EventVoxelTbDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("t", C.c_void_p), ("t_scale", C.c_void_p), ("p", C.c_void_p),
+                ("offsets", C.c_void_p), ("keys", C.c_void_p), ("keys_sorted", C.c_void_p), ("order", C.c_void_p), ("out", C.c_void_p),
+                ("event_mask", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("n_events", C.c_int64),
+                ("n_lists", C.c_int32), ("lists_per_sample", C.c_int32), ("nb", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("crop_h", C.c_int32), ("crop_w", C.c_int32), ("crop_oy", C.c_int32), ("crop_ox", C.c_int32), ("xy_dtype", C.c_int32),
+                ("normalize", C.c_int32), ("mode", C.c_int32), ("norm", C.c_int32), ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
+
+
 # The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
 # plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
 # still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
@@ -317,6 +326,8 @@ SIGNATURES = {
     "sdf_linear_train_fwd": (_i, (_P(LinearTrainDesc), _p)), "sdf_layer_norm_fwd": (_i, (_p, _p, _p, _p, _i64, _i, _f, _p)),
     "sdf_event_voxel_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i)),
     "sdf_event_voxel_keys_fwd": (_i, (_P(EventVoxelDesc), _p)), "sdf_event_voxel_gather_fwd": (_i, (_P(EventVoxelDesc), _p)),
+    "sdf_event_voxel_tb_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i, _i, _i, _i)),
+    "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
 }
 
 
@@ -1825,6 +1836,7 @@ def deconv_col2im(Y, imgs, H, W, Cout, alpha=None, beta=None, out=None):
 
 EVENT_VOXEL_MODES = {"signed": 0, "split": 1, "polarities": 2}
 _EV_WS = {}
+_EV_TB_WS = {}
 
 
 def event_voxel(x, y, t, p, bins, sensor_size, offsets=None, crop=None, mode="signed", norm=None, spike_th=None, rectify_map=None,
@@ -1899,3 +1911,76 @@ def event_voxel(x, y, t, p, bins, sensor_size, offsets=None, crop=None, mode="si
         d.keys_sorted, d.order = keys_sorted.data_ptr(), order.data_ptr()
     _check(lib().sdf_event_voxel_gather_fwd(C.byref(d), _stream()), "sdf_event_voxel_gather_fwd")
     return out
+
+
+def event_voxel_tb(x, y, t, p, num_bins, sensor_size, offsets=None, t_scale=1.0, crop=None, crop_origin=None, normalize=True,
+                   mode="signed", lists_per_sample=1, norm=None, spike_th=None, want_event_mask=False, out=None):
+    """Raw event lists -> the time-bilinear voxel grid of the MVSEC / MDR loaders on the GPU (sdf_event_voxel_tb_keys_fwd | stable sort |
+    sdf_event_voxel_tb_gather_fwd), with the semantics and the per-cell summation order of the reference's
+    EventSequenceToVoxelGrid_Pytorch on the CPU (MDR_dataloader/loader_utils.py:421-577): bit-identical from run to run and independent
+    of how lists are batched.
+
+    x, y: fp32, int32 or uint16 pixels (truncated to integers).  t: float64, each list in time order; `t_scale` multiplies it in
+    float64 first (1e6 for the loaders' seconds).  p: fp32, 0 / 1 or -1 / +1.  `offsets`: L + 1 host ints cutting the arrays into L
+    lists (None: one list).  `sensor_size` (H, W); `crop` (h, w) at `crop_origin` (oy, ox), default torchvision CenterCrop's
+    int(round((H - h) / 2.0)).  `normalize`: each list by the mean / std of the non-zeros of its whole grid.
+    mode "signed": (L, num_bins, h, w) | "polarities": the pol=False form (L, num_bins, 2, h, w) | "split": the model's input
+    (L / lists_per_sample, lists_per_sample * num_bins, 2, h, w) = relu(v) | relu(-v) with a sample's lists (old, new) along the bins,
+    norm "minmax" / spike_th as harness.prepare_chunk applies them; with `want_event_mask` returns (input, mask (B, 1, h, w) fp32)."""
+    for a in (x, y, t, p):
+        _ptr(a)                                                          # (CPU tensors are refused, as everywhere)
+    n = int(t.numel())
+    if not (x.numel() == y.numel() == p.numel() == n and x.dim() == y.dim() == t.dim() == p.dim() == 1):
+        raise SdfError("event_voxel_tb: x, y, t, p are 1-D arrays of one length")
+    if mode not in EVENT_VOXEL_MODES or norm not in (None, "minmax"):
+        raise SdfError(f"event_voxel_tb: unknown mode {mode!r} / norm {norm!r} (norm 'std' is harness.prepare_chunk's, on the un-normalised output)")
+    if mode != "split" and (norm or spike_th is not None or want_event_mask or lists_per_sample != 1):
+        raise SdfError("event_voxel_tb: norm, spike_th, the event mask and paired lists belong to mode 'split'")
+    offs = [0, n] if offsets is None else [int(o) for o in offsets]
+    L, (H, W) = len(offs) - 1, sensor_size
+    if lists_per_sample not in (1, 2) or L < 1 or L % lists_per_sample:
+        raise SdfError(f"event_voxel_tb: {L} lists do not make samples of {lists_per_sample}")
+    h, w = crop if crop else (H, W)
+    oy, ox = crop_origin if crop_origin is not None else ((int(round((H - h) / 2.0)), int(round((W - w) / 2.0))) if crop else (0, 0))
+    dev = t.device
+    d = EventVoxelTbDesc()
+    if x.dtype != y.dtype:
+        raise SdfError("event_voxel_tb: x and y differ in dtype")
+    xy = {torch.float32: 0, torch.int32: 1, torch.uint16: 2}.get(x.dtype)
+    if xy is None:
+        raise SdfError(f"event_voxel_tb: x, y are fp32, int32 or uint16, not {x.dtype}")
+    x, y, t, p = x.contiguous(), y.contiguous(), t.contiguous(), p.contiguous()
+    d.x, d.y, d.t, d.p, d.xy_dtype = x.data_ptr(), y.data_ptr(), _ptr(t, torch.float64), _ptr(p, torch.float32), xy
+    host_scale = C.c_double(float(t_scale))
+    host_offs = (C.c_int64 * (L + 1))(*offs)
+    d.t_scale, d.offsets, d.n_events = C.addressof(host_scale), C.addressof(host_offs), n
+    d.n_lists, d.lists_per_sample, d.nb, d.H, d.W = L, lists_per_sample, num_bins, H, W
+    d.crop_h, d.crop_w, d.crop_oy, d.crop_ox = (h if crop else 0), (w if crop else 0), oy, ox
+    d.normalize, d.mode, d.norm = int(bool(normalize)), EVENT_VOXEL_MODES[mode], int(norm == "minmax")
+    d.use_spike_th, d.spike_th = int(spike_th is not None), float(spike_th or 0.0)
+    need = lib().sdf_event_voxel_tb_workspace_bytes(n, L, num_bins, H, W, d.crop_h, d.crop_w, oy, ox, d.normalize)
+    if need <= 0:
+        raise SdfError(f"event_voxel_tb: geometry refused ({L} lists, bins {num_bins}, sensor {H} x {W}, crop {crop} at {(oy, ox)}, "
+                       f"{n} events)", rc=E_SHAPE)
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    if key not in _EV_TB_WS or _EV_TB_WS[key].numel() < need:
+        _EV_TB_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _EV_TB_WS[key]
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    shape = {"signed": (L, num_bins, h, w), "polarities": (L, num_bins, 2, h, w),
+             "split": (L // lists_per_sample, lists_per_sample * num_bins, 2, h, w)}[mode]
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise SdfError(f"event_voxel_tb: out must be a contiguous {shape} tensor")
+    d.out = _ptr(out, torch.float32)
+    mask = torch.empty((shape[0], 1, h, w), dtype=torch.float32, device=dev) if want_event_mask else None
+    d.event_mask = _ptr(mask, torch.float32)
+    keys = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    d.keys = keys.data_ptr()
+    _check(lib().sdf_event_voxel_tb_keys_fwd(C.byref(d), _stream()), "sdf_event_voxel_tb_keys_fwd")
+    if n:
+        keys_sorted, order = torch.sort(keys, stable=True)               # plumbing: any stable sort serves
+        d.keys_sorted, d.order = keys_sorted.data_ptr(), order.data_ptr()
+    _check(lib().sdf_event_voxel_tb_gather_fwd(C.byref(d), _stream()), "sdf_event_voxel_tb_gather_fwd")
+    return (out, mask) if want_event_mask else out
