@@ -300,6 +300,33 @@ def test_argument_errors_are_reported_before_any_launch():
     assert lib.sdf_ringed_rows_fwd(None, p, 1, 96, 4, 4, None) == E_NULL and lib.sdf_ringed_rows_fwd(p, p, 1, 48, 4, 4, None) == E_SHAPE
 
 
+def test_win_attn_fwd_refuses_what_its_kernels_cannot_serve():
+    """The host dispatcher of csrc/win_attn.hip, with dummy pointers (refused before any launch): a mask whose window count does not
+    divide B_, a SEW token split that is not N, a row map outside the windowed ANN form, and misaligned q / out."""
+    from sdformerflow_amd import hip
+    lib = loaded_lib()
+    p = 0x10000
+    E_NULL, E_SHAPE, E_ALIGN = -1, -2, -4
+
+    def refused(mode=0, **kw):
+        d = hip.WinAttnDesc()
+        d.mode, d.q, d.k, d.v, d.out, d.scale, d.bias = mode, p, p, p, p, p, p
+        d.B_, d.nW, d.nH, d.N, d.hd, d.Tq, d.N1 = 4, 1, 3, 162, 32, 2, 81          # (valid in both modes but for **kw)
+        for f, v in kw.items():
+            setattr(d, f, v)
+        return lib.sdf_win_attn_fwd(C.byref(d), None)
+    assert refused(mask=p, nW=3) == E_SHAPE                     # B_ % nW != 0
+    assert refused(mask=p, nW=0) == E_SHAPE                     # nW < 1
+    assert refused(mode=1, mask=p, nW=3) == E_SHAPE
+    assert refused(mode=1, N1=80) == E_SHAPE                    # Tq * N1 != N
+    assert refused(mode=1, Tq=0, N1=162) == E_SHAPE             # Tq < 1
+    assert refused(mode=1, row_map=p, pad_qkv=p) == E_NULL      # the row map is the windowed ANN form
+    assert refused(row_map=p) == E_NULL                         # ... and needs the pad row
+    assert refused(q=p + 8) == E_ALIGN                          # ANN q: float4 loads
+    assert refused(mode=1, q=p + 2) == E_ALIGN                  # SEW q: 4 spikes per load
+    assert refused(out=p + 2) == E_ALIGN
+
+
 def test_product_never_imports_the_oracle():
     """The oracle is test infrastructure: nothing under sdformerflow_amd/ (nor bench.py outside its cpu_baseline leg) may import
     it, and there is no CPU fallback module to import instead."""
