@@ -1058,6 +1058,59 @@ int64_t sdf_event_voxel_tb_workspace_bytes(int64_t n_events, int n_lists, int nb
 int sdf_event_voxel_tb_keys_fwd(const SdfEventVoxelTbDesc* d, void* stream);
 int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Flow maps -> the per-sample sums of the evaluation metrics (reference loss/flow_supervised.py: AEE :119-149, AAE :163-175).
+ * pred, label (B, 2, H, W), valid (B, H, W), event_mask (B, H, W; may be NULL): fp32, contiguous.  Per pixel, every step one fp32
+ * operation in the reference's order, constants Python doubles rounded to fp32:
+ *   f = pred * flow_scaling;  m = valid [* event_mask];  e = sqrt((fx - lx)^2 + (fy - ly)^2) * m;  mag = sqrt(fx^2 + fy^2) * m;
+ *   gm = sqrt(lx^2 + ly^2) * m;  cos = clamp((fx lx + fy ly + 1e-7) / (mag * gm + 1e-7), -1 + 1e-7, 1 - 1e-7);  ang = acosf(cos) * m.
+ * Sample b writes row row0 + b of `table` (double[rows][8]; every other row is left as it is):
+ *   {n_valid = sum m, sum_err = sum e, n_pe1 = #(e > 1), n_pe2 = #(e > 2), n_pe3 = #(e > 3), n_outlier = #(e > 3 && e > 0.05f * mag),
+ *    sum_ang = sum ang, n_pixels = H W}
+ * with integer counts and fp64 sums of the fp32 values, formed lane -> wave -> workgroup -> one partial record per workgroup in the
+ * workspace, then added per sample in index order: no float atomics, bit-identical from run to run and independent of B.  A sample's
+ * record is that of a batch-1 call of the classes; their batch-coupled forms at B > 1 (`outliers.sum()` over the whole batch, the
+ * (B, 1, H, W) * (B, H, W) broadcast of AAE) are not reproduced.
+ * workspace: sdf_flow_metrics_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: refused geometry). */
+typedef struct SdfFlowMetricsDesc {
+  const float* pred;
+  const float* label;
+  const float* valid;
+  const float* event_mask;
+  double* table;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t B, H, W, row0, rows;
+  float flow_scaling;
+} SdfFlowMetricsDesc;
+
+int64_t sdf_flow_metrics_workspace_bytes(int B, int H, int W);
+int sdf_flow_metrics_fwd(const SdfFlowMetricsDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Signed voxel volume -> the model's input: harness.prepare_chunk(center_crop(voxel, crop), norm_input, spike_th, polarity=True)
+ * (reference eval_DSEC_flow_SNN.py:179-217) with every decision on the device; the output equals the torch composition bit for bit.
+ * voxel (B, bins, Hs, Ws) fp32 -> out (B, bins, 2, h, w) = relu(v) | relu(-v) on the window (crop_h, crop_w) at (crop_oy, crop_ox)
+ * (0, 0 at origin 0, 0: the whole volume).  norm 1: (v - lo) / (hi - lo) on the non-zeros, lo / hi their min / max (integer atomics on
+ * the bit patterns of positive floats: order-independent), when there is a non-zero and lo != hi - over the whole batch tensor
+ * (per_sample 0, the reference's semantics) or over each sample (per_sample 1: what B batch-1 calls compute).  norm 0: none; any other
+ * value ("std") is refused with SDF_E_DTYPE.  use_spike_th: > spike_th -> 1, < spike_th -> 0.  event_mask (may be NULL): (B, 1, h, w)
+ * fp32, 1 where any element of the pixel is non-zero in the result.
+ * workspace: sdf_prepare_chunk_workspace_bytes(B) bytes, 8-byte aligned (0: refused B). */
+typedef struct SdfPrepareChunkDesc {
+  const float* voxel;
+  float* out;
+  float* event_mask;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t B, bins, Hs, Ws, crop_h, crop_w, crop_oy, crop_ox;
+  int32_t norm, per_sample, use_spike_th;
+  float spike_th;
+} SdfPrepareChunkDesc;
+
+int64_t sdf_prepare_chunk_workspace_bytes(int B);
+int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,3 +225,201 @@ def evaluate(model, samples, config, device="cuda"):
             for key, v in zip(("PE1", "PE2", "PE3", "outliers"), m[1:]):
                 tot[key] += float(v.reshape(-1)[b] if v.numel() > 1 else v)
     return {k: v / max(it, 1) for k, v in tot.items()}
+
+
+def deal(items, streams, replicas):
+    """The items of an iterable, in iteration order, cut into groups of `replicas` (the last one may be smaller), the groups dealt
+    round-robin to the streams: yields (stream, index of the group's first item, [items])."""
+    group, first, g = [], 0, 0
+    for item in items:
+        group.append(item)
+        if len(group) == replicas:
+            yield g % streams, first, group
+            first, g, group = first + len(group), g + 1, []
+    if group:
+        yield g % streams, first, group
+
+
+def stream_plan(n, streams, replicas):
+    """How evaluate_stream serves n samples: [(stream, first sample, samples)] in issue order."""
+    return [(j, k, len(group)) for j, k, group in deal(range(n), streams, replicas)]
+
+
+class StreamEvaluator:
+    """The execution scheme of the throughput benchmark as a library call: every sample is a batch-1 evaluation, `replicas` of them go
+    through ONE launch sequence (model.forward_replicas: bit-equal to separate batch-1 forwards), captured as a HIP graph per stream
+    and replayed on `streams` streams; input preparation, metrics (loss.flow_supervised.FlowMetrics) and the optional copy of the flow
+    map are enqueued on the group's stream, and the host synchronises once, when run() forms the result.  An instance keeps its static
+    buffers and graphs between run() calls; `metrics` is the FlowMetrics of the last run (counts(): the raw per-sample table)."""
+
+    def __init__(self, model, config, device="cuda", replicas=10, streams=2, graphs=True):
+        if replicas < 1 or streams < 1:
+            raise ValueError("replicas and streams are at least 1")
+        self.model, self.config, self.device = model, config, torch.device(device)
+        self.R, self.F, self.graphs = int(replicas), int(streams), bool(graphs)
+        self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.F)]
+        self.slots = [None] * self.F                             # per stream: static buffers and {samples: [graph, flow]}
+        self.metrics = None
+        self.polarity = config["loader"].get("polarity", True)
+        self.norm_input, self.spike_th = config["model"].get("norm_input"), config["data"].get("spike_th")
+        self.mask_events = bool(config["metrics"].get("mask_events"))
+        self.crop = tuple(config["loader"]["crop"]) if config["loader"].get("crop") else None
+
+    # -- samples -------------------------------------------------------------------------------------------------------------------
+    def _units(self, samples):
+        """Every sample of every loader item as (kind, payload, label (1, 2, ., .), mask (1, 1, ., .)), label and mask still uncropped
+        and wherever the loader left them; kind: 'voxel' (signed volume (1, bins, Hs, Ws), cropped when prepared), 'events' (one event
+        dict), 'volume' (old | new volumes, no crop), 'pairs' (one (old, new) pair of event dicts)."""
+        chunks = self.config["data"].get("num_chunks", 2)
+        for item in samples:
+            if isinstance(item, dict):
+                label, mask = item["flow"], item["valid"]
+                if label.dim() == 3:
+                    label, mask = label.unsqueeze(0), mask.unsqueeze(0)
+                mask = mask.reshape(mask.shape[0], 1, *mask.shape[-2:])
+                if "events_new" in item:
+                    old, new = item["events_old"], item["events_new"]
+                    pairs = [(old, new)] if isinstance(new, dict) else list(zip(old, new))
+                    for b, pair in enumerate(pairs):
+                        yield "pairs", pair, label[b:b + 1], mask[b:b + 1]
+                else:
+                    vol = item["event_volume_new"]
+                    if chunks == 2:
+                        vol = torch.cat((item["event_volume_old"], vol), dim=1)
+                    for b in range(vol.shape[0]):
+                        yield "volume", vol[b:b + 1], label[b:b + 1], mask[b:b + 1]
+            else:
+                chunk, mask, label = item
+                if isinstance(chunk, dict):
+                    if label.dim() == 3:
+                        label, mask = label.unsqueeze(0), mask.unsqueeze(0)
+                    yield "events", chunk, label, mask.reshape(1, 1, *mask.shape[-2:])
+                else:
+                    for b in range(chunk.shape[0]):
+                        yield "voxel", chunk[b:b + 1], label[b:b + 1], mask[b:b + 1].reshape(1, 1, *mask.shape[-2:])
+
+    def _window(self, kind, label):
+        """(oy, ox, h, w) of the label / mask window the sample is scored on."""
+        H, W = label.shape[-2:]
+        if not self.crop or kind == "volume":
+            return 0, 0, H, W
+        h, w = self.crop
+        if kind == "pairs":
+            size = tuple(self.config["loader"]["resolution"])
+            oy, ox = center_crop_origin(size, self.crop) if (H, W) == size else (0, 0)
+            return oy, ox, (h if (H, W) == size else H), (w if (H, W) == size else W)
+        return (H - h) // 2, (W - w) // 2, h, w
+
+    def _input_shape(self, kind, payload, hw):
+        if kind in ("voxel", "volume"):
+            bins = payload.shape[1]
+        elif kind == "events":
+            bins = self.config["model"]["num_bins"]
+        else:
+            bins = self.config["data"]["num_frames"] * self.config["data"].get("num_chunks", 2)
+        return (bins, 2) + hw if self.polarity else (bins,) + hw
+
+    def _prepare(self, kind, payload, x, em):
+        """The model's input of one sample into x (1, ...), its event mask into em (1, 1, h, w) when asked - on the current stream."""
+        from . import hip
+        dev, cfg = self.device, self.config
+        if kind in ("events", "pairs") and not self.polarity:
+            raise ValueError("the event path builds the two-polarity input (loader.polarity: true)")
+        if kind in ("voxel", "volume"):
+            v = payload.to(dev, torch.float32)
+            crop = self.crop if kind == "voxel" else None
+            if self.polarity and self.norm_input != "std":
+                hip.prepare_chunk(v, crop, self.norm_input, self.spike_th, out=x, event_mask=em)
+                return
+            got = prepare_chunk(center_crop(v, crop) if crop else v, self.norm_input, self.spike_th, self.polarity)
+        elif kind == "events":
+            ev = {k: t.to(dev) for k, t in payload.items()}
+            got = events_to_chunk(ev, cfg["model"]["num_bins"], cfg["loader"]["resolution"], self.crop, self.norm_input, self.spike_th)
+        else:
+            pair = tuple({k: t.to(dev) for k, t in ev.items()} for ev in payload)
+            got = event_pairs_to_chunk([pair], cfg["data"]["num_frames"], tuple(cfg["loader"]["resolution"]), self.crop, self.norm_input,
+                                       self.spike_th, want_event_mask=em is not None, num_chunks=cfg["data"].get("num_chunks", 2))
+            if em is not None:
+                got, mask = got
+                em.copy_(mask)
+                em = None
+        x.copy_(got)
+        if em is not None:
+            # (the loops' own expressions: eval_DSEC_flow_SNN's for the tuple form, eval_MV_flow_SNN's for the dict form)
+            em.copy_(got.sum(1).sum(1, keepdim=True).bool() if self.polarity or kind == "voxel" else got.sum(1, keepdim=True).bool())
+
+    # -- the scheme ----------------------------------------------------------------------------------------------------------------
+    def _fwd(self, x):
+        model = self.model
+        if x.shape[0] > 1 and hasattr(model, "forward_replicas") and not model.training:
+            return model.forward_replicas(x)["flow"][-1]
+        if x.shape[0] == 1:
+            return model(x)["flow"][-1]
+        return torch.cat([model(x[i:i + 1])["flow"][-1] for i in range(x.shape[0])], 0)      # (no replica form: sample by sample)
+
+    def _slot(self, j, in_shape, hw):
+        s = self.slots[j]
+        if s is None or s["x"].shape[1:] != in_shape or s["lab"].shape[-2:] != hw:
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
+            s = self.slots[j] = {"x": z(self.R, *in_shape), "lab": z(self.R, 2, *hw), "msk": z(self.R, 1, *hw),
+                                 "em": z(self.R, 1, *hw) if self.mask_events else None, "fwd": {}}
+        return s
+
+    def _issue(self, j, k, units, flows_out):
+        """Group of len(units) samples numbered from k, on stream j."""
+        from .spikingjelly_compat import functional
+        n, st = len(units), self.streams[j]
+        kind, payload, label, _ = units[0]
+        oy, ox, h, w = self._window(kind, label)
+        st.wait_stream(torch.cuda.current_stream(self.device))              # (what the caller enqueued - samples, the table - comes first)
+        with torch.cuda.stream(st):
+            s = self._slot(j, self._input_shape(kind, payload, (h, w)), (h, w))
+            for i, (kind, payload, label, mask) in enumerate(units):
+                s["lab"][i:i + 1].copy_(label[..., oy:oy + h, ox:ox + w], non_blocking=True)
+                s["msk"][i:i + 1].copy_(mask[..., oy:oy + h, ox:ox + w], non_blocking=True)
+                self._prepare(kind, payload, s["x"][i:i + 1], s["em"][i:i + 1] if self.mask_events else None)
+            x = s["x"][:n]
+            functional.reset_net(self.model)
+            if not self.graphs:
+                flow = self._fwd(x)
+            else:
+                if n not in s["fwd"]:
+                    for _ in range(2):
+                        self._fwd(x)                                     # (also creates this stream's workspaces and plan caches)
+                    torch.cuda.synchronize(self.device)
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=st):
+                        out = self._fwd(x)
+                    s["fwd"][n] = [g, out]
+                g, flow = s["fwd"][n]
+                g.replay()
+            self.metrics.update(flow, s["lab"][:n], s["msk"][:n], s["em"][:n] if self.mask_events else None,
+                                self.config["metrics"]["flow_scaling"], row=k)
+            if flows_out is not None:
+                flows_out[k:k + n].copy_(flow, non_blocking=True)
+
+    def run(self, samples, flows_out=None):
+        """Evaluate the iterable `samples` (the forms of harness.evaluate, or of harness.evaluate_mv when an item is a dict) and return
+        the running-mean metrics dict.  `flows_out` (n, 2, h, w): receives every sample's last flow level, in iteration order."""
+        from .loss.flow_supervised import FlowMetrics
+        names, rows = None, 64
+        if hasattr(samples, "__len__"):
+            rows = max(len(samples), 1)
+        self.metrics = FlowMetrics(rows, self.device)
+        with torch.no_grad():
+            for j, k, units in deal(self._units(samples), self.F, self.R):
+                if names is None:
+                    default = ["AEE", "AAE"] if units[0][0] in ("volume", "pairs") else ["AEE"]
+                    names = self.config["metrics"].get("name", default)
+                if k + len(units) > self.metrics.table.shape[0]:
+                    self.metrics.reserve(max(k + len(units), 2 * self.metrics.table.shape[0]))
+                self._issue(j, k, units, flows_out)
+        return self.metrics.result(tuple(names or ["AEE"]))
+
+
+def evaluate_stream(model, samples, config, device="cuda", replicas=10, streams=2, graphs=True, flows_out=None):
+    """harness.evaluate / evaluate_mv at the throughput scheme's rate (StreamEvaluator): same sample forms, same config keys
+    (loader.crop / polarity, model.norm_input, data.spike_th / num_chunks, metrics.mask_events / flow_scaling / name), every sample a
+    batch-1 evaluation (a loader batch of B yields B of them), one host synchronisation at the end.  `flows_out` (n, 2, h, w) receives
+    the last flow level of every sample in iteration order.  graphs=False issues the launch sequences eagerly."""
+    return StreamEvaluator(model, config, device, replicas, streams, graphs).run(samples, flows_out)

@@ -267,6 +267,19 @@ class EventVoxelTbDesc(C.Structure):
                 ("normalize", C.c_int32), ("mode", C.c_int32), ("norm", C.c_int32), ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
 
 
+class FlowMetricsDesc(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("label", C.c_void_p), ("valid", C.c_void_p), ("event_mask", C.c_void_p), ("table", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("row0", C.c_int32), ("rows", C.c_int32), ("flow_scaling", C.c_float)]
+
+
+class PrepareChunkDesc(C.Structure):
+    _fields_ = [("voxel", C.c_void_p), ("out", C.c_void_p), ("event_mask", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("B", C.c_int32), ("bins", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32),
+                ("crop_h", C.c_int32), ("crop_w", C.c_int32), ("crop_oy", C.c_int32), ("crop_ox", C.c_int32), ("norm", C.c_int32),
+                ("per_sample", C.c_int32), ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
+
+
 # The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
 # plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
 # still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
@@ -328,6 +341,8 @@ SIGNATURES = {
     "sdf_event_voxel_keys_fwd": (_i, (_P(EventVoxelDesc), _p)), "sdf_event_voxel_gather_fwd": (_i, (_P(EventVoxelDesc), _p)),
     "sdf_event_voxel_tb_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i, _i, _i, _i)),
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
+    "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
+    "sdf_prepare_chunk_workspace_bytes": (_i64, (_i,)), "sdf_prepare_chunk_fwd": (_i, (_P(PrepareChunkDesc), _p)),
 }
 
 
@@ -1984,3 +1999,93 @@ def event_voxel_tb(x, y, t, p, num_bins, sensor_size, offsets=None, t_scale=1.0,
         d.keys_sorted, d.order = keys_sorted.data_ptr(), order.data_ptr()
     _check(lib().sdf_event_voxel_tb_gather_fwd(C.byref(d), _stream()), "sdf_event_voxel_tb_gather_fwd")
     return (out, mask) if want_event_mask else out
+
+
+FLOW_METRICS_FIELDS = ("n_valid", "sum_err", "n_pe1", "n_pe2", "n_pe3", "n_outlier", "sum_ang", "n_pixels")
+_FM_WS, _PC_WS = {}, {}
+
+
+def _stream_ws(cache, dev, need):
+    """One scratch buffer per (device, stream) and entry-point family: calls on different streams must not share partial results."""
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    if key not in cache or cache[key].numel() < need:
+        cache[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return cache[key]
+
+
+def flow_metrics(pred, label, valid, event_mask=None, flow_scaling=1.0, table=None, row=0):
+    """Per-sample sums of the evaluation metrics on the GPU (sdf_flow_metrics_fwd: two launches, no read-back): sample b of pred /
+    label (B, 2, H, W), valid and event_mask (B, H, W) or (B, 1, H, W), all fp32, writes row `row` + b of `table` (rows, 8) float64 -
+    FLOW_METRICS_FIELDS - and leaves the other rows as they are.  `table` None: a new zero table of row + B rows.  Returns the table.
+    Per pixel the reference classes' fp32 arithmetic (loss.flow_supervised.AEE / AAE on one sample); fp64 sums in a fixed order:
+    bit-identical from run to run and independent of B."""
+    for a in (pred, label, valid):
+        _ptr(a, torch.float32)
+    if pred.dim() != 4 or pred.shape[1] != 2 or label.shape != pred.shape:
+        raise SdfError(f"flow_metrics: pred and label are (B, 2, H, W), got {tuple(pred.shape)} and {tuple(label.shape)}")
+    B, _, H, W = pred.shape
+
+    def plane(t, name):
+        if t.numel() != B * H * W or tuple(t.shape[-2:]) != (H, W):
+            raise SdfError(f"flow_metrics: {name} is (B, H, W) or (B, 1, H, W) at the flow's size, got {tuple(t.shape)}")
+        return t.contiguous()
+    pred, label, valid = pred.contiguous(), label.contiguous(), plane(valid, "valid")
+    if event_mask is not None:
+        event_mask = plane(event_mask, "event_mask")
+    dev = pred.device
+    if table is None:
+        table = torch.zeros((row + B, len(FLOW_METRICS_FIELDS)), dtype=torch.float64, device=dev)
+    if table.dim() != 2 or table.shape[1] != len(FLOW_METRICS_FIELDS) or not table.is_contiguous():
+        raise SdfError(f"flow_metrics: table must be a contiguous (rows, {len(FLOW_METRICS_FIELDS)}) float64 tensor")
+    if row < 0 or row + B > table.shape[0]:
+        raise SdfError(f"flow_metrics: rows {row} .. {row + B - 1} lie outside the table's {table.shape[0]}", rc=E_SHAPE)
+    need = lib().sdf_flow_metrics_workspace_bytes(B, H, W)
+    if need <= 0:
+        raise SdfError(f"flow_metrics: geometry refused (B {B}, {H} x {W})", rc=E_SHAPE)
+    ws = _stream_ws(_FM_WS, dev, need)
+    d = FlowMetricsDesc()
+    d.pred, d.label, d.valid, d.event_mask = pred.data_ptr(), label.data_ptr(), valid.data_ptr(), _ptr(event_mask, torch.float32)
+    d.table, d.workspace, d.workspace_bytes = _ptr(table, torch.float64), ws.data_ptr(), ws.numel()
+    d.B, d.H, d.W, d.row0, d.rows, d.flow_scaling = B, H, W, row, table.shape[0], float(flow_scaling)
+    _note(bytes=B * H * W * (5 + (event_mask is not None)) * 4, shape=(B, H, W))
+    _check(lib().sdf_flow_metrics_fwd(C.byref(d), _stream()), "sdf_flow_metrics_fwd")
+    return table
+
+
+def prepare_chunk(voxel, crop=None, norm_input="minmax", spike_th=None, per_sample=False, out=None, crop_origin=None, event_mask=None):
+    """harness.prepare_chunk(center_crop(voxel, crop), norm_input, spike_th, polarity=True) on the GPU without a host round trip
+    (sdf_prepare_chunk_fwd), bit for bit: signed voxel (B, bins, Hs, Ws) fp32 -> the model's input (B, bins, 2, h, w).  `crop` (h, w) at
+    `crop_origin` (default harness.center_crop's ((Hs - h) // 2, (Ws - w) // 2)).  norm_input "minmax" or None; "std" raises SdfError
+    with rc E_DTYPE (harness.prepare_chunk serves it).  `per_sample`: min-max over each sample (what B batch-1 calls compute) instead
+    of over the whole batch tensor (the reference's semantics).  `out`: a contiguous (B, bins, 2, h, w) tensor to write into.
+    `event_mask`: a contiguous (B, 1, h, w) fp32 tensor that receives the loop's event mask, input.sum(1).sum(1, keepdim=True).bool()."""
+    _ptr(voxel, torch.float32)
+    if voxel.dim() != 4:
+        raise SdfError(f"prepare_chunk: voxel is (B, bins, H, W), got {tuple(voxel.shape)}")
+    voxel = voxel.contiguous()
+    B, bins, Hs, Ws = voxel.shape
+    h, w = crop if crop else (Hs, Ws)
+    oy, ox = crop_origin if crop_origin is not None else (((Hs - h) // 2, (Ws - w) // 2) if crop else (0, 0))
+    norm = {None: 0, "minmax": 1}.get(norm_input, 2)                    # (anything else is the library's to refuse)
+    dev = voxel.device
+    shape = (B, bins, 2, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise SdfError(f"prepare_chunk: out must be a contiguous {shape} tensor")
+    if event_mask is not None and (tuple(event_mask.shape) != (B, 1, h, w) or not event_mask.is_contiguous()):
+        raise SdfError(f"prepare_chunk: event_mask must be a contiguous {(B, 1, h, w)} tensor")
+    need = lib().sdf_prepare_chunk_workspace_bytes(B)
+    if need <= 0:
+        raise SdfError(f"prepare_chunk: batch of {B} refused", rc=E_SHAPE)
+    ws = _stream_ws(_PC_WS, dev, max(need, 256))
+    d = PrepareChunkDesc()
+    d.voxel, d.out, d.event_mask = voxel.data_ptr(), _ptr(out, torch.float32), _ptr(event_mask, torch.float32)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    d.B, d.bins, d.Hs, d.Ws = B, bins, Hs, Ws
+    d.crop_h, d.crop_w, d.crop_oy, d.crop_ox = (h if crop else 0), (w if crop else 0), oy, ox
+    d.norm, d.per_sample = norm, int(bool(per_sample))
+    d.use_spike_th, d.spike_th = int(spike_th is not None), float(spike_th or 0.0)
+    _note(bytes=B * bins * h * w * 4 * (1 + 2 + 4 * (norm == 1 or spike_th is not None)), shape=shape)
+    _check(lib().sdf_prepare_chunk_fwd(C.byref(d), _stream()), "sdf_prepare_chunk_fwd")
+    return out
