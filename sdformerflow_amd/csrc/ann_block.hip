@@ -31,7 +31,7 @@
 // wavefronts per SIMD) per compute unit.  Built for C = 96 (three heads of 32) and windows of 162 tokens - BASELINE config 3's
 // first stage, where 83 % of the model's window-attention tokens are; other shapes keep the four-launch path.
 // Compiled with -ffp-contract=off.
-#include "common.h"
+#include "f16_split.h"
 
 #ifdef SDF_STAMP
 // diagnostic build only (tools/stamp_ann_block.sh): 100 MHz timestamps of wave 0 of three workgroups along the kernel's phases
@@ -55,43 +55,13 @@ constexpr int WP_BYTES = 2 * C * WPB;           // projection rows, hi then lo p
 constexpr int K_BYTES = 2 * NP * KRS;
 constexpr int V_BYTES = (NP / 4) * HD * 16;
 constexpr int LDS_BYTES = WG_BYTES + WP_BYTES + K_BYTES + V_BYTES;
-constexpr uint32_t INV_OFF = 0x80000000u;
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 struct BlockParams {
   SdfAnnAttnBlockDesc d;
 };
-
-// two fp32 -> their hi and lo fp16 halves, packed (win_attn.hip: split2_f16)
-__device__ __forceinline__ void split2(float x, float y, uint32_t& hi, uint32_t& lo) {
-  const f32x2 v = {x, y};
-  const f16x2 h = __builtin_convertvector(v, f16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const f16x2 l = __builtin_convertvector(r, f16x2);
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
-// eight fp32 -> one hi and one lo operand of v_mfma_f32_16x16x32_f16
-__device__ __forceinline__ void split8(const float (&x)[8], f16x8& hi, f16x8& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) split2(x[2 * i], x[2 * i + 1], h[i], l[i]);
-  hi = __builtin_bit_cast(f16x8, u32x4{h[0], h[1], h[2], h[3]});
-  lo = __builtin_bit_cast(f16x8, u32x4{l[0], l[1], l[2], l[3]});
-}
-// a += A_hi B_hi + A_hi B_lo + A_lo B_hi (the smallest products first)
-__device__ __forceinline__ f32x4 mma3(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, f32x4 a) {
-  a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, a, 0, 0, 0);
-  a = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, a, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, a, 0, 0, 0);
-}
 
 __global__ __launch_bounds__(NTHR) void ann_attn_block_kernel(BlockParams P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -148,7 +118,7 @@ __global__ __launch_bounds__(NTHR) void ann_attn_block_kernel(BlockParams P) {
   f16x8 yh[3], yl[3];
   {
     float xv[3][8];
-    const uint32_t xo = row >= 0 ? (uint32_t)row * (uint32_t)(C * 4) + (uint32_t)(32 * lg) : INV_OFF;
+    const uint32_t xo = row >= 0 ? (uint32_t)row * (uint32_t)(C * 4) + (uint32_t)(32 * lg) : INV;
 #ifdef SDF_STAMP
     asm volatile("" ::"v"(xo));
     STAMP(18);
@@ -215,7 +185,7 @@ __global__ __launch_bounds__(NTHR) void ann_attn_block_kernel(BlockParams P) {
 
   const uint32_t tbytes = (uint32_t)N * (uint32_t)N * 4u;
   const uint32_t rowoff = (uint32_t)tok * (uint32_t)N * 4u;
-  const uint32_t rbase = (worker && tok < N) ? rowoff + 16u * (uint32_t)lg : INV_OFF;
+  const uint32_t rbase = (worker && tok < N) ? rowoff + 16u * (uint32_t)lg : INV;
 
   // the head's q | k | v rows: 2 planes x 96 rows x 12 pieces of 16 bytes = 3 pieces per thread, requested one head ahead (during
   // the attention of the head before) and written to LDS between two barriers - no wave ever waits for a weight load
@@ -248,7 +218,7 @@ __global__ __launch_bounds__(NTHR) void ann_attn_block_kernel(BlockParams P) {
           st[jt] = f32x4{__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w)};
         } else {                                                    // N % 4 == 2: the last piece of a row is 8 bytes
           const int kb = jt * 16 + 4 * lg;
-          const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(tab_rs, (rbase != INV_OFF && kb < N) ? rowoff + (uint32_t)kb * 4u : INV_OFF, 0, 0);
+          const u32x2 t = __builtin_amdgcn_raw_buffer_load_b64(tab_rs, (rbase != INV && kb < N) ? rowoff + (uint32_t)kb * 4u : INV, 0, 0);
           st[jt] = f32x4{kb + 0 < N ? __uint_as_float(t.x) : -INFINITY, kb + 1 < N ? __uint_as_float(t.y) : -INFINITY, -INFINITY, -INFINITY};
         }
       }

@@ -13,7 +13,7 @@
 // A chunk's weights (96 rows of W1, 96 columns of W2; fp16 hi / lo planes, three products per fp32 product: the numerics of
 // dense_linear.hip) are staged in LDS - requested a chunk ahead into registers, written between two barriers.
 // Built for C = 96, hidden 384 (config 3's first stage).  Compiled with -ffp-contract=off.
-#include "common.h"
+#include "f16_split.h"
 
 namespace {
 
@@ -22,44 +22,17 @@ constexpr int NWAVE = 12, NTHR = 64 * NWAVE, ROWS_WG = 16 * NWAVE;
 constexpr int WPB = 2 * 96 + 32;                // weight row pitch in bytes (12 pieces + 2: conflict-free for ds_read_b128's real lane groups)
 constexpr int W1_BYTES = 2 * 96 * WPB, W2_BYTES = 2 * C * WPB;
 constexpr int LDS_BYTES = W1_BYTES + W2_BYTES;
-constexpr uint32_t INV_OFF = 0x80000000u;
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 struct MlpParams {
   SdfAnnMlpBlockDesc d;
 };
 
-__device__ __forceinline__ void split2(float x, float y, uint32_t& hi, uint32_t& lo) {
-  const f32x2 v = {x, y};
-  const f16x2 h = __builtin_convertvector(v, f16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const f16x2 l = __builtin_convertvector(r, f16x2);
-  hi = __builtin_bit_cast(uint32_t, h);
-  lo = __builtin_bit_cast(uint32_t, l);
-}
-__device__ __forceinline__ void split8(const float (&x)[8], f16x8& hi, f16x8& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) split2(x[2 * i], x[2 * i + 1], h[i], l[i]);
-  hi = __builtin_bit_cast(f16x8, u32x4{h[0], h[1], h[2], h[3]});
-  lo = __builtin_bit_cast(f16x8, u32x4{l[0], l[1], l[2], l[3]});
-}
-__device__ __forceinline__ f32x4 mma3(const f16x8& ah, const f16x8& al, const f16x8& bh, const f16x8& bl, f32x4 a) {
-  a = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, a, 0, 0, 0);
-  a = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, a, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, a, 0, 0, 0);
-}
 // erf-form GELU (F.gelu) with erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 absolute, the size of an fp32 rounding of erf itself):
 //   erfc(u) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-u^2), t = 1 / (1 + p u), u = |x| / sqrt 2
 //   gelu(x) = x q for x < 0, x - x q for x >= 0, q = erfc(u) / 2   (no cancellation for large negative x)
 // One reciprocal, one exp2 and ten multiply-adds, branch-free: the library erff (two masked branches, ~ 50 instructions per value) made
 // this kernel's 96 GELUs per lane three times its matrix work (117 us per launch; with this form: see docs/history/DESIGN_rounds1-5.md section 6).
-__device__ __forceinline__ float gelu_erf(float x) {
+__device__ __forceinline__ float gelu_erfc_poly(float x) {
   const float u = fabsf(x) * 0.70710678118654752440f;
   const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, u, 1.f));
   float p = __builtin_fmaf(t, 0.5f * 1.061405429f, 0.5f * -1.453152027f);
@@ -118,7 +91,7 @@ __global__ __launch_bounds__(NTHR) void ann_mlp_block_kernel(MlpParams P) {
   f16x8 yh[3], yl[3];
   {
     float xv[3][8];
-    const uint32_t xo = tok_ok ? (uint32_t)tok * (uint32_t)(C * 4) + (uint32_t)(32 * lg) : INV_OFF;
+    const uint32_t xo = tok_ok ? (uint32_t)tok * (uint32_t)(C * 4) + (uint32_t)(32 * lg) : INV;
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
       const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(x_rs, xo, s * 128, 0);
@@ -188,7 +161,7 @@ __global__ __launch_bounds__(NTHR) void ann_mlp_block_kernel(MlpParams P) {
           acc = mma3(wh, wl, yh[s], yl[s], acc);
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) hv[4 * u + r] = gelu_erf(acc[r]);
+        for (int r = 0; r < 4; ++r) hv[4 * u + r] = gelu_erfc_poly(acc[r]);
       }
       // the pair of tiles (2 j, 2 j + 1) is K step j of the second product: slots 8 lg + i = units 32 j + (i < 4 ? 4 lg + i : 16 + 4 lg + i - 4)
       split8(hv, hh[j], hl[j]);

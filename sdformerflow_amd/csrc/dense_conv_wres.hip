@@ -37,6 +37,7 @@
 // consecutive halo rows; four consecutive pixels cover the four 64-byte quarters of a 256-byte bank row, and the four rows put
 // the slot they all ask for at four different places of its quarter.  Weight rows are 2K + 16 bytes (4 x odd dwords).
 #include "spike_mm.h"
+#include "device_prims.h"
 #include "switches.h"
 #include <stdlib.h>
 
@@ -60,7 +61,6 @@ constexpr int REC = 64;                         // bytes of a pixel record in me
 constexpr int PS = 64;                          // pixel stride in the halo image: 4 slots of 16 B = hi 0-7, hi 8-15, lo 0-7, lo 8-15,
                                                 // stored at slot ^ (halo row & 3) - see the bank note above
 constexpr int RPB = HWID * PS;                  // halo row pitch (640 bytes)
-constexpr uint32_t INV = 0x80000000u;
 // A wave's tile is TPW pixel blocks stacked vertically (4 TPW rows x 8 pixels) over ONE halo image.  TPW = 1: twelve waves (three per
 // SIMD), 3.75 KB images.  TPW = 2: eight waves (two per SIMD), 6.25 KB images; a weight fragment read from LDS feeds two MFMAs (one
 // per block), the halo rows the two blocks share are loaded once, and every per-step instruction is amortised over 54 MFMAs instead
@@ -75,7 +75,6 @@ struct Geo {
   static constexpr int CPL = (PIECES + 63) / 64;
 };
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) _Float16 h2;
 
 struct DenseParams {
@@ -83,10 +82,6 @@ struct DenseParams {
   int wtiles;                                   // wave tiles of the whole output: imgs * ceil(H/4) * ceil(W/8)
   int ranges;                                   // contiguous tile ranges; each is served by N / 32 workgroups, one per column block
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)INV, 0x00020000);
-}
 
 typedef __attribute__((ext_vector_type(2))) float f2;
 // four fp32 values -> one 16-byte piece {hi0..3, lo0..3}: hi = fp16(x), lo = fp16(x - hi), both round to nearest
@@ -585,7 +580,7 @@ extern "C" int sdf_pack_planes(const float* x, void* planes, int imgs, int C, in
   const int nch = (C + 15) / 16;
   const int64_t total = (int64_t)imgs * nch * 4 * H * W;
   SDF_LAUNCH(sdfmm::pack_planes_kernel, dim3(planes_grid(total)), dim3(256), 0, sdf_stream(stream), x,
-                     reinterpret_cast<sdfmm::u32x4*>(planes), imgs, C, nch, H, W);
+                     reinterpret_cast<u32x4*>(planes), imgs, C, nch, H, W);
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -600,10 +595,10 @@ extern "C" int sdf_pack_planes_up2(const float* x, void* planes, int imgs, int C
   const int64_t total = (int64_t)imgs * nch * (2 * h) * (2 * w) * (cl ? 4 : 1);
   if (cl)
     SDF_LAUNCH(sdfmm::pack_planes_up2_kernel<true>, dim3(planes_grid(total)), dim3(256), 0, sdf_stream(stream), x,
-                       reinterpret_cast<sdfmm::u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
+                       reinterpret_cast<u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
   else
     SDF_LAUNCH(sdfmm::pack_planes_up2_kernel<false>, dim3(planes_grid(total)), dim3(256), 0, sdf_stream(stream), x,
-                       reinterpret_cast<sdfmm::u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
+                       reinterpret_cast<u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -618,10 +613,10 @@ extern "C" int sdf_pack_planes_zero_up2(const float* x, void* planes, int imgs, 
   const int64_t total = (int64_t)imgs * nch * (2 * h) * (2 * w) * (cl ? 4 : 1);
   if (cl)
     SDF_LAUNCH((sdfmm::pack_planes_up2_kernel<true, true>), dim3(planes_grid(total)), dim3(256), 0, sdf_stream(stream), x,
-               reinterpret_cast<sdfmm::u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
+               reinterpret_cast<u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
   else
     SDF_LAUNCH((sdfmm::pack_planes_up2_kernel<false, true>), dim3(planes_grid(total)), dim3(256), 0, sdf_stream(stream), x,
-               reinterpret_cast<sdfmm::u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
+               reinterpret_cast<u32x4*>(planes), imgs, C, h, w, sn, sc, sh, sw, rec0, rec_total);
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -633,7 +628,7 @@ extern "C" int sdf_unpack_planes(const void* planes, float* x, int imgs, int C, 
   const int nch = (C + 15) / 16;
   const int64_t total = (int64_t)imgs * nch * 4 * H * W;
   SDF_LAUNCH(sdfmm::unpack_planes_kernel, dim3(planes_grid(total)), dim3(256), 0, sdf_stream(stream),
-                     reinterpret_cast<const sdfmm::u32x4*>(planes), x, imgs, C, nch, H, W);
+                     reinterpret_cast<const u32x4*>(planes), x, imgs, C, nch, H, W);
   SDF_LAUNCH_CHECK();
   return 0;
 }

@@ -15,7 +15,7 @@
 // MFMA's row operand, so a lane's accumulator quads are four consecutive columns of one row of C: bias, GELU (erf form, as
 // F.gelu) and the residual are applied on 16-byte pieces and stored as such.  LDS rows are 64 data bytes + 16 pad (slots 5
 // apart: conflict-free ds_read_b128 over 16 consecutive rows).
-#include "common.h"
+#include "device_prims.h"
 #include "switches.h"
 #include <math.h>
 #include <stdlib.h>
@@ -26,9 +26,7 @@ constexpr int BM = 128, BN = 96, KC = 32;
 constexpr int RS = 80;                                   // LDS row stride in bytes: 32 fp16 + 16 pad
 constexpr int A_PLANE = BM * RS, B_PLANE = BN * RS;
 constexpr int BUF = 2 * A_PLANE + 2 * B_PLANE;           // one stage: A hi, A lo, W hi, W lo
-constexpr uint32_t INV = 0x80000000u;
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) _Float16 h2;
 typedef __attribute__((ext_vector_type(2))) float f2;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
@@ -39,10 +37,6 @@ struct LinearParams {
   int tiles_n;
   int xcd;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // four fp32 values -> {hi0..3} and {lo0..3} as two 8-byte words
 __device__ __forceinline__ void split4(u32x4 v, uint2& hi, uint2& lo) {
@@ -78,9 +72,9 @@ __global__ __launch_bounds__(256) void dense_linear_kernel(LinearParams P) {
   // k = (ky * 3 + kx) * C + c: a chunk of 32 k is 128 contiguous bytes of one tap (C % 32 == 0), zero outside the image
   const bool conv = d.cv_C > 0;
   const int cvH = d.cv_H, cvW = d.cv_W, cvC = d.cv_C, ohw = d.cv_OH * d.cv_OW;
-  const __amdgpu_buffer_rsrc_t A_rs = rsrc(d.a, conv ? (uint32_t)(M / ohw) * (uint32_t)(cvH * cvW) * (uint32_t)cvC * 4u
+  const __amdgpu_buffer_rsrc_t A_rs = make_rsrc_bounded(d.a, conv ? (uint32_t)(M / ohw) * (uint32_t)(cvH * cvW) * (uint32_t)cvC * 4u
                                                      : (uint32_t)M * (uint32_t)K * 4u);
-  const __amdgpu_buffer_rsrc_t W_rs = rsrc(d.w, 2u * (uint32_t)N * (uint32_t)K * 2u);
+  const __amdgpu_buffer_rsrc_t W_rs = make_rsrc_bounded(d.w, 2u * (uint32_t)N * (uint32_t)K * 2u);
 
   // loader pieces of this thread.  A: 128 rows x 8 float4 per chunk, 4 per thread; W: 2 planes x 96 rows x 4 sixteen-byte pieces, 3 per thread
   uint32_t a_off[4], a_lds[4], w_off[3], w_lds[3];
@@ -184,8 +178,8 @@ __global__ __launch_bounds__(256) void dense_linear_kernel(LinearParams P) {
     const int img = m / ohw, pix = m - img * ohw, nb = (M / ohw) / d.out_T;
     m = ((img % nb) * d.out_T + img / nb) * ohw + pix;
   }
-  const __amdgpu_buffer_rsrc_t C_rs = rsrc(d.out, (uint32_t)M * (uint32_t)N * 4u);
-  const __amdgpu_buffer_rsrc_t R_rs = rsrc(d.resid, (uint32_t)M * (uint32_t)N * 4u);
+  const __amdgpu_buffer_rsrc_t C_rs = make_rsrc_bounded(d.out, (uint32_t)M * (uint32_t)N * 4u);
+  const __amdgpu_buffer_rsrc_t R_rs = make_rsrc_bounded(d.resid, (uint32_t)M * (uint32_t)N * 4u);
   const bool gelu = d.gelu != 0, has_res = d.resid != nullptr;
   const float asc = d.acc_scale != 0.f ? d.acc_scale : 1.f;             // 1 / weight scale (a power of two)
 #pragma unroll

@@ -12,11 +12,9 @@
 // depends on how the events are split over workgroups, so two runs - or two different batchings - give the same bits.
 //
 // Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | runs + permute | gather | [finish].
-#include "common.h"
+#include "event_common.h"
 
 namespace {
-
-constexpr int kLongRun = 48;     // runs at least this long are summed by their lane with the whole wave fetching and weighting for it
 
 struct EvGeom {
   int32_t B, C, h, w, ox, oy;    // output window (h, w) at offset (oy, ox) inside the (H, W) sensor grid
@@ -69,21 +67,6 @@ __global__ __launch_bounds__(256) void ev_keys_kernel(const void* __restrict__ x
   rec[e] = make_float4(x, y, tn, p[e]);
 }
 
-// sorted position i: the event's record moves to its sorted place, and the first / last position of a key's run go to the run table
-__global__ __launch_bounds__(256) void ev_runs_kernel(const int* __restrict__ ks, const int64_t* __restrict__ order,
-                                                      const float4* __restrict__ rec, int n, int KT, float4* __restrict__ rec_s,
-                                                      int2* __restrict__ tab) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int k = ks[i];
-  if (k < 0 || k >= KT) return;
-  const int64_t e = order[i];
-  if (e < 0 || e >= n) return;
-  rec_s[i] = rec[e];
-  if (i == 0 || ks[i - 1] != k) tab[k].x = i;
-  if (i == n - 1 || ks[i + 1] != k) tab[k].y = i + 1;
-}
-
 // weight of an event for the corner at (xc, yc, tc): three fp32 products in the reference's order, nothing contracted
 template <int MODE>
 __device__ __forceinline__ void ev_add(const float4 r, float xc, float yc, float tc, float& acc, float& acc2) {
@@ -97,8 +80,13 @@ __device__ __forceinline__ void ev_add(const float4 r, float xc, float yc, float
   }
 }
 
-// relu as ATen's device clamp_min forms it: NaN stays, else fmaxf(v, 0) = v_max_f32, which orders -0 below +0: relu(-0) = +0
-__device__ __forceinline__ float ev_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
+// ev_add as the lane of cell (xc, yc, tc) applies it (event_common.h event_sum_run)
+template <int MODE>
+struct EvTerm {
+  float xc, yc, tc;
+  __device__ __forceinline__ void operator()(const float4 r, float& acc, float& acc2) const { ev_add<MODE>(r, xc, yc, tc, acc, acc2); }
+  __device__ __forceinline__ EvTerm of_lane(int L) const { return EvTerm{__shfl(xc, L), __shfl(yc, L), __shfl(tc, L)}; }
+};
 
 // MODE 0: signed grid (B, C, h, w).  1: relu(v) | relu(-v) as (B, C, 2, h, w) (+ min / max of the non-zeros into mm when asked).
 // 2: convert_CHW_polarities, unsigned weights of the p == 1 | p == 0 events as (B, C, 2, h, w).
@@ -119,29 +107,7 @@ __global__ __launch_bounds__(256) void ev_gather_kernel(const int2* __restrict__
     const int dx = pass >> 2, dy = (pass >> 1) & 1, dt = pass & 1;      // x outer, y middle, t inner
     int2 r = make_int2(0, 0);
     if (active) r = tab[ev_key(g, b, c - dt + 1, yy - dy + 1, xx - dx + 1)];
-    const bool is_long = r.y - r.x >= kLongRun;
-    if (!is_long)
-      for (int i = r.x; i < r.y; ++i) ev_add<MODE>(rec[i], xc, yc, tc, acc, acc2);
-    unsigned long long todo = __ballot(is_long);
-    while (todo) {                                                       // (wave-uniform)
-      const int L = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int s = __shfl(r.x, L), e = __shfl(r.y, L);
-      const float lxc = __shfl(xc, L), lyc = __shfl(yc, L), ltc = __shfl(tc, L);
-      for (int base = s; base < e; base += 64) {
-        float w1 = 0.f, w2 = 0.f;
-        if (base + lane < e) ev_add<MODE>(rec[base + lane], lxc, lyc, ltc, w1, w2);      // 0 + w = w: lane j holds event j's term
-        const int cnt = min(64, e - base);
-        for (int j = 0; j < cnt; ++j) {
-          const float a1 = __shfl(w1, j);
-          if (lane == L) acc += a1;                                      // (adding a skipped event's + 0 leaves acc as it is)
-          if (MODE == 2) {
-            const float a2 = __shfl(w2, j);
-            if (lane == L) acc2 += a2;
-          }
-        }
-      }
-    }
+    event_sum_run<MODE == 2>(r, rec, lane, EvTerm<MODE>{xc, yc, tc}, acc, acc2);
   }
   const int64_t hw = (int64_t)g.h * g.w, plane = (int64_t)yy * g.w + xx, bc = (int64_t)b * g.C + c;
   if (MODE == 0) {
@@ -150,25 +116,20 @@ __global__ __launch_bounds__(256) void ev_gather_kernel(const int2* __restrict__
   }
   float o1 = acc, o2 = acc2;
   if (MODE == 1) {
-    o1 = ev_relu(acc);
-    o2 = ev_relu(-acc);
+    o1 = event_relu(acc);
+    o2 = event_relu(-acc);
   }
   if (active) {
     out[(bc * 2) * hw + plane] = o1;
     out[(bc * 2 + 1) * hw + plane] = o2;
   }
   if (MODE == 1 && want_minmax) {
-    // non-zero values here are positive floats, which order as their bit patterns: integer min / max, any arrival order
     unsigned lo = 0xffffffffu, hi = 0u;
-    if (active && o1 != 0.f) lo = hi = __float_as_uint(o1);
-    if (active && o2 != 0.f) {
-      lo = min(lo, __float_as_uint(o2));
-      hi = max(hi, __float_as_uint(o2));
+    if (active) {
+      minmax_nonzero(o1, lo, hi);
+      minmax_nonzero(o2, lo, hi);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-      lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
-      hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-    }
+    wave_minmax(lo, hi);
     if (lane == 0 && hi != 0u) {
       atomicMin(&mm[0], lo);
       atomicMax(&mm[1], hi);
@@ -191,8 +152,6 @@ __global__ __launch_bounds__(256) void ev_finish_kernel(float* __restrict__ out,
     out[i] = v;
   }
 }
-
-inline int64_t pad256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 struct EvPlan {
   EvGeom g;
@@ -236,9 +195,7 @@ int ev_check(const SdfEventVoxelDesc* d, EvPlan& pl, const int64_t*& offs, int64
     own[1] = d->n_events;
     offs = own;
   }
-  if (offs[0] != 0 || offs[d->B] != d->n_events) return SDF_E_SHAPE;
-  for (int b = 0; b < d->B; ++b)
-    if (offs[b + 1] < offs[b]) return SDF_E_SHAPE;
+  if (!event_offsets_ok(offs, d->B, d->n_events)) return SDF_E_SHAPE;
   if (d->t_range)
     for (int b = 0; b < d->B; ++b)                                       // a list whose first and last time are equal has no t_norm
       if (offs[b + 1] > offs[b] && !(d->t_range[2 * b + 1] != d->t_range[2 * b])) return SDF_E_SHAPE;
@@ -288,8 +245,6 @@ extern "C" int sdf_event_voxel_gather_fwd(const SdfEventVoxelDesc* d, void* stre
   int64_t own[2];
   if (int rc = ev_check(d, pl, offs, own)) return rc;
   const int n = (int)d->n_events;
-  if (n && (!d->keys_sorted || !d->order)) return SDF_E_NULL;
-  if (n && (!sdf_aligned(d->keys_sorted, 4) || !sdf_aligned(d->order, 8))) return SDF_E_ALIGN;
   hipStream_t s = sdf_stream(stream);
   char* ws = static_cast<char*>(d->workspace);
   const float4* rec = reinterpret_cast<const float4*>(ws + pl.off_rec);
@@ -297,17 +252,7 @@ extern "C" int sdf_event_voxel_gather_fwd(const SdfEventVoxelDesc* d, void* stre
   int2* tab = reinterpret_cast<int2*>(ws + pl.off_tab);
   unsigned* mm = reinterpret_cast<unsigned*>(ws + pl.off_mm);
   const EvGeom& g = pl.g;
-  hipError_t e = hipMemsetAsync(tab, 0, (size_t)g.KT * 8, s);           // every run empty
-  if (e != hipSuccess) return (int)e;
-  if (d->norm) {
-    e = hipMemsetAsync(mm, 0xff, 4, s);                                  // min over nothing
-    if (e == hipSuccess) e = hipMemsetAsync(mm + 1, 0, 4, s);            // max over nothing: "no non-zero element"
-    if (e != hipSuccess) return (int)e;
-  }
-  if (n) {
-    SDF_LAUNCH(ev_runs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d->keys_sorted, d->order, rec, n, g.KT, rec_s, tab);
-    SDF_LAUNCH_CHECK();
-  }
+  if (int rc = event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, mm, n, g.KT, d->norm, s)) return rc;
   const int64_t cells = (int64_t)g.B * g.C * g.h * g.w;
   const dim3 grid((unsigned)((cells + 255) / 256)), block(256);
   float* out = static_cast<float*>(d->out);

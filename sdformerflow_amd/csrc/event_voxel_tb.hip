@@ -14,11 +14,9 @@
 //
 // Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | runs + permute | gather (+ partial
 // statistics) | [statistics] | [normalise / split / min-max] | [finish: min-max, threshold, event mask].
-#include "common.h"
+#include "event_common.h"
 
 namespace {
-
-constexpr int kLongRun = 48;     // runs at least this long are summed by their lane with the whole wave fetching and weighting for it
 
 struct TbGeom {
   int32_t L, S, nb;              // lists, lists per sample, bins per list
@@ -71,21 +69,6 @@ __global__ __launch_bounds__(256) void tb_keys_kernel(const void* __restrict__ x
   rec[e] = make_float2(dts, pol);
 }
 
-// sorted position i: the event's record moves to its sorted place, and the first / last position of a key's run go to the run table
-__global__ __launch_bounds__(256) void tb_runs_kernel(const int* __restrict__ ks, const int64_t* __restrict__ order,
-                                                      const float2* __restrict__ rec, int n, int KT, float2* __restrict__ rec_s,
-                                                      int2* __restrict__ tab) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int k = ks[i];
-  if (k < 0 || k >= KT) return;
-  const int64_t e = order[i];
-  if (e < 0 || e >= n) return;
-  rec_s[i] = rec[e];
-  if (i == 0 || ks[i - 1] != k) tab[k].x = i;
-  if (i == n - 1 || ks[i + 1] != k) tab[k].y = i + 1;
-}
-
 // one event's term: r = (dts, pol); the left pass weights with 1 - dts, the right pass with dts, each one fp32 product with pol
 template <bool POLS>
 __device__ __forceinline__ void tb_add(const float2 r, int right, float& acc, float& acc2) {
@@ -98,8 +81,13 @@ __device__ __forceinline__ void tb_add(const float2 r, int right, float& acc, fl
   }
 }
 
-// relu as ATen's device clamp_min forms it: NaN stays, else fmaxf(v, 0) = v_max_f32, which orders -0 below +0: relu(-0) = +0
-__device__ __forceinline__ float tb_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
+// tb_add of the left or the right pass (the same for every cell: event_common.h event_sum_run)
+template <bool POLS>
+struct TbTerm {
+  int right;
+  __device__ __forceinline__ void operator()(const float2 r, float& acc, float& acc2) const { tb_add<POLS>(r, right, acc, acc2); }
+  __device__ __forceinline__ TbTerm of_lane(int) const { return *this; }
+};
 
 // a cell's value as the reference normalises it: non-zeros become (v - mean) / std, evaluated in fp64 and rounded once
 __device__ __forceinline__ float tb_normalise(float v, const double* __restrict__ st) {
@@ -124,29 +112,7 @@ __global__ __launch_bounds__(256) void tb_gather_kernel(const int2* __restrict__
   for (int pass = 0; pass < 2; ++pass) {                                  // left: the events of bin c; right: those of bin c - 1
     int2 r = make_int2(0, 0);
     if (active && c - pass >= 0) r = tab[l * cells + cell - pass * g.dh * g.dw];
-    const bool is_long = r.y - r.x >= kLongRun;
-    if (!is_long)
-      for (int i = r.x; i < r.y; ++i) tb_add<POLS>(rec[i], pass, acc, acc2);
-    unsigned long long todo = __ballot(is_long);
-    while (todo) {                                                       // (wave-uniform)
-      const int Lo = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int s = __shfl(r.x, Lo), e = __shfl(r.y, Lo);
-      for (int base = s; base < e; base += 64) {
-        float w1 = 0.f, w2 = 0.f;
-        if (base + lane < e) tb_add<POLS>(rec[base + lane], pass, w1, w2);  // 0 + w = w: lane j holds event j's term
-        const int cnt = min(64, e - base);
-        for (int j = 0; j < cnt; ++j) {
-          const float a1 = __shfl(w1, j);
-          // (POLS: an event of the other polarity holds + 0 here, and adding it leaves acc as it is - acc is never - 0)
-          if (lane == Lo) acc += a1;
-          if (POLS) {
-            const float a2 = __shfl(w2, j);
-            if (lane == Lo) acc2 += a2;
-          }
-        }
-      }
-    }
+    event_sum_run<POLS>(r, rec, lane, TbTerm<POLS>{pass}, acc, acc2);
   }
   const int oy = yy + g.doy - g.oy, ox = xx + g.dox - g.ox;
   if (active && oy >= 0 && oy < g.h && ox >= 0 && ox < g.w) {
@@ -229,23 +195,14 @@ __global__ __launch_bounds__(256) void tb_norm_kernel(float* __restrict__ out, i
       out[at] = v;
       continue;
     }
-    const float o1 = tb_relu(v), o2 = tb_relu(-v);
+    const float o1 = event_relu(v), o2 = event_relu(-v);
     out[at] = o1;
     out[at + hw] = o2;
-    if (o1 != 0.f) {
-      lo = min(lo, __float_as_uint(o1));
-      hi = max(hi, __float_as_uint(o1));
-    }
-    if (o2 != 0.f) {
-      lo = min(lo, __float_as_uint(o2));
-      hi = max(hi, __float_as_uint(o2));
-    }
+    minmax_nonzero(o1, lo, hi);
+    minmax_nonzero(o2, lo, hi);
   }
   if (SPLIT && want_minmax) {
-    for (int off = 32; off > 0; off >>= 1) {
-      lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
-      hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-    }
+    wave_minmax(lo, hi);
     // one pair of atomics per workgroup: same-address atomics serialise in L2, and a pair per wave cost more than the pass itself
     __shared__ unsigned red[4][2];
     if (lane == 0) {
@@ -288,8 +245,6 @@ __global__ __launch_bounds__(256) void tb_finish_kernel(float* __restrict__ out,
   }
   if (mask) mask[i] = any ? 1.f : 0.f;
 }
-
-inline int64_t pad256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 struct TbPlan {
   TbGeom g;
@@ -343,9 +298,7 @@ int tb_check(const SdfEventVoxelTbDesc* d, TbPlan& pl) {
   if (!d->workspace || !d->out || !d->offsets) return SDF_E_NULL;
   if (d->workspace_bytes < pl.bytes) return SDF_E_SHAPE;
   if (!sdf_aligned(d->workspace, 16) || !sdf_aligned(d->out, 4) || !sdf_aligned(d->event_mask, 4)) return SDF_E_ALIGN;
-  if (d->offsets[0] != 0 || d->offsets[d->n_lists] != d->n_events) return SDF_E_SHAPE;
-  for (int l = 0; l < d->n_lists; ++l)
-    if (d->offsets[l + 1] < d->offsets[l]) return SDF_E_SHAPE;
+  if (!event_offsets_ok(d->offsets, d->n_lists, d->n_events)) return SDF_E_SHAPE;
   return 0;
 }
 
@@ -387,8 +340,6 @@ extern "C" int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void*
   TbPlan pl;
   if (int rc = tb_check(d, pl)) return rc;
   const int n = (int)d->n_events;
-  if (n && (!d->keys_sorted || !d->order)) return SDF_E_NULL;
-  if (n && (!sdf_aligned(d->keys_sorted, 4) || !sdf_aligned(d->order, 8))) return SDF_E_ALIGN;
   hipStream_t s = sdf_stream(stream);
   char* ws = static_cast<char*>(d->workspace);
   const float2* rec = reinterpret_cast<const float2*>(ws + pl.off_rec);
@@ -398,17 +349,7 @@ extern "C" int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void*
   double* stats = reinterpret_cast<double*>(ws + pl.off_stats);
   unsigned* mm = reinterpret_cast<unsigned*>(ws + pl.off_mm);
   const TbGeom& g = pl.g;
-  hipError_t e = hipMemsetAsync(tab, 0, (size_t)g.KT * 8, s);           // every run empty
-  if (e != hipSuccess) return (int)e;
-  if (d->norm) {
-    e = hipMemsetAsync(mm, 0xff, 4, s);                                  // min over nothing
-    if (e == hipSuccess) e = hipMemsetAsync(mm + 1, 0, 4, s);            // max over nothing: "no non-zero element"
-    if (e != hipSuccess) return (int)e;
-  }
-  if (n) {
-    SDF_LAUNCH(tb_runs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d->keys_sorted, d->order, rec, n, g.KT, rec_s, tab);
-    SDF_LAUNCH_CHECK();
-  }
+  if (int rc = event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, mm, n, g.KT, d->norm, s)) return rc;
   const dim3 block(256), ggrid(g.nblk, g.L);
   float* out = static_cast<float*>(d->out);
   if (d->mode == 2) SDF_LAUNCH(tb_gather_kernel<true>, ggrid, block, 0, s, tab, rec_s, out, part, g, 2, d->normalize);

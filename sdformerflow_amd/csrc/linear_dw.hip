@@ -30,19 +30,14 @@
 // in chunks of 32 through a double-buffered LDS image (next chunk requested before the MFMAs, split / written after them, one
 // barrier per chunk).  The m ranges of a tile (split count chosen for ~3 workgroups per compute unit) leave fp32 partial tiles that a
 // second kernel adds in a fixed order - no atomics, the same bits every run.
-#include "common.h"
+#include "bf16_split.h"
 
 namespace {
 
 constexpr int TN = 96, TK = 96, MC = 32;
 constexpr int RP = 224;                                  // LDS row pitch in bytes: 96 x 16 bit + 32 pad = 7 x 32 (see above)
 constexpr int PLANE = MC * RP;
-constexpr uint32_t INV = 0x80000000u;
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 struct DwParams {
@@ -51,39 +46,6 @@ struct DwParams {
   int x_ld;                                              // row pitch of X in floats (Linear: K; convolution form: C)
   int cblocks, Wp;                                       // convolution form: 96-channel blocks of C, padded image width
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-
-// two fp32 values -> the dword {bf16(a), bf16(b)} of their top halves
-__device__ __forceinline__ uint32_t top2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-
-// four fp32 values -> three 8-byte words of bf16 planes, hi + mid + lo == v exactly (truncation splits)
-__device__ __forceinline__ void split3(u32x4 v, uint2& hi, uint2& mid, uint2& lo) {
-  uint32_t h[4], m[4], l[4];
-  const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h[i] = x[i] & 0xFFFF0000u;
-    const float r1 = __uint_as_float(x[i]) - __uint_as_float(h[i]);
-    m[i] = __float_as_uint(r1) & 0xFFFF0000u;
-    l[i] = __float_as_uint(r1 - __uint_as_float(m[i]));            // <= 8 significant bits: its top half is all of it
-  }
-  hi = make_uint2(top2(h[0], h[1]), top2(h[2], h[3]));
-  mid = make_uint2(top2(m[0], m[1]), top2(m[2], m[3]));
-  lo = make_uint2(top2(l[0], l[1]), top2(l[2], l[3]));
-}
-
-__device__ __forceinline__ bf16x8 tr_frag(const uint8_t* p) {
-  // rows 4g + q (this read) and 16 + 4g + q (the next): element j of the lane = reduction index 4g + j, 16 + 4g + (j - 4)
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * RP));
-  s16x8 r;
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3]; r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-  return __builtin_bit_cast(bf16x8, r);
-}
 
 // TAPS = 1: the Linear form.  TAPS = 3: the 3x3 / stride 1 / pad 1 CONVOLUTION form on zero-ringed channels-last images - row m is a
 // pixel of the (H + 2) x (W + 2) grid, dY is zero on the ring, and tap (ky, kx) multiplies dY[m] with X[m + (ky - 1) Wp + kx - 1]: a
@@ -115,8 +77,8 @@ __global__ __launch_bounds__(256, 2) void linear_dw_kernel(DwParams P) {
   const int nchunk = m_end > m_begin ? (int)((m_end - m_begin + MC - 1) / MC) : 0;
   const int64_t xshift = TAPS == 3 ? (int64_t)(ky - 1) * P.Wp - 1 : 0;  // X row of tap 0 for dY row 0 (may be before the tensor)
 
-  const __amdgpu_buffer_rsrc_t Y_rs = rsrc(d.dy, (uint32_t)(d.M * N * 4));
-  const __amdgpu_buffer_rsrc_t X_rs = rsrc(d.x, (uint32_t)(d.M * P.x_ld * 4));
+  const __amdgpu_buffer_rsrc_t Y_rs = make_rsrc_bounded(d.dy, (uint32_t)(d.M * N * 4));
+  const __amdgpu_buffer_rsrc_t X_rs = make_rsrc_bounded(d.x, (uint32_t)(d.M * P.x_ld * 4));
 
   // loader: a chunk is 32 rows x 24 float4 of dY (3 pieces per thread) and XR rows x 24 of X.  No bounds arithmetic: a range is a
   // whole number of chunks, so only the tensors' ends matter and the buffer descriptor returns zero past them - also for the rows
@@ -180,12 +142,12 @@ __global__ __launch_bounds__(256, 2) void linear_dw_kernel(DwParams P) {
     for (int pl = 2; pl >= 0; --pl) {                                   // small terms first
       bf16x8 a[3];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) a[i] = tr_frag(cur + pl * PLANE + a_base + i * 32);
+      for (int i = 0; i < 3; ++i) a[i] = tr_frag<RP>(cur + pl * PLANE + a_base + i * 32);
 #pragma unroll
       for (int t = 0; t < TAPS; ++t) {
         bf16x8 b[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) b[j] = tr_frag(cur + b_base + t * RP + j * 32);
+        for (int j = 0; j < 3; ++j) b[j] = tr_frag<RP>(cur + b_base + t * RP + j * 32);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll

@@ -15,19 +15,14 @@
 // of 32; inside a chunk lane group g takes indices 4g..4g+3 and 16+4g..16+4g+3 for both operands - for dX the weight tile lies in
 // LDS as it lies in memory ([n][k], the reduction index is the row) and is read with ds_read_b64_tr_b16, and that dealing is what makes
 // those reads conflict-free at a 224-byte pitch (csrc/linear_dw.hip); row-major operands read the same indices as two 8-byte pieces.
-#include "common.h"
+#include "bf16_split.h"
 
 namespace {
 
 constexpr int BM = 128, BC = 96, RC = 32;
 constexpr int RS = 80;                                   // row-major images: 32 x 16 bit + 16 pad (16 rows x 8 bytes: conflict-free)
 constexpr int RP = 224;                                  // [reduction][column] weight image of mode 1: 96 x 16 bit + 32 pad
-constexpr uint32_t INV = 0x80000000u;
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 struct TrainParams {
@@ -36,41 +31,10 @@ struct TrainParams {
   int cchunks;                                           // convolution form (mode 0): chunks of 32 per tap = cv_C / 32, else 0
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint32_t top2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-__device__ __forceinline__ uint2 top4(u32x4 v) { return make_uint2(top2(v.x, v.y), top2(v.z, v.w)); }
-
-// four fp32 values -> three 8-byte words of bf16 planes, hi + mid + lo == v exactly (truncation splits)
-__device__ __forceinline__ void split3(u32x4 v, uint2& hi, uint2& mid, uint2& lo) {
-  uint32_t h[4], m[4], l[4];
-  const uint32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    h[i] = x[i] & 0xFFFF0000u;
-    const float r1 = __uint_as_float(x[i]) - __uint_as_float(h[i]);
-    m[i] = __float_as_uint(r1) & 0xFFFF0000u;
-    l[i] = __float_as_uint(r1 - __uint_as_float(m[i]));
-  }
-  hi = make_uint2(top2(h[0], h[1]), top2(h[2], h[3]));
-  mid = make_uint2(top2(m[0], m[1]), top2(m[2], m[3]));
-  lo = make_uint2(top2(l[0], l[1]), top2(l[2], l[3]));
-}
-
 // reduction indices 4g..4g+3 | 16+4g..16+4g+3 of one row of a row-major image (p points at index 4g of the row)
 __device__ __forceinline__ bf16x8 row_frag(const uint8_t* p) {
   const uint2 a = *reinterpret_cast<const uint2*>(p), b = *reinterpret_cast<const uint2*>(p + 32);
   const u32x4 r = {a.x, a.y, b.x, b.y};
-  return __builtin_bit_cast(bf16x8, r);
-}
-// the same indices of 16 COLUMNS of a [reduction][column] image through the transposing read (csrc/linear_dw.hip)
-__device__ __forceinline__ bf16x8 tr_frag(const uint8_t* p) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * RP));
-  s16x8 r;
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3]; r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
   return __builtin_bit_cast(bf16x8, r);
 }
 
@@ -96,8 +60,8 @@ __global__ __launch_bounds__(256) void linear_train_kernel(TrainParams P) {
   const int tm = wg / P.tiles_c, tc = wg - tm * P.tiles_c;
   const int m0 = tm * BM, c0 = tc * BC;
 
-  const __amdgpu_buffer_rsrc_t A_rs = rsrc(d.a, (uint32_t)M * (uint32_t)lda * 4u);
-  const __amdgpu_buffer_rsrc_t W_rs = rsrc(d.w, (uint32_t)N * (uint32_t)K * 4u);
+  const __amdgpu_buffer_rsrc_t A_rs = make_rsrc_bounded(d.a, (uint32_t)M * (uint32_t)lda * 4u);
+  const __amdgpu_buffer_rsrc_t W_rs = make_rsrc_bounded(d.w, (uint32_t)N * (uint32_t)K * 4u);
 
   // loader.  A: 128 rows x 8 float4 per chunk, 4 per thread.  W: mode 0 - 96 rows (n) x 8 float4; mode 1 - 32 rows (n) x 24 float4: 3 per thread
   uint32_t a_off[4], a_lds[4], w_off[3], w_lds[3];
@@ -187,7 +151,7 @@ __global__ __launch_bounds__(256) void linear_train_kernel(TrainParams P) {
       bf16x8 w[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
-        w[pl] = MODE == 0 ? row_frag(smem + pl * W_PLANE + w_frag + j * 16 * RS) : tr_frag(smem + pl * W_PLANE + w_frag + j * 32);
+        w[pl] = MODE == 0 ? row_frag(smem + pl * W_PLANE + w_frag + j * 16 * RS) : tr_frag<RP>(smem + pl * W_PLANE + w_frag + j * 32);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         // the hi x hi products have their own accumulator: the matrix pipe aligns a product to the running sum with a bounded number
@@ -213,7 +177,7 @@ __global__ __launch_bounds__(256) void linear_train_kernel(TrainParams P) {
   }
 
   // accumulator register r of block (i, j): out[m0 + 32 wave + 16 i + li][c0 + 16 j + 4 g + r]
-  const __amdgpu_buffer_rsrc_t C_rs = rsrc(d.out, (uint32_t)M * (uint32_t)Cn * 4u);
+  const __amdgpu_buffer_rsrc_t C_rs = make_rsrc_bounded(d.out, (uint32_t)M * (uint32_t)Cn * 4u);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = m0 + wave * 32 + 16 * i + li;

@@ -30,6 +30,7 @@
 // distinct bank quads).
 // Compiled with -ffp-contract=off (the neuron arithmetic is the separately-rounded op sequence of neuron.hip).
 #include "spike_mm.h"
+#include "device_prims.h"
 #include "switches.h"
 
 #ifdef SDF_STAMP
@@ -48,35 +49,6 @@ namespace {
 constexpr int TH = 8, TW = 16;                  // output pixels of a tile: 4 waves x (2 rows x 16 pixels)
 constexpr int HH = TH + 2, HWID = TW + 2;       // halo image
 constexpr int NB = 32;                          // output columns of a workgroup
-constexpr uint32_t INV = 0x80000000u;
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)INV, 0x00020000);
-}
-__device__ __forceinline__ float4 buf_load16f(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  const uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
-  return make_float4(__uint_as_float(x), __uint_as_float(y), __uint_as_float(z), __uint_as_float(w));
-}
-__device__ __forceinline__ void buf_store16f(__amdgpu_buffer_rsrc_t r, uint32_t off, float4 o) {
-  u32x4 v;
-  v.x = __float_as_uint(o.x); v.y = __float_as_uint(o.y); v.z = __float_as_uint(o.z); v.w = __float_as_uint(o.w);
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
-}
-__device__ __forceinline__ void wait_ge(uint32_t* p, uint32_t target) {
-  while (true) {
-    const uint32_t v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-    if ((int32_t)(v - target) >= 0) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void signal(uint32_t* p, int lane) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // 8 activation bytes -> 8 x 16-bit values (spike_mm.h `expand_spikes`: fp16 planes take any byte value exactly)
 template <int NSPLIT>
@@ -394,23 +366,6 @@ __global__ __launch_bounds__(512) void spike_conv_wres_kernel(GemmParams P) {
 // row blocks that share every weight fragment.
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(16))) int i32x16;
-
-// 4 x 4 transpose of dwords among the four lanes of a quad (two DPP butterflies, v_mov_dpp without an `old` operand):
-// in: lane q holds a_i = X[q][i]; out: a_i = X[i][q].  o1 / o2 = bit 0 / 1 of the lane's index in its quad.
-template <int CTRL>
-__device__ __forceinline__ float dpp_quad(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ void qt4(float& a0, float& a1, float& a2, float& a3, bool o1, bool o2) {
-  float r = dpp_quad<0xB1>(o1 ? a0 : a1);
-  a0 = o1 ? r : a0; a1 = o1 ? a1 : r;
-  r = dpp_quad<0xB1>(o1 ? a2 : a3);
-  a2 = o1 ? r : a2; a3 = o1 ? a3 : r;
-  r = dpp_quad<0x4E>(o2 ? a0 : a2);
-  a0 = o2 ? r : a0; a2 = o2 ? a2 : r;
-  r = dpp_quad<0x4E>(o2 ? a1 : a3);
-  a1 = o2 ? r : a1; a3 = o2 ? a3 : r;
-}
 
 template <int CIN16, int RB, bool S2, int KH = 1>
 struct GeoI8 {

@@ -47,7 +47,6 @@ constexpr int RCH = HWD * C16;                            // 16-byte pieces of a
 
 static_assert(LDS_BYTES <= 160 * 1024 && RCH <= 256 && C16 % 2 == 1, "geometry");
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(16))) int i32x16;
 
@@ -61,36 +60,6 @@ struct DeconvParams {
   int cls_start[5], cls_nr[4];
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)INV, 0x00020000);
-}
-__device__ __forceinline__ void wait_ge(uint32_t* p, uint32_t target) {
-  while (true) {
-    const uint32_t v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-    if ((int32_t)(v - target) >= 0) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void signal(uint32_t* p, int lane) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_quad(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// 4 x 4 transpose of dwords among the four lanes of a quad (spike_conv_wres.hip)
-__device__ __forceinline__ void qt4(float& a0, float& a1, float& a2, float& a3, bool o1, bool o2) {
-  float r = dpp_quad<0xB1>(o1 ? a0 : a1);
-  a0 = o1 ? r : a0; a1 = o1 ? a1 : r;
-  r = dpp_quad<0xB1>(o1 ? a2 : a3);
-  a2 = o1 ? r : a2; a3 = o1 ? a3 : r;
-  r = dpp_quad<0x4E>(o2 ? a0 : a2);
-  a0 = o2 ? r : a0; a2 = o2 ? a2 : r;
-  r = dpp_quad<0x4E>(o2 ? a1 : a3);
-  a1 = o2 ? r : a1; a3 = o2 ? a3 : r;
-}
 // halo offset of the lower half wave's piece of K step ks, and which lane base it goes with
 __device__ __forceinline__ constexpr int step_off(int ks) {
   if (ks < 4 * (C16 / 2)) {                                  // pairs inside quadrant q = dh + 2 dw
@@ -190,7 +159,7 @@ __global__ __launch_bounds__(NT) void spike_deconv_wres_kernel(DeconvParams P) {
   const int hpx = (hj_ok ? gl : 0) / C16, hc16 = (hj_ok ? gl : 0) - hpx * C16;
   const uint32_t h_lds0 = (uint32_t)(hpx * PS + hc16 * 16);
   const int h_rel0 = hpx * CIN + hc16 * 16;
-  const __amdgpu_buffer_rsrc_t A_rs = rsrc(P.A), out_rs = rsrc(P.out);
+  const __amdgpu_buffer_rsrc_t A_rs = make_rsrc(P.A), out_rs = make_rsrc(P.out);
   u32x4 hreg[HH];
   auto halo_load = [&](int img, int y0, int x0) __attribute__((always_inline)) {
     const uint32_t org = (uint32_t)(((img * H + y0) * W + x0) * CIN) + (uint32_t)h_rel0;

@@ -30,6 +30,7 @@
 // LDS rows are padded (A 18-dword stride for ds_read_b64, W 36-dword stride for ds_read_b128): conflict-free.
 // Compiled with -ffp-contract=off (the neuron arithmetic is the separately-rounded op sequence of neuron.hip).
 #include "spike_mm.h"
+#include "device_prims.h"
 #include "switches.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -51,46 +52,6 @@ constexpr int BM = 256, BN = 96, KC = 64;
 constexpr int A_LD = KC + 8;                 // bytes per A row   (72 B  = 18 dwords; 80-byte rows with ds_write_b128 measured no faster)
 constexpr int W_LD = KC + 8;                 // 16-bit elements per W row (144 B = 36 dwords)
 constexpr int A_BYTES = BM * A_LD;           // 18432
-
-// Raw buffer access (32-bit byte offset against a wave-uniform descriptor of 2^31 records): an offset with bit 31 set is
-// out of range, so the hardware returns zeros for such a load and drops such a store - row / tap / K bounds become an
-// offset select instead of an exec-masked branch (hipcc puts a vmcnt wait behind every one of those).
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-constexpr uint32_t INV = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)INV, 0x00020000);
-}
-__device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ float4 buf_load16f(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  // (element copies first: __builtin_bit_cast applied directly to a vector-element expression reads element 0 - clang bug)
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  const uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
-  return make_float4(__uint_as_float(x), __uint_as_float(y), __uint_as_float(z), __uint_as_float(w));
-}
-__device__ __forceinline__ void buf_store16f(__amdgpu_buffer_rsrc_t r, uint32_t off, float4 o) {
-  u32x4 v;
-  v.x = __float_as_uint(o.x); v.y = __float_as_uint(o.y); v.z = __float_as_uint(o.z); v.w = __float_as_uint(o.w);
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0);
-}
-
-// spin until the LDS counter reaches `target` (wave-uniform); later LDS accesses are not hoisted above it
-__device__ __forceinline__ void wait_ge(uint32_t* p, uint32_t target) {
-  while (true) {
-    const uint32_t v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-    if ((int32_t)(v - target) >= 0) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  asm volatile("" ::: "memory");
-}
-// all LDS operations of this wave have completed -> bump the counter (one lane).  vmcnt is deliberately not waited
-// for: the producers' prefetch and the consumers' epilogue stores stay in flight.
-__device__ __forceinline__ void signal(uint32_t* p, int lane) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // The kernel's body: `blk` / `G` = this workgroup's index and the number of workgroups that share P's work items (the plain kernel's
 // blockIdx.x / gridDim.x; the multi-problem kernel below deals a range of its grid to every problem).

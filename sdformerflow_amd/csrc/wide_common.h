@@ -1,7 +1,8 @@
 // Helpers shared by the int8-digit spike kernels of the wide stages (ms_wide.hip) and of the small-M products (ms_smallm.hip):
-// buffer resources, the in-place int8 MFMA, the digit recombination, spike bits -> bytes and the quad transpose.
+// the in-place int8 MFMA, the digit recombination, spike bits -> bytes and the quad transpose.
 #pragma once
 #include "spike_mm.h"
+#include "device_prims.h"
 
 namespace sdfmm {
 
@@ -71,12 +72,6 @@ int launch_res_front(WideFrontParams& P, bool keep, int nk, hipStream_t s);
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-constexpr uint32_t INV = 0x80000000u;               // buffer offset of "no such row": loads return zeros, stores are dropped
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)INV, 0x00020000);
-}
 
 // 4 bits -> 4 bytes {0, 1}: bit i lands in byte i (i + 7 i = 8 i; the cross terms i + 7 k, k != i, miss every byte's bit 0)
 __device__ __forceinline__ uint32_t spread4(uint32_t nib) { return __umul24(nib & 0xFu, 0x204081u) & 0x01010101u; }

@@ -16,7 +16,7 @@
 // LDS round trip and no shuffle between the two matrix products.  Row max / sum reduce in-lane over the 4*NT
 // registers and across the 4 lane groups with two DPP-free shuffles.  Bias and mask are read as float4
 // (4 consecutive keys) from L2-resident tables.
-#include "common.h"
+#include "device_prims.h"
 #include "switches.h"
 
 namespace {
@@ -238,8 +238,6 @@ __global__ __launch_bounds__(256) void win_attn_kernel(AttnParams P) {
 //   * no control flow inside the strip (NTC is a template parameter): the compiler software-pipelines LDS reads;
 //   * softmax normalisation multiplies by one reciprocal per row.
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-constexpr uint32_t INV_OFF = 0x80000000u;
 
 #ifndef SDF_ATTN_WPE
 #define SDF_ATTN_WPE 3
@@ -389,10 +387,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
       for (int jt = 0; jt < NTC; ++jt) {
         const int kb = jt * 16 + 4 * lg;
         if (jt < NTC - 1) {                                        // 16 (NTC-1) < N: every tile but the last is whole
-          dst[jt] = __builtin_amdgcn_raw_buffer_load_b128(rs, qi < N ? rowoff + (uint32_t)kb * 4u : INV_OFF, 0, 0);
+          dst[jt] = __builtin_amdgcn_raw_buffer_load_b128(rs, qi < N ? rowoff + (uint32_t)kb * 4u : INV, 0, 0);
         } else {
-          const uint32_t o0 = (qi < N && kb < N) ? rowoff + (uint32_t)kb * 4u : INV_OFF;
-          const uint32_t o1 = (qi < N && kb + 2 < N) ? rowoff + (uint32_t)kb * 4u + 8u : INV_OFF;
+          const uint32_t o0 = (qi < N && kb < N) ? rowoff + (uint32_t)kb * 4u : INV;
+          const uint32_t o1 = (qi < N && kb + 2 < N) ? rowoff + (uint32_t)kb * 4u + 8u : INV;
           const u32x2 lo = __builtin_amdgcn_raw_buffer_load_b64(rs, o0, 0, 0);
           const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(rs, o1, 0, 0);
           dst[jt] = u32x4{lo.x, lo.y, hi.x, hi.y};
@@ -697,7 +695,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
     // one lane offset per strip (its query's row + the lane group's four keys; out of range as a whole for a padding query), the
     // key tile is the instruction's scalar offset: no address arithmetic per load
     const uint32_t rowoff = (uint32_t)qi * (uint32_t)N * 4u;
-    const uint32_t rbase = qi < N ? rowoff + 16u * (uint32_t)lg : INV_OFF;
+    const uint32_t rbase = qi < N ? rowoff + 16u * (uint32_t)lg : INV;
     auto load_strip = [&](const __amdgpu_buffer_rsrc_t& rs, u32x4 (&dst)[NTC]) __attribute__((always_inline)) {
 #pragma unroll
       for (int jt = 0; jt < NTC; ++jt) {
@@ -705,8 +703,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
         if (jt < NTC - 1) {
           dst[jt] = __builtin_amdgcn_raw_buffer_load_b128(rs, rbase, jt * 64, 0);
         } else {
-          const uint32_t o0 = (qi < N && kb < N) ? rowoff + (uint32_t)kb * 4u : INV_OFF;
-          const uint32_t o1 = (qi < N && kb + 2 < N) ? rowoff + (uint32_t)kb * 4u + 8u : INV_OFF;
+          const uint32_t o0 = (qi < N && kb < N) ? rowoff + (uint32_t)kb * 4u : INV;
+          const uint32_t o1 = (qi < N && kb + 2 < N) ? rowoff + (uint32_t)kb * 4u + 8u : INV;
           const u32x2 lo = __builtin_amdgcn_raw_buffer_load_b64(rs, o0, 0, 0);
           const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(rs, o1, 0, 0);
           dst[jt] = u32x4{lo.x, lo.y, hi.x, hi.y};
@@ -820,7 +818,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
       const int i = qt * 16 + 4 * lg + r;
       if (MODE == SDF_ATTN_ANN) {                                    // window reverse + roll back + crop: the row map (< 0: a padding token)
         orow[r] = b * N + i;
-        if (d.row_map) orow[r] = (int)__builtin_amdgcn_raw_buffer_load_b32(map_rs, i < N ? (uint32_t)(b * N + i) * 4u : INV_OFF, 0, 0);
+        if (d.row_map) orow[r] = (int)__builtin_amdgcn_raw_buffer_load_b32(map_rs, i < N ? (uint32_t)(b * N + i) * 4u : INV, 0, 0);
         if (i >= N) orow[r] = -1;
       } else {
         const int t = i / d.N1, n1 = i - t * d.N1;
@@ -829,7 +827,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const uint32_t off = orow[r] >= 0 ? ((uint32_t)orow[r] * (uint32_t)C + (uint32_t)(g * HD + l15)) * 4u : INV_OFF;
+      const uint32_t off = orow[r] >= 0 ? ((uint32_t)orow[r] * (uint32_t)C + (uint32_t)(g * HD + l15)) * 4u : INV;
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o0[r] * rinv[r]), out_rs, off, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o1[r] * rinv[r]), out_rs, off, 64, 0);
     }

@@ -1850,8 +1850,56 @@ def deconv_col2im(Y, imgs, H, W, Cout, alpha=None, beta=None, out=None):
 
 
 EVENT_VOXEL_MODES = {"signed": 0, "split": 1, "polarities": 2}
-_EV_WS = {}
-_EV_TB_WS = {}
+_EV_WS, _EV_TB_WS = {}, {}
+
+
+def _stream_ws(cache, dev, need):
+    """One scratch buffer per (device, stream) and entry-point family: calls on different streams must not share partial results."""
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    if key not in cache or cache[key].numel() < need:
+        cache[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return cache[key]
+
+
+def _event_lists(fn, x, y, t, p, offsets, xy_kinds):
+    """What the two event front ends check alike: x, y, t, p are 1-D GPU arrays of one length, x and y of one dtype the entry point takes
+    (`xy_kinds` words them; `fn` prefixes every message).  Returns the arrays contiguous, n, the list offsets as ints and as the
+    descriptor's host array (keep it alive across the calls), and the descriptor's xy_dtype."""
+    for a in (x, y, t, p):
+        _ptr(a)                                                          # (CPU tensors are refused, as everywhere)
+    n = int(t.numel())
+    if not (x.numel() == y.numel() == p.numel() == n and x.dim() == y.dim() == t.dim() == p.dim() == 1):
+        raise SdfError(f"{fn}: x, y, t, p are 1-D arrays of one length")
+    if x.dtype != y.dtype:
+        raise SdfError(f"{fn}: x and y differ in dtype")
+    xy = {torch.float32: 0, torch.int32: 1, torch.uint16: 2}.get(x.dtype)
+    if xy is None:
+        raise SdfError(f"{fn}: x, y are {xy_kinds}, not {x.dtype}")
+    offs = [0, n] if offsets is None else [int(o) for o in offsets]
+    return x.contiguous(), y.contiguous(), t.contiguous(), p.contiguous(), n, offs, (C.c_int64 * len(offs))(*offs), xy
+
+
+def _event_gather(fn, d, cache, need, refused, shape, out, n, dev):
+    """The tail the two event front ends share, on a descriptor filled up to the geometry: workspace of `need` bytes (<= 0: the
+    library refused the geometry - `refused` says which), `out` (None: a new tensor of `shape`), keys | stable sort | gather.
+    `fn` names the entry-point pair sdf_<fn>_keys_fwd / sdf_<fn>_gather_fwd and prefixes the messages."""
+    if need <= 0:
+        raise SdfError(f"{fn}: geometry refused ({refused})", rc=E_SHAPE)
+    ws = _stream_ws(cache, dev, need)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or not out.is_contiguous():
+        raise SdfError(f"{fn}: out must be a contiguous {shape} tensor")
+    d.out = _ptr(out, torch.float32)
+    keys = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    d.keys = keys.data_ptr()
+    _check(getattr(lib(), f"sdf_{fn}_keys_fwd")(C.byref(d), _stream()), f"sdf_{fn}_keys_fwd")
+    if n:
+        keys_sorted, order = torch.sort(keys, stable=True)               # plumbing: any stable sort serves
+        d.keys_sorted, d.order = keys_sorted.data_ptr(), order.data_ptr()
+    _check(getattr(lib(), f"sdf_{fn}_gather_fwd")(C.byref(d), _stream()), f"sdf_{fn}_gather_fwd")
+    return out
 
 
 def event_voxel(x, y, t, p, bins, sensor_size, offsets=None, crop=None, mode="signed", norm=None, spike_th=None, rectify_map=None,
@@ -1867,31 +1915,19 @@ def event_voxel(x, y, t, p, bins, sensor_size, offsets=None, crop=None, mode="si
     harness.prepare_chunk applies them | "polarities": convert_CHW_polarities (B, bins, 2, h, w).
     A non-empty list whose first and last time are equal raises SdfError (`check` reads the two times back: one small copy; False
     skips it, and such a list then adds nothing)."""
-    for a in (x, y, t, p):
-        _ptr(a)                                                          # (CPU tensors are refused, as everywhere)
-    n = int(t.numel())
-    if not (x.numel() == y.numel() == p.numel() == n and x.dim() == y.dim() == t.dim() == p.dim() == 1):
-        raise SdfError("event_voxel: x, y, t, p are 1-D arrays of one length")
+    x, y, t, p, n, offs, host_offs, xy = _event_lists("event_voxel", x, y, t, p, offsets, "fp32, or int32 / uint16 with a rectify_map")
     if mode not in EVENT_VOXEL_MODES or norm not in (None, "minmax"):
         raise SdfError(f"event_voxel: unknown mode {mode!r} / norm {norm!r} (norm 'std' is harness.prepare_chunk's, on the un-normalised output)")
-    offs = [0, n] if offsets is None else [int(o) for o in offsets]
     B, (H, W) = len(offs) - 1, sensor_size
     h, w = crop if crop else (H, W)
     dev = t.device
     d = EventVoxelDesc()
-    if x.dtype != y.dtype:
-        raise SdfError("event_voxel: x and y differ in dtype")
-    xy = {torch.float32: 0, torch.int32: 1, torch.uint16: 2}.get(x.dtype)
-    if xy is None:
-        raise SdfError(f"event_voxel: x, y are fp32, or int32 / uint16 with a rectify_map, not {x.dtype}")
-    x, y, t, p = x.contiguous(), y.contiguous(), t.contiguous(), p.contiguous()
     d.x, d.y, d.t, d.p, d.xy_dtype = x.data_ptr(), y.data_ptr(), _ptr(t, torch.float32), _ptr(p, torch.float32), xy
     if rectify_map is not None:
         if rectify_map.dim() != 3 or rectify_map.shape[2] != 2:
             raise SdfError("event_voxel: rectify_map is (H_s, W_s, 2)")
         rectify_map = rectify_map.contiguous()
         d.rectify_map, d.map_h, d.map_w = _ptr(rectify_map, torch.float32), rectify_map.shape[0], rectify_map.shape[1]
-    host_offs = (C.c_int64 * (B + 1))(*offs)
     d.offsets, d.n_events = C.addressof(host_offs), n
     d.B, d.C, d.H, d.W, d.crop_h, d.crop_w = B, bins, H, W, (h if crop else 0), (w if crop else 0)
     d.mode, d.norm = EVENT_VOXEL_MODES[mode], int(norm == "minmax")
@@ -1905,27 +1941,8 @@ def event_voxel(x, y, t, p, bins, sensor_size, offsets=None, crop=None, mode="si
         host_range = (C.c_float * (2 * B))(*flat)
         d.t_range = C.addressof(host_range)
     need = lib().sdf_event_voxel_workspace_bytes(n, B, bins, H, W, d.crop_h, d.crop_w)
-    if need <= 0:
-        raise SdfError(f"event_voxel: geometry refused (B {B}, bins {bins}, sensor {H} x {W}, crop {crop}, {n} events)", rc=E_SHAPE)
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _EV_WS or _EV_WS[key].numel() < need:
-        _EV_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    ws = _EV_WS[key]
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     shape = (B, bins, h, w) if mode == "signed" else (B, bins, 2, h, w)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != shape or not out.is_contiguous():
-        raise SdfError(f"event_voxel: out must be a contiguous {shape} tensor")
-    d.out = _ptr(out, torch.float32)
-    keys = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    d.keys = keys.data_ptr()
-    _check(lib().sdf_event_voxel_keys_fwd(C.byref(d), _stream()), "sdf_event_voxel_keys_fwd")
-    if n:
-        keys_sorted, order = torch.sort(keys, stable=True)               # plumbing: any stable sort serves
-        d.keys_sorted, d.order = keys_sorted.data_ptr(), order.data_ptr()
-    _check(lib().sdf_event_voxel_gather_fwd(C.byref(d), _stream()), "sdf_event_voxel_gather_fwd")
-    return out
+    return _event_gather("event_voxel", d, _EV_WS, need, f"B {B}, bins {bins}, sensor {H} x {W}, crop {crop}, {n} events", shape, out, n, dev)
 
 
 def event_voxel_tb(x, y, t, p, num_bins, sensor_size, offsets=None, t_scale=1.0, crop=None, crop_origin=None, normalize=True,
@@ -1942,16 +1959,11 @@ def event_voxel_tb(x, y, t, p, num_bins, sensor_size, offsets=None, t_scale=1.0,
     mode "signed": (L, num_bins, h, w) | "polarities": the pol=False form (L, num_bins, 2, h, w) | "split": the model's input
     (L / lists_per_sample, lists_per_sample * num_bins, 2, h, w) = relu(v) | relu(-v) with a sample's lists (old, new) along the bins,
     norm "minmax" / spike_th as harness.prepare_chunk applies them; with `want_event_mask` returns (input, mask (B, 1, h, w) fp32)."""
-    for a in (x, y, t, p):
-        _ptr(a)                                                          # (CPU tensors are refused, as everywhere)
-    n = int(t.numel())
-    if not (x.numel() == y.numel() == p.numel() == n and x.dim() == y.dim() == t.dim() == p.dim() == 1):
-        raise SdfError("event_voxel_tb: x, y, t, p are 1-D arrays of one length")
+    x, y, t, p, n, offs, host_offs, xy = _event_lists("event_voxel_tb", x, y, t, p, offsets, "fp32, int32 or uint16")
     if mode not in EVENT_VOXEL_MODES or norm not in (None, "minmax"):
         raise SdfError(f"event_voxel_tb: unknown mode {mode!r} / norm {norm!r} (norm 'std' is harness.prepare_chunk's, on the un-normalised output)")
     if mode != "split" and (norm or spike_th is not None or want_event_mask or lists_per_sample != 1):
         raise SdfError("event_voxel_tb: norm, spike_th, the event mask and paired lists belong to mode 'split'")
-    offs = [0, n] if offsets is None else [int(o) for o in offsets]
     L, (H, W) = len(offs) - 1, sensor_size
     if lists_per_sample not in (1, 2) or L < 1 or L % lists_per_sample:
         raise SdfError(f"event_voxel_tb: {L} lists do not make samples of {lists_per_sample}")
@@ -1959,58 +1971,25 @@ def event_voxel_tb(x, y, t, p, num_bins, sensor_size, offsets=None, t_scale=1.0,
     oy, ox = crop_origin if crop_origin is not None else ((int(round((H - h) / 2.0)), int(round((W - w) / 2.0))) if crop else (0, 0))
     dev = t.device
     d = EventVoxelTbDesc()
-    if x.dtype != y.dtype:
-        raise SdfError("event_voxel_tb: x and y differ in dtype")
-    xy = {torch.float32: 0, torch.int32: 1, torch.uint16: 2}.get(x.dtype)
-    if xy is None:
-        raise SdfError(f"event_voxel_tb: x, y are fp32, int32 or uint16, not {x.dtype}")
-    x, y, t, p = x.contiguous(), y.contiguous(), t.contiguous(), p.contiguous()
     d.x, d.y, d.t, d.p, d.xy_dtype = x.data_ptr(), y.data_ptr(), _ptr(t, torch.float64), _ptr(p, torch.float32), xy
     host_scale = C.c_double(float(t_scale))
-    host_offs = (C.c_int64 * (L + 1))(*offs)
     d.t_scale, d.offsets, d.n_events = C.addressof(host_scale), C.addressof(host_offs), n
     d.n_lists, d.lists_per_sample, d.nb, d.H, d.W = L, lists_per_sample, num_bins, H, W
     d.crop_h, d.crop_w, d.crop_oy, d.crop_ox = (h if crop else 0), (w if crop else 0), oy, ox
     d.normalize, d.mode, d.norm = int(bool(normalize)), EVENT_VOXEL_MODES[mode], int(norm == "minmax")
     d.use_spike_th, d.spike_th = int(spike_th is not None), float(spike_th or 0.0)
     need = lib().sdf_event_voxel_tb_workspace_bytes(n, L, num_bins, H, W, d.crop_h, d.crop_w, oy, ox, d.normalize)
-    if need <= 0:
-        raise SdfError(f"event_voxel_tb: geometry refused ({L} lists, bins {num_bins}, sensor {H} x {W}, crop {crop} at {(oy, ox)}, "
-                       f"{n} events)", rc=E_SHAPE)
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _EV_TB_WS or _EV_TB_WS[key].numel() < need:
-        _EV_TB_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    ws = _EV_TB_WS[key]
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     shape = {"signed": (L, num_bins, h, w), "polarities": (L, num_bins, 2, h, w),
              "split": (L // lists_per_sample, lists_per_sample * num_bins, 2, h, w)}[mode]
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != shape or not out.is_contiguous():
-        raise SdfError(f"event_voxel_tb: out must be a contiguous {shape} tensor")
-    d.out = _ptr(out, torch.float32)
     mask = torch.empty((shape[0], 1, h, w), dtype=torch.float32, device=dev) if want_event_mask else None
     d.event_mask = _ptr(mask, torch.float32)
-    keys = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    d.keys = keys.data_ptr()
-    _check(lib().sdf_event_voxel_tb_keys_fwd(C.byref(d), _stream()), "sdf_event_voxel_tb_keys_fwd")
-    if n:
-        keys_sorted, order = torch.sort(keys, stable=True)               # plumbing: any stable sort serves
-        d.keys_sorted, d.order = keys_sorted.data_ptr(), order.data_ptr()
-    _check(lib().sdf_event_voxel_tb_gather_fwd(C.byref(d), _stream()), "sdf_event_voxel_tb_gather_fwd")
+    out = _event_gather("event_voxel_tb", d, _EV_TB_WS, need,
+                        f"{L} lists, bins {num_bins}, sensor {H} x {W}, crop {crop} at {(oy, ox)}, {n} events", shape, out, n, dev)
     return (out, mask) if want_event_mask else out
 
 
 FLOW_METRICS_FIELDS = ("n_valid", "sum_err", "n_pe1", "n_pe2", "n_pe3", "n_outlier", "sum_ang", "n_pixels")
 _FM_WS, _PC_WS = {}, {}
-
-
-def _stream_ws(cache, dev, need):
-    """One scratch buffer per (device, stream) and entry-point family: calls on different streams must not share partial results."""
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    if key not in cache or cache[key].numel() < need:
-        cache[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return cache[key]
 
 
 def flow_metrics(pred, label, valid, event_mask=None, flow_scaling=1.0, table=None, row=0):
