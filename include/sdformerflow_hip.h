@@ -115,6 +115,34 @@ int sdf_plif_bwd(const float* x, const float* plif_k, const float* grad_spike, f
                  int64_t workspace_bytes, int T, int64_t N, float v_th, int soft_reset, float v_reset, int detach_reset,
                  int surrogate, float alpha, void* stream);
 
+/* Online gradient of SLTTLIFNode (the reference's `neuron_type: SLTTlif`, Spiking_submodules.py:11-90): the forward is sdf_lif_fwd;
+ * the backward is sdf_lif_bwd's with the membrane detached between steps (:41), gv == 0 at every step:
+ *   gx_t = grad_spike_t * g'(h_t - v_th) / tau
+ * detach_reset has no effect (the reset only feeds the detached membrane), so the entry point does not take it.  Same shapes,
+ * T set and trajectory recomputation as sdf_lif_bwd; tau > 1; a surrogate other than SDF_SURROGATE_ATAN returns SDF_E_SHAPE. */
+int sdf_sltt_bwd(const float* x, const float* grad_spike, float* grad_x, int T, int64_t N, float tau, float v_th, int soft_reset,
+                 float v_reset, int surrogate, float alpha, void* stream);
+
+/* GLIF neuron (the reference's GatedLIFNode with layer-wise gates, `neuron_type: glif`, Spiking_submodules.py:94-181), forward and
+ * BPTT.  `tab` = [L, Dk, g, R, th, c_0 .. c_{T-1}], 5 + T fp32 in DEVICE memory, formed by the caller on the same stream from the
+ * 7 + T gate logits (a = sigmoid(alpha), b = sigmoid(beta)):
+ *   L = 1 - a (1 - sigmoid(tau))   Dk = (1 - a) sigmoid(linear_decay)   g = sigmoid(gamma)   R = (1 - g) sigmoid(v_subreset)
+ *   th = sigmoid(v_threshold)      c_t = 1 - b (1 - sigmoid(conduct_t))
+ * The host never reads it.  Forward, from v = 0, s = 0, every op separately rounded in the reference's order:
+ *   u = (L v - Dk) + x_t c_t ;  u = u - ((L v) g) s - R s ;  s = (u - th >= 0) ;  v = u
+ * x (T, N) fp32 contiguous, N % 4 == 0, 16-byte aligned; spikes fp32 or u8; T in {2, 4, 5, 10, 20}, otherwise SDF_E_SHAPE.
+ * Backward (the spike is NOT detached between steps): the trajectory is recomputed from x, then for t = T-1 .. 0
+ *   S_t = gs_t + gu_{t+1} (-(L v_t) g - R) ;  gu_t = gu_{t+1} (L - L g s_t) + g'(u_t - th) S_t ;  grad_x_t = gu_t c_t
+ * grad_tab (5 + T fp32): dL = sum gu_t (v_{t-1} - v_{t-1} g s_{t-1}), dDk = -sum gu_t, dg = -sum gu_t L v_{t-1} s_{t-1},
+ * dR = -sum gu_t s_{t-1}, dth = -sum g'(u_t - th) S_t, dc_t = sum_n gu_t x_t; reduced lane -> wave -> workgroup -> one row of
+ * partials per workgroup in `workspace` (sdf_glif_bwd_workspace_bytes(T, N) = 4 (5 + T) ceil(N / 1024) bytes, caller-owned) -> one
+ * fixed-order finish: no atomics, two calls give bit-equal results.  ATan surrogate only: another one returns SDF_E_SHAPE, as does
+ * a workspace that is too small. */
+int sdf_glif_fwd(const float* x, const float* tab, void* spike, int T, int64_t N, int spike_dtype, void* stream);
+int64_t sdf_glif_bwd_workspace_bytes(int T, int64_t N);
+int sdf_glif_bwd(const float* x, const float* tab, const float* grad_spike, float* grad_x, float* grad_tab, void* workspace,
+                 int64_t workspace_bytes, int T, int64_t N, int surrogate, float alpha, void* stream);
+
 /* Batch-statistics BatchNorm over the last dim of a channel-last (R, C) fp32 buffer, forward and backward (training form of
  * the SpikingNormLayer "BN": spikingjelly layer.BatchNorm2d multi-step -> nn.BatchNorm2d on the view the reference makes with
  * permute(0,1,4,2,3); Spiking_modules.py:101-146, Spiking_swin_transformer3D.py:172, 178, 673, 677, 714, 972) - no permute

@@ -25,9 +25,9 @@ surrogate = _Surrogate
 
 
 class Spiking_neuron(nn.Module):
-    """reference Spiking_modules.py:26-99 - the `neuron_type` switch.  lif / if / psn / plif / SLTTlif run on the HIP kernels
-    (plif: the multiplicative charge through the `tau` field; SLTTlif: LIF forward); glif is torch element-wise ops on the
-    tensor's device (module-level only - the fused engines refuse it)."""
+    """reference Spiking_modules.py:26-99 - the `neuron_type` switch.  Every type runs on HIP kernels, forward and backward
+    (plif: the multiplicative charge through the `tau` field; SLTTlif: LIF forward, online gradient; glif: csrc/glif.hip on the
+    derived gate table - module level and training only, the fused engines refuse it)."""
 
     def __init__(self, num_steps, spike_norm=None, neuron_type="plif", v_th=1.0, v_reset=0, surrogate_fun="surrogate.ATan()",
                  tau=2.0, detach_reset=True):

@@ -66,12 +66,14 @@ class IFNode(LIFNode):
 
 class SLTTLIFNode(LIFNode):
     """reference Spiking_submodules.py:11-90.  "The forward propagation is the same as the Leaky Integrate-and-Fire neuron's"
-    (:17-19): inference runs on the LIF kernels.  What differs is the gradient (the membrane is detached between steps, :41),
-    which the training path here does not build."""
+    (:17-19): the LIF kernels.  What differs is the gradient: the membrane is detached between steps (:41), which the training
+    path takes from the LIF BPTT kernel with that flag (`autograd.SLTTFunction`, sdf_sltt_bwd)."""
 
     def forward(self, x_seq):
-        if torch.is_grad_enabled() and x_seq.requires_grad:
-            raise NotImplementedError("SLTTLIFNode: the online (detached-membrane) gradient is not built; inference only")
+        if torch.is_grad_enabled() and x_seq.requires_grad:        # training path: HIP forward + the online gradient
+            from ..autograd import SLTTFunction
+            return SLTTFunction.apply(x_seq, self.tau, self.v_threshold, self.v_reset,
+                                      getattr(self.surrogate_function, "alpha", 2.0))
         return super().forward(x_seq)
 
 
@@ -113,11 +115,12 @@ class ParametricLIFNode(LIFNode):
 
 class GatedLIFNode(nn.Module):
     """reference Spiking_submodules.py:94-181 (GLIF, layer-wise gates as `Spiking_neuron` builds it: `inplane=None`,
-    Spiking_modules.py:84-92).  No HIP kernel: the recurrence below is torch element-wise ops on the tensor's own device (what
-    SURVEY.md section 2 row 4 asks: API-complete, torch fallback), so the module works stand-alone; the fused engines refuse a
-    model built with it (no shipped configuration uses it).  Same operation order as the reference's `multi_step_forward`."""
+    Spiking_modules.py:84-92).  The recurrence runs on csrc/glif.hip: one launch in eval mode, `autograd.GLIFFunction` (forward +
+    BPTT with the gradients of all 7 + T gate logits) in train mode.  The kernels take the gates as the derived table `table()`
+    builds on the device.  Every call starts from v = 0, s = 0 (the harness resets the net before every forward).  The fused
+    engines refuse a model built with it (no shipped configuration uses it)."""
     kind = "glif"
-    supported_backends = ("torch",)
+    supported_backends = ("torch", "hip")
 
     def __init__(self, T, inplane=None, init_linear_decay=None, init_v_subreset=None, init_tau=0.25, init_v_threshold=0.5,
                  init_conduct=0.5, surrogate_function=None, step_mode="m", backend="torch"):
@@ -138,30 +141,31 @@ class GatedLIFNode(nn.Module):
     def reset(self):
         self.v = self.u = 0.0
 
+    def table(self):
+        """[L, Dk, g, R, th, c_0 .. c_{T-1}] (include/sdformerflow_hip.h sdf_glif_fwd) as a (5 + T) fp32 tensor on the parameters'
+        device, differentiable to the 7 + T logits; the products in the reference's order (Spiking_submodules.py:153-162)."""
+        al, be, ga = self.alpha.float().sigmoid(), self.beta.float().sigmoid(), self.gamma.float().sigmoid()
+        head = torch.stack([1 - al * (1 - self.tau.float().sigmoid()), (1 - al) * self.linear_decay.float().sigmoid(), ga,
+                            (1 - ga) * self.v_subreset.float().sigmoid(), self.v_threshold.float().sigmoid()])
+        return torch.cat([head, 1 - be * (1 - self.conduct.float().sigmoid())])
+
     def forward(self, x_seq):
-        if torch.is_grad_enabled() and (x_seq.requires_grad or self.training):
-            raise NotImplementedError("GatedLIFNode: inference only (the surrogate gradient is not built)")
         if x_seq.shape[0] != self.T:
             raise hip.SdfError(f"GatedLIFNode(T={self.T}) got {x_seq.shape[0]} steps")
+        train = torch.is_grad_enabled() and (x_seq.requires_grad or self.training)
+        if train and not x_seq.is_cuda:                            # (the wording and type of STSwinNet.forward's refusal)
+            raise NotImplementedError("GatedLIFNode trains on the GPU only: forward and BPTT are HIP kernels (no CPU fallback)")
         if not x_seq.is_cuda:
             raise hip.SdfError("GatedLIFNode runs on the GPU tensor's device only (no CPU path in the product; the CPU restatement "
                                "is oracle.sdformer_oracle.glif_multistep)")
+        if train:                                                  # training path: HIP forward + BPTT, dL/dgates
+            from ..autograd import GLIFFunction
+            return GLIFFunction.apply(x_seq, self.table(), getattr(self.surrogate_function, "alpha", 2.0))
         with torch.no_grad():
-            al, be, ga = self.alpha.sigmoid(), self.beta.sigmoid(), self.gamma.sigmoid()
-            leak = 1 - al * (1 - self.tau.sigmoid())
-            v, spike, out = self.v, torch.zeros_like(x_seq[0]), []
-            for t in range(self.T):
-                inp = x_seq[t] * (1 - be * (1 - self.conduct[t].sigmoid()))                     # neuronal_charge :155-159
-                u = (leak * v - (1 - al) * self.linear_decay.sigmoid()) + inp
-                u = u - leak * v * ga * spike - (1 - ga) * self.v_subreset.sigmoid() * spike     # neuronal_reset  :163-165
-                spike = (u - self.v_threshold.sigmoid() >= 0).to(x_seq.dtype)                    # neuronal_fire   :169
-                v = u
-                out.append(spike)
-            self.v = self.u = v
-        return torch.stack(out)
+            return hip.glif_fwd(x_seq.float(), self.table()).to(x_seq.dtype)
 
     def extra_repr(self):
-        return f"T={self.T}, backend=torch"
+        return f"T={self.T}, backend=hip"
 
 
 class PSN(nn.Module):

@@ -54,6 +54,49 @@ class PLIFFunction(torch.autograd.Function):
         return gx.to(ctx.in_dtype), gk.view(kshape).to(kdtype), None, None, None, None
 
 
+class SLTTFunction(torch.autograd.Function):
+    """Multi-step SLTT-LIF over dim 0 (reference SLTTLIFNode, Spiking_submodules.py:11-90): the LIF forward; the backward is the LIF
+    BPTT with the membrane detached between steps (:41), dL/dx_t = dL/ds_t g'(h_t - v_th) / tau.  `detach_reset` does not enter: the
+    reset only feeds the detached membrane."""
+
+    @staticmethod
+    def forward(ctx, x, tau, v_th, v_reset, alpha):
+        ctx.in_dtype = x.dtype
+        x = x.float().contiguous()
+        ctx.save_for_backward(x)
+        ctx.cfg = (tau, v_th, v_reset, alpha)
+        return hip.lif_fwd(x, tau, v_th, v_reset, torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_spike):
+        (x,) = ctx.saved_tensors
+        tau, v_th, v_reset, alpha = ctx.cfg
+        return hip.sltt_bwd(x, grad_spike.float(), tau, v_th, v_reset, alpha).to(ctx.in_dtype), None, None, None, None
+
+
+class GLIFFunction(torch.autograd.Function):
+    """Multi-step GatedLIFNode over dim 0: spikes = GLIF(x; tab); (dL/dx, dL/dtab) by BPTT with the ATan surrogate and the spike NOT
+    detached between steps (reference: autograd through GatedLIFNode.multi_step_forward, Spiking_submodules.py:152-180).  `tab` is
+    the derived gate table as a device tensor (`GatedLIFNode.table()`): autograd carries dL/dtab on to the 7 + T gate logits, and no
+    kernel argument is read back to the host."""
+
+    @staticmethod
+    def forward(ctx, x, tab, alpha):
+        ctx.in_dtype = x.dtype
+        x = x.float().contiguous()
+        tf = tab.detach().float().contiguous()
+        ctx.save_for_backward(x, tf)
+        ctx.cfg = (alpha, tab.dtype)
+        return hip.glif_fwd(x, tf)
+
+    @staticmethod
+    def backward(ctx, grad_spike):
+        x, tf = ctx.saved_tensors
+        alpha, tdtype = ctx.cfg
+        gx, gtab = hip.glif_bwd(x, tf, grad_spike.float(), alpha)
+        return gx.to(ctx.in_dtype), gtab.to(tdtype), None
+
+
 class PSNFunction(torch.autograd.Function):
     """Parallel spiking neuron over dim 0: spikes = (b + W x >= 0); (dL/dx, dL/dW, dL/db) with the ATan surrogate
     (reference PSN.forward, Spiking_submodules.py:207-211)."""

@@ -26,6 +26,7 @@ struct BwdParams {
   float* gx;
   int64_t N;
   int T, kind, soft, detach;
+  int sltt;                        // SLTT-LIF: the membrane is detached between steps (gv == 0 at every step)
   float tau, inv_tau, v_th, v_reset;
   float c_atan, half_alpha;        // (float)(pi/2 * alpha), (float)(alpha/2)
   const float* W;
@@ -41,6 +42,8 @@ __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<floa
 // LIF / IF, and PLIF (spikingjelly ParametricLIFNode, h = v + d * k with k = sigmoid(w) read from device memory): the same
 // streaming shape and BPTT with gx = gh * k, gv = gh - gh * k (k = 0.5 is LIF tau = 2 bit for bit), plus dL/dk = sum_t sum_i gh_t * d_t,
 // d_t the charge difference the forward used, kept beside h_t (167 VGPRs at T = 10, 3 waves per SIMD; LIF: 128, 4).
+// SLTT-LIF (P.sltt, wave-uniform; reference SLTTLIFNode.neuronal_charge detaches v, Spiking_submodules.py:41): the same kernel with
+// gv held at zero, so gx_t = sg_atan(h_t - v_th, gs_t) / tau and the reset path (which only feeds the detached membrane) drops out.
 // dL/dk: per lane over its steps and neurons -> wave butterfly -> workgroup (LDS) -> one partial per workgroup ->
 // psn_bwd_finish_kernel (fixed order).
 template <int TT, bool PLIF>
@@ -89,6 +92,7 @@ __global__ __launch_bounds__(256) void lif_bwd_kernel(BwdParams P) {
         acc = __builtin_fmaf(gh, dx[t][j], acc);
       } else {
         neuron_charge_bwd(is_if, gh, P.tau, P.inv_tau, gx[j], gv[j]);
+        if (P.sltt) gv[j] = 0.f;                               // online gradient: nothing flows back through v_{t-1}
       }
     }
     if (live) st4(P.gx + (int64_t)t * P.N + e, make_float4(gx[0], gx[1], gx[2], gx[3]));
@@ -250,6 +254,30 @@ extern "C" int sdf_lif_bwd(const float* x, const float* grad_spike, float* grad_
   P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = kind; P.soft = soft_reset; P.detach = detach_reset;
   P.tau = tau; P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
   P.inv_tau = sdf_inv_tau(kind, tau);
+  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
+  dim3 grid((unsigned)((N / 4 + 255) / 256)), block(256);
+  hipStream_t s = sdf_stream(stream);
+#define SDF_T_CASE(TT) case TT: SDF_LAUNCH((lif_bwd_kernel<TT, false>), grid, block, 0, s, P); break;
+  switch (T) {
+    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
+    default: return SDF_E_SHAPE;
+  }
+#undef SDF_T_CASE
+  SDF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sdf_sltt_bwd(const float* x, const float* grad_spike, float* grad_x, int T, int64_t N, float tau, float v_th,
+                            int soft_reset, float v_reset, int surrogate, float alpha, void* stream) {
+  if (!x || !grad_spike || !grad_x) return SDF_E_NULL;
+  if (N < 4 || N % 4 || !(tau > 1.f)) return SDF_E_SHAPE;
+  if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_SHAPE;        // ATan is the only surrogate built
+  if (T != 1 && T != 2 && T != 4 && T != 5 && T != 8 && T != 10 && T != 16 && T != 20) return SDF_E_SHAPE;
+  if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16)) return SDF_E_ALIGN;
+  BwdParams P = {};
+  P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = SDF_LIF; P.soft = soft_reset; P.detach = 1; P.sltt = 1;
+  P.tau = tau; P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
+  P.inv_tau = sdf_inv_tau(SDF_LIF, tau);
   sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   dim3 grid((unsigned)((N / 4 + 255) / 256)), block(256);
   hipStream_t s = sdf_stream(stream);

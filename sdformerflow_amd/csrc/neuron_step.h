@@ -87,3 +87,29 @@ __device__ __forceinline__ void plif_charge_bwd(float gh, float k, float& gx, fl
   gx = qd;
   gv = gh - qd;
 }
+
+// GLIF (the reference's GatedLIFNode with layer-wise gates, Spiking_submodules.py:152-180).  The host forms the derived gates once:
+// L = 1 - a (1 - sigmoid(tau)), Dk = (1 - a) sigmoid(linear_decay), g = sigmoid(gamma), R = (1 - g) sigmoid(v_subreset),
+// th = sigmoid(v_threshold), and per step c_t = 1 - b (1 - sigmoid(conduct_t)), a = sigmoid(alpha), b = sigmoid(beta).
+struct GlifGates { float L, Dk, g, R, th; };
+
+// one step: charge with the previous membrane v and spike s, reset by s, fire; v becomes u (the spike is NOT subtracted from v:
+// the reset of step t acts inside step t + 1).  Returns u_t.
+__device__ __forceinline__ float glif_step(float& v, float& s, float x, float c, const GlifGates& G) {
+  const float inp = x * c;
+  const float lv = G.L * v;
+  float u = (lv - G.Dk) + inp;
+  u = (u - (lv * G.g) * s) - G.R * s;
+  s = spike_of(u, G.th);
+  v = u;
+  return u;
+}
+
+// one step of its backward: gu = dL/du_{t+1} on entry, dL/du_t on return; u, s = u_t, s_t; gs = dL/ds_t.  sg = the surrogate term
+// (dL/dth sums its negative).  The spike is not detached: dL/ds_t takes the reset path of step t + 1.
+__device__ __forceinline__ float glif_bwd_step(float gu, float gs, float u, float s, const GlifGates& G, float c_atan, float ha, float& sg) {
+  const float S = gs + gu * (-((G.L * u) * G.g) - G.R);
+  const float V = gu * (G.L - (G.L * G.g) * s);
+  sg = sg_atan(u - G.th, S, c_atan, ha);
+  return V + sg;
+}

@@ -294,6 +294,9 @@ SIGNATURES = {
     "sdf_psn_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i, _f, _p)),
     "sdf_plif_fwd": (_i, (_p, _p, _p, _i, _i64, _f, _i, _f, _p)), "sdf_plif_bwd_workspace_bytes": (_i64, (_i, _i64)),
     "sdf_plif_bwd": (_i, (_p, _p, _p, _p, _p, _p, _i64, _i, _i64, _f, _i, _f, _i, _i, _f, _p)),
+    "sdf_sltt_bwd": (_i, (_p, _p, _p, _i, _i64, _f, _f, _i, _f, _i, _f, _p)),
+    "sdf_glif_fwd": (_i, (_p, _p, _p, _i, _i64, _i, _p)), "sdf_glif_bwd_workspace_bytes": (_i64, (_i, _i64)),
+    "sdf_glif_bwd": (_i, (_p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i, _f, _p)),
     "sdf_bn_train_workspace_bytes": (_i64, (_i64, _i)),
     "sdf_bn_train_fwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _f, _f, _p, _i64, _p)),
     "sdf_bn_train_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p)),
@@ -595,6 +598,57 @@ def plif_bwd(x, k, grad_spike, v_th=1.0, v_reset=None, detach_reset=True, alpha=
                             nbytes, T, N, v_th, *_reset(v_reset), 1 if detach_reset else 0, 0, alpha, _stream())
     _check(rc, "sdf_plif_bwd")
     return gx, gk
+
+
+def sltt_bwd(x, grad_spike, tau=2.0, v_th=1.0, v_reset=None, alpha=2.0):
+    """Online gradient of the multi-step SLTT-LIF (sdf_sltt_bwd): dL/dx with the membrane detached between steps; ATan surrogate."""
+    (x, g), info = _pad4(x, grad_spike)
+    if info is not None:
+        return _unpad4(sltt_bwd(x, g, tau, v_th, v_reset, alpha), info)
+    T, N = x.shape[0], x[0].numel()
+    gx = torch.empty_like(x)
+    rc = lib().sdf_sltt_bwd(_ptr(x, torch.float32), _ptr(g, torch.float32), _ptr(gx), T, N, tau, v_th, *_reset(v_reset), 0, alpha,
+                            _stream())
+    _check(rc, "sdf_sltt_bwd")
+    return gx
+
+
+def glif_fwd(x, tab, out_dtype=torch.float32):
+    """Multi-step GatedLIFNode over dim 0 (sdf_glif_fwd) from v = 0, s = 0; `tab` = [L, Dk, g, R, th, c_0 .. c_{T-1}], 5 + T fp32 in
+    DEVICE memory (read by the kernel, never by the host).  Padded columns are sliced off."""
+    (x,), info = _pad4(x)
+    if info is not None:
+        return _unpad4(glif_fwd(x, tab, out_dtype), info)
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise SdfError(f"spike dtype {out_dtype} unsupported")
+    T, N = x.shape[0], x[0].numel()
+    if tab.numel() != 5 + T:
+        raise SdfError(f"glif_fwd: the gate table has {tab.numel()} entries, T = {T} needs {5 + T}")
+    out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    rc = lib().sdf_glif_fwd(_ptr(x, torch.float32), _ptr(tab, torch.float32), _ptr(out), T, N,
+                            SDF_F32 if out_dtype == torch.float32 else SDF_U8, _stream())
+    _check(rc, "sdf_glif_fwd")
+    return out
+
+
+def glif_bwd(x, tab, grad_spike, alpha=2.0):
+    """BPTT through the multi-step GatedLIFNode (sdf_glif_bwd): (dL/dx, dL/dtab), dL/dtab 5 + T fp32 reduced in a fixed order (no
+    atomics); ATan surrogate.  Padded columns (x = 0, dL/ds = 0) carry dL/du = 0 at every step: they add nothing to dL/dtab."""
+    (x, g), info = _pad4(x, grad_spike)
+    if info is not None:
+        gx, gtab = glif_bwd(x, tab, g, alpha)
+        return _unpad4(gx, info), gtab
+    T, N = x.shape[0], x[0].numel()
+    if tab.numel() != 5 + T:
+        raise SdfError(f"glif_bwd: the gate table has {tab.numel()} entries, T = {T} needs {5 + T}")
+    gx = torch.empty_like(x)
+    gtab = torch.empty((5 + T,), dtype=torch.float32, device=x.device)
+    nbytes = lib().sdf_glif_bwd_workspace_bytes(T, N)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
+    rc = lib().sdf_glif_bwd(_ptr(x, torch.float32), _ptr(tab, torch.float32), _ptr(g, torch.float32), _ptr(gx), _ptr(gtab), _ptr(ws),
+                            nbytes, T, N, 0, alpha, _stream())
+    _check(rc, "sdf_glif_bwd")
+    return gx, gtab
 
 
 def psn_bwd(x, W, b, grad_spike, alpha=2.0, need_param_grads=True):

@@ -1,8 +1,8 @@
 """Training path of the MS SDformerFlow models (BASELINE config 4): train-mode forward under
 autograd, the supervised loss, one optimiser step, and the data-parallel gradient all-reduce.
 
-What is hand-written HIP here: every spiking neuron, forward AND backward (`autograd.LIFFunction` / `PSNFunction` ->
-csrc/neuron.hip, csrc/neuron_bwd.hip; 105 neuron calls per forward), the batch-statistics BatchNorm, the token gate, and -
+What is hand-written HIP here: every spiking neuron, forward AND backward (`autograd.LIFFunction` / `PSNFunction` / `PLIFFunction` /
+`SLTTFunction` / `GLIFFunction` -> csrc/neuron.hip, csrc/neuron_bwd.hip, csrc/glif.hip; 105 neuron calls per forward), the batch-statistics BatchNorm, the token gate, and -
 since round 5 - ALL THREE products of every Linear layer (`autograd.LinearHipFunction`: forward and dX on csrc/linear_train.hip,
 dW on csrc/linear_dw.hip: 35 ms of library fp32 GEMM -> 13 ms; no rocBLAS GEMM of a Linear layer is left in a step) and the forward and
 weight gradient of the MS_ResBlock convolutions (`autograd.Conv3x3HipFunction`: products over zero-ringed channels-last pixel rows).
@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .STSwinNet_SNN.Spiking_submodules import ParametricLIFNode
+from .STSwinNet_SNN.Spiking_submodules import GatedLIFNode, ParametricLIFNode, SLTTLIFNode
 
 
 # ---------------------------------------------------------------------------------------------- layers
@@ -171,7 +171,8 @@ def qk_attention(x, attn):
     k = _bn_last(_linear(xs, attn.linear_k), attn.bn_k.norm_layer)
     k = attn.sn_k(k + attn.positional_encoding.reshape(Tq, 1, N1, C))
     gate = attn.sn2_q.spiking_neuron
-    if hd == 32 and Tq in (1, 2, 4):                                    # token gate, forward and backward one HIP launch each
+    composed = isinstance(gate, (GatedLIFNode, SLTTLIFNode))            # GLIF / SLTT-LIF gate: head sum -> the node's own Function -> * k
+    if hd == 32 and Tq in (1, 2, 4) and not composed:                   # token gate, forward and backward one HIP launch each
         from .autograd import QKGateFunction
         alpha = getattr(gate.surrogate_function, "alpha", 2.0)
         if isinstance(gate, ParametricLIFNode):                          # (its `kind` stays "lif": the inference engine reads that)
@@ -181,7 +182,7 @@ def qk_attention(x, attn):
             e = QKGateFunction.apply(q, k, gate.weight, gate.bias, "psn", 2.0, 0.0, None, True, alpha)
         else:
             e = QKGateFunction.apply(q, k, None, None, gate.kind, gate.tau, gate.v_threshold, gate.v_reset, gate.detach_reset, alpha)
-    else:                                                               # other head widths / window depths: composed expression
+    else:                                                               # other head widths / window depths / gates: composed expression
         a = attn.sn2_q(q.reshape(Tq, B_, N1, nH, hd).sum(-1))
         e = k * a.repeat_interleave(hd, dim=-1)
     z = e.reshape(B_, nH, Tq, N1, hd).permute(2, 0, 3, 1, 4).reshape(Tq, B_, N1, C)     # the reference's raw head reshape
