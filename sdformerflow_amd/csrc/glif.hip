@@ -12,6 +12,7 @@
 // partials per workgroup in the caller's workspace -> glif_bwd_finish_kernel, a fixed-shape tree: no atomics, two calls give
 // bit-equal results.  Lanes past the end re-read the last quad and add nothing.
 #include "common.h"
+#include "host_launch.h"
 #include "neuron_step.h"
 
 namespace {
@@ -151,42 +152,33 @@ __global__ __launch_bounds__(256) void glif_bwd_finish_kernel(const float* parti
   }
   if (threadIdx.x == 0) grad_tab[i] = sm[0];
 }
-
-bool glif_T_ok(int T) { return T == 2 || T == 4 || T == 5 || T == 10 || T == 20; }
-int64_t glif_blocks(int64_t N) { return (N / 4 + 255) / 256; }
-
 }  // namespace
 
 extern "C" int sdf_glif_fwd(const float* x, const float* tab, void* spike, int T, int64_t N, int spike_dtype, void* stream) {
   if (!x || !tab || !spike) return SDF_E_NULL;
-  if (N < 4 || N % 4 || !glif_T_ok(T) || glif_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
+  if (N < 4 || N % 4 || !sdf_T_in(SDF_T_GLIF, T) || sdf_quad_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
   if (spike_dtype != SDF_F32 && spike_dtype != SDF_U8) return SDF_E_DTYPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(spike, spike_dtype == SDF_F32 ? 16 : 4) || !sdf_aligned(tab, 4)) return SDF_E_ALIGN;
-  dim3 grid((unsigned)glif_blocks(N)), block(256);
+  dim3 grid((unsigned)sdf_quad_blocks(N)), block(256);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT)                                                                        \
-  case TT:                                                                                    \
-    if (spike_dtype == SDF_U8) SDF_LAUNCH((glif_fwd_kernel<TT, true>), grid, block, 0, s, x, tab, spike, N); \
-    else SDF_LAUNCH((glif_fwd_kernel<TT, false>), grid, block, 0, s, x, tab, spike, N);       \
-    break;
-  switch (T) {
-    SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(10) SDF_T_CASE(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_T_CASE
+  if (!sdf_for_T(SDF_T_GLIF, T, [&](auto tt) {
+        if (spike_dtype == SDF_U8) SDF_LAUNCH((glif_fwd_kernel<tt, true>), grid, block, 0, s, x, tab, spike, N);
+        else SDF_LAUNCH((glif_fwd_kernel<tt, false>), grid, block, 0, s, x, tab, spike, N);
+      }))
+    return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int64_t sdf_glif_bwd_workspace_bytes(int T, int64_t N) {
-  if (!glif_T_ok(T) || N < 4) return 0;
-  return glif_blocks(N) * (5 + T) * (int64_t)sizeof(float);      // one row of 5 + T fp32 partials per workgroup
+  if (!sdf_T_in(SDF_T_GLIF, T) || N < 4) return 0;
+  return sdf_quad_blocks(N) * (5 + T) * (int64_t)sizeof(float);      // one row of 5 + T fp32 partials per workgroup
 }
 
 extern "C" int sdf_glif_bwd(const float* x, const float* tab, const float* grad_spike, float* grad_x, float* grad_tab,
                             void* workspace, int64_t workspace_bytes, int T, int64_t N, int surrogate, float alpha, void* stream) {
   if (!x || !tab || !grad_spike || !grad_x || !grad_tab || !workspace) return SDF_E_NULL;
-  if (N < 4 || N % 4 || !glif_T_ok(T) || glif_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
+  if (N < 4 || N % 4 || !sdf_T_in(SDF_T_GLIF, T) || sdf_quad_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_SHAPE;        // ATan is the only surrogate built
   if (workspace_bytes < sdf_glif_bwd_workspace_bytes(T, N)) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16) || !sdf_aligned(tab, 4) ||
@@ -195,15 +187,10 @@ extern "C" int sdf_glif_bwd(const float* x, const float* tab, const float* grad_
   GlifBwdParams P = {};
   P.x = x; P.tab = tab; P.gs = grad_spike; P.gx = grad_x; P.partial = reinterpret_cast<float*>(workspace); P.N = N;
   sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
-  const int64_t nblk = glif_blocks(N);
+  const int64_t nblk = sdf_quad_blocks(N);
   dim3 grid((unsigned)nblk), block(256);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH(glif_bwd_kernel<TT>, grid, block, 0, s, P); break;
-  switch (T) {
-    SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(10) SDF_T_CASE(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_T_CASE
+  if (!sdf_for_T(SDF_T_GLIF, T, [&](auto tt) { SDF_LAUNCH(glif_bwd_kernel<tt>, grid, block, 0, s, P); })) return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   SDF_LAUNCH(glif_bwd_finish_kernel, dim3(5 + T), dim3(256), 0, s, P.partial, nblk, 5 + T, grad_tab);
   SDF_LAUNCH_CHECK();

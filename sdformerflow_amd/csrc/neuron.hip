@@ -10,6 +10,7 @@
 // rounded IEEE fp32 op - this file is compiled with -ffp-contract=off - and the only fused
 // operations are the explicit fmaf() of the BN prologue and of the PSN chain.
 #include "common.h"
+#include "host_launch.h"
 #include "neuron_step.h"
 
 namespace {
@@ -268,27 +269,28 @@ int validate(const SdfNeuronDesc& d) {
   return 0;
 }
 
+NeuronParams neuron_params(const SdfNeuronDesc& d) {               // of a validated descriptor
+  NeuronParams P;
+  P.d = d;
+  P.quads = (d.nrep > 1 ? d.nrep : 1) * d.nb * d.ni / 4;
+  P.rows = d.rowmap ? d.nb * d.ni / d.rowlen : 0;
+  P.inv_tau = sdf_inv_tau(d.kind, d.tau);
+  return P;
+}
+
 }  // namespace
 
 extern "C" int sdf_neuron_fwd(const SdfNeuronDesc* dp, void* stream) {
   if (!dp) return SDF_E_NULL;
   int rc = validate(*dp);
   if (rc) return rc;
-  NeuronParams P;
-  P.d = *dp;
-  P.quads = (dp->nrep > 1 ? dp->nrep : 1) * dp->nb * dp->ni / 4;
-  P.rows = dp->rowmap ? dp->nb * dp->ni / dp->rowlen : 0;
-  P.inv_tau = sdf_inv_tau(dp->kind, dp->tau);
-  dim3 grid((unsigned)((P.quads + 255) / 256)), block(256);
+  const NeuronParams P = neuron_params(*dp);
+  dim3 grid((unsigned)sdf_quad_blocks(P.quads * 4)), block(256);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH(neuron_kernel<TT>, grid, block, 0, s, P); break;
-  switch (dp->T) {
-    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
-    default:
-      if (dp->kind == SDF_PSN) return SDF_E_SHAPE;
-      SDF_LAUNCH(neuron_kernel<0>, grid, block, 0, s, P);
+  if (!sdf_for_T(SDF_T_STREAM, dp->T, [&](auto tt) { SDF_LAUNCH(neuron_kernel<tt>, grid, block, 0, s, P); })) {
+    if (dp->kind == SDF_PSN) return SDF_E_SHAPE;
+    SDF_LAUNCH(neuron_kernel<0>, grid, block, 0, s, P);            // any other T: the runtime-T kernel
   }
-#undef SDF_T_CASE
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -298,7 +300,7 @@ extern "C" int sdf_neuron_multi_fwd(const SdfNeuronDesc* descs, int n, void* str
   if (n < 1) return SDF_E_SHAPE;
   if (n == 1) return sdf_neuron_fwd(descs, stream);
   const int T = descs[0].T;
-  bool one = n <= MULTI_MAX && (T == 2 || T == 4 || T == 5 || T == 10 || T == 20);
+  bool one = n <= MULTI_MAX && sdf_T_in(SDF_T_GLIF, T);
   for (int i = 0; i < n; ++i) {
     const int rc = validate(descs[i]);
     if (rc) return rc;
@@ -315,25 +317,15 @@ extern "C" int sdf_neuron_multi_fwd(const SdfNeuronDesc* descs, int n, void* str
   M.n = n;
   int64_t wgs = 0;
   for (int i = 0; i < n; ++i) {
-    NeuronParams& P = M.p[i];
-    P.d = descs[i];
-    P.quads = (descs[i].nrep > 1 ? descs[i].nrep : 1) * descs[i].nb * descs[i].ni / 4;
-    P.rows = descs[i].rowmap ? descs[i].nb * descs[i].ni / descs[i].rowlen : 0;
-    P.inv_tau = sdf_inv_tau(descs[i].kind, descs[i].tau);
+    M.p[i] = neuron_params(descs[i]);
     M.first[i] = (int)wgs;
-    wgs += (P.quads + 255) / 256;
+    wgs += sdf_quad_blocks(M.p[i].quads * 4);
     if (wgs >= (1LL << 31)) return SDF_E_SHAPE;
   }
   for (int i = n; i <= MULTI_MAX; ++i) M.first[i] = (int)wgs;
   dim3 grid((unsigned)wgs), block(256);
   hipStream_t s = sdf_stream(stream);
-  switch (T) {
-    case 2: SDF_LAUNCH(neuron_multi_kernel<2>, grid, block, 0, s, M); break;
-    case 4: SDF_LAUNCH(neuron_multi_kernel<4>, grid, block, 0, s, M); break;
-    case 5: SDF_LAUNCH(neuron_multi_kernel<5>, grid, block, 0, s, M); break;
-    case 10: SDF_LAUNCH(neuron_multi_kernel<10>, grid, block, 0, s, M); break;
-    default: SDF_LAUNCH(neuron_multi_kernel<20>, grid, block, 0, s, M); break;
-  }
+  sdf_for_T(SDF_T_GLIF, T, [&](auto tt) { SDF_LAUNCH(neuron_multi_kernel<tt>, grid, block, 0, s, M); });   // `one`: T is in the list
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -350,7 +342,7 @@ extern "C" int sdf_lif_fwd(const float* x, void* spike, float* v_last, int T, in
 
 extern "C" int sdf_psn_fwd(const float* x, const float* W, const float* b, void* spike, int T, int64_t N,
                            int spike_dtype, void* stream) {
-  if (N % 4 || (T != 1 && T != 2 && T != 4 && T != 5 && T != 8 && T != 10 && T != 16 && T != 20))
+  if (N % 4 || !sdf_T_in(SDF_T_STREAM, T))
     return launch_scalar(x, spike, nullptr, T, N, SDF_PSN, 2.f, 0.f, 1, 0.f, spike_dtype, W, b, stream);
   SdfNeuronDesc d = {};
   d.x = x; d.out = spike; d.T = T; d.out_dtype = spike_dtype;
@@ -400,14 +392,12 @@ extern "C" int sdf_plif_fwd(const float* x, const float* plif_k, float* spike, i
   if (N < 4 || N % 4) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(spike, 16) || !sdf_aligned(plif_k, 4)) return SDF_E_ALIGN;
   if (soft_reset) v_reset = 0.f;
-  dim3 grid((unsigned)((N / 4 + 255) / 256)), block(256);
+  dim3 grid((unsigned)sdf_quad_blocks(N)), block(256);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH(plif_fwd_kernel<TT>, grid, block, 0, s, x, plif_k, spike, N, v_th, soft_reset, v_reset); break;
-  switch (T) {
-    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_T_CASE
+  if (!sdf_for_T(SDF_T_STREAM, T, [&](auto tt) {
+        SDF_LAUNCH(plif_fwd_kernel<tt>, grid, block, 0, s, x, plif_k, spike, N, v_th, soft_reset, v_reset);
+      }))
+    return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   return 0;
 }

@@ -16,6 +16,7 @@
 // workgroup (LDS) -> per-workgroup partials in the caller's workspace, summed in a fixed order by a second tiny kernel
 // (deterministic, no atomics).
 #include "common.h"
+#include "host_launch.h"
 #include "neuron_step.h"
 
 namespace {
@@ -232,11 +233,29 @@ __global__ __launch_bounds__(256) void psn_bwd_finish_kernel(const float* partia
   }
 }
 
-int psn_vec(int T, bool reduce) { return (reduce && T >= 8) ? 2 : 4; }
+// Neurons per lane of the reducing PSN backward at each T of SDF_T_STREAM (see psn_bwd_kernel); 0: no reducing variant is built
+constexpr int psn_reduce_vec(int T) { return T < 8 ? 4 : T <= 10 ? 2 : 0; }
+
+int psn_vec(int T, bool reduce) { return reduce && psn_reduce_vec(T) ? psn_reduce_vec(T) : 4; }
 
 int psn_blocks(int T, int64_t N, bool reduce) {
   const int64_t need = (N / psn_vec(T, reduce) + 255) / 256;
   return (int)(need < 512 ? need : 512);     // two resident workgroups per CU; the end-of-block reduction is amortised over the grid-stride loop
+}
+
+// What sdf_lif_bwd / sdf_sltt_bwd / sdf_plif_bwd share once their own argument checks have passed: the common fields of P (the caller
+// has set those that are its own: kind / tau, sltt / detach, plif_k / partial), the grid and the launch of lif_bwd_kernel<T, PLIF>.
+template <bool PLIF>
+int lif_bwd_launch(BwdParams& P, const float* x, const float* grad_spike, float* grad_x, int T, int64_t N, float v_th, int soft_reset,
+                   float v_reset, float alpha, hipStream_t s) {
+  P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.soft = soft_reset;
+  P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
+  P.inv_tau = PLIF ? 0.f : sdf_inv_tau(P.kind, P.tau);
+  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
+  dim3 grid((unsigned)sdf_quad_blocks(N)), block(256);
+  if (!sdf_for_T(SDF_T_STREAM, T, [&](auto tt) { SDF_LAUNCH((lif_bwd_kernel<tt, PLIF>), grid, block, 0, s, P); })) return SDF_E_SHAPE;
+  SDF_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace
@@ -251,20 +270,8 @@ extern "C" int sdf_lif_bwd(const float* x, const float* grad_spike, float* grad_
   if (kind == SDF_LIF && !(tau > 1.f)) return SDF_E_SHAPE;        // the multiplicative (PLIF) form has no backward here
   if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16)) return SDF_E_ALIGN;
   BwdParams P = {};
-  P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = kind; P.soft = soft_reset; P.detach = detach_reset;
-  P.tau = tau; P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
-  P.inv_tau = sdf_inv_tau(kind, tau);
-  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
-  dim3 grid((unsigned)((N / 4 + 255) / 256)), block(256);
-  hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH((lif_bwd_kernel<TT, false>), grid, block, 0, s, P); break;
-  switch (T) {
-    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_T_CASE
-  SDF_LAUNCH_CHECK();
-  return 0;
+  P.kind = kind; P.tau = tau; P.detach = detach_reset;
+  return lif_bwd_launch<false>(P, x, grad_spike, grad_x, T, N, v_th, soft_reset, v_reset, alpha, sdf_stream(stream));
 }
 
 extern "C" int sdf_sltt_bwd(const float* x, const float* grad_spike, float* grad_x, int T, int64_t N, float tau, float v_th,
@@ -272,23 +279,11 @@ extern "C" int sdf_sltt_bwd(const float* x, const float* grad_spike, float* grad
   if (!x || !grad_spike || !grad_x) return SDF_E_NULL;
   if (N < 4 || N % 4 || !(tau > 1.f)) return SDF_E_SHAPE;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_SHAPE;        // ATan is the only surrogate built
-  if (T != 1 && T != 2 && T != 4 && T != 5 && T != 8 && T != 10 && T != 16 && T != 20) return SDF_E_SHAPE;
+  if (!sdf_T_in(SDF_T_STREAM, T)) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16)) return SDF_E_ALIGN;
   BwdParams P = {};
-  P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = SDF_LIF; P.soft = soft_reset; P.detach = 1; P.sltt = 1;
-  P.tau = tau; P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
-  P.inv_tau = sdf_inv_tau(SDF_LIF, tau);
-  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
-  dim3 grid((unsigned)((N / 4 + 255) / 256)), block(256);
-  hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH((lif_bwd_kernel<TT, false>), grid, block, 0, s, P); break;
-  switch (T) {
-    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_T_CASE
-  SDF_LAUNCH_CHECK();
-  return 0;
+  P.kind = SDF_LIF; P.tau = tau; P.detach = 1; P.sltt = 1;
+  return lif_bwd_launch<false>(P, x, grad_spike, grad_x, T, N, v_th, soft_reset, v_reset, alpha, sdf_stream(stream));
 }
 
 extern "C" int64_t sdf_psn_bwd_workspace_bytes(int T, int64_t N) {
@@ -315,19 +310,17 @@ extern "C" int sdf_psn_bwd(const float* x, const float* W, const float* b, const
   const int nblk = psn_blocks(T, N, reduce);
   dim3 grid((unsigned)nblk), block(256);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT, V)                                                                  \
-  case TT:                                                                                 \
-    if (reduce) SDF_LAUNCH((psn_bwd_kernel<TT, true, V>), grid, block, 0, s, P);   \
-    else SDF_LAUNCH((psn_bwd_kernel<TT, false, 4>), grid, block, 0, s, P);         \
-    break;
-#define SDF_T_CASE_NR(TT) case TT: SDF_LAUNCH((psn_bwd_kernel<TT, false, 4>), grid, block, 0, s, P); break;
-  switch (T) {
-    SDF_T_CASE(1, 4) SDF_T_CASE(2, 4) SDF_T_CASE(4, 4) SDF_T_CASE(5, 4) SDF_T_CASE(8, 2) SDF_T_CASE(10, 2)
-    SDF_T_CASE_NR(16) SDF_T_CASE_NR(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_T_CASE
-#undef SDF_T_CASE_NR
+  if (!sdf_for_T(SDF_T_STREAM, T, [&](auto tt) {
+        constexpr int V = psn_reduce_vec(tt);
+        if constexpr (V != 0) {
+          if (reduce) {
+            SDF_LAUNCH((psn_bwd_kernel<tt, true, V>), grid, block, 0, s, P);
+            return;
+          }
+        }
+        SDF_LAUNCH((psn_bwd_kernel<tt, false, 4>), grid, block, 0, s, P);
+      }))
+    return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   if (reduce) {
     const int nacc = T * T + T;
@@ -339,7 +332,7 @@ extern "C" int sdf_psn_bwd(const float* x, const float* W, const float* b, const
 
 extern "C" int64_t sdf_plif_bwd_workspace_bytes(int T, int64_t N) {
   if (T < 1 || N < 4) return 0;
-  return (N / 4 + 255) / 256 * (int64_t)sizeof(float);          // one fp32 partial of dL/dk per workgroup
+  return sdf_quad_blocks(N) * (int64_t)sizeof(float);           // one fp32 partial of dL/dk per workgroup
 }
 
 extern "C" int sdf_plif_bwd(const float* x, const float* plif_k, const float* grad_spike, float* grad_x, float* grad_k,
@@ -348,27 +341,17 @@ extern "C" int sdf_plif_bwd(const float* x, const float* plif_k, const float* gr
   if (!x || !plif_k || !grad_spike || !grad_x || !grad_k || !workspace) return SDF_E_NULL;
   if (N < 4 || N % 4) return SDF_E_SHAPE;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_DTYPE;
-  if (T != 1 && T != 2 && T != 4 && T != 5 && T != 8 && T != 10 && T != 16 && T != 20) return SDF_E_SHAPE;
+  if (!sdf_T_in(SDF_T_STREAM, T)) return SDF_E_SHAPE;
   if (workspace_bytes < sdf_plif_bwd_workspace_bytes(T, N)) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16) || !sdf_aligned(plif_k, 4) ||
       !sdf_aligned(grad_k, 4) || !sdf_aligned(workspace, 4))
     return SDF_E_ALIGN;
   BwdParams P = {};
-  P.x = x; P.gs = grad_spike; P.gx = grad_x; P.N = N; P.T = T; P.kind = SDF_LIF; P.soft = soft_reset; P.detach = detach_reset;
-  P.v_th = v_th; P.v_reset = soft_reset ? 0.f : v_reset;
-  sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
-  P.partial = reinterpret_cast<float*>(workspace); P.plif_k = plif_k;
-  const int nblk = (int)((N / 4 + 255) / 256);
-  dim3 grid((unsigned)nblk), block(256);
+  P.kind = SDF_LIF; P.detach = detach_reset; P.plif_k = plif_k; P.partial = reinterpret_cast<float*>(workspace);
   hipStream_t s = sdf_stream(stream);
-#define SDF_T_CASE(TT) case TT: SDF_LAUNCH((lif_bwd_kernel<TT, true>), grid, block, 0, s, P); break;
-  switch (T) {
-    SDF_T_CASE(1) SDF_T_CASE(2) SDF_T_CASE(4) SDF_T_CASE(5) SDF_T_CASE(8) SDF_T_CASE(10) SDF_T_CASE(16) SDF_T_CASE(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_T_CASE
-  SDF_LAUNCH_CHECK();
-  SDF_LAUNCH(psn_bwd_finish_kernel, dim3(1), dim3(256), 0, s, P.partial, nblk, 1, 0, (float*)nullptr, grad_k);
+  const int rc = lif_bwd_launch<true>(P, x, grad_spike, grad_x, T, N, v_th, soft_reset, v_reset, alpha, s);
+  if (rc) return rc;
+  SDF_LAUNCH(psn_bwd_finish_kernel, dim3(1), dim3(256), 0, s, P.partial, (int)sdf_quad_blocks(N), 1, 0, (float*)nullptr, grad_k);
   SDF_LAUNCH_CHECK();
   return 0;
 }

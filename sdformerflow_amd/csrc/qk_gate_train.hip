@@ -11,6 +11,7 @@
 // carry gradients (the inference kernel of qk_gate.hip moves bytes).  PSN gates carry a learnable T' x T' matrix and bias: their
 // gradients are reduced wave -> workgroup -> per-workgroup partials -> fixed-order finish (deterministic, no atomics).
 #include "common.h"
+#include "host_launch.h"
 #include "neuron_step.h"
 
 namespace {
@@ -192,16 +193,14 @@ __global__ __launch_bounds__(256) void gate_finish_kernel(const float* partial, 
   }
 }
 
+// workgroups of the gate kernel (and rows of its partials): 8 lanes per (row, head), 256 lanes per workgroup
+int64_t gate_blocks(int64_t rows, int C) { return (rows * (C / 32) * 8 + 255) / 256; }
+
 template <bool BWD, bool PLIF = false>
 int launch(const GateTrainParams& P, int Tq, hipStream_t s) {
-  const int64_t lanes = P.rows * P.G * 8;
-  dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-  switch (Tq) {
-    case 1: SDF_LAUNCH((qk_gate_train_kernel<1, BWD, PLIF>), grid, block, 0, s, P); break;
-    case 2: SDF_LAUNCH((qk_gate_train_kernel<2, BWD, PLIF>), grid, block, 0, s, P); break;
-    case 4: SDF_LAUNCH((qk_gate_train_kernel<4, BWD, PLIF>), grid, block, 0, s, P); break;
-    default: return SDF_E_SHAPE;
-  }
+  dim3 grid((unsigned)gate_blocks(P.rows, P.C)), block(256);
+  if (!sdf_for_T(SDF_T_GATE, Tq, [&](auto tt) { SDF_LAUNCH((qk_gate_train_kernel<tt, BWD, PLIF>), grid, block, 0, s, P); }))
+    return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -222,8 +221,7 @@ extern "C" int sdf_qk_gate_f32_fwd(const float* q, const float* k, float* e, int
 
 extern "C" int64_t sdf_qk_gate_bwd_workspace_bytes(int Tq, int64_t rows, int C) {
   if (Tq < 1 || rows < 1 || C < 32) return 0;
-  const int64_t nblk = (rows * (C / 32) * 8 + 255) / 256;
-  return nblk * (Tq * Tq + Tq) * (int64_t)sizeof(float);
+  return gate_blocks(rows, C) * (Tq * Tq + Tq) * (int64_t)sizeof(float);
 }
 
 extern "C" int sdf_qk_gate_bwd(const float* q, const float* k, const float* grad_e, float* grad_q, float* grad_k, int Tq,
@@ -246,9 +244,9 @@ extern "C" int sdf_qk_gate_bwd(const float* q, const float* k, const float* grad
   sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   const int rc2 = launch<true>(P, Tq, sdf_stream(stream));
   if (rc2 || kind != SDF_PSN) return rc2;
-  const int64_t nblk = (rows * (C / 32) * 8 + 255) / 256;
   const int nacc = Tq * Tq + Tq;
-  SDF_LAUNCH(gate_finish_kernel, dim3(nacc), dim3(256), 0, sdf_stream(stream), P.partial, nblk, nacc, Tq, grad_psn_w, grad_psn_b);
+  SDF_LAUNCH(gate_finish_kernel, dim3(nacc), dim3(256), 0, sdf_stream(stream), P.partial, gate_blocks(rows, C), nacc, Tq, grad_psn_w,
+             grad_psn_b);
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -268,7 +266,7 @@ extern "C" int sdf_qk_gate_plif_f32_fwd(const float* q, const float* k, float* e
 
 extern "C" int64_t sdf_qk_gate_plif_bwd_workspace_bytes(int Tq, int64_t rows, int C) {
   if (Tq < 1 || rows < 1 || C < 32) return 0;
-  return (rows * (C / 32) * 8 + 255) / 256 * (int64_t)sizeof(float);     // one fp32 partial of dL/dk per workgroup
+  return gate_blocks(rows, C) * (int64_t)sizeof(float);                  // one fp32 partial of dL/dk per workgroup
 }
 
 extern "C" int sdf_qk_gate_plif_bwd(const float* q, const float* k, const float* grad_e, float* grad_q, float* grad_k,
@@ -277,7 +275,7 @@ extern "C" int sdf_qk_gate_plif_bwd(const float* q, const float* k, const float*
                                     float alpha, void* stream) {
   if (!q || !k || !grad_e || !grad_q || !grad_k || !plif_k || !grad_plif_k || !workspace) return SDF_E_NULL;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_DTYPE;
-  if (Tq != 1 && Tq != 2 && Tq != 4) return SDF_E_SHAPE;
+  if (!sdf_T_in(SDF_T_GATE, Tq)) return SDF_E_SHAPE;
   GateTrainParams P = {};
   const int rc = fill(P, rows, C, SDF_LIF, 2.f, v_th, soft_reset, v_reset);
   if (rc) return rc;
@@ -290,8 +288,8 @@ extern "C" int sdf_qk_gate_plif_bwd(const float* q, const float* k, const float*
   sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   const int rc2 = launch<true, true>(P, Tq, sdf_stream(stream));
   if (rc2) return rc2;
-  const int64_t nblk = (rows * (C / 32) * 8 + 255) / 256;
-  SDF_LAUNCH(gate_finish_kernel, dim3(1), dim3(256), 0, sdf_stream(stream), P.partial, nblk, 1, 0, (float*)nullptr, grad_plif_k);
+  SDF_LAUNCH(gate_finish_kernel, dim3(1), dim3(256), 0, sdf_stream(stream), P.partial, gate_blocks(rows, C), 1, 0, (float*)nullptr,
+             grad_plif_k);
   SDF_LAUNCH_CHECK();
   return 0;
 }

@@ -9,6 +9,8 @@ the GPU the call raises.
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import inspect
 import os
 
 import torch
@@ -529,19 +531,34 @@ def neuron_multi_fwd(calls):
     _check(lib().sdf_neuron_multi_fwd(descs, len(calls), _stream()), "sdf_neuron_multi_fwd")
 
 
-def _pad4(*ts):
+def _pad4(*padded):
     """The streaming neuron kernels move 4 neurons per lane: a per-step size that is not a multiple of 4 (e.g. the
-    (T', B_, 81, 3) token gate of the QK attention) is run on a zero-padded (T, N4) copy and sliced back."""
-    shape = ts[0].shape
-    T, N = shape[0], ts[0][0].numel()
-    if N % 4 == 0:
-        return [t.contiguous() for t in ts], None
-    pad = 4 - N % 4
-    return [torch.nn.functional.pad(t.reshape(T, N), (0, pad)) for t in ts], (shape, N)
+    (T', B_, 81, 3) token gate of the QK attention) is run on a zero-padded (T, N4) copy and sliced back.  Decorator: the arguments
+    named in `padded` (the first one gives T and N) reach the wrapper contiguous and, where needed, padded; its result - of a tuple
+    the first entry, dL/dx - is sliced back to the caller's shape.  Padded columns carry x = 0 and dL/ds = 0, hence dL/dh = 0 at
+    every step: they add nothing to the parameter gradients (dL/dk, dL/dtab, dW / db), which pass through as they are."""
+    def deco(fn):
+        sig = inspect.signature(fn)
+
+        @functools.wraps(fn)
+        def wrapper(*args, **kw):
+            call = sig.bind(*args, **kw)
+            first = call.arguments[padded[0]]
+            shape, T, N = first.shape, first.shape[0], first[0].numel()
+            for name in padded:
+                t = call.arguments[name]
+                call.arguments[name] = torch.nn.functional.pad(t.reshape(T, N), (0, -N % 4)) if N % 4 else t.contiguous()
+            res = fn(*call.args, **call.kwargs)
+            if N % 4 == 0:
+                return res
+            return (res[0][:, :N].reshape(shape), *res[1:]) if isinstance(res, tuple) else res[:, :N].reshape(shape)
+        return wrapper
+    return deco
 
 
-def _unpad4(out, info):
-    return out if info is None else out[:, :info[1]].reshape(info[0])
+def _ws_f32(nbytes, device):
+    """fp32 workspace of at least `nbytes` (what a *_workspace_bytes function asked for) and never empty."""
+    return torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=device)
 
 
 def lif_fwd(x, tau=2.0, v_th=1.0, v_reset=None, out_dtype=torch.float32, return_v=False):
@@ -556,25 +573,21 @@ def lif_fwd(x, tau=2.0, v_th=1.0, v_reset=None, out_dtype=torch.float32, return_
     return (out, v) if return_v else out
 
 
+@_pad4("x", "grad_spike")
 def lif_bwd(x, grad_spike, tau=2.0, v_th=1.0, v_reset=None, detach_reset=True, alpha=2.0, kind="lif"):
     """BPTT through the multi-step LIF / IF over dim 0 (sdf_lif_bwd): dL/dx from x and dL/dspike; ATan surrogate."""
-    (x, g), info = _pad4(x, grad_spike)
-    if info is not None:
-        return _unpad4(lif_bwd(x, g, tau, v_th, v_reset, detach_reset, alpha, kind), info)
     T, N = x.shape[0], x[0].numel()
     gx = torch.empty_like(x)
-    rc = lib().sdf_lif_bwd(_ptr(x, torch.float32), _ptr(g, torch.float32), _ptr(gx), T, N, KIND[kind], tau, v_th, *_reset(v_reset),
-                           1 if detach_reset else 0, 0, alpha, _stream())
+    rc = lib().sdf_lif_bwd(_ptr(x, torch.float32), _ptr(grad_spike, torch.float32), _ptr(gx), T, N, KIND[kind], tau, v_th,
+                           *_reset(v_reset), 1 if detach_reset else 0, 0, alpha, _stream())
     _check(rc, "sdf_lif_bwd")
     return gx
 
 
+@_pad4("x")
 def plif_fwd(x, k, v_th=1.0, v_reset=None):
     """Multi-step ParametricLIFNode over dim 0 for the training path (sdf_plif_fwd): fp32 spikes; `k` = sigmoid(w), a one-element
     fp32 DEVICE tensor (read by the kernel, never by the host)."""
-    (x,), info = _pad4(x)
-    if info is not None:
-        return _unpad4(plif_fwd(x, k, v_th, v_reset), info)
     T, N = x.shape[0], x[0].numel()
     out = torch.empty_like(x)
     rc = lib().sdf_plif_fwd(_ptr(x, torch.float32), _ptr(k, torch.float32), _ptr(out), T, N, v_th, *_reset(v_reset), _stream())
@@ -582,43 +595,36 @@ def plif_fwd(x, k, v_th=1.0, v_reset=None):
     return out
 
 
+@_pad4("x", "grad_spike")
 def plif_bwd(x, k, grad_spike, v_th=1.0, v_reset=None, detach_reset=True, alpha=2.0):
     """BPTT through the multi-step ParametricLIFNode (sdf_plif_bwd): (dL/dx, dL/dk), dL/dk a one-element fp32 tensor reduced in a
-    fixed order (no atomics); ATan surrogate.  Padded columns (x = 0, dL/ds = 0) add nothing to dL/dk."""
-    (x, g), info = _pad4(x, grad_spike)
-    if info is not None:
-        gx, gk = plif_bwd(x, k, g, v_th, v_reset, detach_reset, alpha)
-        return _unpad4(gx, info), gk
+    fixed order (no atomics); ATan surrogate."""
     T, N = x.shape[0], x[0].numel()
     gx = torch.empty_like(x)
     gk = torch.empty((1,), dtype=torch.float32, device=x.device)
     nbytes = lib().sdf_plif_bwd_workspace_bytes(T, N)
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
-    rc = lib().sdf_plif_bwd(_ptr(x, torch.float32), _ptr(k, torch.float32), _ptr(g, torch.float32), _ptr(gx), _ptr(gk), _ptr(ws),
-                            nbytes, T, N, v_th, *_reset(v_reset), 1 if detach_reset else 0, 0, alpha, _stream())
+    ws = _ws_f32(nbytes, x.device)
+    rc = lib().sdf_plif_bwd(_ptr(x, torch.float32), _ptr(k, torch.float32), _ptr(grad_spike, torch.float32), _ptr(gx), _ptr(gk),
+                            _ptr(ws), nbytes, T, N, v_th, *_reset(v_reset), 1 if detach_reset else 0, 0, alpha, _stream())
     _check(rc, "sdf_plif_bwd")
     return gx, gk
 
 
+@_pad4("x", "grad_spike")
 def sltt_bwd(x, grad_spike, tau=2.0, v_th=1.0, v_reset=None, alpha=2.0):
     """Online gradient of the multi-step SLTT-LIF (sdf_sltt_bwd): dL/dx with the membrane detached between steps; ATan surrogate."""
-    (x, g), info = _pad4(x, grad_spike)
-    if info is not None:
-        return _unpad4(sltt_bwd(x, g, tau, v_th, v_reset, alpha), info)
     T, N = x.shape[0], x[0].numel()
     gx = torch.empty_like(x)
-    rc = lib().sdf_sltt_bwd(_ptr(x, torch.float32), _ptr(g, torch.float32), _ptr(gx), T, N, tau, v_th, *_reset(v_reset), 0, alpha,
-                            _stream())
+    rc = lib().sdf_sltt_bwd(_ptr(x, torch.float32), _ptr(grad_spike, torch.float32), _ptr(gx), T, N, tau, v_th, *_reset(v_reset),
+                            0, alpha, _stream())
     _check(rc, "sdf_sltt_bwd")
     return gx
 
 
+@_pad4("x")
 def glif_fwd(x, tab, out_dtype=torch.float32):
     """Multi-step GatedLIFNode over dim 0 (sdf_glif_fwd) from v = 0, s = 0; `tab` = [L, Dk, g, R, th, c_0 .. c_{T-1}], 5 + T fp32 in
-    DEVICE memory (read by the kernel, never by the host).  Padded columns are sliced off."""
-    (x,), info = _pad4(x)
-    if info is not None:
-        return _unpad4(glif_fwd(x, tab, out_dtype), info)
+    DEVICE memory (read by the kernel, never by the host)."""
     if out_dtype not in (torch.float32, torch.uint8):
         raise SdfError(f"spike dtype {out_dtype} unsupported")
     T, N = x.shape[0], x[0].numel()
@@ -631,33 +637,27 @@ def glif_fwd(x, tab, out_dtype=torch.float32):
     return out
 
 
+@_pad4("x", "grad_spike")
 def glif_bwd(x, tab, grad_spike, alpha=2.0):
     """BPTT through the multi-step GatedLIFNode (sdf_glif_bwd): (dL/dx, dL/dtab), dL/dtab 5 + T fp32 reduced in a fixed order (no
-    atomics); ATan surrogate.  Padded columns (x = 0, dL/ds = 0) carry dL/du = 0 at every step: they add nothing to dL/dtab."""
-    (x, g), info = _pad4(x, grad_spike)
-    if info is not None:
-        gx, gtab = glif_bwd(x, tab, g, alpha)
-        return _unpad4(gx, info), gtab
+    atomics); ATan surrogate."""
     T, N = x.shape[0], x[0].numel()
     if tab.numel() != 5 + T:
         raise SdfError(f"glif_bwd: the gate table has {tab.numel()} entries, T = {T} needs {5 + T}")
     gx = torch.empty_like(x)
     gtab = torch.empty((5 + T,), dtype=torch.float32, device=x.device)
     nbytes = lib().sdf_glif_bwd_workspace_bytes(T, N)
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
-    rc = lib().sdf_glif_bwd(_ptr(x, torch.float32), _ptr(tab, torch.float32), _ptr(g, torch.float32), _ptr(gx), _ptr(gtab), _ptr(ws),
-                            nbytes, T, N, 0, alpha, _stream())
+    ws = _ws_f32(nbytes, x.device)
+    rc = lib().sdf_glif_bwd(_ptr(x, torch.float32), _ptr(tab, torch.float32), _ptr(grad_spike, torch.float32), _ptr(gx), _ptr(gtab),
+                            _ptr(ws), nbytes, T, N, 0, alpha, _stream())
     _check(rc, "sdf_glif_bwd")
     return gx, gtab
 
 
+@_pad4("x", "grad_spike")
 def psn_bwd(x, W, b, grad_spike, alpha=2.0, need_param_grads=True):
     """Backward of the parallel spiking neuron (sdf_psn_bwd): (dL/dx, dL/dW, dL/db); ATan surrogate.
     T <= 10 reduces dW / db in the kernel; larger T takes grad_h from the kernel and one library GEMM."""
-    (x, g), info = _pad4(x, grad_spike)
-    if info is not None:                     # padded columns carry x = 0, dL/ds = 0: they add nothing to dW / db
-        gx, gW, gb = psn_bwd(x, W, b, g, alpha, need_param_grads)
-        return _unpad4(gx, info), gW, gb
     T, N = x.shape[0], x[0].numel()
     gx = torch.empty_like(x)
     fused = need_param_grads and T <= 10
@@ -665,9 +665,10 @@ def psn_bwd(x, W, b, grad_spike, alpha=2.0, need_param_grads=True):
     gb = torch.empty((T,), dtype=torch.float32, device=x.device) if fused else None
     gh = torch.empty_like(x) if (need_param_grads and not fused) else None
     nbytes = lib().sdf_psn_bwd_workspace_bytes(T, N) if fused else 0
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device) if fused else None
+    ws = _ws_f32(nbytes, x.device) if fused else None
     rc = lib().sdf_psn_bwd(_ptr(x, torch.float32), _ptr(W.contiguous(), torch.float32), _ptr(b.contiguous().view(-1), torch.float32),
-                           _ptr(g, torch.float32), _ptr(gx), _ptr(gW), _ptr(gb), _ptr(gh), _ptr(ws), nbytes, T, N, 0, alpha, _stream())
+                           _ptr(grad_spike, torch.float32), _ptr(gx), _ptr(gW), _ptr(gb), _ptr(gh), _ptr(ws), nbytes, T, N, 0, alpha,
+                           _stream())
     _check(rc, "sdf_psn_bwd")
     if gh is not None:
         gW, gb = gh.view(T, -1) @ x.view(T, -1).t(), gh.view(T, -1).sum(1)
@@ -1179,7 +1180,7 @@ def qk_gate_bwd(q, k, grad_e, p: NeuronParams, detach_reset=True, alpha=2.0):
     gW = torch.empty((Tq, Tq), dtype=torch.float32, device=q.device) if psn else None
     gb = torch.empty((Tq,), dtype=torch.float32, device=q.device) if psn else None
     nbytes = lib().sdf_qk_gate_bwd_workspace_bytes(Tq, rows, Cc) if psn else 0
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=q.device) if psn else None
+    ws = _ws_f32(nbytes, q.device) if psn else None
     rc = lib().sdf_qk_gate_bwd(_ptr(q, torch.float32), _ptr(k, torch.float32), _ptr(g, torch.float32), _ptr(gq), _ptr(gk), Tq, rows, Cc,
                                KIND[p.kind], p.tau, p.v_th, *_reset(p.v_reset), 1 if detach_reset else 0, 0, alpha,
                                _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32), _ptr(gW), _ptr(gb), _ptr(ws), nbytes, _stream())
@@ -1206,7 +1207,7 @@ def qk_gate_plif_bwd(q, k, grad_e, plif_k, v_th=1.0, v_reset=None, detach_reset=
     gq, gk = torch.empty_like(q), torch.empty_like(k)
     gpk = torch.empty((1,), dtype=torch.float32, device=q.device)
     nbytes = lib().sdf_qk_gate_plif_bwd_workspace_bytes(Tq, rows, Cc)
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=q.device)
+    ws = _ws_f32(nbytes, q.device)
     rc = lib().sdf_qk_gate_plif_bwd(_ptr(q, torch.float32), _ptr(k, torch.float32), _ptr(g, torch.float32), _ptr(gq), _ptr(gk),
                                     _ptr(plif_k, torch.float32), _ptr(gpk), _ptr(ws), nbytes, Tq, rows, Cc, v_th, *_reset(v_reset),
                                     1 if detach_reset else 0, 0, alpha, _stream())
