@@ -11,13 +11,16 @@ Turns the module tree (state_dict holder) into a flat schedule of C-ABI kernel l
   * the convolutions either side of the swin stages (patch embedding, U-Net tail: SURVEY.md 8f rows 1-2) are implicit-GEMM
     spike convolutions with the BN / residual / neuron epilogues fused; the large 96-channel 3x3 launches take int8 digit
     planes and the weight-resident kernel (csrc/spike_conv_wres.hip); no library kernel is left in the SNN forward
-  * `forward(x, replicas=True)`: the B samples are B independent batch-1 forwards in one launch sequence (round 6; `_rb`, `_slice_map`)
+  * `forward(x, replicas=True)`: the B samples are B independent batch-1 forwards in one launch sequence (round 6; the route functions, `_slice_map`)
   * `tape` (tests only) keeps every neuron layer's spikes for the spike-forced oracle replay (tests/replay.py)
 
 Reference schedule being replaced: models/STSwinNet_SNN/Spiking_STSwinNet.py:161-182,278-305 and the
 call tree of SURVEY.md 3.2.  No CPU fallback: everything here raises off-GPU.
 """
 from __future__ import annotations
+
+from collections import namedtuple
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -184,13 +187,163 @@ def deconv_tap_weights(w, cin_pad, nsplit):
     wk = torch.zeros((9 * Cout, cin_pad), dtype=torch.float32, device=w.device)
     wk[:, :Cin] = w.detach().float().permute(2, 3, 1, 0).reshape(9 * Cout, Cin)
     planes = hip.split_weight(wk, nsplit)
-    if nsplit == 2 and cin_pad % 16 == 0:
-        dg = hip.split_weight_i8x3(wk)
-        if cin_pad % 64 == 0 and cin_pad >= 1024:            # (the small-M kernel's operand: the same matrix as int8 digits in fragment order)
-            planes.digits = hip.tile_weight_i8x3(dg)
-        elif cin_pad <= 1024:                                # (row-major digits: the weight-resident row-loop kernel, csrc/ms_res.hip)
-            planes.digits_rm = dg
+    form = _tap_digits(nsplit, cin_pad)
+    if form == "tiled":
+        planes.digits = hip.tile_weight_i8x3(hip.split_weight_i8x3(wk))
+    elif form == "rm":
+        planes.digits_rm = hip.split_weight_i8x3(wk)
     return planes
+
+
+def _tap_digits(nsplit, cin_pad):
+    """The int8 digit form the stacked tap matrix of a decoder also has: "tiled" (fragment order: the small-M kernel's operand),
+    "rm" (row-major: the weight-resident row-loop kernel, csrc/ms_res.hip) or None (16-bit planes only)."""
+    if nsplit != 2 or cin_pad % 16:
+        return None
+    if cin_pad % 64 == 0 and cin_pad >= 1024:
+        return "tiled"
+    return "rm" if cin_pad <= 1024 else None
+
+
+def _center_pad(p, h, w):
+    """(B,D,h',w',C) centred in (h, w) (cropped where larger): the reference's skip_concat alignment."""
+    dh, dw = h - p.shape[2], w - p.shape[3]
+    return F.pad(p, (0, 0, dw // 2, dw - dw // 2, dh // 2, dh - dh // 2))
+
+
+def _pred_planes(conv, device, nsplit):
+    """Flow prediction = 1x1 convolution with 2 output channels on spikes: the spike GEMM with the weight rows padded to one 32-column
+    block (columns 2.. are zero and never read back).  -> (planes, bias (32), the (2, Cin) weight itself)"""
+    w2 = conv.weight.detach().float().reshape(conv.weight.shape[0], -1)
+    wp = torch.zeros((32, w2.shape[1]), dtype=torch.float32, device=device)
+    wp[:w2.shape[0]] = w2
+    bp = torch.zeros(32, dtype=torch.float32, device=device)
+    bp[:w2.shape[0]] = conv.bias.detach().float()
+    return hip.split_weight(wp, nsplit), bp, w2
+
+
+# A decoder level: ConvTranspose2d weight (Cin, Cout, 3, 3) in the reference's channel order, the BN behind it, the neuron in front.
+_Decoder = namedtuple("_Decoder", "w bn sn")
+# A prediction head: the padded GEMM form (planes, bias, nout of its 32 columns) and, in the MS family, its neuron with the (nout, Cin)
+# weight and the bias the one-launch head kernel reads.
+_Pred = namedtuple("_Pred", "planes bias nout sn w b", defaults=(None, None, None))
+
+
+# ------------------------------------------------------------------ routes
+# Which kernel serves a layer, and how many samples go into one launch, is decided HERE - by pure functions of shapes and flags (no
+# tensors: they answer on a machine without a GPU, tests/test_engine_routes_cpu.py) - and nowhere else; the methods below ask, allocate
+# and launch.  Two rules are stated in these functions only:
+#   replicas (DESIGN.md 2 (ii)): every layer takes the kernel family and weight representation of its batch-1 forward, whatever the
+#     size rules say about B-fold rows - else the flows are not the batch-1 flows bit for bit - in the largest sample chunk per launch
+#     that is still routed like ONE sample;
+#   31-bit operand offsets: a launch too large for them goes in equal chunks of whole samples (batch elements are independent).
+def _largest_divisor(B, ok):
+    """Largest n among the DIVISORS of B with ok(n), 0: none.  Divisors, so that every chunk is the same launch: a ragged last chunk
+    could miss a kernel's "enough tiles" rule and fall to a streaming kernel that has no T = 5 / 20 form."""
+    return next((n for n in range(B, 0, -1) if B % n == 0 and ok(n)), 0)
+
+
+class ConvRoute(NamedTuple):
+    form: str           # "smallm" | "wres" | "wres_neuron" | "stream": the `_conv_<form>` launch helper of the engine
+    samples: int        # batch elements per launch (a divisor of B)
+
+
+def conv3x3_route(B, D, h, w, Cin, Cout, stride, digits, kind=None, replicas=False):
+    """Kernel form of a 3x3 / pad 1 spike convolution on (B,D,h,w,Cin) and the samples per launch.  `digits`: the layer has int8 digit
+    planes beside its 16-bit planes; `kind`: the neuron the caller hands over (None: fp32 output)."""
+    if not digits:
+        # 16-bit planes only: the streaming kernels' tile family and split-K plan follow the row count - replicas go sample by sample
+        return ConvRoute("stream", 1 if replicas else B)
+
+    def asked(n):           # what the size rules say about n samples in one launch
+        return (hip.smallm_conv_applicable(n * D, h, w, Cin, Cout, stride, D), hip.conv_wres_applicable(n * D, h, w, Cin, Cout, stride, 1),
+                hip.conv_wres_applicable(n * D, h, w, Cin, Cout, stride, D))
+    n = B
+    if replicas and B > 1:
+        one = asked(1)
+        n = _largest_divisor(B, lambda m: asked(m) == one)
+    if n > 1 and not hip.conv_wres_applicable(n * D, h, w, Cin, Cout, stride, 1):
+        # too large for the digit kernel's 31-bit operand offsets as one launch (configs[4]: 80 images of 240 x 320 x 96 fp32)
+        n = _largest_divisor(n, lambda m: hip.conv_wres_applicable(m * D, h, w, Cin, Cout, stride, 1)) or n
+    smallm, wres, wres_fused = asked(n)
+    if smallm and kind in (None, "lif", "if", "psn"):
+        # few rows against many weights (the U-Net bottleneck: 1 080 rows x 768 x 6 912): one launch, K split over the waves of a
+        # workgroup, sum + BN + shortcut + neuron in its epilogue (csrc/ms_smallm.hip)
+        return ConvRoute("smallm", n)
+    # wres: large launches on 96 channels - int8 digit planes, weights resident in LDS (csrc/spike_conv_wres.hip); else the streaming
+    # kernels on the 16-bit planes, fused or fp32
+    if kind is None:
+        return ConvRoute("wres" if wres else "stream", n)
+    if kind == "psn" or D not in (5, 10, 20):
+        # the digit kernel's fused form is LIF / IF over T = 5 / 10 / 20; other neurons (the shipped PSN) take its fp32 form and
+        # the neuron kernel behind it - still ahead of the streaming kernel's fused epilogue (profiles/r2j_psn.txt)
+        return ConvRoute("wres_neuron" if wres else "stream", n)
+    return ConvRoute("wres" if wres_fused else "stream", n)
+
+
+def conv3x3_carries_neuron(B, D, h, w, Cin, Cout, stride, digits, kind, replicas=False):
+    """Whether the caller of a 3x3 convolution hands the neuron behind it to `_conv3x3` (else: the bare fp32 convolution, whose epilogue
+    can split K over the chip, then BN + neuron as one launch of their own).  The fused-neuron epilogue pays off once the tiles fill the
+    chip.  The streaming kernels have it for T = 10; the weight-resident digit kernel rolls its time loop and takes T = 5 / 20 as well
+    (configs[4]), at stride 2 (the patch embedding's first 3x3) as at stride 1; the small-M kernel always carries its neuron."""
+    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
+    big = ((1 if replicas else B) * D * oh * ow + 255) // 256 * (Cout // 96) >= 128
+    if big and D == 10:
+        return True
+    if conv3x3_route(B, D, h, w, Cin, Cout, stride, digits, kind, replicas).form == "smallm":
+        return True
+    return big and conv3x3_route(B, D, h, w, Cin, Cout, stride, digits, "lif", replicas).form == "wres"
+
+
+class DeconvRoute(NamedTuple):
+    form: str           # "taps_smallm" | "taps_res" | "taps_stream" | "one_product" | "classes_multi" | "classes_each"
+    cp: int             # padded channel count of the level's NHWC spike image
+    images: int         # images (sample x time step) per launch
+
+
+class _Level(NamedTuple):
+    """A decoder level as `unet_tail` plans it.  `same`: the level's input y has the skip tensor's size, so its spike image is assembled
+    without a concatenation, in the physical channel order [y | skip | prediction padded to 4]; else the reference's concatenation
+    [prediction | y | skip] is made.  `cin`: channels of that image before padding."""
+    same: bool
+    cin: int
+    route: DeconvRoute
+
+
+def deconv_route(B, D, h, w, cin, cout, nsplit, replicas=False):
+    """Route of a decoder's ConvTranspose2d(k 3, s 2, p 1, op 1) on (B,D,h,w,cin) spikes, the padded channel count of its spike image and
+    the images per launch."""
+    one, rows, imgs = (1 if replicas else B), D * h * w, B * D
+    if one * rows * 9 * cout * 4 <= 64 << 20:
+        # small levels: ONE plain spike GEMM over the nine stacked tap matrices + a col2im pass fills the chip; the four parity-class
+        # convolutions (no 9x intermediate) are kept where that intermediate would cost more than it saves
+        cp = _pad32(cin)
+        form = _tap_digits(nsplit, cp)
+        if form == "tiled" and hip.smallm_gemm_applicable(one * rows, 9 * cout, cp):
+            # few rows against many weights (level 0: 1 080 x 3 456 x 1 536): csrc/ms_smallm.hip
+            return DeconvRoute("taps_smallm", cp, D * _largest_divisor(B, lambda n: hip.smallm_gemm_rows_ok(n * rows)))
+        if form == "rm" and hip.res_gemm_applicable(one * rows, 9 * cout, cp):
+            # the middle levels (4 320 x 1 728 x 800, 17 280 x 864 x 416): csrc/ms_res.hip
+            return DeconvRoute("taps_res", cp, D * _largest_divisor(B, lambda n: hip.res_gemm_applicable(n * rows, 9 * cout, cp)))
+        return DeconvRoute("taps_stream", cp, D * one)      # (16-bit planes: the streaming kernels' split-K plan follows the row count)
+    cp = _pad16(cin)
+    # the conv kernels address their operands with 31-bit byte offsets: a larger z (config 5: 80 images of 240 x 320 x 96 fp32) goes
+    # image chunk by image chunk - whole batch elements in equal chunks where that fits
+    fits = lambda n: n * 4 * h * w * cout * 4 < 1 << 31
+    per = D * (_largest_divisor(B, lambda n: fits(n * D)) or B)
+    while not fits(per):
+        per = (per + 1) // 2
+    if nsplit == 2 and per % D == 0 and imgs % per == 0 and hip.deconv2x2_applicable(per, D, h, w, cp, cout, fast_only=True):
+        # the last level: the transposed convolution as ONE digit product over the 2 x 2 input neighbourhood (a row = an input pixel,
+        # its 4 cout columns = the 2 x 2 output block; halo tiles in LDS, weights resident: csrc/spike_deconv_wres.hip) instead of
+        # four parity-class convolutions
+        return DeconvRoute("one_product", cp, per)
+    if replicas and B > 1:
+        # the parity classes run on the streaming kernels (16-bit planes: tile family and split-K plan follow the row count): every
+        # sample goes through the launches of its batch-1 forward
+        return DeconvRoute("classes_multi", cp, D)
+    # the four parity classes write disjoint rows of z and each fills about half of the chip: one launch for all of them where z fits
+    return DeconvRoute("classes_multi" if per == imgs else "classes_each", cp, per)
 
 
 class MSFlowEngine:
@@ -247,18 +400,11 @@ class MSFlowEngine:
                 d = layer.downsample
                 self.merges.append((_Lin(d.reduction, d.norm.norm_layer, dev, ns), _np(d.sn, dev)))
         self.unet_res = [_ResBlock(rb, dev, ns, U + f"resblocks.{i}.") for i, rb in enumerate(unet.resblocks)]
-        self.decoders = [(d.deconv[0].weight.detach(), bn_affine(d.norm_layer.norm_layer, dev), _np(d.sn, dev)) for d in unet.decoders]
-        # flow prediction = 1x1 convolution with 2 output channels on spikes: the spike GEMM with the weight rows padded
-        # to one 32-column block (columns 2.. are zero and never read back)
+        self.decoders = [_Decoder(d.deconv[0].weight.detach(), bn_affine(d.norm_layer.norm_layer, dev), _np(d.sn, dev)) for d in unet.decoders]
         self.preds = []
         for p in unet.preds:
-            w2 = p.conv[0].weight.detach().float().reshape(p.conv[0].weight.shape[0], -1)        # (2, Cin)
-            wp = torch.zeros((32, w2.shape[1]), dtype=torch.float32, device=dev)
-            wp[:w2.shape[0]] = w2
-            bp = torch.zeros(32, dtype=torch.float32, device=dev)
-            bp[:w2.shape[0]] = p.conv[0].bias.detach().float()
-            self.preds.append((hip.split_weight(wp, ns), bp, _np(p.sn, dev), w2.shape[0], w2.to(dev).contiguous(),
-                               p.conv[0].bias.detach().float().to(dev).contiguous()))
+            planes, bp, w2 = _pred_planes(p.conv[0], dev, ns)
+            self.preds.append(_Pred(planes, bp, w2.shape[0], _np(p.sn, dev), w2.to(dev).contiguous(), p.conv[0].bias.detach().float().to(dev).contiguous()))
 
     # ------------------------------------------------------------------ helpers
     def _slice_map(self, B, D, H, W, ws, ss):
@@ -308,133 +454,77 @@ class MSFlowEngine:
         if self.tape is not None:
             self.tape.append((name, spikes.clone(), layout))
 
-    def _neuron_bd(self, x, p, bn=None, out_dtype=torch.uint8):
+    def _neuron_bd(self, x, p, bn=None, out_dtype=torch.uint8, out=None):
         """Neuron over D of a channel-last (B,D,h,w,C) activation, BN fused when given."""
         self._check_cl(x)
         B, D, h, w, Cc = x.shape
-        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+        if out is None:
+            out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
         a, b = bn if bn is not None else (None, None)
         n = h * w * Cc
         hip.neuron_fwd(x, out, D, B, n, D * n, n, D * n, n, p, alpha=a, beta=b, Cch=Cc, inner=1)
         return out
 
-    def _conv3x3(self, s, Wp, Cout, stride=1, bn=None, resid=None, sn=None, membrane=False, _dst=None):
+    def _conv3x3(self, s, Wp, Cout, stride=1, bn=None, resid=None, sn=None, membrane=False):
         """3x3 / pad 1 spike convolution on (B,D,h,w,Cin) u8 -> (B,D,oh,ow,Cout): fp32 (BN, + resid) or, with `sn`,
-        spikes of the fused BN + neuron over D; with `membrane` as well, (fp32 BN + resid, spikes of SN(that)) from one launch."""
+        spikes of the fused BN + neuron over D; with `membrane` as well, (fp32 BN + resid, spikes of SN(that)) from one launch.
+        The route (conv3x3_route) says which `_conv_<form>` helper launches it and how many samples each launch takes; every launch
+        writes its slice of the outputs."""
         B, D, h, w, Cin = s.shape
-        oh, ow = (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1
+        route = conv3x3_route(B, D, h, w, Cin, Cout, stride, getattr(Wp, "digits", None) is not None, None if sn is None else sn.kind, self.replicas)
+        shape = (B, D, (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1, Cout)
+        m = torch.empty(shape, dtype=torch.float32, device=s.device) if sn is None or membrane else None
+        sp = torch.empty(shape, dtype=torch.uint8, device=s.device) if sn is not None else None
+        n = route.samples
+        if m is None:
+            resid = None                                          # (the shortcut goes into the membrane; spikes alone take none)
+        elif resid is not None and n < B:
+            resid = resid.view(shape)                             # (callers also hand it over as (B * D, oh, ow, Cout) images)
+        launch, io = getattr(self, "_conv_" + route.form), (s, resid, m, sp)
+        for b0 in range(0, B, n):
+            launch(Wp, stride, bn, sn, *(io if n == B else [None if t is None else t[b0:b0 + n] for t in io]))
+        return m if sn is None else ((m, sp) if membrane else sp)
+
+    @staticmethod
+    def _spike_conv(W, stride, bn, sn, s, resid, m, sp):
+        """ONE 3x3 launch on the weights W (16-bit planes or digits): fp32 epilogue into m; with `sn`, spikes into sp (and the membrane
+        into m where the caller wants it)."""
+        B, D, h, w, Cin = s.shape
+        oh, ow = (sp if m is None else m).shape[2:4]
         a, b = bn if bn is not None else (None, None)
-        # large 3x3 / stride-1 launches on 96 channels: int8 digit planes, weights resident in LDS (csrc/spike_conv_wres.hip)
-        digits = getattr(Wp, "digits", None)
-        if self.replicas and B > 1 and _dst is None and digits is None:
-            # 16-bit planes only (no digit form of this layer): the streaming kernels' tile family and split-K plan follow the row count
-            return self._conv3x3_chunks(s, Wp, Cout, stride, bn, resid, sn, membrane, 1)
-        if self.replicas and B > 1 and _dst is None and digits is not None:
-            # replicas: every layer must take the kernel family (and weight representation) its batch-1 forward takes, whatever the
-            # size rules say about B-fold rows - else the flows are not the batch-1 flows bit for bit.  Where the rules answer
-            # differently for B samples, the largest sample chunk that is routed like ONE sample runs per launch.
-            route = lambda n: (hip.smallm_conv_applicable(n * D, h, w, Cin, Cout, stride, D), hip.conv_wres_applicable(n * D, h, w, Cin, Cout, stride, 1),
-                               hip.conv_wres_applicable(n * D, h, w, Cin, Cout, stride, D))
-            r1 = route(1)
-            if route(B) != r1:
-                bc = max(n for n in range(1, B) if B % n == 0 and route(n) == r1)
-                return self._conv3x3_chunks(s, Wp, Cout, stride, bn, resid, sn, membrane, bc)
-        if digits is not None and (sn is None or sn.kind in ("lif", "if", "psn")) and hip.smallm_conv_applicable(B * D, h, w, Cin, Cout, stride, D):
-            # few rows against many weights (the U-Net bottleneck: 1 080 rows x 768 x 6 912): one launch, K split over the waves of a
-            # workgroup, sum + BN + shortcut + neuron in its epilogue (csrc/ms_smallm.hip)
-            out = None if sn is not None and not membrane else torch.empty((B, D, oh, ow, Cout), dtype=torch.float32, device=s.device)
-            sp = torch.empty((B, D, oh, ow, Cout), dtype=torch.uint8, device=s.device) if sn is not None else None
-            try:
-                hip.spike_conv2d(s, digits, B * D, h, w, Cin, oh, ow, 3, 3, stride, (-1, 0, 1), (-1, 0, 1), out=out, out_spike=sp, alpha=a, beta=b,
-                                 resid=resid if (membrane or sn is None) else None, sn=sn, sn_T=D if sn is not None else 0,
-                                 pos=(B * oh * ow, oh * ow, D * oh * ow, oh * ow))
-                return sp if sn is not None and not membrane else ((out, sp) if sn is not None else out)
-            except hip.SdfError as e:
-                # the Python mirror `smallm_conv_applicable` admits a shape the library's own rule refuses (size / alignment, 31-bit sizes,
-                # an unusual tau: ADVICE r4 / r5): the 16-bit planes are still here - the general path below serves it
-                if e.rc not in (hip.E_SHAPE, hip.E_ALIGN):
-                    raise
-                if sn is not None and sn.kind == "psn":
-                    # a PSN res-block was sent here because the small-M kernel fuses its neuron; refused, it runs as the fp32
-                    # convolution (streaming kernels, 16-bit planes) + the neuron kernel, not on the streaming kernels' fused epilogue
-                    m = torch.empty((B, D, oh, ow, Cout), dtype=torch.float32, device=s.device)
-                    hip.spike_conv2d(s, Wp, B * D, h, w, Cin, oh, ow, 3, 3, stride, (-1, 0, 1), (-1, 0, 1), out=m, alpha=a, beta=b,
-                                     resid=resid if membrane else None)
-                    sp = self._neuron_bd(m, sn)
-                    return (m, sp) if membrane else sp
-        if digits is not None and B > 1 and not hip.conv_wres_applicable(B * D, h, w, Cin, Cout, stride, 1):
-            # too large for the digit kernel's 31-bit operand offsets as one launch (configs[4]: 80 images of 240 x 320 x 96 fp32):
-            # batch elements are independent - the largest batch chunk that fits runs per launch, writing into its slice of the outputs
-            bc = self._digit_chunk(B, D, h, w, Cin, Cout, stride)
-            if bc:
-                return self._conv3x3_chunks(s, Wp, Cout, stride, bn, resid, sn, membrane, bc)
-        if digits is not None and sn is not None and (sn.kind == "psn" or D not in (5, 10, 20)) and \
-                hip.conv_wres_applicable(B * D, h, w, Cin, Cout, stride, 1):
-            # the digit kernel's fused form is LIF / IF over T = 5 / 10 / 20; other neurons (the shipped PSN) take its fp32 form and
-            # the neuron kernel behind it - still ahead of the streaming kernel's fused epilogue (profiles/r2j_psn.txt)
-            m = self._conv3x3(s, Wp, Cout, stride, bn=bn, resid=resid if membrane else None)
-            sp = self._neuron_bd(m, sn)
-            return (m, sp) if membrane else sp
-        if digits is not None and (sn is None or (sn.kind != "psn" and D in (5, 10, 20))) and \
-                hip.conv_wres_applicable(B * D, h, w, Cin, Cout, stride, D if sn is not None else 1):
-            Wp = digits                                               # (the kernel's fused form: LIF / IF over T = 5 / 10 / 20)
-        if sn is None:
-            out = _dst[0] if _dst is not None and len(_dst) == 1 and _dst[0].dtype == torch.float32 else \
-                torch.empty((B, D, oh, ow, Cout), dtype=torch.float32, device=s.device)
-            hip.spike_conv2d(s, Wp, B * D, h, w, Cin, oh, ow, 3, 3, stride, (-1, 0, 1), (-1, 0, 1), out=out, alpha=a, beta=b,
-                             resid=resid)
-            return out
-        if _dst is not None and len(_dst) == (2 if membrane else 1) and _dst[-1].dtype == torch.uint8:
-            out, m = _dst[-1], (_dst[0] if membrane else None)
-        else:
-            out = torch.empty((B, D, oh, ow, Cout), dtype=torch.uint8, device=s.device)
-            m = torch.empty((B, D, oh, ow, Cout), dtype=torch.float32, device=s.device) if membrane else None
-        hip.spike_conv2d(s, Wp, B * D, h, w, Cin, oh, ow, 3, 3, stride, (-1, 0, 1), (-1, 0, 1), out=m, out_spike=out, alpha=a, beta=b,
-                         resid=resid if membrane else None, sn=sn, sn_T=D, pos=(B * oh * ow, oh * ow, D * oh * ow, oh * ow))
-        return (m, out) if membrane else out
+        hip.spike_conv2d(s, W, B * D, h, w, Cin, oh, ow, 3, 3, stride, (-1, 0, 1), (-1, 0, 1), out=m, out_spike=sp, alpha=a, beta=b, resid=resid,
+                         sn=sn, sn_T=D if sn is not None else 0, pos=(B * oh * ow, oh * ow, D * oh * ow, oh * ow))
 
-    def _conv3x3_chunks(self, s, Wp, Cout, stride, bn, resid, sn, membrane, bc):
-        """_conv3x3 in chunks of bc batch elements (batch elements are independent), every chunk writing its slice of the outputs."""
-        B, D, h, w, _ = s.shape
-        oh, ow = (h + 2 - 3) // stride + 1, (w + 2 - 3) // stride + 1
-        kinds = [torch.float32] if sn is None else ([torch.float32, torch.uint8] if membrane else [torch.uint8])
-        outs = tuple(torch.empty((B, D, oh, ow, Cout), dtype=k, device=s.device) for k in kinds)
-        if resid is not None:
-            resid = resid.view(B, D, oh, ow, Cout)                # (callers also hand it over as (B * D, oh, ow, Cout) images)
-        for b0 in range(0, B, bc):
-            dst = tuple(o[b0:b0 + bc] for o in outs)
-            r = self._conv3x3(s[b0:b0 + bc], Wp, Cout, stride, bn, None if resid is None else resid[b0:b0 + bc], sn, membrane, dst)
-            r = r if isinstance(r, tuple) else (r,)
-            for o, t in zip(dst, r):
-                if t.data_ptr() != o.data_ptr():                  # (the two-launch PSN form allocates its own)
-                    o.copy_(t)
-        return outs if len(outs) > 1 else outs[0]
+    def _conv_then_neuron(self, W, stride, bn, sn, s, resid, m, sp):
+        """Convolution with BN into the membrane (a scratch one when the caller wants spikes only), then the bare neuron."""
+        if m is None:
+            m = torch.empty(sp.shape, dtype=torch.float32, device=s.device)
+        self._spike_conv(W, stride, bn, None, s, resid, m, None)
+        self._neuron_bd(m, sn, out=sp)
 
-    def _rb(self, B):
-        """The batch size the ROUTING rules are asked about: with replicas every layer is routed like its batch-1 forward."""
-        return 1 if self.replicas else B
+    def _conv_stream(self, Wp, *launch):
+        self._spike_conv(Wp, *launch)
 
-    @staticmethod
-    def _digit_chunk(B, D, h, w, Cin, Cout, stride):
-        """Largest number of batch elements per launch the digit kernel addresses, chosen among the DIVISORS of B so that every chunk is
-        the same launch (a ragged last chunk could miss the kernel's "enough tiles" rule and fall to a streaming kernel that has no T = 5 / 20
-        form); 0: none."""
-        for bc in range(B - 1, 0, -1):
-            if B % bc == 0 and hip.conv_wres_applicable(bc * D, h, w, Cin, Cout, stride, 1):
-                return bc
-        return 0
+    def _conv_wres(self, Wp, *launch):
+        self._spike_conv(Wp.digits, *launch)
 
-    @staticmethod
-    def _fusable(B, D, h, w, C, Wp=None):
-        """The fused-neuron convolution epilogue pays off once the tiles fill the chip.  The streaming kernels have it for T = 10; the
-        weight-resident digit kernel (96 -> 96 channels, `Wp.digits`) rolls its time loop and takes T = 5 / 20 as well (configs[4])."""
-        big = (B * D * h * w + 255) // 256 * (C // 96) >= 128
-        if D == 10:
-            return big
-        if not (big and D in (5, 20) and C == 96 and getattr(Wp, "digits", None) is not None and Wp.shape[-1] == 9 * 96):
-            return False
-        bc = B if hip.conv_wres_applicable(B * D, h, w, 96, C, 1, 1) else MSFlowEngine._digit_chunk(B, D, h, w, 96, C, 1)
-        return bc > 0 and hip.conv_wres_applicable(bc * D, h, w, 96, C, 1, D)
+    def _conv_wres_neuron(self, Wp, *launch):
+        self._conv_then_neuron(Wp.digits, *launch)
+
+    def _conv_smallm(self, Wp, stride, bn, sn, *io):
+        try:
+            self._spike_conv(Wp.digits, stride, bn, sn, *io)
+        except hip.SdfError as e:
+            # the Python mirror `smallm_conv_applicable` admits a shape the library's own rule refuses (size / alignment, 31-bit sizes,
+            # an unusual tau: ADVICE r4 / r5): the 16-bit planes are still here - the streaming kernels serve it
+            if e.rc not in (hip.E_SHAPE, hip.E_ALIGN):
+                raise
+            if sn is not None and sn.kind == "psn":
+                # a PSN res-block was sent here because the small-M kernel fuses its neuron; refused, it runs as the fp32
+                # convolution + the neuron kernel, not on the streaming kernels' fused epilogue
+                self._conv_then_neuron(Wp, stride, bn, sn, *io)
+            else:
+                self._conv_stream(Wp, stride, bn, sn, *io)
 
     def _resblock(self, m, rb, s1=None, next_sn=None):
         """MS_ResBlock on a (B,D,h,w,C) membrane: SN -> conv+BN+SN (one kernel) -> conv+BN+identity (one kernel)
@@ -444,11 +534,10 @@ class MSFlowEngine:
         if s1 is None:
             s1 = self._neuron_bd(m, rb.sn1)
         self._rec(rb.name + "sn1.spiking_neuron.", s1, "BDHWC->TBCHW")
-        fus = self._fusable(self._rb(B), D, h, w, rb.C, rb.w1) or \
-            (getattr(rb.w1, "digits", None) is not None and rb.sn2.kind in ("lif", "if", "psn") and hip.smallm_conv_applicable(self._rb(B) * D, h, w, rb.C, rb.C, 1, D))
+        fus = conv3x3_carries_neuron(B, D, h, w, rb.C, rb.C, 1, getattr(rb.w1, "digits", None) is not None, rb.sn2.kind, self.replicas)
         if fus:
             s2 = self._conv3x3(s1, rb.w1, rb.C, bn=rb.bn1, sn=rb.sn2)
-        else:       # few rows (U-Net bottleneck): the fp32 epilogue can split K over the chip; neuron as its own launch
+        else:       # few rows: the fp32 epilogue can split K over the chip; neuron as its own launch
             s2 = self._neuron_bd(self._conv3x3(s1, rb.w1, rb.C), rb.sn2, bn=rb.bn1)
         self._rec(rb.name + "sn2.spiking_neuron.", s2, "BDHWC->TBCHW")
         if next_sn is not None and fus:
@@ -481,14 +570,7 @@ class MSFlowEngine:
         # every membrane of the patch embedding leaves its convolution together with the spikes of the neuron that reads it
         sns = [rb.sn1 for rb in self.pe_res] + [self.proj_sn]
         C0 = self.conv_w.shape[1]
-        oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        fus = self._fusable(self._rb(B), T, oh, ow, C0)
-        if not fus and T in (5, 20) and getattr(self.conv_w, "digits", None) is not None and sns[0].kind != "psn":
-            # T = 5 / 20 (configs[4]): the digit kernel's stride-2 form rolls its time loop as the stride-1 form does (_fusable's rule)
-            c0 = s.shape[-1]
-            Br = self._rb(B)
-            bc = Br if hip.conv_wres_applicable(Br * T, H, W, c0, C0, 2, 1) else self._digit_chunk(Br, T, H, W, c0, C0, 2)
-            fus = bc > 0 and hip.conv_wres_applicable(bc * T, H, W, c0, C0, 2, T)
+        fus = conv3x3_carries_neuron(B, T, H, W, s.shape[-1], C0, 2, getattr(self.conv_w, "digits", None) is not None, sns[0].kind, self.replicas)
         if fus:
             m, s1 = self._conv3x3(s, self.conv_w, C0, stride=2, bn=self.conv_bn, sn=sns[0], membrane=True)
         else:
@@ -648,75 +730,165 @@ class MSFlowEngine:
                 self.tail_spikes = emit[0]
         return feats
 
-    def _deconv_classes(self, i, B, D, h, w, cin_pad, wkey="ref", wuse=None):
-        key = (i, B, D, h, w, wkey)
+    def _cached(self, key, make):
         if key not in self._deconv:
-            self._deconv[key] = deconv_classes(self.decoders[i][0] if wuse is None else wuse, B * D, h, w, cin_pad, self.nsplit, self.device)
+            self._deconv[key] = make()
         return self._deconv[key]
 
     def _decoder_weight(self, i, wkey, C1, C2):
         """ConvTranspose2d weight (Cin, Cout, 3, 3) of decoder i in the reference's input-channel order [pred | y | skip] ("ref")
         or in the physical order of the concatenation-free path [y | skip | pred, 0, 0] ("perm")."""
-        wdec = self.decoders[i][0]
+        wdec = self.decoders[i].w
         if wkey == "ref" or i == 0:
             return wdec
-        key = ("wperm", i)
-        if key not in self._deconv:
+
+        def perm():
             n = wdec.shape[0] - C1 - C2                                   # prediction channels in front (2)
             pad = torch.zeros((4 - n,) + tuple(wdec.shape[1:]), dtype=wdec.dtype, device=wdec.device)
-            self._deconv[key] = torch.cat([wdec[n:n + C1], wdec[n + C1:], wdec[:n], pad], 0).contiguous()
-        return self._deconv[key]
+            return torch.cat([wdec[n:n + C1], wdec[n + C1:], wdec[:n], pad], 0).contiguous()
+        return self._cached(("wperm", i), perm)
 
-    def _decoder_geometry(self, i, B, D, h, w, cin):
-        """(as_gemm, padded channel count of the NHWC spike image) of decoder level i on an (h, w) input with cin channels.
-        Small levels: ONE plain spike GEMM over the nine stacked tap matrices + a col2im pass fills the chip; the four parity-class
-        convolutions (no 9x intermediate) are kept where that intermediate would cost more than it saves."""
-        cout = self.decoders[i][0].shape[1]
-        as_gemm = self._rb(B) * D * h * w * 9 * cout * 4 <= 64 << 20
-        return as_gemm, (_pad32(cin) if as_gemm else _pad16(cin))
+    def _decoder_levels(self, feats, y0):
+        """Every decoder level (_Level) decided before anything is launched."""
+        levels, (hy, wy, C1), E = [], y0.shape[2:], len(feats)
+        for i in range(E):
+            B, D, h, w, C2 = feats[E - 1 - i].shape
+            same = (hy, wy) == (h, w)
+            cin = C1 + C2 + (0 if i == 0 else (4 if same else self.preds[i - 1].nout))
+            cout = self.decoders[i].w.shape[1]
+            levels.append(_Level(same, cin, deconv_route(B, D, h, w, cin, cout, self.nsplit, self.replicas)))
+            hy, wy, C1 = 2 * h, 2 * w, cout
+        return levels
 
-    def _prepare_decoder_images(self, feats, y0, out_size):
+    def _prepare_decoder_images(self, feats, y0, out_size, levels):
         """NHWC u8 spike images of every decoder level with the skip slices written by one multi-descriptor neuron launch, or None
         when the pyramid is not regular / a level's head has no one-launch kernel (the per-level path handles those)."""
         E = len(feats)
-        if out_size is None or E < 2 or E > 6:
-            return None
-        B, D, h0, w0, _ = feats[-1].shape
-        if tuple(y0.shape[2:4]) != (h0, w0):
+        if out_size is None or E < 2 or E > 6 or not all(lv.same for lv in levels):
             return None
         imgs, calls, c1 = [], [], y0.shape[-1]
-        for i in range(E):
+        for i, lv in enumerate(levels):
             skip = feats[E - 1 - i]
-            h, w = h0 << i, w0 << i
-            if tuple(skip.shape[2:4]) != (h, w):
+            B, D, h, w, C2 = skip.shape
+            dec, pr = self.decoders[i], self.preds[i]
+            cout = dec.w.shape[1]
+            if not (pr.nout == 2 and out_size[0] % (2 * h) == 0 and out_size[1] % (2 * w) == 0 and
+                    hip.pred_head_supported(D, cout, out_size[0], out_size[1], 2 * h, 2 * w, pr.sn, self.decoders[i + 1].sn if i + 1 < E else None)):
                 return None
-            wdec, bn, sn = self.decoders[i]
-            cout = wdec.shape[1]
-            pw, pb, psn, nout, w2, b2 = self.preds[i]
-            ok = nout == 2 and out_size[0] % (2 * h) == 0 and out_size[1] % (2 * w) == 0 and \
-                hip.pred_head_supported(D, cout, out_size[0], out_size[1], 2 * h, 2 * w, psn, self.decoders[i + 1][2] if i + 1 < E else None)
-            if not ok:
-                return None
-            C2 = skip.shape[-1]
-            cin = c1 + C2 + (4 if i > 0 else 0)
-            _, cp = self._decoder_geometry(i, B, D, h, w, cin)
+            cin, cp, hw = lv.cin, lv.route.cp, h * w
             img = torch.empty((B, D, h, w, cp), dtype=torch.uint8, device=y0.device)
             if i == 0 and cp != cin:
                 img[..., cin:].zero_()                                  # (levels >= 1: zeroed by the head of the level above)
-            hw = h * w
             # (the batch elements are the descriptor's outermost dimension: one multi-descriptor launch for the whole batch)
-            calls.append((skip, img.view(-1)[c1:], D, hw, C2, C2, hw * C2, cp, hw * cp, sn, None, 0, None, None, 0, 1, None, 0, 0, None,
-                          (B, D * hw * C2, D * hw * cp)))
+            calls.append(((skip, img.view(-1)[c1:], D, hw, C2, C2, hw * C2, cp, hw * cp, dec.sn), {"rep": (B, D * hw * C2, D * hw * cp)}))
             imgs.append(img)
             c1 = cout
         # level 0's own input y rides in the same launch (its neuron is the level's `sn` too; six descriptors at most)
         self._ready_has_y = len(calls) < 6
         if self._ready_has_y:
-            cy, hw0, cp0 = y0.shape[-1], h0 * w0, imgs[0].shape[-1]
-            calls.append((y0, imgs[0].view(-1), D, hw0, cy, cy, hw0 * cy, cp0, hw0 * cp0, self.decoders[0][2], None, 0, None, None, 0, 1, None, 0, 0,
-                          None, (B, D * hw0 * cy, D * hw0 * cp0)))
+            B, D, h0, w0, cy = y0.shape
+            hw0, cp0 = h0 * w0, imgs[0].shape[-1]
+            calls.append(((y0, imgs[0].view(-1), D, hw0, cy, cy, hw0 * cy, cp0, hw0 * cp0, self.decoders[0].sn), {"rep": (B, D * hw0 * cy, D * hw0 * cp0)}))
         hip.neuron_multi_fwd(calls)
         return imgs
+
+    def _decoder_image(self, i, level, y, skip, preds, ready, carried):
+        """-> (NHWC u8 spike image (B,D,h,w,cp) of decoder level i, order of its channels: "perm" / "ref" as _decoder_weight has them):
+        SN(skip_concat(pred, skip_concat(y, skip))) on channels (:168-172); the prediction has y's size (both come from z)."""
+        same, cin, cp = level.same, level.cin, level.route.cp
+        B, D, h, w, C2 = skip.shape
+        sn, C1, name = self.decoders[i].sn, y.shape[-1], f"sttmultires_unet.decoders.{i}.sn.spiking_neuron."
+        if not same:
+            parts = [_center_pad(p, h, w) for p in ([preds[-1][..., :self.preds[i - 1].nout]] if i > 0 else []) + [y, skip]]
+            if cp != cin:
+                cat = torch.zeros((B, D, h, w, cp), dtype=torch.float32, device=y.device)
+                torch.cat(parts, dim=-1, out=cat[..., :cin])
+            else:
+                cat = torch.cat(parts, dim=-1)
+            s = self._neuron_bd(cat, sn)                                  # MS decoder: SN -> ConvT -> BN
+            self._rec(name, s[..., :cin], "BDHWC->TBCHW")
+            return s, "ref"
+        # no concatenation: the decoder's neuron runs on each source and writes its spikes straight into that source's channel slice
+        # of the spike image (the transposed-convolution weight rows are permuted to match once, at pack time)
+        if ready is not None:
+            s, c0 = ready[i], 0                                           # skip slice (and padding) already in place; level 0 takes y now
+            srcs = [(y, C1, C1)] if i == 0 and not self._ready_has_y else []
+        elif carried is not None:
+            s, srcs, c0 = carried, [(skip, C2, C2)], C1                  # [y | . | prediction | zeros] came from the level above
+        else:
+            s = (torch.zeros if cp != cin else torch.empty)((B, D, h, w, cp), dtype=torch.uint8, device=y.device)
+            srcs, c0 = [(y, C1, C1), (skip, C2, C2)] + ([(preds[-1], 4, preds[-1].shape[-1])] if i > 0 else []), 0
+        hw = h * w
+        for src, take, pitch in srcs:                                     # (tensor, channels taken, pitch)
+            for b in range(B):
+                hip.neuron_fwd(src[b], s[b].view(-1)[c0:], D, hw, take, pitch, hw * pitch, cp, hw * cp, sn)
+            c0 += take
+        if self.tape is not None:                                         # the reference's channel order is [prediction | y | skip]
+            npred = self.preds[i - 1].nout if i > 0 else 0
+            self._rec(name, torch.cat([s[..., C1 + C2:C1 + C2 + npred], s[..., :C1 + C2]], -1), "BDHWC->TBCHW")
+        return s, "perm"
+
+    def _transposed_conv(self, i, route, s, wkey, wuse):
+        """z (B,D,2h,2w,cout) fp32 = BN(ConvTranspose2d(k 3, s 2, p 1, op 1)(s)) of decoder level i, launched as deconv_route decided."""
+        form, cp, per = route
+        B, D, h, w, _ = s.shape
+        bn, cout, imgs = self.decoders[i].bn, wuse.shape[1], B * D
+        z = torch.empty((B, D, 2 * h, 2 * w, cout), dtype=torch.float32, device=s.device)
+        sv, zv, zrows = s.view(imgs, h, w, cp), z.view(imgs, 2 * h, 2 * w, cout), z.view(imgs, 4 * h * w, cout)
+        if form.startswith("taps"):
+            planes = self._cached(("taps", i, cp, wkey), lambda: deconv_tap_weights(wuse, cp, self.nsplit))
+            taps = planes if form == "taps_stream" else (planes.digits if form == "taps_smallm" else planes.digits_rm)
+            Y = torch.empty((imgs * h * w, 9 * cout), dtype=torch.float32, device=s.device)
+            mc = per * h * w
+            for m0 in range(0, imgs * h * w, mc):
+                hip.spike_gemm(s.view(-1, cp)[m0:m0 + mc], taps, Y[m0:m0 + mc], mc, 9 * cout, cp)
+            hip.deconv_col2im(Y, imgs, h, w, cout, alpha=bn[0], beta=bn[1], out=z)
+        elif form == "one_product":
+            pl, a4, b4 = self._cached(("d2x2", i, cp, wkey), lambda: (hip.pack_deconv2x2_weight(wuse, cp), bn[0].repeat(4).contiguous(),
+                                                                      bn[1].repeat(4).contiguous()))
+            for i0 in range(0, imgs, per):
+                hip.spike_deconv3x3s2(sv[i0:i0 + per], pl, per, D, h, w, cp, cout, alpha=a4, beta=b4, out=zv[i0:i0 + per], tiled_bn=True)
+        elif form == "classes_multi":
+            # (replicas: the classes, and their row maps, of the first D images serve every sample's slice)
+            classes = self._cached((i, per // D, D, h, w, wkey), lambda: deconv_classes(wuse, per, h, w, cp, self.nsplit, self.device))
+            for i0 in range(0, imgs, per):
+                hip.spike_conv2d_multi(sv[i0:i0 + per], classes, per, h, w, cp, h, w, zrows[i0:i0 + per], alpha=bn[0], beta=bn[1])
+        else:
+            # (the row map of the first n images serves every chunk)
+            for cls in self._cached((i, B, D, h, w, wkey), lambda: deconv_classes(wuse, imgs, h, w, cp, self.nsplit, self.device)):
+                for i0 in range(0, imgs, per):
+                    n = min(per, imgs - i0)
+                    hip.spike_conv2d(sv[i0:i0 + n], cls["Wp"], n, h, w, cp, h, w, cls["KH"], cls["KW"], 1, cls["dy"], cls["dx"],
+                                     out=zrows[i0:i0 + n], alpha=bn[0], beta=bn[1], out_rowmap=cls["rowmap"][:n * h * w])
+        return z
+
+    def _prediction(self, i, z, feats, out_size, levels, ready):
+        """Prediction head of level i on z (B,D,H2,W2,cout) -> (prediction (B,D,H2,W2,>= nout) fp32 or None, the next level's spike image
+        with its [y | prediction] slices written, or None).  MS pred: SN -> conv1x1 (+bias), 2 outputs."""
+        B, D, H2, W2, cout = z.shape
+        pr, E, name = self.preds[i], len(feats), f"sttmultires_unet.preds.{i}.sn.spiking_neuron."
+        nxt_skip = feats[E - 2 - i] if i + 1 < E else None
+        fs = out_size if out_size is not None and out_size[0] % H2 == 0 and out_size[1] % W2 == 0 else None
+        if not (pr.nout == 2 and hip.pred_head_supported(D, cout, fs[0] if fs else H2, fs[1] if fs else W2, H2, W2, pr.sn,
+                                                         self.decoders[i + 1].sn if nxt_skip is not None else None)
+                and B * D * H2 * W2 * max(cout, 16) * 4 < 1 << 40):
+            sp = self._neuron_bd(z, pr.sn)
+            self._rec(name, sp, "BDHWC->TBCHW")
+            po = torch.empty((B * D * H2 * W2, 32), dtype=torch.float32, device=z.device)
+            hip.spike_gemm(sp, pr.planes, po, po.shape[0], 32, cout, bias=pr.bias)
+            return po.view(B, D, H2, W2, 32), None                        # columns nout.. are exactly zero (zero weight rows, zero bias)
+        # its time sum + upsampling, and the next level's [y | prediction] spikes - one launch, z read once (csrc/pred_head.hip)
+        nxt = carried = None
+        if nxt_skip is not None and levels[i + 1].same:
+            cin_n, cp_n = levels[i + 1].cin, levels[i + 1].route.cp
+            carried = ready[i + 1] if ready is not None else torch.empty((B, D, H2, W2, cp_n), dtype=torch.uint8, device=z.device)
+            nxt = (carried, self.decoders[i + 1].sn, 0, cin_n - 4, (cin_n, cp_n - cin_n))
+        pred, self._flows[i], sp = hip.pred_head(z, pr.w, pr.b, pr.sn, fs[0] if fs else None, fs[1] if fs else None,
+                                                 want_pred=self.tape is not None or fs is None or (i + 1 < E and nxt is None),
+                                                 nxt=nxt, keep=self.tape is not None)
+        if sp is not None:
+            self._rec(name, sp, "BDHWC->TBCHW")
+        return pred, carried
 
     def unet_tail(self, feats, out_size=None, s1=None):
         """res-blocks + decoders + per-scale predictions on channel-last (B,D,h,w,C) features
@@ -731,151 +903,19 @@ class MSFlowEngine:
             y, s1 = r if nxt is not None else (r, None)
         preds, E = [], len(feats)
         self._flows = [None] * E
-        carried = None          # this level's spike image with the [y | prediction] slices already written by the previous level's head
+        levels = self._decoder_levels(feats, y)
         # Regular pyramid (every level twice the size of the one before, every prediction head on its one-launch kernel): the
         # spike images of ALL levels are laid out now and the decoders' neuron on the four skip tensors - four small launches
         # before - is ONE launch (sdf_neuron_multi_fwd); the [y | prediction] slices arrive from the level above's head.
-        ready = self._prepare_decoder_images(feats, y, out_size) if self.tape is None else None
-        for i in range(E):
+        ready = self._prepare_decoder_images(feats, y, out_size, levels) if self.tape is None else None
+        carried = None          # this level's spike image with the [y | prediction] slices already written by the previous level's head
+        for i, level in enumerate(levels):
             skip = feats[E - 1 - i]
-            B, D, h, w, _ = skip.shape
-            # skip_concat(pred, skip_concat(y, skip)) on channels (:168-172); the prediction has y's size (both come from z)
-            wdec, bn, sn = self.decoders[i]
-            cout = wdec.shape[1]
-            same = tuple(y.shape[2:4]) == (h, w)
-            if same:
-                # no concatenation: the decoder's neuron runs on each source and writes its spikes straight into that source's
-                # channel slice of the NHWC spike image (physical channel order [y | skip | prediction padded to 4]; the
-                # transposed-convolution weight rows are permuted to match once, at pack time)
-                C1, C2 = y.shape[-1], skip.shape[-1]
-                cin = C1 + C2 + (4 if i > 0 else 0)
-                as_gemm, cp = self._decoder_geometry(i, B, D, h, w, cin)
-                if ready is not None:
-                    s, c0 = ready[i], 0                                   # skip slice (and padding) already in place; level 0 takes y now
-                    srcs = [(y, C1, C1)] if i == 0 and not self._ready_has_y else []
-                elif carried is not None:
-                    s, srcs, c0 = carried, [(skip, C2, C2)], C1          # [y | . | prediction | zeros] came from the level above
-                else:
-                    s = (torch.zeros if cp != cin else torch.empty)((B, D, h, w, cp), dtype=torch.uint8, device=y.device)
-                    srcs, c0 = [(y, C1, C1), (skip, C2, C2)] + ([(preds[-1], 4, preds[-1].shape[-1])] if i > 0 else []), 0
-                hw = h * w
-                for src, take, pitch in srcs:                             # (tensor, channels taken, pitch)
-                    for b in range(B):
-                        hip.neuron_fwd(src[b], s[b].view(-1)[c0:], D, hw, take, pitch, hw * pitch, cp, hw * cp, sn)
-                    c0 += take
-                wkey = "perm"
-                if self.tape is not None:             # the reference's channel order is [prediction | y | skip]
-                    npred = self.preds[i - 1][3] if i > 0 else 0
-                    self._rec(f"sttmultires_unet.decoders.{i}.sn.spiking_neuron.",
-                              torch.cat([s[..., C1 + C2:C1 + C2 + npred], s[..., :C1 + C2]], -1), "BDHWC->TBCHW")
-            else:
-                parts = ([preds[-1][..., :self.preds[i - 1][3]]] if i > 0 else []) + [y, skip]
-                parts = [F.pad(p, (0, 0, (w - p.shape[3]) // 2, w - p.shape[3] - (w - p.shape[3]) // 2,
-                                   (h - p.shape[2]) // 2, h - p.shape[2] - (h - p.shape[2]) // 2)) for p in parts]
-                cin = sum(p.shape[-1] for p in parts)
-                as_gemm, cp = self._decoder_geometry(i, B, D, h, w, cin)
-                cat = torch.zeros((B, D, h, w, cp), dtype=torch.float32, device=y.device) if cp != cin else None
-                if cat is None:
-                    cat = torch.cat(parts, dim=-1)
-                else:
-                    torch.cat(parts, dim=-1, out=cat[..., :cin])
-                s = self._neuron_bd(cat, sn)                              # MS decoder: SN -> ConvT -> BN
-                wkey = "ref"
-                self._rec(f"sttmultires_unet.decoders.{i}.sn.spiking_neuron.", s[..., :cin], "BDHWC->TBCHW")
-            carried = None
-            wuse = self._decoder_weight(i, wkey, y.shape[-1], skip.shape[-1])
-            z = torch.empty((B, D, 2 * h, 2 * w, cout), dtype=torch.float32, device=y.device)
-            if as_gemm:
-                key = ("taps", i, cp, wkey)
-                if key not in self._deconv:
-                    self._deconv[key] = deconv_tap_weights(wuse, cp, self.nsplit)
-                Y = torch.empty((B * D * h * w, 9 * cout), dtype=torch.float32, device=y.device)
-                taps = self._deconv[key]
-                M1, bc = self._rb(B) * D * h * w, B                  # (rows the routing rules are asked about; samples per launch)
-                if getattr(taps, "digits", None) is not None and hip.smallm_gemm_applicable(M1, 9 * cout, cp):
-                    taps = taps.digits                        # few rows against many weights (level 0: 1 080 x 3 456 x 1 536): csrc/ms_smallm.hip
-                    bc = max(n for n in range(1, B + 1) if B % n == 0 and hip.smallm_gemm_rows_ok(n * D * h * w))
-                elif getattr(taps, "digits_rm", None) is not None and hip.res_gemm_applicable(M1, 9 * cout, cp):
-                    taps = taps.digits_rm                     # the middle levels (4 320 x 1 728 x 800, 17 280 x 864 x 416): csrc/ms_res.hip
-                    bc = max(n for n in range(1, B + 1) if B % n == 0 and hip.res_gemm_applicable(n * D * h * w, 9 * cout, cp))
-                if self.replicas and taps is self._deconv[key]:
-                    bc = 1            # (16-bit planes on the streaming kernels: their split-K plan follows the row count - one sample per launch)
-                mc = bc * D * h * w                                   # (replicas: the kernel family of ONE sample, in sample chunks it admits)
-                for m0 in range(0, B * D * h * w, mc):
-                    hip.spike_gemm(s.view(-1, cp)[m0:m0 + mc], taps, Y[m0:m0 + mc], mc, 9 * cout, cp)
-                hip.deconv_col2im(Y, B * D, h, w, cout, alpha=bn[0], beta=bn[1], out=z)
-            # the conv kernel addresses its operands with 31-bit byte offsets: a larger z (config 5: 80 images of
-            # 240 x 320 x 96 fp32) goes image chunk by image chunk - the row map of the first n images serves every chunk
-            imgs = per = B * D
-            fits = lambda n: n * 4 * h * w * cout * 4 < 1 << 31
-            if not fits(per):
-                whole = [n * D for n in range(B, 0, -1) if B % n == 0 and fits(n * D)]      # whole batch elements, equal chunks
-                per = whole[0] if whole else per
-            while not fits(per):
-                per = (per + 1) // 2
-            # the last level: the transposed convolution as ONE digit product over the 2 x 2 input neighbourhood (a row = an input pixel,
-            # its 4 cout columns = the 2 x 2 output block; halo tiles in LDS, weights resident: csrc/spike_deconv_wres.hip) instead of
-            # four parity-class convolutions
-            one_gemm = not as_gemm and self.nsplit == 2 and per % D == 0 and imgs % per == 0 and \
-                hip.deconv2x2_applicable(per, D, h, w, cp, cout, fast_only=True)
-            if one_gemm:
-                key = ("d2x2", i, cp, wkey)
-                if key not in self._deconv:
-                    self._deconv[key] = (hip.pack_deconv2x2_weight(wuse, cp), bn[0].repeat(4).contiguous(), bn[1].repeat(4).contiguous())
-                pl, a4, b4 = self._deconv[key]
-                sv, zv = s.view(imgs, h, w, cp), z.view(imgs, 2 * h, 2 * w, cout)
-                for i0 in range(0, imgs, per):                            # (image chunks: the kernel's 31-bit offsets, as below)
-                    hip.spike_deconv3x3s2(sv[i0:i0 + per], pl, per, D, h, w, cp, cout, alpha=a4, beta=b4, out=zv[i0:i0 + per], tiled_bn=True)
-            classes = [] if as_gemm or one_gemm else self._deconv_classes(i, B, D, h, w, cp, wkey, wuse)
-            if classes and self.replicas and B > 1:
-                # the parity classes run on the streaming kernels (16-bit planes: tile family and split-K plan follow the row count): every
-                # sample goes through the launches of its batch-1 forward (the row maps of the first D images serve every sample's slice)
-                c1 = self._deconv_classes(i, 1, D, h, w, cp, wkey, wuse)
-                sv, zv = s.view(imgs, h, w, cp), z.view(imgs, 4 * h * w, cout)
-                for b0 in range(0, imgs, D):
-                    hip.spike_conv2d_multi(sv[b0:b0 + D], c1, D, h, w, cp, h, w, zv[b0:b0 + D], alpha=bn[0], beta=bn[1])
-                classes = []
-            if classes and per == imgs:
-                # the four parity classes write disjoint rows of z and each fills about half of the chip: one launch for all of them
-                hip.spike_conv2d_multi(s.view(imgs, h, w, cp), classes, imgs, h, w, cp, h, w, z.view(imgs, 4 * h * w, cout), alpha=bn[0], beta=bn[1])
-                classes = []
-            for cls in classes:
-                for i0 in range(0, imgs, per):
-                    n = min(per, imgs - i0)
-                    hip.spike_conv2d(s.view(imgs, h, w, cp)[i0:i0 + n], cls["Wp"], n, h, w, cp, h, w, cls["KH"], cls["KW"], 1,
-                                     cls["dy"], cls["dx"], out=z.view(imgs, 4 * h * w, cout)[i0:i0 + n], alpha=bn[0], beta=bn[1],
-                                     out_rowmap=cls["rowmap"][:n * h * w])
-            pw, pb, psn, nout, w2, b2 = self.preds[i]
-            H2, W2 = 2 * h, 2 * w
-            nxt_skip = feats[E - 2 - i] if i + 1 < E else None
-            fs = out_size if out_size is not None and out_size[0] % H2 == 0 and out_size[1] % W2 == 0 else None
-            if nout == 2 and hip.pred_head_supported(D, cout, fs[0] if fs else H2, fs[1] if fs else W2, H2, W2, psn,
-                                                      self.decoders[i + 1][2] if nxt_skip is not None else None) \
-                    and B * D * H2 * W2 * max(cout, 16) * 4 < 1 << 40:
-                # MS pred: SN -> conv1x1 (+bias), 2 outputs, its time sum + upsampling, and the next level's [y | prediction]
-                # spikes - one launch, z read once (csrc/pred_head.hip)
-                nxt = None
-                if nxt_skip is not None and tuple(nxt_skip.shape[2:4]) == (H2, W2):
-                    C1n, C2n = cout, nxt_skip.shape[-1]
-                    cin_n = C1n + C2n + 4
-                    _, cp_n = self._decoder_geometry(i + 1, B, D, H2, W2, cin_n)
-                    carried = ready[i + 1] if ready is not None else torch.empty((B, D, H2, W2, cp_n), dtype=torch.uint8, device=y.device)
-                    nxt = (carried, self.decoders[i + 1][2], 0, C1n + C2n, (cin_n, cp_n - cin_n))
-                pred, flow, sp = hip.pred_head(z, w2, b2, psn, fs[0] if fs else None, fs[1] if fs else None,
-                                               want_pred=self.tape is not None or fs is None or (i + 1 < E and nxt is None),
-                                               nxt=nxt, keep=self.tape is not None)
-                if sp is not None:
-                    self._rec(f"sttmultires_unet.preds.{i}.sn.spiking_neuron.", sp, "BDHWC->TBCHW")
-                self._flows[i] = flow
-                preds.append(pred)
-            else:
-                sp = self._neuron_bd(z, psn)                              # MS pred: SN -> conv1x1 (+bias), 2 outputs
-                self._rec(f"sttmultires_unet.preds.{i}.sn.spiking_neuron.", sp, "BDHWC->TBCHW")
-                po = torch.empty((B * D * 4 * h * w, 32), dtype=torch.float32, device=y.device)
-                hip.spike_gemm(sp, pw, po, po.shape[0], 32, cout, bias=pb)
-                preds.append(po.view(B, D, 2 * h, 2 * w, 32))             # columns nout.. are exactly zero (zero weight rows, zero bias)
-            y = z
-        return [None if p is None else p[..., :self.preds[0][3]] for p in preds]
+            s, wkey = self._decoder_image(i, level, y, skip, preds, ready, carried)
+            y = self._transposed_conv(i, level.route, s, wkey, self._decoder_weight(i, wkey, y.shape[-1], skip.shape[-1]))
+            pred, carried = self._prediction(i, y, feats, out_size, levels, ready)
+            preds.append(pred)
+        return [None if p is None else p[..., :self.preds[0].nout] for p in preds]
 
     def forward(self, x, scores=None, replicas=False):
         """(B,bins,2,H,W) fp32 on the GPU -> list of E flow maps (B,2,H,W) (reference :278-305).  `scores` (a list) receives the

@@ -25,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .engine import MSFlowEngine, _Lin, _ResBlock, _conv_planes, _np, _pad32, bn_affine
+from .engine import MSFlowEngine, _Decoder, _Lin, _Pred, _ResBlock, _center_pad, _np, _pred_planes, bn_affine
 from .STSwinNet.swin_transformer3D_v2 import compute_mask
 from .STSwinNet_SNN.Spiking_swin_transformer3D import get_window_size
 
@@ -82,17 +82,13 @@ class SEWFlowEngine(MSFlowEngine):
         self.unet_res = []
         for i, rb in enumerate(unet.resblocks):
             self.unet_res.append(_ResBlock(rb, dev, ns, U + f"resblocks.{i}."))  # conv2 reads spikes, conv1 the integer stream as bytes
-        self.decoders = [(d.deconv[0].weight.detach().float().to(dev), bn_affine(d.norm_layer.norm_layer, dev), _np(d.sn, dev))
+        self.decoders = [_Decoder(d.deconv[0].weight.detach().float().to(dev), bn_affine(d.norm_layer.norm_layer, dev), _np(d.sn, dev))
                          for d in unet.decoders]
         self._deconv_dense = {}
         self.preds = []
         for p in unet.preds:
-            w2 = p.conv[0].weight.detach().float().reshape(p.conv[0].weight.shape[0], -1)
-            wp = torch.zeros((32, w2.shape[1]), dtype=torch.float32, device=dev)
-            wp[:w2.shape[0]] = w2
-            bp = torch.zeros(32, dtype=torch.float32, device=dev)
-            bp[:w2.shape[0]] = p.conv[0].bias.detach().float()
-            self.preds.append((hip.split_weight(wp, ns), bp, w2.shape[0]))
+            planes, bp, w2 = _pred_planes(p.conv[0], dev, ns)
+            self.preds.append(_Pred(planes, bp, w2.shape[0]))
         self._masks = {}
 
     # ------------------------------------------------------------------ helpers
@@ -257,16 +253,13 @@ class SEWFlowEngine(MSFlowEngine):
         for i in range(E):
             skip = feats[E - 1 - i]
             B, D, h, w, _ = skip.shape
-            parts = ([preds[-1][..., :self.preds[i - 1][2]]] if i > 0 else []) + [y, skip]      # [prediction | y | skip] (:168-172)
-            parts = [F.pad(p, (0, 0, (w - p.shape[3]) // 2, w - p.shape[3] - (w - p.shape[3]) // 2,
-                               (h - p.shape[2]) // 2, h - p.shape[2] - (h - p.shape[2]) // 2)) for p in parts]
-            wdec, bn, sn = self.decoders[i]
-            z = self._deconv_dense_fwd(i, parts, wdec)
-            sp = self._neuron_bd(z, sn, bn=bn)                                    # u8 spikes
+            parts = ([preds[-1][..., :self.preds[i - 1].nout]] if i > 0 else []) + [y, skip]      # [prediction | y | skip] (:168-172)
+            dec, pr = self.decoders[i], self.preds[i]
+            z = self._deconv_dense_fwd(i, [_center_pad(p, h, w) for p in parts], dec.w)
+            sp = self._neuron_bd(z, dec.sn, bn=dec.bn)                                    # u8 spikes
             self._rec(f"sttmultires_unet.decoders.{i}.sn.spiking_neuron.", sp, "BDHWC->TBCHW")
-            pw, pb, nout = self.preds[i]
             po = torch.empty((B * D * 4 * h * w, 32), dtype=torch.float32, device=y.device)
-            hip.spike_gemm(sp, pw, po, po.shape[0], 32, sp.shape[-1], bias=pb)
+            hip.spike_gemm(sp, pr.planes, po, po.shape[0], 32, sp.shape[-1], bias=pr.bias)
             preds.append(po.view(B, D, 2 * h, 2 * w, 32))
             y = sp.float()
-        return [p[..., :self.preds[0][2]] for p in preds]
+        return [p[..., :self.preds[0].nout] for p in preds]

@@ -526,8 +526,9 @@ def neuron_fwd(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, rowma
 
 
 def neuron_multi_fwd(calls):
-    """sdf_neuron_multi_fwd: `calls` = argument tuples of neuron_fwd; one launch when they share T and are at most six."""
-    descs = (NeuronDesc * len(calls))(*[_neuron_desc(*c) for c in calls])
+    """sdf_neuron_multi_fwd: `calls` = (args, kwargs) pairs of neuron_fwd - kwargs also takes `rep` = (count, stride in x, stride in out)
+    of a descriptor's outermost dimension; one launch when they share T and are at most six."""
+    descs = (NeuronDesc * len(calls))(*[_neuron_desc(*a, **k) for a, k in calls])
     _check(lib().sdf_neuron_multi_fwd(descs, len(calls), _stream()), "sdf_neuron_multi_fwd")
 
 

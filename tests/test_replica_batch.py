@@ -168,10 +168,9 @@ def test_neuron_descriptor_outermost_dimension(kind):
     p = hip.NeuronParams("psn", psn_w=rnd((T, T), 6, -0.3, 0.6).to(DEV), psn_b=rnd((T,), 7, -0.2, 0.1).to(DEV)) if kind == "psn" else \
         hip.NeuronParams("lif", 2.0, 0.1, None)
     one = torch.zeros((B, T, hw, cp), dtype=torch.uint8, device=DEV)
-    hip.neuron_multi_fwd([(x, one.view(-1)[c1:], T, hw, C2, C2, hw * C2, cp, hw * cp, p, None, 0, None, None, 0, 1, None, 0, 0, None,
-                           (B, T * hw * C2, T * hw * cp)),
-                          (x, one.view(-1)[c1 + C2:], T, hw, 32, C2, hw * C2, cp, hw * cp, p, None, 0, None, None, 0, 1, None, 0, 0, None,
-                           (B, T * hw * C2, T * hw * cp))])
+    rep = {"rep": (B, T * hw * C2, T * hw * cp)}
+    hip.neuron_multi_fwd([((x, one.view(-1)[c1:], T, hw, C2, C2, hw * C2, cp, hw * cp, p), rep),
+                          ((x, one.view(-1)[c1 + C2:], T, hw, 32, C2, hw * C2, cp, hw * cp, p), rep)])
     ref = torch.zeros_like(one)
     for b in range(B):
         hip.neuron_fwd(x[b], ref[b].view(-1)[c1:], T, hw, C2, C2, hw * C2, cp, hw * cp, p)
