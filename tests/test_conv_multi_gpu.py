@@ -11,8 +11,32 @@ from sdformerflow_amd.synthetic import synth_uniform as rnd
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
+PP, REDUCE, MULTI = "spike_mm_pp_kernel<2, 0, true>", "splitk_reduce_kernel", "spike_mm_pp_multi_kernel<2>"
+# What `sdf_spike_conv2d_multi_fwd` launches per shape: (kernel, workgroups) in order (csrc/spike_mm_pp.hip: tiles of 256 rows x 96 columns,
+# K stages of 64; a class with at most 128 tiles and S >= 4 stages splits K, and then the library launches one by one).
+LAUNCHES = {
+    # M = 69 120: 270 tiles a class, no split-K; 270 items in pairs = 135 workgroups a class: ONE launch of 540
+    (10, 72, 96, 196, 96): [(MULTI, 540)],
+    # M = 252, 2 tiles a class, K = 48 .. 192 (S <= 3: no split-K): 2 workgroups a class: ONE launch of 8
+    (4, 9, 7, 48, 192): [(MULTI, 8)],
+    # M = 1920: 8 tiles; 112 channels, K = 112 | 224 | 224 | 448, S = 2 | 4 | 4 | 7: three of the classes split K -> one by one:
+    # no split, 8 items | 2 chunks: 16 items in pairs | the same | 3 chunks: 24 items in pairs; reduce: 1920 * 24 quads / 256 = 180
+    (10, 12, 16, 100, 96): [(PP, 8), (PP, 8), (REDUCE, 180), (PP, 8), (REDUCE, 180), (PP, 12), (REDUCE, 180)],
+    # M = 252: 2 tiles; K = 64 | 128 | 128 | 256, S = 1 | 2 | 2 | 4: the 2 x 2 class splits K (2 chunks) -> one by one; 252 * 48 quads / 256 -> 48
+    (4, 9, 7, 64, 192): [(PP, 2), (PP, 2), (PP, 2), (PP, 4), (REDUCE, 48)],
+}
+# under SDF_CONV_MULTI=0 the two shapes of the multi launch run their classes as four launches
+ONE_BY_ONE = {(10, 72, 96, 196, 96): [(PP, 135)] * 4, (4, 9, 7, 48, 192): [(PP, 2)] * 4}
 
-@pytest.mark.parametrize("imgs,H,W,Cin,Cout", [(10, 72, 96, 196, 96), (10, 12, 16, 100, 96), (4, 9, 7, 64, 192)])
+
+def _assert_launches(log, want):
+    assert len(log.rows) == len(want), (log.rows, want)
+    for (name, wgs, *_), (kernel, wwgs) in zip(log.rows, want):
+        mangled = kernel.replace("<2, 0, true>", "ILi2ELi0ELb1EE").replace("<2>", "ILi2EE")
+        assert (kernel in name or mangled in name) and wgs == wwgs, (name, wgs, kernel, wwgs)
+
+
+@pytest.mark.parametrize("imgs,H,W,Cin,Cout", [(10, 72, 96, 196, 96), (10, 12, 16, 100, 96), (4, 9, 7, 64, 192), (4, 9, 7, 48, 192)])
 def test_parity_classes_in_one_launch(imgs, H, W, Cin, Cout, monkeypatch):
     cp = (Cin + 15) // 16 * 16
     s = torch.zeros((imgs, H, W, cp), dtype=torch.uint8)
@@ -22,20 +46,25 @@ def test_parity_classes_in_one_launch(imgs, H, W, Cin, Cout, monkeypatch):
     classes = deconv_classes(w.to(DEV), imgs, H, W, cp, 2, DEV)
     sd = s.to(DEV)
 
-    def run(multi):
+    def run(multi, want=None):
         z = torch.full((imgs, 4 * H * W, Cout), float("nan"), device=DEV)
         if multi:
-            hip.spike_conv2d_multi(sd, classes, imgs, H, W, cp, H, W, z, alpha=alpha, beta=beta)
+            with hip.launch_log() as log:
+                hip.spike_conv2d_multi(sd, classes, imgs, H, W, cp, H, W, z, alpha=alpha, beta=beta)
+            if want is not None:
+                _assert_launches(log, want)
         else:
             for c in classes:
                 hip.spike_conv2d(sd, c["Wp"], imgs, H, W, cp, H, W, c["KH"], c["KW"], 1, c["dy"], c["dx"], out=z, alpha=alpha, beta=beta,
                                  out_rowmap=c["rowmap"])
         torch.cuda.synchronize()
         return z
-    one, four = run(True), run(False)
+    want = LAUNCHES[(imgs, H, W, Cin, Cout)]
+    one, four = run(True, want), run(False)
     assert torch.equal(one, four) and not torch.isnan(one).any()
     monkeypatch.setenv("SDF_CONV_MULTI", "0")                   # the entry point's own one-by-one path
-    assert torch.equal(run(True), four)
+    single = ONE_BY_ONE.get((imgs, H, W, Cin, Cout), want)      # (the fallback IS the one-by-one path)
+    assert torch.equal(run(True, single), four)
     ref = torch.nn.functional.conv_transpose2d(s[..., :Cin].permute(0, 3, 1, 2).double(), w.double(), None, 2, 1, 1)
     ref = ref.permute(0, 2, 3, 1) * alpha.cpu().double() + beta.cpu().double()
     err = (one.cpu().view(imgs, 2 * H, 2 * W, Cout).double() - ref).abs().max().item()
