@@ -156,12 +156,12 @@ __global__ __launch_bounds__(256) void glif_bwd_finish_kernel(const float* parti
 
 extern "C" int sdf_glif_fwd(const float* x, const float* tab, void* spike, int T, int64_t N, int spike_dtype, void* stream) {
   if (!x || !tab || !spike) return SDF_E_NULL;
-  if (N < 4 || N % 4 || !sdf_T_in(SDF_T_GLIF, T) || sdf_quad_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
+  if (N < 4 || N % 4 || !sdf_in(SDF_T_GLIF, T) || sdf_quad_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
   if (spike_dtype != SDF_F32 && spike_dtype != SDF_U8) return SDF_E_DTYPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(spike, spike_dtype == SDF_F32 ? 16 : 4) || !sdf_aligned(tab, 4)) return SDF_E_ALIGN;
   dim3 grid((unsigned)sdf_quad_blocks(N)), block(256);
   hipStream_t s = sdf_stream(stream);
-  if (!sdf_for_T(SDF_T_GLIF, T, [&](auto tt) {
+  if (!sdf_dispatch(SDF_T_GLIF, T, [&](auto tt) {
         if (spike_dtype == SDF_U8) SDF_LAUNCH((glif_fwd_kernel<tt, true>), grid, block, 0, s, x, tab, spike, N);
         else SDF_LAUNCH((glif_fwd_kernel<tt, false>), grid, block, 0, s, x, tab, spike, N);
       }))
@@ -171,14 +171,14 @@ extern "C" int sdf_glif_fwd(const float* x, const float* tab, void* spike, int T
 }
 
 extern "C" int64_t sdf_glif_bwd_workspace_bytes(int T, int64_t N) {
-  if (!sdf_T_in(SDF_T_GLIF, T) || N < 4) return 0;
+  if (!sdf_in(SDF_T_GLIF, T) || N < 4) return 0;
   return sdf_quad_blocks(N) * (5 + T) * (int64_t)sizeof(float);      // one row of 5 + T fp32 partials per workgroup
 }
 
 extern "C" int sdf_glif_bwd(const float* x, const float* tab, const float* grad_spike, float* grad_x, float* grad_tab,
                             void* workspace, int64_t workspace_bytes, int T, int64_t N, int surrogate, float alpha, void* stream) {
   if (!x || !tab || !grad_spike || !grad_x || !grad_tab || !workspace) return SDF_E_NULL;
-  if (N < 4 || N % 4 || !sdf_T_in(SDF_T_GLIF, T) || sdf_quad_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
+  if (N < 4 || N % 4 || !sdf_in(SDF_T_GLIF, T) || sdf_quad_blocks(N) >= (1LL << 31)) return SDF_E_SHAPE;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_SHAPE;        // ATan is the only surrogate built
   if (workspace_bytes < sdf_glif_bwd_workspace_bytes(T, N)) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16) || !sdf_aligned(tab, 4) ||
@@ -190,7 +190,7 @@ extern "C" int sdf_glif_bwd(const float* x, const float* tab, const float* grad_
   const int64_t nblk = sdf_quad_blocks(N);
   dim3 grid((unsigned)nblk), block(256);
   hipStream_t s = sdf_stream(stream);
-  if (!sdf_for_T(SDF_T_GLIF, T, [&](auto tt) { SDF_LAUNCH(glif_bwd_kernel<tt>, grid, block, 0, s, P); })) return SDF_E_SHAPE;
+  if (!sdf_dispatch(SDF_T_GLIF, T, [&](auto tt) { SDF_LAUNCH(glif_bwd_kernel<tt>, grid, block, 0, s, P); })) return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   SDF_LAUNCH(glif_bwd_finish_kernel, dim3(5 + T), dim3(256), 0, s, P.partial, nblk, 5 + T, grad_tab);
   SDF_LAUNCH_CHECK();

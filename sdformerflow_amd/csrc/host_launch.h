@@ -1,37 +1,48 @@
-// Host side shared by the stand-alone neuron entry points (neuron.hip, neuron_bwd.hip, glif.hip, qk_gate_train.hip): the T values
-// their kernels are instantiated for, the dispatch from a runtime T to one instantiation, and the grid of the streaming shape.
-// Host code only - the device side of the family is neuron_step.h / device_prims.h.
+// Host side shared by the entry points: the dispatch from a runtime value to one template instantiation over a stated list, the
+// launch-error tail, the T values of the stand-alone neuron kernels (neuron.hip, neuron_bwd.hip, glif.hip, qk_gate_train.hip) and the
+// grid of their streaming shape.  The digit-plane product kernels' own host rules are in digit_host.h.
+// Host code only - the device side of the neuron family is neuron_step.h / device_prims.h.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
-template <int... Ts>
-struct SdfTList {};
+template <int... Vs>
+struct SdfList {};
 
-// Each legal set of T is written here and nowhere else.
-inline constexpr SdfTList<1, 2, 4, 5, 8, 10, 16, 20> SDF_T_STREAM{};   // streaming neuron kernels (T loads in flight per lane)
-inline constexpr SdfTList<2, 4, 5, 10, 20> SDF_T_GLIF{};               // GLIF forward / backward and the multi-descriptor forward
-inline constexpr SdfTList<1, 2, 4> SDF_T_GATE{};                       // T' attention steps of the training token gate
+// The legal T sets of the neuron entry points are written here and nowhere else; a kernel family with a set of its own (T, neuron
+// class, column blocks, a boolean as <0, 1>) writes it at the dispatch, where `if constexpr` leaves out the combinations it has no
+// kernel for.
+inline constexpr SdfList<1, 2, 4, 5, 8, 10, 16, 20> SDF_T_STREAM{};   // streaming neuron kernels (T loads in flight per lane)
+inline constexpr SdfList<2, 4, 5, 10, 20> SDF_T_GLIF{};               // GLIF forward / backward and the multi-descriptor forward
+inline constexpr SdfList<1, 2, 4> SDF_T_GATE{};                       // T' attention steps of the training token gate
 
-template <int... Ts>
-static inline bool sdf_T_in(SdfTList<Ts...>, int T) {
-  return ((T == Ts) || ...);
+template <int... Vs>
+static inline bool sdf_in(SdfList<Vs...>, int v) {
+  return ((v == Vs) || ...);
 }
 
-// Calls f(std::integral_constant<int, TT>{}) for the TT of the list equal to T; false when T is not in the list (f is not called).
-// The SDF_LAUNCH of kernel<tt, ...> stays in f at the call site, so the launch log sees the kernel's own function pointer.
-// (Head-first recursion with f named before the tail, not a fold: the compiler then emits the kernels in the order of the list.)
+// Calls f(std::integral_constant<int, V>{}) for the V of the list equal to v; false when v is not in the list (f is not called).
+// The SDF_LAUNCH of kernel<V, ...> stays in f at the call site, so the launch log sees the kernel's own function pointer; several
+// runtime values nest.  (Head-first recursion with f named before the tail, not a fold: the compiler then emits the kernels in the
+// order of the list.)
 template <class F>
-static inline bool sdf_for_T(SdfTList<>, int, F&&) {
+static inline bool sdf_dispatch(SdfList<>, int, F&&) {
   return false;
 }
-template <int T0, int... Ts, class F>
-static inline bool sdf_for_T(SdfTList<T0, Ts...>, int T, F&& f) {
-  if (T == T0) {
-    f(std::integral_constant<int, T0>{});
+template <int V0, int... Vs, class F>
+static inline bool sdf_dispatch(SdfList<V0, Vs...>, int v, F&& f) {
+  if (v == V0) {
+    f(std::integral_constant<int, V0>{});
     return true;
   }
-  return sdf_for_T(SdfTList<Ts...>{}, T, f);
+  return sdf_dispatch(SdfList<Vs...>{}, v, f);
+}
+
+// What a launch function returns behind its last SDF_LAUNCH: 0 or the hipError_t of the launch (SDF_LAUNCH_CHECK as a value).
+static inline int sdf_launch_rc() {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? (int)e : 0;
 }
 
 // Workgroups of the streaming shape - 4 consecutive neurons per lane, 256 lanes per workgroup - over n neurons.  Every launch of

@@ -25,10 +25,7 @@
 //                      shortcut [+ the next layer's first neuron]), patch merging    reference Spiking_swin_transformer3D.py:164-181,
 //                      :709-714, :810-820, :840-845, :952-974
 //   res_front_kernel : q | k = SN_q/k( BN( xs [Wq;Wk]^T ) [+ PE] ), E = k AND SN2_q( head sums of q )      reference :671-694
-#include "wide_common.h"
-#include "switches.h"
-#include <stdlib.h>
-#include <type_traits>
+#include "digit_host.h"
 
 #ifdef SDF_STAMP
 // diagnostic build only (tools/stamp_res.sh): cycle stamps of wave 0 of the middle workgroup per kernel kind (0 = front, 1 / 2 / 3 = the
@@ -604,37 +601,10 @@ int res_raise(KernelT kern) {
   return sdf_lds_opt_in(done, reinterpret_cast<const void*>(kern), 158 * 1024);
 }
 
-template <int T, int EPI, int NK, int AM, bool STRIP = false>
-int res_pm_launch(const WidePmParams& P, dim3 grid, size_t lds, hipStream_t s) {
-  if (P.K <= 256) {
-    auto kern = res_pm_kernel<T, EPI, NK, AM, true, STRIP>;
-    if (int rc = res_raise(kern)) return rc;
-    SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P);
-  } else {
-    auto kern = res_pm_kernel<T, EPI, NK, AM, false, STRIP>;
-    if (int rc = res_raise(kern)) return rc;
-    SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P);
-  }
-  return 0;
-}
-
 bool res_strip(const WidePmParams& P) {
   const char* e = sdf_sw(SW_RES_STRIP);              // A/B: 0 = fragment-shaped loads everywhere
   if (e && e[0] == '0') return false;
   return P.cv_Cin != 0 || (!P.a_tiled && !P.zsrc);
-}
-
-template <int T, int AM>
-int res_pm_launch_t(const WidePmParams& P, int epi, int nk, dim3 grid, size_t lds, hipStream_t s) {
-  // row-major operands through the full-line loads + LDS strip: patch merging always, the plain fp32 product (the decoders' stacked taps,
-  // fc2 on the parity tape's row-major spikes) where the rows are a plain tensor
-  if (epi == 2 && res_strip(P)) return res_pm_launch<T, 2, 0, AM, true>(P, grid, lds, s);
-  if (epi == 2) return res_pm_launch<T, 2, 0, AM>(P, grid, lds, s);
-  if constexpr (AM == 0) {
-    if (epi == 1) return nk == 0 ? res_pm_launch<T, 1, 0, 0>(P, grid, lds, s) : (nk == 1 ? res_pm_launch<T, 1, 1, 0>(P, grid, lds, s) : res_pm_launch<T, 1, 2, 0>(P, grid, lds, s));
-    return nk == 0 ? res_pm_launch<T, 3, 0, 0>(P, grid, lds, s) : (nk == 1 ? res_pm_launch<T, 3, 1, 0>(P, grid, lds, s) : res_pm_launch<T, 3, 2, 0>(P, grid, lds, s));
-  }
-  return SDF_E_SHAPE;
 }
 
 size_t res_pm_lds(int K, int epi, int T, int nk) {
@@ -660,37 +630,44 @@ bool res_pm_takes(const WidePmParams& P, int T, int epi) {
 }
 
 int launch_res_pm(WidePmParams& P, int T, int epi, hipStream_t s) {
-  const int PPW = 4 * (20 / T);
-  const int64_t units = (P.P + PPW - 1) / PPW;
+  const int64_t units = pm_units(P.P, T);
   if (units >= (1LL << 28)) return SDF_E_SHAPE;
   P.nunits = (int)units;
   P.ncg = P.N / 32;
-  // one workgroup per compute unit, all resident in one round: the smallest number r of units per wave for which
-  // (column groups) x (row ranges of 8 r units) fits the chip's 256 compute units
-  int r = 1;
-  while ((int64_t)P.ncg * ((units + 8 * r - 1) / (8 * r)) > 256) ++r;
-  if (const char* e = sdf_sw(SW_RES_UPW)) { const int v = atoi(e); if (v >= 1 && v <= 4096) r = v; }     // tuning override: units per wave
-  if (const char* e = sdf_sw(SW_RES_RMUL)) { const int v = atoi(e); if (v >= 1 && v <= 16) r *= v; }       // tuning: fewer, longer-lived workgroups
-  P.passes = 8 * r;                                       // units per row range
-  P.nrg = (int)((units + P.passes - 1) / P.passes);
-  const int64_t items = (int64_t)P.ncg * P.nrg;
-  if (items >= (1LL << 31) - 8) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
+  P.nrg = (int)res_row_ranges(P.ncg, units, P.passes);    // (passes = units per row range)
+  dim3 grid;
+  if (int rc = grid8((int64_t)P.ncg * P.nrg, grid)) return rc;
   const int nk = (epi & 1) ? neuron_class(P.sn) : 0;
   const size_t lds = res_pm_lds(P.K, epi, T, nk);
-  int rc;
   if (P.cv_Cin) {                                         // patch merging: cv_cpt carries ceil(2^16 / (C / 16)) for the per-piece quadrant decode
     P.cv_cpt = (65536 + (P.cv_Cin >> 4) - 1) / (P.cv_Cin >> 4);
     for (int p = 0; p < (P.K >> 4) + 8; ++p)
       if ((int)(((uint32_t)p * (uint32_t)P.cv_cpt) >> 16) != p / (P.cv_Cin >> 4)) return SDF_E_SHAPE;
-    if (P.dc_cout) rc = T == 10 ? res_pm_launch_t<10, 3>(P, epi, nk, grid, lds, s) : res_pm_launch_t<20, 3>(P, epi, nk, grid, lds, s);
-    else rc = T == 10 ? res_pm_launch_t<10, 2>(P, epi, nk, grid, lds, s) : res_pm_launch_t<20, 2>(P, epi, nk, grid, lds, s);
-  } else {
-    rc = T == 10 ? res_pm_launch_t<10, 0>(P, epi, nk, grid, lds, s) : res_pm_launch_t<20, 0>(P, epi, nk, grid, lds, s);
   }
-  if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  // row-major operands through the full-line loads + LDS strip: patch merging always, the plain fp32 product (the decoders' stacked taps,
+  // fc2 on the parity tape's row-major spikes) where the rows are a plain tensor
+  const bool strip = epi == 2 && res_strip(P);
+  const int am = P.cv_Cin ? (P.dc_cout ? 3 : 2) : 0;      // A addressing: plain rows / patch merging / the 2 x 2 transposed convolution
+  int rc = SDF_E_SHAPE;
+  // built: the fp32 epilogue (2) has no neuron and alone reads the merged / transposed operands and the strip; small-K from K <= 256 down
+  sdf_dispatch(SdfList<10, 20>{}, T, [&](auto t) {
+    sdf_dispatch(SdfList<0, 2, 3>{}, am, [&](auto a) {
+      sdf_dispatch(SdfList<1, 2, 3>{}, epi, [&](auto e) {
+        sdf_dispatch(SdfList<0, 1, 2>{}, nk, [&](auto n) {
+          sdf_dispatch(SdfList<0, 1>{}, strip, [&](auto st) {
+            sdf_dispatch(SdfList<0, 1>{}, P.K <= 256, [&](auto sk) {
+              if constexpr ((e == 2 || (a == 0 && st == 0)) && (e != 2 || n == 0)) {
+                auto kern = res_pm_kernel<t, e, n, a, sk != 0, st != 0>;
+                rc = res_raise(kern);
+                if (!rc) SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P);
+              }
+            });
+          });
+        });
+      });
+    });
+  });
+  return rc ? rc : sdf_launch_rc();
 }
 
 bool res_front_takes(const WideFrontParams& P) {
@@ -702,27 +679,19 @@ int launch_res_front(WideFrontParams& P, bool keep, int nk, hipStream_t s) {
   const int64_t ntiles = (P.rows + 15) / 16;
   if (ntiles >= (1LL << 30)) return SDF_E_SHAPE;
   P.ntiles = (int)ntiles;
-  int r = 1;
-  while ((int64_t)P.nH * ((ntiles + 8 * r - 1) / (8 * r)) > 256) ++r;
-  if (const char* e = sdf_sw(SW_RES_UPW)) { const int v = atoi(e); if (v >= 1 && v <= 4096) r = v; }
-  if (const char* e = sdf_sw(SW_RES_RMUL)) { const int v = atoi(e); if (v >= 1 && v <= 16) r *= v; }
-  P.ntiles_per = 8 * r;
-  P.nrg = (int)((ntiles + P.ntiles_per - 1) / P.ntiles_per);
-  const int64_t items = (int64_t)P.nrg * P.nH;
-  if (items >= (1LL << 31) - 8) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
+  P.nrg = (int)res_row_ranges(P.nH, ntiles, P.ntiles_per);
+  dim3 grid;
+  if (int rc = grid8((int64_t)P.nrg * P.nH, grid)) return rc;
   const size_t lds = (size_t)res_wbytes(P.C, 64) + NWV * 32 * s_pitch(keep ? 96 : 32);
-#define SDF_RF(NK_)                                                                                       \
-  do {                                                                                                    \
-    if (keep) { auto kern = res_front_kernel<NK_, true>; if (int rc = res_raise(kern)) return rc;        \
-                SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P); }                             \
-    else { auto kern = res_front_kernel<NK_, false>; if (int rc = res_raise(kern)) return rc;            \
-           SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P); }                                  \
-  } while (0)
-  if (nk == 0) SDF_RF(0); else if (nk == 1) SDF_RF(1); else SDF_RF(2);
-#undef SDF_RF
-  hipError_t err = hipGetLastError();
-  return err != hipSuccess ? (int)err : 0;
+  int rc = SDF_E_SHAPE;
+  sdf_dispatch(SdfList<0, 1, 2>{}, nk, [&](auto n) {
+    sdf_dispatch(SdfList<1, 0>{}, keep, [&](auto kp) {
+      auto kern = res_front_kernel<n, kp != 0>;
+      rc = res_raise(kern);
+      if (!rc) SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P);
+    });
+  });
+  return rc ? rc : sdf_launch_rc();
 }
 
 }  // namespace sdfmm

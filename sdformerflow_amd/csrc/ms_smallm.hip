@@ -28,9 +28,7 @@
 // What bounds it: 22 KB of operands per 60 MFMAs and wave, i.e. the L2 -> L1 path (64 B / clk / CU), not the matrix pipe.
 //
 // Results are bit-equal to any other order of the same integer sums (wide_pm_kernel, the row-major reference in the tests).
-#include "wide_common.h"
-#include "switches.h"
-#include <stdlib.h>
+#include "digit_host.h"
 
 #ifdef SDF_STAMP
 // diagnostic build only (tools/smallm_ablate.sh stamp): cycle accounting of every wave of the middle workgroup and every workgroup's
@@ -418,24 +416,19 @@ __global__ __launch_bounds__(256, CB == 2 ? 2 : 1) void smallm_kernel(SmallMPara
 #endif
 }
 
-template <int T, int AM, bool BT, int CB>
-void launch_t(const SmallMParams& P, int epi, int nk, dim3 grid, hipStream_t s) {
-  if (epi == 2) SDF_LAUNCH((smallm_kernel<T, 2, 0, AM, BT, CB>), grid, dim3(256), 0, s, P);
-  else if (epi == 1) {
-    if (nk == 0) SDF_LAUNCH((smallm_kernel<T, 1, 0, AM, BT, CB>), grid, dim3(256), 0, s, P);
-    else if (nk == 1) SDF_LAUNCH((smallm_kernel<T, 1, 1, AM, BT, CB>), grid, dim3(256), 0, s, P);
-    else SDF_LAUNCH((smallm_kernel<T, 1, 2, AM, BT, CB>), grid, dim3(256), 0, s, P);
-  } else {
-    if (nk == 0) SDF_LAUNCH((smallm_kernel<T, 3, 0, AM, BT, CB>), grid, dim3(256), 0, s, P);
-    else if (nk == 1) SDF_LAUNCH((smallm_kernel<T, 3, 1, AM, BT, CB>), grid, dim3(256), 0, s, P);
-    else SDF_LAUNCH((smallm_kernel<T, 3, 2, AM, BT, CB>), grid, dim3(256), 0, s, P);
-  }
-}
-
-template <int T, int AM>
-void launch_bt(const SmallMParams& P, int epi, int nk, bool bt, int cb, dim3 grid, hipStream_t s) {
-  if (bt) { if (cb == 3) launch_t<T, AM, true, 3>(P, epi, nk, grid, s); else launch_t<T, AM, true, 2>(P, epi, nk, grid, s); }
-  else launch_t<T, AM, false, 2>(P, epi, nk, grid, s);
+// One launch of the kernel.  AM (plain rows / 3x3 convolution) and BT (digits in fragment order) are the caller's form, and so are the
+// lists of T, column blocks and epilogues it has builds for; the fp32 epilogue (2) has no neuron.
+template <int AM, bool BT, class TList, class CbList, class EpiList>
+void launch_smallm(TList ts, CbList cbs, EpiList epis, const SmallMParams& P, int T, int cb, int epi, int nk, dim3 grid, hipStream_t s) {
+  sdf_dispatch(ts, T, [&](auto t) {
+    sdf_dispatch(cbs, cb, [&](auto c) {
+      sdf_dispatch(epis, epi, [&](auto e) {
+        sdf_dispatch(SdfList<0, 1, 2>{}, e == 2 ? 0 : nk, [&](auto n) {
+          if constexpr (e != 2 || n == 0) SDF_LAUNCH((smallm_kernel<t, e, n, AM, BT, c>), grid, dim3(256), 0, s, P);
+        });
+      });
+    });
+  });
 }
 
 // fp32 digit planes [3][N][K] -> fragment order [N / 16][K / 64][3][64 lanes][16 B]: lane l of fragment (column block, step, plane) holds
@@ -470,63 +463,59 @@ static int64_t smallm_conv_rows() {
   return 400 * 80;
 }
 
-bool smallm_conv_supports(const GemmParams& P) {
+bool smallm_conv_plan(const GemmParams& P, SmallmConvPlan& pl) {
   const SdfSpikeGemmDesc& d = P.d;
   const ConvGeom& cv = P.cv;
   if (const char* e = sdf_sw(SW_SMALLM)) { if (e[0] == '0') return false; }
-  if ((d.nsplit != SDF_PLANES_I8X3 && d.nsplit != SDF_PLANES_I8X3_TILED) || !d.col_scale) return false;
-  if (cv.KWc != 3 || d.K != 9 * cv.Cin || cv.Cin % 64 || cv.sy != 1 || cv.sx != 1 || cv.OH != cv.H || cv.OW != cv.W) return false;
-  if (cv.dy[0] != -1 || cv.dy[1] != 0 || cv.dy[2] != 1 || cv.dx[0] != -1 || cv.dx[1] != 0 || cv.dx[2] != 1) return false;
+  const bool bt = d.nsplit == SDF_PLANES_I8X3_TILED;
+  if ((d.nsplit != SDF_PLANES_I8X3 && !bt) || !d.col_scale) return false;
+  if (!conv_3x3_s1_p1(cv, d.K) || cv.Cin % 64) return false;
   if (d.N % 32 || d.out_rowmap || d.bias || d.add || d.zg_nH) return false;
   const int64_t hw = (int64_t)cv.H * cv.W, imgs = d.M / hw;
-  int T = d.sn_T;
-  if (T == 0) T = imgs % 10 == 0 ? 10 : (imgs % 20 == 0 ? 20 : 0);
+  const int T = pl.T = conv_T(d, imgs);
   if (T != 10 && T != 20) return false;
   if (imgs % T || d.M > smallm_conv_rows()) return false;
   if (d.sn_T > 0) {
-    if (!smallm_neuron_ok({d.sn_kind, d.tau, d.v_th, d.v_reset, d.soft_reset, d.psn_w, d.psn_b})) return false;
+    if (!smallm_neuron_ok(gemm_neuron(d))) return false;
     if (d.pos_inner != hw || d.t_stride != hw || d.pos_ostride != (int64_t)T * hw || d.pos_count * T != d.M) return false;   // rows (b, t, pixel)
     if (!d.out_spike) return false;
   } else if (!d.out) {
     return false;
   }
   if (d.M * (int64_t)cv.Cin >= (1LL << 31) || d.M * (int64_t)d.N * 4 >= (1LL << 31) || (int64_t)d.N * d.K * 3 >= (1LL << 31)) return false;
+  // tile width: 32 columns, two workgroups per compute unit.  The 48-column tile (one workgroup per compute unit, two operand steps in
+  // flight) is 2 us faster on its own at the bottleneck shape (25.2 vs 27.5 us) but holds 224 whole compute units where this one packs
+  // 336 workgroups onto 168: with three forwards in flight the headline measured +0.9 % with the narrow tile (three alternating pairs
+  // of runs on one box: 687.8 / 683.5 / 685.7 against 680.7 / 677.2 / 679.6 samples/s).  SDF_SMALLM_CB=3 selects the wide tile.
+  pl.cb = 2;
+  if (const char* e = sdf_sw(SW_SMALLM_CB)) { if (bt && e[0] == '3' && d.N % 48 == 0) pl.cb = 3; }      // tuning override
   return sdf_aligned(d.A, 16) && sdf_aligned(d.Wp, 16) && (!d.out || sdf_aligned(d.out, 16)) && (!d.resid || sdf_aligned(d.resid, 16)) &&
          (!d.out_spike || sdf_aligned(d.out_spike, 16)) && (!d.out || d.ldo == d.N);
 }
 
-int launch_smallm_conv(const GemmParams& G, hipStream_t s) {
+int launch_smallm_conv(const GemmParams& G, const SmallmConvPlan& pl, hipStream_t s) {
   const SdfSpikeGemmDesc& d = G.d;
   const ConvGeom& cv = G.cv;
   const int64_t hw = (int64_t)cv.H * cv.W, imgs = d.M / hw;
-  int T = d.sn_T;
-  if (T == 0) T = imgs % 10 == 0 ? 10 : 20;
+  const int T = pl.T;
   SmallMParams P = {};
   P.A = d.A; P.W = reinterpret_cast<const int8_t*>(d.Wp); P.cscale = d.col_scale; P.N = d.N; P.K = d.K; P.HW = (int)hw; P.P = (imgs / T) * hw;
   P.alpha = d.alpha; P.beta = d.beta; P.resid = d.resid; P.out = d.out; P.ldo = d.N;
   P.out_spike = d.sn_T > 0 ? d.out_spike : nullptr; P.ldsp = d.N;
-  P.sn = {d.sn_kind, d.tau, d.v_th, d.v_reset, d.soft_reset, d.psn_w, d.psn_b};
+  P.sn = gemm_neuron(d);
   P.inv_tau = d.sn_T > 0 ? inv_tau_of(P.sn) : 0.f;
   P.cv_H = cv.H; P.cv_W = cv.W; P.cv_Cin = cv.Cin; P.cv_spt = cv.Cin / 64;
   P.cv_inv = (65536 + P.cv_spt - 1) / P.cv_spt;
   for (int st = 0; st < 9 * P.cv_spt + 64; ++st)            // (steps up to a few rounds beyond the last are formed and must decode to tap >= 9)
     if ((int)(((uint32_t)st * (uint32_t)P.cv_inv) >> 16) != st / P.cv_spt) return SDF_E_SHAPE;
-  const int PPW = 4 * (20 / T);
-  P.nunits = (int)((P.P + PPW - 1) / PPW);
-  const bool bt = d.nsplit == SDF_PLANES_I8X3_TILED;
-  // tile width: 32 columns, two workgroups per compute unit.  The 48-column tile (one workgroup per compute unit, two operand steps in
-  // flight) is 2 us faster on its own at the bottleneck shape (25.2 vs 27.5 us) but holds 224 whole compute units where this one packs
-  // 336 workgroups onto 168: with three forwards in flight the headline measured +0.9 % with the narrow tile (three alternating pairs
-  // of runs on one box: 687.8 / 683.5 / 685.7 against 680.7 / 677.2 / 679.6 samples/s).  SDF_SMALLM_CB=3 selects the wide tile.
-  int cb = 2;
-  if (const char* e = sdf_sw(SW_SMALLM_CB)) { if (bt && e[0] == '3' && d.N % 48 == 0) cb = 3; else if (e[0] == '2') cb = 2; }   // tuning override
-  P.ncg = d.N / (16 * cb);
-  const int64_t items = (int64_t)P.ncg * P.nunits;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
+  P.nunits = (int)pm_units(P.P, T);
+  P.ncg = d.N / (16 * pl.cb);
+  dim3 grid;
+  grid8((int64_t)P.ncg * P.nunits, grid, false);
   const int epi = d.sn_T > 0 ? (d.out ? 3 : 1) : 2, nk = d.sn_T > 0 ? neuron_class(P.sn) : 0;
-  if (T == 10) launch_bt<10, 1>(P, epi, nk, bt, cb, grid, s); else launch_bt<20, 1>(P, epi, nk, bt, cb, grid, s);
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  if (d.nsplit == SDF_PLANES_I8X3_TILED) launch_smallm<1, true>(SdfList<10, 20>{}, SdfList<3, 2>{}, SdfList<2, 1, 3>{}, P, T, pl.cb, epi, nk, grid, s);
+  else launch_smallm<1, false>(SdfList<10, 20>{}, SdfList<2>{}, SdfList<2, 1, 3>{}, P, T, pl.cb, epi, nk, grid, s);
+  return sdf_launch_rc();
 }
 
 // fc2 of the wide-stage MLP (reference Spiking_swin_transformer3D.py:175-178, :845): x += BN2( s2 W2^T ) in place on the (B, D, HW, C)
@@ -542,7 +531,7 @@ bool smallm_fc2_supports(const SdfMsMlpDesc* d) {
   if (tokens > SMALLM_MAX_ROWS || tokens * d->Ch >= (1LL << 31) || tokens * d->C * 4 >= (1LL << 31) || (int64_t)d->C * d->Ch * 3 >= (1LL << 31)) return false;
   if (d->emit_next && !smallm_neuron_ok(d->emit_sn)) return false;
   {
-    const int64_t ppw = 4 * (20 / d->D), units = ((int64_t)d->B * d->HW + ppw - 1) / ppw;
+    const int64_t units = pm_units((int64_t)d->B * d->HW, d->D);
     const char* e = sdf_sw(SW_SMALLM_FC2);
     if (units * (d->C / 32) > 512 && !(e && e[0] == '2')) return false;       // (SDF_SMALLM_FC2=2: at any size, tests / A/B)
   }
@@ -554,16 +543,14 @@ int launch_smallm_fc2(const SdfMsMlpDesc* d, const uint8_t* s2, hipStream_t s) {
   P.A = s2; P.W = d->fc2_tiled; P.cscale = d->fc2_cscale; P.N = d->C; P.K = d->Ch; P.HW = (int)d->HW; P.P = (int64_t)d->B * d->HW;
   P.alpha = d->fc2_alpha; P.beta = d->fc2_beta; P.resid = d->x; P.out = d->x; P.ldo = d->C;        // (a lane reads its shortcut values before it writes them)
   P.out_spike = d->emit_next; P.ldsp = d->C; P.sn = d->emit_sn; P.inv_tau = d->emit_next ? inv_tau_of(d->emit_sn) : 0.f;
-  const int T = d->D, PPW = 4 * (20 / T);
-  P.nunits = (int)((P.P + PPW - 1) / PPW);
+  const int T = d->D;
+  P.nunits = (int)pm_units(P.P, T);
   P.ncg = d->C / 32;                                              // 32-column tiles: two workgroups per compute unit
-  const int64_t items = (int64_t)P.ncg * P.nunits;
-  if (items >= (1LL << 31) - 8) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
+  dim3 grid;
+  if (int rc = grid8((int64_t)P.ncg * P.nunits, grid)) return rc;
   const int epi = d->emit_next ? 3 : 2, nk = d->emit_next ? neuron_class(d->emit_sn) : 0;
-  if (T == 10) launch_t<10, 0, true, 2>(P, epi, nk, grid, s); else launch_t<20, 0, true, 2>(P, epi, nk, grid, s);
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  launch_smallm<0, true>(SdfList<10, 20>{}, SdfList<2>{}, SdfList<2, 1, 3>{}, P, T, 2, epi, nk, grid, s);
+  return sdf_launch_rc();
 }
 
 // out (M, N) fp32 = [BN]( A (M, K) u8 x W^T + bias ) + resid with the digits in fragment order: the stacked-tap product of the first
@@ -584,17 +571,14 @@ int launch_smallm_gemm(const GemmParams& G, hipStream_t s) {
   SmallMParams P = {};
   P.A = d.A; P.W = reinterpret_cast<const int8_t*>(d.Wp); P.cscale = d.col_scale; P.N = d.N; P.K = d.K; P.HW = (int)(d.M / 10); P.P = d.M / 10;
   P.alpha = d.alpha; P.beta = d.beta; P.bias = d.bias; P.resid = d.resid; P.out = d.out; P.ldo = (int)d.ldo;
-  P.nunits = (int)((P.P + 7) / 8);
+  P.nunits = (int)pm_units(P.P, 10);
   int cb = 2;                                                     // (as the convolution: the narrow tile packs two workgroups per compute unit)
   if (const char* e = sdf_sw(SW_SMALLM_CB)) { if (e[0] == '3' && d.N % 48 == 0) cb = 3; else if (e[0] == '2') cb = 2; }   // tuning override
   P.ncg = d.N / (16 * cb);
-  const int64_t items = (int64_t)P.ncg * P.nunits;
-  if (items >= (1LL << 31) - 8) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
-  if (cb == 3) SDF_LAUNCH((smallm_kernel<10, 2, 0, 0, true, 3>), grid, dim3(256), 0, s, P);
-  else SDF_LAUNCH((smallm_kernel<10, 2, 0, 0, true, 2>), grid, dim3(256), 0, s, P);
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  dim3 grid;
+  if (int rc = grid8((int64_t)P.ncg * P.nunits, grid)) return rc;
+  launch_smallm<0, true>(SdfList<10>{}, SdfList<3, 2>{}, SdfList<2>{}, P, 10, cb, 2, 0, grid, s);
+  return sdf_launch_rc();
 }
 
 }  // namespace sdfmm

@@ -32,8 +32,7 @@
 // 4 x 4 byte transpose inside each lane quad (two DPP moves + two v_perm) so that a lane holds four consecutive CHANNELS of a row,
 // one ds_write_b32 into a per-wave LDS tile and 16-byte global stores.  The fp32 shortcut is read and written in the accumulator
 // layout (64-byte runs per row and column block; the buffers are L2-resident at these sizes).
-#include "wide_common.h"
-#include "switches.h"
+#include "digit_host.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -750,59 +749,31 @@ int pick_cb(int64_t units, int N, const int* cbs, int ncb) {
   return 0;
 }
 
-template <int T, int CB, int EPI>
-int launch_pm_nk(const WidePmParams& P, int nk, dim3 grid, hipStream_t s) {
-  if constexpr (EPI == 2) {
-    SDF_LAUNCH((wide_pm_kernel<T, CB, EPI, 0>), grid, dim3(256), 0, s, P);
-  } else {
-    if (nk == 0) SDF_LAUNCH((wide_pm_kernel<T, CB, EPI, 0>), grid, dim3(256), 0, s, P);
-    else if (nk == 1) SDF_LAUNCH((wide_pm_kernel<T, CB, EPI, 1>), grid, dim3(256), 0, s, P);
-    else SDF_LAUNCH((wide_pm_kernel<T, CB, EPI, 2>), grid, dim3(256), 0, s, P);
-  }
-  return 0;
-}
-
-template <int T>
-int launch_pm_t(WidePmParams& P, int epi, hipStream_t s) {
-  constexpr int PPW = 4 * (20 / T);
-  const int64_t units = (P.P + PPW - 1) / PPW;
+int launch_pm(WidePmParams& P, int T, int epi, hipStream_t s) {
+  if (res_pm_takes(P, T, epi)) return launch_res_pm(P, T, epi, s);      // narrow stages: weights LDS-resident, row loop (ms_res.hip)
+  if (T != 10 && T != 20) return SDF_E_SHAPE;
   // the fp32 epilogues hold the shortcut values and the updated stream beside the accumulators: two column blocks; the neuron-only
   // epilogue (fc1) takes three where that still fills the chip
   static const int cbs[2] = {2, 3};
-  int cb = pick_cb(units, P.N, cbs, epi == 1 ? 2 : 1);
+  int cb = pick_cb(pm_units(P.P, T), P.N, cbs, epi == 1 ? 2 : 1);
   if (const char* e = sdf_sw(SW_WIDE_CB)) {                     // tuning override (fc1): 2 / 3
     const int v = e[0] - '0';
     if (epi == 1 && (v == 2 || v == 3) && P.N % (16 * v) == 0) cb = v;
   }
-  if (!cb || units >= (1LL << 28)) return SDF_E_SHAPE;
-  P.nunits = (int)units;
-  P.nrg = (int)((units + 3) / 4);
-  P.ncg = P.N / (16 * cb);
-  // one workgroup per compute unit (the kernels take most of its registers): a launch of up to four rounds runs as ONE round of
-  // workgroups that walk several row groups (the prologue is paid once, no second dispatch wave)
-  const int64_t all = (int64_t)P.ncg * P.nrg;
-  P.passes = all > 256 && all <= 1024 ? (int)((all + 255) / 256) : 1;
-  if (const char* e = sdf_sw(SW_WIDE_PASSES)) { const int v = atoi(e); if (v >= 1 && v <= 8) P.passes = v; }     // tuning override
-  const int64_t items = (int64_t)P.ncg * ((P.nrg + P.passes - 1) / P.passes);
-  if (items >= (1LL << 31) - 8) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
-  const int nk = neuron_class(P.sn);
-  if (epi == 1) return cb == 3 ? launch_pm_nk<T, 3, 1>(P, nk, grid, s) : launch_pm_nk<T, 2, 1>(P, nk, grid, s);
-  if (epi == 2) return launch_pm_nk<T, 2, 2>(P, 0, grid, s);
-  return launch_pm_nk<T, 2, 3>(P, nk, grid, s);
-}
-
-int launch_pm(WidePmParams& P, int T, int epi, hipStream_t s) {
-  if (res_pm_takes(P, T, epi)) return launch_res_pm(P, T, epi, s);      // narrow stages: weights LDS-resident, row loop (ms_res.hip)
-  int rc;
-  switch (T) {
-    case 10: rc = launch_pm_t<10>(P, epi, s); break;
-    case 20: rc = launch_pm_t<20>(P, epi, s); break;
-    default: return SDF_E_SHAPE;
-  }
-  if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  dim3 grid;
+  if (int rc = pm_ring_grid(P, T, cb, true, grid)) return rc;
+  const int nk = epi == 2 ? 0 : neuron_class(P.sn);
+  // built: three column blocks for the neuron-only epilogue alone, no neuron in the fp32 epilogue (2); any other epi runs as 3
+  sdf_dispatch(SdfList<10, 20>{}, T, [&](auto t) {
+    sdf_dispatch(SdfList<3, 2>{}, cb, [&](auto c) {
+      sdf_dispatch(SdfList<1, 2, 3>{}, epi == 1 || epi == 2 ? epi : 3, [&](auto e) {
+        sdf_dispatch(SdfList<0, 1, 2>{}, nk, [&](auto n) {
+          if constexpr ((c == 2 || e == 1) && (e != 2 || n == 0)) SDF_LAUNCH((wide_pm_kernel<t, c, e, n>), grid, dim3(256), 0, s, P);
+        });
+      });
+    });
+  });
+  return sdf_launch_rc();
 }
 
 // These kernels are built for problems that are small in rows (one workgroup per compute unit, a prologue per 320 rows): up to 400
@@ -907,25 +878,14 @@ bool wide_merge_supports(const SdfMsMergeDesc* d) {
 }
 
 int launch_wide_merge(const SdfMsMergeDesc* d, hipStream_t s) {
-  WidePmParams P = {};
-  P.A = d->spikes; P.W = d->digits; P.cscale = d->cscale; P.N = d->N; P.K = 4 * d->C;
-  P.HW = ((d->H + 1) / 2) * ((d->W + 1) / 2); P.P = (int64_t)d->B * P.HW;
-  P.alpha = d->alpha; P.beta = d->beta; P.x = d->out; P.ldo = d->N; P.no_resid = 1;
-  P.cv_H = d->H; P.cv_W = d->W; P.cv_Cin = d->C; P.cv_cpt = d->C / 64;          // (64-deep steps per quadrant)
-  const int T = d->D, PPW = 4 * (20 / T);
+  WidePmParams P = pm_merge(d);
+  const int T = d->D;
   P.res_stage = res_stage_ok(d->C, true);
   if (res_pm_takes(P, T, 2)) return launch_res_pm(P, T, 2, s);
-  const int64_t units = (P.P + PPW - 1) / PPW;
-  if (units >= (1LL << 28)) return SDF_E_SHAPE;
-  P.nunits = (int)units; P.nrg = (int)((units + 3) / 4); P.ncg = d->N / 32;
-  const int64_t all = (int64_t)P.ncg * P.nrg;
-  P.passes = all > 256 && all <= 1024 ? (int)((all + 255) / 256) : 1;
-  const int64_t items = (int64_t)P.ncg * ((P.nrg + P.passes - 1) / P.passes);
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
-  if (T == 10) SDF_LAUNCH((wide_pm_kernel<10, 2, 2, 0, 2>), grid, dim3(256), 0, s, P);
-  else SDF_LAUNCH((wide_pm_kernel<20, 2, 2, 0, 2>), grid, dim3(256), 0, s, P);
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  dim3 grid;
+  if (int rc = pm_ring_grid(P, T, 2, false, grid)) return rc;
+  sdf_dispatch(SdfList<10, 20>{}, T, [&](auto t) { SDF_LAUNCH((wide_pm_kernel<t, 2, 2, 0, 2>), grid, dim3(256), 0, s, P); });
+  return sdf_launch_rc();
 }
 
 bool ms_wide_attn_supports(const SdfQkAttnDesc* d) {
@@ -984,20 +944,14 @@ int launch_ms_wide_front(const SdfQkAttnDesc* d, const uint8_t* xs, uint8_t* e, 
   const int64_t ntiles = big ? t5 : t2;
   P.ntiles = (int)ntiles;
   P.nrg = (int)((ntiles + 3) / 4);
-  const int64_t items = (int64_t)P.nrg * d->nH;
-  if (items >= (1LL << 31) - 8) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
-  const int nk = neuron_class(d->sn_q);
-#define SDF_WF(RB_, NK_)                                                                                  \
-  do {                                                                                                    \
-    if (keep) SDF_LAUNCH((wide_front_kernel<RB_, NK_, true>), grid, dim3(256), 0, s, P);          \
-    else SDF_LAUNCH((wide_front_kernel<RB_, NK_, false>), grid, dim3(256), 0, s, P);              \
-  } while (0)
-  if (big) { if (nk == 0) SDF_WF(4, 0); else if (nk == 1) SDF_WF(4, 1); else SDF_WF(4, 2); }
-  else { if (nk == 0) SDF_WF(2, 0); else if (nk == 1) SDF_WF(2, 1); else SDF_WF(2, 2); }
-#undef SDF_WF
-  hipError_t err = hipGetLastError();
-  return err != hipSuccess ? (int)err : 0;
+  dim3 grid;
+  if (int rc = grid8((int64_t)P.nrg * d->nH, grid)) return rc;
+  sdf_dispatch(SdfList<4, 2>{}, big ? 4 : 2, [&](auto rb) {
+    sdf_dispatch(SdfList<0, 1, 2>{}, neuron_class(d->sn_q), [&](auto n) {
+      sdf_dispatch(SdfList<1, 0>{}, keep, [&](auto kp) { SDF_LAUNCH((wide_front_kernel<rb, n, kp != 0>), grid, dim3(256), 0, s, P); });
+    });
+  });
+  return sdf_launch_rc();
 }
 
 int launch_ms_wide_proj(const SdfQkAttnDesc* d, const uint8_t* e, hipStream_t s) {
@@ -1015,7 +969,7 @@ int launch_ms_wide_proj(const SdfQkAttnDesc* d, const uint8_t* e, hipStream_t s)
 // ---- 3x3 convolution of few rows against many weights (the U-Net bottleneck's res-blocks: 1 080 rows x 768 x 6 912) -----------------
 // K is split over workgroups so that the weight digits (16 MB) leave HBM once, spread over the whole chip; the partial sums meet in
 // wide_reduce_kernel together with BN, the shortcut and the neuron.
-bool wide_conv_supports(const GemmParams& P) {
+bool wide_conv_plan(const GemmParams& P, WideConvPlan& pl) {
   const SdfSpikeGemmDesc& d = P.d;
   const ConvGeom& cv = P.cv;
   if (wide_env_off()) return false;
@@ -1028,16 +982,14 @@ bool wide_conv_supports(const GemmParams& P) {
     if (!(e && e[0] == '1')) return false;
   }
   if (d.nsplit != SDF_PLANES_I8X3 || !d.col_scale) return false;
-  if (cv.KWc != 3 || d.K != 9 * cv.Cin || cv.Cin % KCH || cv.sy != 1 || cv.sx != 1 || cv.OH != cv.H || cv.OW != cv.W) return false;
-  if (cv.dy[0] != -1 || cv.dy[1] != 0 || cv.dy[2] != 1 || cv.dx[0] != -1 || cv.dx[1] != 0 || cv.dx[2] != 1) return false;
+  if (!conv_3x3_s1_p1(cv, d.K) || cv.Cin % KCH) return false;
   if (d.N % 32 || d.out_rowmap || d.bias || d.add || d.zg_nH) return false;
   const int64_t hw = (int64_t)cv.H * cv.W, imgs = d.M / hw;
-  int T = d.sn_T;
-  if (T == 0) T = imgs % 10 == 0 ? 10 : (imgs % 20 == 0 ? 20 : 0);
+  const int T = pl.T = conv_T(d, imgs);
   if (T != 10 && T != 20) return false;
   if (imgs % T || d.M > WIDE_MAX_ROWS) return false;
   if (d.sn_T > 0) {
-    if (!neuron_ok({d.sn_kind, d.tau, d.v_th, d.v_reset, d.soft_reset, nullptr, nullptr})) return false;
+    if (!neuron_ok(gemm_neuron(d, false))) return false;          // (no PSN form of the reduce pass: its pointers are not passed on)
     if (d.pos_inner != hw || d.t_stride != hw || d.pos_ostride != (int64_t)T * hw || d.pos_count * T != d.M) return false;   // rows (b, t, pixel)
   }
   if (d.M * (int64_t)cv.Cin >= (1LL << 31) || d.M * (int64_t)d.N * 4 >= (1LL << 31) || (int64_t)d.N * d.K * 3 >= (1LL << 31)) return false;
@@ -1046,47 +998,44 @@ bool wide_conv_supports(const GemmParams& P) {
   int ks = 1;
   while (ks < nchunks && (ncg * ks < 200 || nchunks % ks)) ++ks;
   if (nchunks % ks) return false;
+  pl.ks = ks;
   if (!d.workspace || d.workspace_bytes < (int64_t)ks * d.M * d.N * 4) return false;
   return sdf_aligned(d.A, 16) && sdf_aligned(d.Wp, 16) && sdf_aligned(d.workspace, 16) && (!d.out || sdf_aligned(d.out, 16)) &&
          (!d.resid || sdf_aligned(d.resid, 16)) && (!d.alpha || (sdf_aligned(d.alpha, 16) && sdf_aligned(d.beta, 16))) &&
          (!d.out_spike || sdf_aligned(d.out_spike, 4)) && d.ldo == d.N;
 }
 
-int launch_wide_conv(const GemmParams& G, hipStream_t s) {
+int launch_wide_conv(const GemmParams& G, const WideConvPlan& pl, hipStream_t s) {
   const SdfSpikeGemmDesc& d = G.d;
   const ConvGeom& cv = G.cv;
   const int64_t hw = (int64_t)cv.H * cv.W, imgs = d.M / hw;
-  int T = d.sn_T;
-  if (T == 0) T = imgs % 10 == 0 ? 10 : 20;
-  const int nchunks = d.K / KCH, ncg = d.N / 32;
-  int ks = 1;
-  while (ks < nchunks && (ncg * ks < 200 || nchunks % ks)) ++ks;
+  const int T = pl.T, ks = pl.ks, nchunks = d.K / KCH, ncg = d.N / 32;
   WidePmParams P = {};
   P.A = d.A; P.W = reinterpret_cast<const int8_t*>(d.Wp); P.cscale = d.col_scale; P.N = d.N; P.K = d.K; P.HW = (int)hw; P.P = (imgs / T) * hw;
   P.cv_H = cv.H; P.cv_W = cv.W; P.cv_Cin = cv.Cin; P.cv_cpt = cv.Cin / KCH;
   P.ksplit = ks;                                            // (one range: the same path, slot 0 of the partial buffer)
   P.cps = nchunks / ks;
   P.partial = reinterpret_cast<float*>(d.workspace);
-  const int PPW = 4 * (20 / T);
-  const int64_t units = (P.P + PPW - 1) / PPW;
+  const int64_t units = pm_units(P.P, T);
   P.nunits = (int)units; P.nrg = (int)((units + 3) / 4); P.ncg = ncg;
   P.passes = P.nrg;                                         // one workgroup per (column group, K range) walks every row group
-  const int64_t items = (int64_t)ncg * ks;
-  const dim3 grid((unsigned)((items + 7) / 8 * 8));
-  if (T == 10) SDF_LAUNCH((wide_pm_kernel<10, 2, 4, 0>), grid, dim3(256), 0, s, P);
-  else SDF_LAUNCH((wide_pm_kernel<20, 2, 4, 0>), grid, dim3(256), 0, s, P);
+  dim3 grid;
+  grid8((int64_t)ncg * ks, grid, false);
+  sdf_dispatch(SdfList<10, 20>{}, T, [&](auto t) { SDF_LAUNCH((wide_pm_kernel<t, 2, 4, 0>), grid, dim3(256), 0, s, P); });
   WideReduceParams R = {};
   R.partial = P.partial; R.ksplit = ks; R.N = d.N; R.HW = (int)hw; R.P = P.P;
   R.alpha = d.alpha; R.beta = d.beta; R.resid = d.resid; R.out = d.out; R.out_spike = d.sn_T > 0 ? d.out_spike : nullptr;
-  R.sn = {d.sn_kind, d.tau, d.v_th, d.v_reset, d.soft_reset, nullptr, nullptr};
+  R.sn = gemm_neuron(d, false);
   R.inv_tau = d.sn_T > 0 ? inv_tau_of(R.sn) : 0.f;
   const int64_t nthr = R.P * (d.N / 4);
   const dim3 rgrid((unsigned)((nthr + 255) / 256));
-  const int nk = d.sn_T > 0 ? neuron_class(R.sn) : 0;
-  if (T == 10) { if (nk == 0) SDF_LAUNCH((wide_reduce_kernel<10, 0>), rgrid, dim3(256), 0, s, R); else SDF_LAUNCH((wide_reduce_kernel<10, 2>), rgrid, dim3(256), 0, s, R); }
-  else { if (nk == 0) SDF_LAUNCH((wide_reduce_kernel<20, 0>), rgrid, dim3(256), 0, s, R); else SDF_LAUNCH((wide_reduce_kernel<20, 2>), rgrid, dim3(256), 0, s, R); }
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  // (class 1 cannot come: the neuron is read without its PSN pointers)
+  sdf_dispatch(SdfList<10, 20>{}, T, [&](auto t) {
+    sdf_dispatch(SdfList<0, 2>{}, d.sn_T > 0 && neuron_class(R.sn) != 0 ? 2 : 0, [&](auto n) {
+      SDF_LAUNCH((wide_reduce_kernel<t, n>), rgrid, dim3(256), 0, s, R);
+    });
+  });
+  return sdf_launch_rc();
 }
 
 }  // namespace sdfmm

@@ -287,7 +287,7 @@ extern "C" int sdf_neuron_fwd(const SdfNeuronDesc* dp, void* stream) {
   const NeuronParams P = neuron_params(*dp);
   dim3 grid((unsigned)sdf_quad_blocks(P.quads * 4)), block(256);
   hipStream_t s = sdf_stream(stream);
-  if (!sdf_for_T(SDF_T_STREAM, dp->T, [&](auto tt) { SDF_LAUNCH(neuron_kernel<tt>, grid, block, 0, s, P); })) {
+  if (!sdf_dispatch(SDF_T_STREAM, dp->T, [&](auto tt) { SDF_LAUNCH(neuron_kernel<tt>, grid, block, 0, s, P); })) {
     if (dp->kind == SDF_PSN) return SDF_E_SHAPE;
     SDF_LAUNCH(neuron_kernel<0>, grid, block, 0, s, P);            // any other T: the runtime-T kernel
   }
@@ -300,7 +300,7 @@ extern "C" int sdf_neuron_multi_fwd(const SdfNeuronDesc* descs, int n, void* str
   if (n < 1) return SDF_E_SHAPE;
   if (n == 1) return sdf_neuron_fwd(descs, stream);
   const int T = descs[0].T;
-  bool one = n <= MULTI_MAX && sdf_T_in(SDF_T_GLIF, T);
+  bool one = n <= MULTI_MAX && sdf_in(SDF_T_GLIF, T);
   for (int i = 0; i < n; ++i) {
     const int rc = validate(descs[i]);
     if (rc) return rc;
@@ -325,7 +325,7 @@ extern "C" int sdf_neuron_multi_fwd(const SdfNeuronDesc* descs, int n, void* str
   for (int i = n; i <= MULTI_MAX; ++i) M.first[i] = (int)wgs;
   dim3 grid((unsigned)wgs), block(256);
   hipStream_t s = sdf_stream(stream);
-  sdf_for_T(SDF_T_GLIF, T, [&](auto tt) { SDF_LAUNCH(neuron_multi_kernel<tt>, grid, block, 0, s, M); });   // `one`: T is in the list
+  sdf_dispatch(SDF_T_GLIF, T, [&](auto tt) { SDF_LAUNCH(neuron_multi_kernel<tt>, grid, block, 0, s, M); });   // `one`: T is in the list
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -342,7 +342,7 @@ extern "C" int sdf_lif_fwd(const float* x, void* spike, float* v_last, int T, in
 
 extern "C" int sdf_psn_fwd(const float* x, const float* W, const float* b, void* spike, int T, int64_t N,
                            int spike_dtype, void* stream) {
-  if (N % 4 || !sdf_T_in(SDF_T_STREAM, T))
+  if (N % 4 || !sdf_in(SDF_T_STREAM, T))
     return launch_scalar(x, spike, nullptr, T, N, SDF_PSN, 2.f, 0.f, 1, 0.f, spike_dtype, W, b, stream);
   SdfNeuronDesc d = {};
   d.x = x; d.out = spike; d.T = T; d.out_dtype = spike_dtype;
@@ -394,7 +394,7 @@ extern "C" int sdf_plif_fwd(const float* x, const float* plif_k, float* spike, i
   if (soft_reset) v_reset = 0.f;
   dim3 grid((unsigned)sdf_quad_blocks(N)), block(256);
   hipStream_t s = sdf_stream(stream);
-  if (!sdf_for_T(SDF_T_STREAM, T, [&](auto tt) {
+  if (!sdf_dispatch(SDF_T_STREAM, T, [&](auto tt) {
         SDF_LAUNCH(plif_fwd_kernel<tt>, grid, block, 0, s, x, plif_k, spike, N, v_th, soft_reset, v_reset);
       }))
     return SDF_E_SHAPE;

@@ -253,7 +253,7 @@ int lif_bwd_launch(BwdParams& P, const float* x, const float* grad_spike, float*
   P.inv_tau = PLIF ? 0.f : sdf_inv_tau(P.kind, P.tau);
   sdf_atan_consts(alpha, P.c_atan, P.half_alpha);
   dim3 grid((unsigned)sdf_quad_blocks(N)), block(256);
-  if (!sdf_for_T(SDF_T_STREAM, T, [&](auto tt) { SDF_LAUNCH((lif_bwd_kernel<tt, PLIF>), grid, block, 0, s, P); })) return SDF_E_SHAPE;
+  if (!sdf_dispatch(SDF_T_STREAM, T, [&](auto tt) { SDF_LAUNCH((lif_bwd_kernel<tt, PLIF>), grid, block, 0, s, P); })) return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   return 0;
 }
@@ -279,7 +279,7 @@ extern "C" int sdf_sltt_bwd(const float* x, const float* grad_spike, float* grad
   if (!x || !grad_spike || !grad_x) return SDF_E_NULL;
   if (N < 4 || N % 4 || !(tau > 1.f)) return SDF_E_SHAPE;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_SHAPE;        // ATan is the only surrogate built
-  if (!sdf_T_in(SDF_T_STREAM, T)) return SDF_E_SHAPE;
+  if (!sdf_in(SDF_T_STREAM, T)) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16)) return SDF_E_ALIGN;
   BwdParams P = {};
   P.kind = SDF_LIF; P.tau = tau; P.detach = 1; P.sltt = 1;
@@ -310,7 +310,7 @@ extern "C" int sdf_psn_bwd(const float* x, const float* W, const float* b, const
   const int nblk = psn_blocks(T, N, reduce);
   dim3 grid((unsigned)nblk), block(256);
   hipStream_t s = sdf_stream(stream);
-  if (!sdf_for_T(SDF_T_STREAM, T, [&](auto tt) {
+  if (!sdf_dispatch(SDF_T_STREAM, T, [&](auto tt) {
         constexpr int V = psn_reduce_vec(tt);
         if constexpr (V != 0) {
           if (reduce) {
@@ -341,7 +341,7 @@ extern "C" int sdf_plif_bwd(const float* x, const float* plif_k, const float* gr
   if (!x || !plif_k || !grad_spike || !grad_x || !grad_k || !workspace) return SDF_E_NULL;
   if (N < 4 || N % 4) return SDF_E_SHAPE;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_DTYPE;
-  if (!sdf_T_in(SDF_T_STREAM, T)) return SDF_E_SHAPE;
+  if (!sdf_in(SDF_T_STREAM, T)) return SDF_E_SHAPE;
   if (workspace_bytes < sdf_plif_bwd_workspace_bytes(T, N)) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(grad_spike, 16) || !sdf_aligned(grad_x, 16) || !sdf_aligned(plif_k, 4) ||
       !sdf_aligned(grad_k, 4) || !sdf_aligned(workspace, 4))

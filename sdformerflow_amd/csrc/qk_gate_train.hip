@@ -199,7 +199,7 @@ int64_t gate_blocks(int64_t rows, int C) { return (rows * (C / 32) * 8 + 255) / 
 template <bool BWD, bool PLIF = false>
 int launch(const GateTrainParams& P, int Tq, hipStream_t s) {
   dim3 grid((unsigned)gate_blocks(P.rows, P.C)), block(256);
-  if (!sdf_for_T(SDF_T_GATE, Tq, [&](auto tt) { SDF_LAUNCH((qk_gate_train_kernel<tt, BWD, PLIF>), grid, block, 0, s, P); }))
+  if (!sdf_dispatch(SDF_T_GATE, Tq, [&](auto tt) { SDF_LAUNCH((qk_gate_train_kernel<tt, BWD, PLIF>), grid, block, 0, s, P); }))
     return SDF_E_SHAPE;
   SDF_LAUNCH_CHECK();
   return 0;
@@ -275,7 +275,7 @@ extern "C" int sdf_qk_gate_plif_bwd(const float* q, const float* k, const float*
                                     float alpha, void* stream) {
   if (!q || !k || !grad_e || !grad_q || !grad_k || !plif_k || !grad_plif_k || !workspace) return SDF_E_NULL;
   if (surrogate != SDF_SURROGATE_ATAN) return SDF_E_DTYPE;
-  if (!sdf_T_in(SDF_T_GATE, Tq)) return SDF_E_SHAPE;
+  if (!sdf_in(SDF_T_GATE, Tq)) return SDF_E_SHAPE;
   GateTrainParams P = {};
   const int rc = fill(P, rows, C, SDF_LIF, 2.f, v_th, soft_reset, v_reset);
   if (rc) return rc;

@@ -29,9 +29,7 @@
 // wave continues that sequence; weight rows 2K + 16 bytes (4 x odd dwords: the 16 lanes of a ds_read_b128 group hit 16
 // distinct bank quads).
 // Compiled with -ffp-contract=off (the neuron arithmetic is the separately-rounded op sequence of neuron.hip).
-#include "spike_mm.h"
-#include "device_prims.h"
-#include "switches.h"
+#include "digit_host.h"
 
 #ifdef SDF_STAMP
 // diagnostic build only (tools/stamp_wres.sh): cycle accounting of wave 0 of each group of workgroup 0
@@ -801,25 +799,27 @@ int launch_c(const GemmParams& P, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
-// true when the weight-resident kernel has an instantiation for this convolution and the launch is big enough to use it
-bool spike_conv_wres_supports(const GemmParams& P, bool any_size) {
+// true when the weight-resident kernel has an instantiation for this convolution and the launch is big enough to use it; the plan
+// then holds the tile height, the wave groups and the grid of the launch
+bool spike_conv_wres_plan(const GemmParams& P, bool any_size, ConvWresPlan& pl) {
   const SdfSpikeGemmDesc& d = P.d;
   const ConvGeom& c = P.cv;
+  const bool i8 = d.nsplit == SDF_PLANES_I8X3;
   // 96 channels at stride 1 (every form), or - digit planes only - 48 channels at stride 2 (the patch embedding's first 3x3: halo
   // tiles with the even / odd columns as two planes, GeoI8<.., S2>)
-  const bool s1 = c.Cin == 96 && c.sy == 1 && c.sx == 1 && c.H == c.OH && c.W == c.OW;
+  const bool s1 = c.Cin == 96 && conv_3x3_s1_p1(c, d.K);
   // (and 96 channels at stride 2 in two channel passes, fp32 epilogue only: the patch embedding's projection)
-  const bool s2 = (c.Cin == 48 || (c.Cin == 96 && d.sn_T == 0)) && c.sy == 2 && c.sx == 2 && c.OH == (c.H - 1) / 2 + 1 &&
-                  c.OW == (c.W - 1) / 2 + 1 && d.nsplit == SDF_PLANES_I8X3 && !(d.sn_T > 0 && d.resid);
-  if ((!s1 && !s2) || c.KWc != 3 || d.K != 9 * c.Cin) return false;
-  if (c.dy[0] != -1 || c.dy[1] != 0 || c.dy[2] != 1 || c.dx[0] != -1 || c.dx[1] != 0 || c.dx[2] != 1) return false;
-  if (d.N % NB || (d.nsplit != 1 && d.nsplit != 2 && d.nsplit != SDF_PLANES_I8X3) || d.out_rowmap || d.add || d.zg_nH > 0) return false;
-  if (d.nsplit == SDF_PLANES_I8X3 && (!d.col_scale || d.bias)) return false;
-  if (d.sn_T != 0 && d.sn_T != 10 && !(d.nsplit == SDF_PLANES_I8X3 && (d.sn_T == 5 || d.sn_T == 20))) return false;
+  const bool s2 = (c.Cin == 48 || (c.Cin == 96 && d.sn_T == 0)) && conv_taps_3x3_p1(c, d.K) && c.sy == 2 && c.sx == 2 &&
+                  c.OH == (c.H - 1) / 2 + 1 && c.OW == (c.W - 1) / 2 + 1 && i8 && !(d.sn_T > 0 && d.resid);
+  if (!s1 && !s2) return false;
+  if (d.N % NB || (d.nsplit != 1 && d.nsplit != 2 && !i8) || d.out_rowmap || d.add || d.zg_nH > 0) return false;
+  if (i8 && (!d.col_scale || d.bias)) return false;
+  if (d.sn_T != 0 && d.sn_T != 10 && !(i8 && (d.sn_T == 5 || d.sn_T == 20))) return false;
   const int64_t imgs = d.M / ((int64_t)c.OH * c.OW);
+  const int T = d.sn_T > 0 ? d.sn_T : 1;
   if (d.sn_T > 0) {
     if (d.sn_kind == SDF_PSN || d.bias) return false;
-    if (d.nsplit != SDF_PLANES_I8X3 && !any_size) return false;     // 16-bit planes: the fused form measured slower than the streaming kernel
+    if (!i8 && !any_size) return false;     // 16-bit planes: the fused form measured slower than the streaming kernel
     // positions must enumerate whole images, time steps and outer blocks must be whole images apart
     const int64_t ohw = (int64_t)c.OH * c.OW;
     if (d.pos_inner % ohw || d.pos_ostride % ohw || d.t_stride % ohw || d.pos_count % ohw || d.t_stride == 0) return false;
@@ -828,56 +828,57 @@ bool spike_conv_wres_supports(const GemmParams& P, bool any_size) {
   if (d.ldo % 4 || (d.out && !sdf_aligned(d.out, 16)) || (d.resid && !sdf_aligned(d.resid, 16))) return false;
   const int64_t lim = (int64_t)1 << 31;
   if (imgs * c.H * c.W * c.Cin >= lim || d.M * d.ldo * 4 >= lim || d.M * d.N >= lim) return false;
-  const int64_t tiles = imgs * ((c.OH + TH - 1) / TH) * ((c.OW + TW - 1) / TW) / (d.sn_T > 0 ? d.sn_T : 1);
-  return any_size || tiles * (d.N / NB) >= 512;                                  // two rounds of the chip at least: below that the split-K paths win
-}
+  const int64_t tiles = imgs * ((c.OH + TH - 1) / TH) * ((c.OW + TW - 1) / TW) / T;
+  if (!any_size && tiles * (d.N / NB) < 512) return false;                       // two rounds of the chip at least: below that the split-K paths win
 
-int launch_spike_conv_wres(const GemmParams& Pin, hipStream_t s) {
-  GemmParams P = Pin;
-  const SdfSpikeGemmDesc& d = P.d;
-  const ConvGeom& c = P.cv;
-  const int64_t imgs = d.M / ((int64_t)c.OH * c.OW);
-  const int T = d.sn_T > 0 ? d.sn_T : 1;
   // digit-plane kernel: 16 x 16 pixel tiles (two row blocks per wave share every weight fragment) when that still leaves every
   // half workgroup several items, 8 x 16 otherwise (fused-neuron items are T steps long: few and coarse at batch 1)
-  int th = TH;
-  if (d.nsplit == SDF_PLANES_I8X3) {
+  pl.th = TH;
+  if (i8) {
     const int64_t items16 = (imgs / T) * ((c.OH + 15) / 16) * ((c.OW + TW - 1) / TW) * (d.N / NB);
     const char* erb = sdf_sw(SW_CONV_WRES_RB);                     // tuning override
-    th = (c.sy == 1 && (erb ? erb[0] == '2' : items16 >= 2048)) ? 16 : 8;
+    pl.th = (c.sy == 1 && (erb ? erb[0] == '2' : items16 >= 2048)) ? 16 : 8;
   }
-  P.tiles_m = (int)((imgs / T) * ((c.OH + th - 1) / th) * ((c.OW + TW - 1) / TW));   // fused: imgs / T = pos_count / (OH*OW) batch elements
-  P.tiles_n = d.N / NB;
-  P.ntiles = P.tiles_m * P.tiles_n;
-  P.ksplit = 1; P.spc = 0; P.partial = nullptr;
-  int G = P.ntiles < 256 ? P.ntiles : 256;
-  int rc;
-  if (d.nsplit == SDF_PLANES_I8X3) {
-    if (c.Cin != 96 && c.Cin != 48) return SDF_E_SHAPE;
-    {
-      // a workgroup's wave groups take its items in turn: give every workgroup a whole number of items per group and size the
-      // grid for equal rounds (648 fused items, 3 groups: 216 workgroups x 3 items instead of 256 of which 120 leave a group
-      // idle) - same duration, and the compute units this launch does not need go to the other in-flight forwards' kernels
-      const char* eg0 = sdf_sw(SW_CONV_WRES_GROUPS);
-      const int ng = (d.sn_T > 0 && th == 8 && (eg0 ? eg0[0] == '3' : true)) ? 3 : 2;
-      const int rounds = (P.ntiles + 256 * ng - 1) / (256 * ng), per = ng * rounds;
-      if (P.ntiles >= 64) G = (P.ntiles + per - 1) / per;
-      // column blocks of a tile range side by side on one XCD (see the kernel): the grid becomes a multiple of 8 * tiles_n, or of
-      // tiles_n with every workgroup's share still `per` items
-      const bool cbi = [] { const char* e = sdf_sw(SW_CONV_WRES_CB_INNER); return !e || e[0] != '0'; }();
-      if (cbi && P.ntiles >= 64) {
-        int nr = (P.tiles_m + per - 1) / per;                           // tile ranges of at most `per` items ...
-        while (nr * P.tiles_n <= 256 && (nr * P.tiles_n) % 8) ++nr;     // ... a few more of them where that makes the grid a multiple of 8
-        const int g2 = nr * P.tiles_n;                                  // (the kernel splits tiles_m evenly over the ranges)
-        if (g2 <= 256 && g2 % 8 == 0) { G = g2; P.cb_inner = 1; }
-      }
-    }
+  pl.tiles_m = (int)((imgs / T) * ((c.OH + pl.th - 1) / pl.th) * ((c.OW + TW - 1) / TW));   // fused: imgs / T = pos_count / (OH*OW) batch elements
+  pl.tiles_n = d.N / NB;
+  const int ntiles = pl.tiles_m * pl.tiles_n;
+  pl.grid = ntiles < 256 ? ntiles : 256;
+  pl.groups = 2;
+  pl.cb_inner = 0;
+  if (i8) {
     // fused-neuron items are T steps long and their epilogue (neuron + two stores) outweighs their MFMAs: with few of them
     // (batch 1: 648 on this shape) THREE groups of waves per workgroup - 768 slots, one item each, the matrix pipe shared
     // three ways - instead of two groups with one or two items each
     const char* eg = sdf_sw(SW_CONV_WRES_GROUPS);                   // tuning override: 2 or 3
-    const bool g3 = d.sn_T > 0 && th == 8 && (eg ? eg[0] == '3' : true);
-    const dim3 grid((unsigned)G);
+    pl.groups = (d.sn_T > 0 && pl.th == 8 && (eg ? eg[0] == '3' : true)) ? 3 : 2;
+    // a workgroup's wave groups take its items in turn: give every workgroup a whole number of items per group and size the
+    // grid for equal rounds (648 fused items, 3 groups: 216 workgroups x 3 items instead of 256 of which 120 leave a group
+    // idle) - same duration, and the compute units this launch does not need go to the other in-flight forwards' kernels
+    const int rounds = (ntiles + 256 * pl.groups - 1) / (256 * pl.groups), per = pl.groups * rounds;
+    if (ntiles >= 64) pl.grid = (ntiles + per - 1) / per;
+    // column blocks of a tile range side by side on one XCD (see the kernel): the grid becomes a multiple of 8 * tiles_n, or of
+    // tiles_n with every workgroup's share still `per` items
+    const char* ecb = sdf_sw(SW_CONV_WRES_CB_INNER);
+    if ((!ecb || ecb[0] != '0') && ntiles >= 64) {
+      int nr = (pl.tiles_m + per - 1) / per;                          // tile ranges of at most `per` items ...
+      while (nr * pl.tiles_n <= 256 && (nr * pl.tiles_n) % 8) ++nr;   // ... a few more of them where that makes the grid a multiple of 8
+      const int g2 = nr * pl.tiles_n;                                 // (the kernel splits tiles_m evenly over the ranges)
+      if (g2 <= 256 && g2 % 8 == 0) { pl.grid = g2; pl.cb_inner = 1; }
+    }
+  }
+  return true;
+}
+
+int launch_spike_conv_wres(const GemmParams& Pin, const ConvWresPlan& pl, hipStream_t s) {
+  GemmParams P = Pin;
+  const SdfSpikeGemmDesc& d = P.d;
+  const ConvGeom& c = P.cv;
+  P.tiles_m = pl.tiles_m; P.tiles_n = pl.tiles_n; P.ntiles = pl.tiles_m * pl.tiles_n; P.cb_inner = pl.cb_inner;
+  P.ksplit = 1; P.spc = 0; P.partial = nullptr;
+  const dim3 grid((unsigned)pl.grid);
+  if (d.nsplit == SDF_PLANES_I8X3) {
+    if (c.Cin != 96 && c.Cin != 48) return SDF_E_SHAPE;
+    const bool g3 = pl.groups == 3, th16 = pl.th == 16;
     if (c.sy == 2 && c.Cin == 96) {
       SDF_LAUNCH((spike_conv_wres_i8_kernel<0, 3, 1, 2, true, 2>), grid, dim3(512), 0, s, P, d.col_scale);
     } else if (c.Cin == 48) {
@@ -885,22 +886,20 @@ int launch_spike_conv_wres(const GemmParams& Pin, hipStream_t s) {
       else if (g3) SDF_LAUNCH((spike_conv_wres_i8_kernel<10, 3, 1, 3, true>), grid, dim3(768), 0, s, P, d.col_scale);
       else SDF_LAUNCH((spike_conv_wres_i8_kernel<10, 3, 1, 2, true>), grid, dim3(512), 0, s, P, d.col_scale);
     } else
-    if (d.sn_T == 0 && th == 16) SDF_LAUNCH((spike_conv_wres_i8_kernel<0, 6, 2, 2>), grid, dim3(512), 0, s, P, d.col_scale);
+    if (d.sn_T == 0 && th16) SDF_LAUNCH((spike_conv_wres_i8_kernel<0, 6, 2, 2>), grid, dim3(512), 0, s, P, d.col_scale);
     else if (d.sn_T == 0) SDF_LAUNCH((spike_conv_wres_i8_kernel<0, 6, 1, 2>), grid, dim3(512), 0, s, P, d.col_scale);
-    else if (th == 16) SDF_LAUNCH((spike_conv_wres_i8_kernel<10, 6, 2, 2>), grid, dim3(512), 0, s, P, d.col_scale);
+    else if (th16) SDF_LAUNCH((spike_conv_wres_i8_kernel<10, 6, 2, 2>), grid, dim3(512), 0, s, P, d.col_scale);
     else if (g3 && !d.out && !d.resid && !sdf_sw(SW_CONV_WRES_NOSPK))
       SDF_LAUNCH((spike_conv_wres_i8_kernel<10, 6, 1, 3, false, 1, true>), grid, dim3(768), 0, s, P, d.col_scale);
     else if (g3) SDF_LAUNCH((spike_conv_wres_i8_kernel<10, 6, 1, 3>), grid, dim3(768), 0, s, P, d.col_scale);
     else SDF_LAUNCH((spike_conv_wres_i8_kernel<10, 6, 1, 2>), grid, dim3(512), 0, s, P, d.col_scale);
-    rc = 0;
-  } else {
-    const dim3 grid((unsigned)G);
-    if (d.sn_T == 0) rc = d.nsplit == 1 ? launch_c<1, 0>(P, grid, s) : launch_c<2, 0>(P, grid, s);
-    else rc = d.nsplit == 1 ? launch_c<1, 10>(P, grid, s) : launch_c<2, 10>(P, grid, s);
+    return sdf_launch_rc();
   }
-  if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  int rc = SDF_E_SHAPE;                                              // 16-bit planes: 96 channels, T = 10
+  sdf_dispatch(SdfList<0, 10>{}, d.sn_T, [&](auto t) {
+    sdf_dispatch(SdfList<1, 2>{}, d.nsplit, [&](auto ns) { rc = launch_c<ns, t>(P, grid, s); });
+  });
+  return rc ? rc : sdf_launch_rc();
 }
 
 }  // namespace sdfmm

@@ -23,9 +23,7 @@
 //           t = slot % T), i.e. the recurrence runs in registers straight out of the MFMA accumulators and the
 //           fp32 pre-activation never touches HBM.  Spikes are staged through LDS to leave as 16-byte stores.
 // Compiled with -ffp-contract=off: the neuron arithmetic is the same separately-rounded op sequence as neuron.hip.
-#include "wide_common.h"
-#include "switches.h"
-#include <stdlib.h>
+#include "digit_host.h"
 
 namespace {
 using namespace sdfmm;
@@ -478,10 +476,7 @@ extern "C" int sdf_spike_gemm_fwd(const SdfSpikeGemmDesc* d, void* stream) {
     if (d->resid && d->resid != d->out) return SDF_E_SHAPE;
     if (d->M * (int64_t)d->K >= (1LL << 31) || d->M * (int64_t)d->ldo * 4 >= (1LL << 31) || (int64_t)d->N * d->K * 3 >= (1LL << 31)) return SDF_E_SHAPE;
     if (!sdf_aligned(d->A, 16) || !sdf_aligned(d->Wp, 16) || !sdf_aligned(d->out, 16)) return SDF_E_ALIGN;
-    WidePmParams P = {};
-    P.A = d->A; P.W = reinterpret_cast<const int8_t*>(d->Wp); P.cscale = d->col_scale; P.N = d->N; P.K = d->K;
-    P.HW = (int)(d->M / 10); P.P = d->M / 10;
-    P.bias = d->bias; P.alpha = d->alpha; P.beta = d->beta; P.x = d->out; P.ldo = (int)d->ldo; P.no_resid = d->resid ? 0 : 1;
+    WidePmParams P = pm_plain(d);
     P.res_stage = 1;
     if (!res_pm_takes(P, 10, 2)) return SDF_E_SHAPE;
     return launch_res_pm(P, 10, 2, sdf_stream(stream));
@@ -632,14 +627,32 @@ extern "C" int sdf_spike_deconv3x3s2_fwd(const SdfSpikeDeconvDesc* d, void* stre
   // other shapes: the row-loop kernel's form of the same product (ms_res.hip, AM = 3)
   if (spike_deconv_wres_supports(d->imgs, d->H, d->W, d->Cin, d->Cout))
     return launch_spike_deconv_wres(d->spikes, d->digits, d->cscale, d->alpha, d->beta, d->out, d->imgs, d->H, d->W, d->Cout, sdf_stream(stream));
-  WidePmParams P = {};
-  P.A = d->spikes; P.W = d->digits; P.cscale = d->cscale; P.N = 4 * d->Cout; P.K = 4 * d->Cin;
-  P.HW = d->H * d->W; P.P = (int64_t)(d->imgs / d->T) * P.HW;
-  P.alpha = d->alpha; P.beta = d->beta; P.x = d->out; P.ldo = d->Cout; P.no_resid = 1;
-  P.cv_H = d->H; P.cv_W = d->W; P.cv_Cin = d->Cin; P.dc_cout = d->Cout;
+  WidePmParams P = pm_deconv2x2(d);
   P.res_stage = 1;
   if (!res_pm_takes(P, d->T, 2)) return SDF_E_SHAPE;
   return launch_res_pm(P, d->T, 2, sdf_stream(stream));
+}
+
+// Which kernel family a validated convolution runs on, with the family's plan: sdf_spike_conv2d_fwd launches what this says, and
+// sdf_spike_conv2d_multi_fwd asks it whether a member would take the ping-pong kernel.
+enum ConvRoute { CONV_WIDE, CONV_SMALLM, CONV_WRES, CONV_PP, CONV_REST };      // (CONV_REST: image chunks of the ping-pong kernel, or nothing)
+struct ConvPlan {
+  WideConvPlan wide;
+  SmallmConvPlan smallm;
+  ConvWresPlan wres;
+};
+static ConvRoute conv2d_route(const GemmParams& P, bool i8x3, bool tiled, ConvPlan& pl) {
+  // few rows against many weights (the U-Net bottleneck's res-blocks) with digit planes: one launch, K split over the waves of a
+  // workgroup (csrc/ms_smallm.hip); SDF_WIDE_CONV=1 selects the split-K-over-workgroups form it replaced (csrc/ms_wide.hip, A/B)
+  if (i8x3 && wide_conv_plan(P, pl.wide)) return CONV_WIDE;
+  if (i8x3 && smallm_conv_plan(P, pl.smallm)) return CONV_SMALLM;
+  if (tiled) return CONV_REST;
+  // 3x3 / stride 1 on 96 channels with enough tiles to fill the chip: weights resident in LDS, halo tiles instead of im2col
+  const char* ewr = sdf_sw(SW_CONV_WRES);                  // A/B override: 0 = always the streaming kernels below, 2 = at any size
+  if (!(ewr && ewr[0] == '0') && spike_conv_wres_plan(P, i8x3 || (ewr && ewr[0] == '2'), pl.wres)) return CONV_WRES;
+  if (i8x3) return CONV_REST;                                   // digit planes have no streaming-kernel form: the caller packs per shape
+  // 256 x 96 tiles, producer waves do the im2col addressing; the ping-pong kernel overlaps epilogues with the MFMAs
+  return spike_mm_pp_supports(P, true) ? CONV_PP : CONV_REST;
 }
 
 extern "C" int sdf_spike_conv2d_fwd(const SdfSpikeConvDesc* c, void* stream) {
@@ -651,17 +664,15 @@ extern "C" int sdf_spike_conv2d_fwd(const SdfSpikeConvDesc* c, void* stream) {
   }
   const SdfSpikeGemmDesc* d = &c->g;
   const bool spike = d->sn_T > 0;
-  // few rows against many weights (the U-Net bottleneck's res-blocks) with digit planes: one launch, K split over the waves of a
-  // workgroup (csrc/ms_smallm.hip); SDF_WIDE_CONV=1 selects the split-K-over-workgroups form it replaced (csrc/ms_wide.hip, A/B)
-  if (i8x3 && wide_conv_supports(P)) return launch_wide_conv(P, sdf_stream(stream));
-  if (i8x3 && smallm_conv_supports(P)) return launch_smallm_conv(P, sdf_stream(stream));
-  if (tiled) return SDF_E_SHAPE;
-  // 3x3 / stride 1 on 96 channels with enough tiles to fill the chip: weights resident in LDS, halo tiles instead of im2col
-  const char* ewr = sdf_sw(SW_CONV_WRES);                  // A/B override: 0 = always the streaming kernels below, 2 = at any size
-  if (!(ewr && ewr[0] == '0') && spike_conv_wres_supports(P, i8x3 || (ewr && ewr[0] == '2'))) return launch_spike_conv_wres(P, sdf_stream(stream));
-  if (i8x3) return SDF_E_SHAPE;                                 // digit planes have no streaming-kernel form: the caller packs per shape
-  // 256 x 96 tiles, producer waves do the im2col addressing; the ping-pong kernel overlaps epilogues with the MFMAs
-  if (spike_mm_pp_supports(P, true)) return launch_spike_mm_pp(P, true, sdf_stream(stream));
+  ConvPlan pl;
+  switch (conv2d_route(P, i8x3, tiled, pl)) {
+    case CONV_WIDE: return launch_wide_conv(P, pl.wide, sdf_stream(stream));
+    case CONV_SMALLM: return launch_smallm_conv(P, pl.smallm, sdf_stream(stream));
+    case CONV_WRES: return launch_spike_conv_wres(P, pl.wres, sdf_stream(stream));
+    case CONV_PP: return launch_spike_mm_pp(P, true, sdf_stream(stream));
+    case CONV_REST: break;
+  }
+  if (i8x3) return SDF_E_SHAPE;
   // operands beyond the kernel's 31-bit buffer offsets (e.g. 80 images of 240 x 320 x 96 fp32 out): images are
   // independent, so the fp32 epilogue form is launched in image chunks that fit
   const int64_t imgs = d->M / ((int64_t)c->OH * c->OW);
@@ -704,9 +715,8 @@ extern "C" int sdf_spike_conv2d_multi_fwd(const SdfSpikeConvDesc* cs, int n, voi
       bool i8x3 = false, tiled = false;
       const int rc = conv2d_build(cs + i, Ps[i], i8x3, tiled);
       if (rc) return rc;
-      const char* ewr = sdf_sw(SW_CONV_WRES);
-      const bool wres = !(ewr && ewr[0] == '0') && spike_conv_wres_supports(Ps[i], i8x3 || (ewr && ewr[0] == '2'));
-      one = one && !i8x3 && cs[i].g.sn_T == 0 && !wres && spike_mm_pp_supports(Ps[i], true);
+      ConvPlan pl;
+      one = one && cs[i].g.sn_T == 0 && conv2d_route(Ps[i], i8x3, tiled, pl) == CONV_PP;
     }
     if (one) {
       const int rc = launch_spike_mm_pp_multi(Ps, n, sdf_stream(stream));

@@ -255,10 +255,17 @@ int launch_spike_mm_pp_multi(const GemmParams* Ps, int n, hipStream_t s);
 // ping-pong kernel (spike_mm_pp.hip): same tiles, consumer groups alternate tiles so epilogues overlap the MFMAs
 bool spike_mm_pp_supports(const GemmParams& P, bool conv);
 int launch_spike_mm_pp(const GemmParams& P, bool conv, hipStream_t s);
+// The convolution families below answer "is this mine" by filling a plan; the launch takes the plan and derives nothing again.
 // weight-resident 3x3 / stride-1 spike convolution (spike_conv_wres.hip): one 32-column block's weights stay in LDS, the
-// activations enter as halo tiles (no im2col); `supports` is false for shapes it has no instantiation for
-bool spike_conv_wres_supports(const GemmParams& P, bool any_size);
-int launch_spike_conv_wres(const GemmParams& P, hipStream_t s);
+// activations enter as halo tiles (no im2col); false for shapes it has no instantiation for or - unless any_size - too few tiles
+struct ConvWresPlan {
+  int th;                     // tile height in pixels: 8, or 16 (two row blocks per wave)
+  int groups;                 // wave groups per workgroup: 2 (512 threads) or 3 (768)
+  int tiles_m, tiles_n, grid;
+  int cb_inner;               // GemmParams::cb_inner
+};
+bool spike_conv_wres_plan(const GemmParams& P, bool any_size, ConvWresPlan& pl);
+int launch_spike_conv_wres(const GemmParams& P, const ConvWresPlan& pl, hipStream_t s);
 // MS MLP as one launch (ms_mlp_fused.hip); keep_s1 / keep_s2: optional u8 copies of the SN1 / SN2 spikes (parity tape)
 bool ms_mlp_fused_supports(const SdfMsMlpDesc* d);
 int launch_ms_mlp_fused(const SdfMsMlpDesc* d, uint8_t* keep_s1, uint8_t* keep_s2, hipStream_t s);
@@ -268,8 +275,11 @@ int launch_ms_wide_mlp(const SdfMsMlpDesc* d, const uint8_t* s1, bool s1_tiled, 
 bool ms_wide_attn_supports(const SdfQkAttnDesc* d);
 int launch_ms_wide_front(const SdfQkAttnDesc* d, const uint8_t* xs, uint8_t* e, uint8_t* qk, bool keep, hipStream_t s);
 int launch_ms_wide_proj(const SdfQkAttnDesc* d, const uint8_t* e, hipStream_t s);
-bool smallm_conv_supports(const GemmParams& P);          // ms_smallm.hip: few rows against many weights, K split inside the workgroup
-int launch_smallm_conv(const GemmParams& P, hipStream_t s);
+struct SmallmConvPlan {                                   // ms_smallm.hip: few rows against many weights, K split inside the workgroup
+  int T, cb;                                              // time steps of a position; column blocks of a tile (2, or 3 by SDF_SMALLM_CB)
+};
+bool smallm_conv_plan(const GemmParams& P, SmallmConvPlan& pl);
+int launch_smallm_conv(const GemmParams& P, const SmallmConvPlan& pl, hipStream_t s);
 bool smallm_fc2_supports(const SdfMsMlpDesc* d);          // the wide-stage MLP's second product on the small-M kernel
 int launch_smallm_fc2(const SdfMsMlpDesc* d, const uint8_t* s2, hipStream_t s);
 bool smallm_gemm_supports(const GemmParams& P);          // plain rows, fp32 epilogue (the decoders' stacked-tap product)
@@ -277,8 +287,11 @@ int launch_smallm_gemm(const GemmParams& P, hipStream_t s);
 bool wide_merge_supports(const SdfMsMergeDesc* d);
 int launch_wide_merge(const SdfMsMergeDesc* d, hipStream_t s);
 // 3x3 / stride 1 convolution of few rows against many weights on the wide-stage main loop (split-K + one reduce / BN / neuron pass)
-bool wide_conv_supports(const GemmParams& P);
-int launch_wide_conv(const GemmParams& P, hipStream_t s);
+struct WideConvPlan {
+  int T, ks;                                              // time steps of a position; K ranges (split-K over workgroups)
+};
+bool wide_conv_plan(const GemmParams& P, WideConvPlan& pl);
+int launch_wide_conv(const GemmParams& P, const WideConvPlan& pl, hipStream_t s);
 // split-K planning (fills ksplit / spc / partial from the descriptor's workspace) and the k-ordered second pass
 void plan_splitk(GemmParams& P, int kc);
 int launch_splitk_reduce(const GemmParams& P, hipStream_t s);

@@ -32,8 +32,8 @@
 #include "spike_mm.h"
 #include "device_prims.h"
 #include "switches.h"
+#include "host_launch.h"
 #include <stdlib.h>
-#include <type_traits>
 
 #ifdef SDF_STAMP
 // diagnostic build only (tools/stamp_conv.sh): per-role cycle accounting of workgroup 0
@@ -635,21 +635,6 @@ __global__ __launch_bounds__(768) void spike_mm_pp_multi_kernel(GemmMulti M) {
   spike_mm_pp_body<NSPLIT, 0, true>(P, (int)blockIdx.x - f0, f1 - f0);
 }
 
-template <int NSPLIT, bool CONV>
-int launch_t(const GemmParams& P, dim3 grid, hipStream_t s) {
-  switch (P.d.sn_T) {
-    case 0: SDF_LAUNCH((spike_mm_pp_kernel<NSPLIT, 0, CONV>), grid, dim3(768), 0, s, P); return 0;
-    case 2:
-      if constexpr (!CONV) { SDF_LAUNCH((spike_mm_pp_kernel<NSPLIT, 2, CONV>), grid, dim3(768), 0, s, P); return 0; }
-      return SDF_E_SHAPE;
-    case 10: SDF_LAUNCH((spike_mm_pp_kernel<NSPLIT, 10, CONV>), grid, dim3(768), 0, s, P); return 0;
-    case 20:                                                       // one position per lane half (20 of its 32 accumulator slots)
-      if constexpr (!CONV && NSPLIT == 2) { SDF_LAUNCH((spike_mm_pp_kernel<NSPLIT, 20, CONV>), grid, dim3(768), 0, s, P); return 0; }
-      return SDF_E_SHAPE;
-    default: return SDF_E_SHAPE;
-  }
-}
-
 }  // namespace
 
 // true when the ping-pong kernel has an instantiation for this problem (the caller refuses the shape otherwise)
@@ -709,14 +694,21 @@ int launch_spike_mm_pp(const GemmParams& Pin, bool conv, hipStream_t s) {
   const int G = pp_plan(P);
   if (G < 0) return G;
   dim3 grid((unsigned)G);
-  int rc;
-  if (conv)
-    rc = d.nsplit == 1 ? launch_t<1, true>(P, grid, s) : (d.nsplit == 2 ? launch_t<2, true>(P, grid, s) : launch_t<3, true>(P, grid, s));
-  else
-    rc = d.nsplit == 1 ? launch_t<1, false>(P, grid, s) : (d.nsplit == 2 ? launch_t<2, false>(P, grid, s) : launch_t<3, false>(P, grid, s));
-  if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  // built: T = 2 for the plain product only; T = 20 - one position per lane half, 20 of its 32 accumulator slots - for the plain product
+  // on two planes only
+  bool found = false;
+  sdf_dispatch(SdfList<1, 0>{}, conv, [&](auto cv) {
+    sdf_dispatch(SdfList<1, 2, 3>{}, d.nsplit, [&](auto ns) {
+      sdf_dispatch(SdfList<0, 2, 10, 20>{}, d.sn_T, [&](auto t) {
+        if constexpr ((t != 2 || cv == 0) && (t != 20 || (cv == 0 && ns == 2))) {
+          SDF_LAUNCH((spike_mm_pp_kernel<ns, t, cv != 0>), grid, dim3(768), 0, s, P);
+          found = true;
+        }
+      });
+    });
+  });
+  if (!found) return SDF_E_SHAPE;
+  if (int rc = sdf_launch_rc()) return rc;
   return launch_splitk_reduce(P, s);
 }
 
@@ -757,14 +749,9 @@ int launch_spike_mm_pp_multi(const GemmParams* Ps, int n, hipStream_t s) {
   for (int i = n; i < PP_MULTI_MAX; ++i) { M.Wp[i] = M.Wp[0]; M.rowmap[i] = M.rowmap[0]; M.K[i] = M.K[0]; M.spc[i] = M.spc[0]; M.KWc[i] = M.KWc[0];
                                             M.kw_mul[i] = M.kw_mul[0]; M.acc_scale[i] = M.acc_scale[0]; }
   const dim3 grid((unsigned)wgs);
-  switch (M.base.d.nsplit) {
-    case 1: SDF_LAUNCH((spike_mm_pp_multi_kernel<1>), grid, dim3(768), 0, s, M); break;
-    case 2: SDF_LAUNCH((spike_mm_pp_multi_kernel<2>), grid, dim3(768), 0, s, M); break;
-    case 3: SDF_LAUNCH((spike_mm_pp_multi_kernel<3>), grid, dim3(768), 0, s, M); break;
-    default: return SDF_E_SHAPE;
-  }
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  if (!sdf_dispatch(SdfList<1, 2, 3>{}, M.base.d.nsplit, [&](auto ns) { SDF_LAUNCH((spike_mm_pp_multi_kernel<ns>), grid, dim3(768), 0, s, M); }))
+    return SDF_E_SHAPE;
+  return sdf_launch_rc();
 }
 
 }  // namespace sdfmm

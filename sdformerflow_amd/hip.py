@@ -726,7 +726,7 @@ def split_weight_i8x3(W):
 
 
 def conv_wres_applicable(imgs, H, W, Cin, Cout, stride, T=1):
-    """Mirror of the library's dispatch rule (csrc/spike_conv_wres.hip: spike_conv_wres_supports): 3x3 on 96 input channels at
+    """Mirror of the library's dispatch rule (csrc/spike_conv_wres.hip: spike_conv_wres_plan): 3x3 on 96 input channels at
     stride 1 or - digit planes only - at stride 2 on 48 (the patch embedding's first 3x3) or 96 channels (its projection), output columns in blocks of 32, and enough
     8 x 16 pixel OUTPUT tiles (x T steps each when the neuron is fused) to give every half workgroup of the chip work - below that
     the streaming kernels' split-K wins.  H, W: the input image."""
@@ -742,7 +742,7 @@ def conv_wres_applicable(imgs, H, W, Cin, Cout, stride, T=1):
 
 
 def wide_conv_applicable(imgs, H, W, Cin, Cout, stride, T):
-    """Mirror of the library's dispatch rule for the small-M digit convolution (csrc/ms_wide.hip: wide_conv_supports): 3x3 / stride 1
+    """Mirror of the library's dispatch rule for the small-M digit convolution (csrc/ms_wide.hip: wide_conv_plan): 3x3 / stride 1
     on Cin % 128 == 0 channels, at most 131 072 output rows (SDF_WIDE_MAXROWS) in (B, T, H, W) order with T in {10, 20}."""
     if sw("SDF_WIDE", "") == "0" or sw("SDF_WIDE_CONV", "") != "1" or stride != 1 or Cin % 128 or Cout % 32:
         return False                                             # (opt-in: measured no faster than the streaming kernel + split-K, docs/history/DESIGN_rounds1-5.md)
@@ -750,7 +750,7 @@ def wide_conv_applicable(imgs, H, W, Cin, Cout, stride, T):
 
 
 def smallm_conv_applicable(imgs, H, W, Cin, Cout, stride, T):
-    """Mirror of the library's dispatch rule for the small-M digit convolution (csrc/ms_smallm.hip: smallm_conv_supports): 3x3 / stride 1
+    """Mirror of the library's dispatch rule for the small-M digit convolution (csrc/ms_smallm.hip: smallm_conv_plan): 3x3 / stride 1
     on Cin % 64 == 0 channels, at most 32 000 output rows (SDF_SMALLM_CONV_ROWS; 5 120 until round 5) in (B, T, H, W) order with T in {10, 20}."""
     if sw("SDF_SMALLM", "") == "0" or stride != 1 or Cin % 64 or Cout % 32:
         return False

@@ -1,5 +1,5 @@
 """The stand-alone neuron entry points launch the instantiation their T names, on the grid their size needs (csrc/host_launch.h:
-sdf_for_T over the T lists, sdf_quad_blocks).  For every launching entry point and every T of its list, at N = 1028 - two workgroups,
+sdf_dispatch over the T lists, sdf_quad_blocks).  For every launching entry point and every T of its list, at N = 1028 - two workgroups,
 the second one ragged, the smallest size at which a wrong grid or a wrong instantiation shows (the gate: rows = 9, C = 96) - each
 call goes through the C ABI and
   * runs under hip.launch_log(): the recorded kernels carry exactly that T (and PLIF / U8 / the vector width) in their template

@@ -569,7 +569,7 @@ def test_wres8_stride2_fused(monkeypatch, H, W, N, wgs, kind, groups):
 
 @gpu
 def test_wres8_stride2_fused_with_residual_is_refused(monkeypatch):
-    """The stride-2 fused form has no shortcut (spike_conv_wres_supports), and digit planes have no streaming form: SDF_E_SHAPE."""
+    """The stride-2 fused form has no shortcut (spike_conv_wres_plan), and digit planes have no streaming form: SDF_E_SHAPE."""
     _route(monkeypatch)
     c = C.sn_case(5, 2, 17, 33, 48, 96, "i8", 2, "lif", "bt", resid=True)
     with pytest.raises(hip.SdfError) as e:
