@@ -230,7 +230,7 @@ extern "C" int sdf_dense_linear_fwd(const SdfDenseLinearDesc* d, void* stream) {
   LinearParams P;
   P.d = *d;
   P.tiles_n = d->N / BN;
-  const bool xcd = [] { const char* e = sdf_sw(SW_DENSE_LINEAR_XCD); return !e || e[0] != '0'; }();
+  const bool xcd = !sdf_sw_is(SW_DENSE_LINEAR_XCD, '0');
   P.xcd = xcd ? 1 : 0;
   const int64_t tiles = (int64_t)((d->M + BM - 1) / BM) * P.tiles_n;
   SDF_LAUNCH(dense_linear_kernel, dim3((unsigned)tiles), dim3(256), 0, sdf_stream(stream), P);

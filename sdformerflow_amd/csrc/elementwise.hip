@@ -3,6 +3,7 @@
 // (reference: SpikingNormLayer after a conv + the MS shortcut, Spiking_modules.py:922-926, 816-818).
 // HBM-bound: one 16-byte load per operand per lane, 16-byte store.
 #include "common.h"
+#include "host_launch.h"
 
 namespace {
 __global__ __launch_bounds__(256) void affine_resid_kernel(const float* __restrict__ x, const float* __restrict__ alpha,
@@ -144,21 +145,6 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const float* __restrict
   }
 }
 
-template <int L>
-int launch_layer_norm(const float* x, const float* g, const float* b, float* out, int64_t rows, int C, float eps, hipStream_t s) {
-  const int V = (C + 4 * L - 1) / (4 * L);
-  const dim3 grid((unsigned)((rows * L + 255) / 256));
-  switch (V) {
-    case 1: SDF_LAUNCH((layer_norm_kernel<L, 1>), grid, dim3(256), 0, s, x, g, b, out, rows, C, eps); break;
-    case 2: SDF_LAUNCH((layer_norm_kernel<L, 2>), grid, dim3(256), 0, s, x, g, b, out, rows, C, eps); break;
-    case 3: SDF_LAUNCH((layer_norm_kernel<L, 3>), grid, dim3(256), 0, s, x, g, b, out, rows, C, eps); break;
-    case 4: SDF_LAUNCH((layer_norm_kernel<L, 4>), grid, dim3(256), 0, s, x, g, b, out, rows, C, eps); break;
-    case 5: case 6: SDF_LAUNCH((layer_norm_kernel<L, 6>), grid, dim3(256), 0, s, x, g, b, out, rows, C, eps); break;
-    case 7: case 8: SDF_LAUNCH((layer_norm_kernel<L, 8>), grid, dim3(256), 0, s, x, g, b, out, rows, C, eps); break;
-    default: return SDF_E_SHAPE;
-  }
-  return 0;
-}
 }  // namespace
 
 extern "C" int sdf_layer_norm_fwd(const float* x, const float* gamma, const float* beta, float* out, int64_t rows, int C, float eps,
@@ -166,9 +152,16 @@ extern "C" int sdf_layer_norm_fwd(const float* x, const float* gamma, const floa
   if (!x || !gamma || !beta || !out) return SDF_E_NULL;
   if (rows <= 0 || C <= 0 || C % 4 || C > 2048) return SDF_E_SHAPE;
   if (!sdf_aligned(x, 16) || !sdf_aligned(out, 16) || !sdf_aligned(gamma, 16) || !sdf_aligned(beta, 16)) return SDF_E_ALIGN;
-  const int rc = C <= 512 ? launch_layer_norm<16>(x, gamma, beta, out, rows, C, eps, sdf_stream(stream))
-                          : launch_layer_norm<64>(x, gamma, beta, out, rows, C, eps, sdf_stream(stream));
-  if (rc) return rc;
-  SDF_LAUNCH_CHECK();
-  return 0;
+  const int L = C <= 512 ? 16 : 64;                                     // lanes per row
+  int V = (C + 4 * L - 1) / (4 * L);                                    // float4 per lane: 1 - 4, 6, 8 are built
+  V += V == 5 || V == 7;
+  const dim3 grid((unsigned)((rows * L + 255) / 256));
+  hipStream_t s = sdf_stream(stream);
+  bool built = false;
+  sdf_dispatch(SdfList<16, 64>{}, L, [&](auto l) {
+    built = sdf_dispatch(SdfList<1, 2, 3, 4, 6, 8>{}, V, [&](auto v) {
+      SDF_LAUNCH((layer_norm_kernel<l, v>), grid, dim3(256), 0, s, x, gamma, beta, out, rows, C, eps);
+    });
+  });
+  return built ? sdf_launch_rc() : SDF_E_SHAPE;
 }

@@ -13,6 +13,7 @@
 // Compiled with -ffp-contract=off (the neuron arithmetic is the separately-rounded op sequence of neuron.hip).
 #include "spike_mm.h"
 #include "switches.h"
+#include "host_launch.h"
 #include <stdlib.h>
 
 namespace {
@@ -422,37 +423,44 @@ __global__ __launch_bounds__(256) void deconv_col2im_kernel(const float* __restr
   *reinterpret_cast<float4*>(out + pix * Cout + c4) = acc;
 }
 
-template <int T>
-int launch_head_mfma(const HeadParams& P, hipStream_t s) {
+// What the head is built for: T, and the (Cin, Cout) pairs as one value each.  Both kernels take every pair
+// (head_conv_sn_kernel's <Cout / 16, Cin> follows from it); the PSN form of the matrix-pipe kernel takes the first two.
+// head_shape packs a pair into one SdfList value, Cin * 256 + Cout, unpacked as sh / 256 and sh % 256: both members of a listed pair
+// are below 256, and a descriptor's value outside [0, 256) packs to -1, so no other pair equals a listed one by accident.
+constexpr int head_shape(int cin, int cout) { return cin >= 0 && cin < 256 && cout >= 0 && cout < 256 ? cin * 256 + cout : -1; }
+constexpr SdfList<5, 10, 20> HEAD_T{};
+constexpr SdfList<head_shape(2, 48), head_shape(2, 32), head_shape(2, 64), head_shape(4, 48)> HEAD_SHAPES{};
+constexpr SdfList<head_shape(2, 48), head_shape(2, 32)> HEAD_SHAPES_PSN{};
+
+// mfma: the matrix-pipe kernels over 32-pixel tiles (its PSN form where that has a kernel: the entry point asks first); else the
+// 16-pixel kernel on `grid`
+int launch_head(const HeadParams& P, bool mfma, dim3 grid, hipStream_t s) {
   const int tiles = P.d.B * P.d.H * (P.d.W / 32);
   const int want = (tiles + 3) / 4;
-  dim3 grid((unsigned)(want < 768 ? want : 768));                  // three workgroups per CU are resident; the rest of the tiles loop
-  if (P.d.sn_kind == SDF_PSN) {
-    if constexpr (T <= 10) {
-      if (P.d.Cin == 2 && P.d.Cout == 48) { SDF_LAUNCH((head_conv_mfma_psn_kernel<T, 2, 48>), grid, dim3(256), 0, s, P, tiles); return 0; }
-      if (P.d.Cin == 2 && P.d.Cout == 32) { SDF_LAUNCH((head_conv_mfma_psn_kernel<T, 2, 32>), grid, dim3(256), 0, s, P, tiles); return 0; }
-    }
-    return SDF_E_SHAPE;
-  }
+  const dim3 mgrid((unsigned)(want < 768 ? want : 768));           // three workgroups per CU are resident; the rest of the tiles loop
+  const bool psn = P.d.sn_kind == SDF_PSN;
   const bool fast = P.d.sn_kind == SDF_LIF && P.d.soft_reset != 0 && P.inv_tau != 0.f;
-#define SDF_HEAD_CASE(CI, CO)                                                                                              \
-  if (P.d.Cin == CI && P.d.Cout == CO) {                                                                                   \
-    if (fast) SDF_LAUNCH((head_conv_mfma_kernel<T, CI, CO, true>), grid, dim3(256), 0, s, P, tiles);               \
-    else SDF_LAUNCH((head_conv_mfma_kernel<T, CI, CO, false>), grid, dim3(256), 0, s, P, tiles);                   \
-    return 0;                                                                                                              \
-  }
-  SDF_HEAD_CASE(2, 48) SDF_HEAD_CASE(2, 32) SDF_HEAD_CASE(2, 64) SDF_HEAD_CASE(4, 48)
-#undef SDF_HEAD_CASE
-  return SDF_E_SHAPE;
-}
-
-template <int T>
-int launch_head(const HeadParams& P, dim3 grid, hipStream_t s) {
-  if (P.d.Cin == 2 && P.d.Cout == 48) { SDF_LAUNCH((head_conv_sn_kernel<T, 3, 2>), grid, dim3(256), 0, s, P); return 0; }
-  if (P.d.Cin == 2 && P.d.Cout == 32) { SDF_LAUNCH((head_conv_sn_kernel<T, 2, 2>), grid, dim3(256), 0, s, P); return 0; }
-  if (P.d.Cin == 2 && P.d.Cout == 64) { SDF_LAUNCH((head_conv_sn_kernel<T, 4, 2>), grid, dim3(256), 0, s, P); return 0; }
-  if (P.d.Cin == 4 && P.d.Cout == 48) { SDF_LAUNCH((head_conv_sn_kernel<T, 3, 4>), grid, dim3(256), 0, s, P); return 0; }
-  return SDF_E_SHAPE;
+  int rc = SDF_E_SHAPE;
+  sdf_dispatch(HEAD_T, P.d.T, [&](auto t) {
+    sdf_dispatch(HEAD_SHAPES, head_shape(P.d.Cin, P.d.Cout), [&](auto sh) {
+      constexpr int CI = sh / 256, CO = sh % 256;
+      if (!mfma) {
+        SDF_LAUNCH((head_conv_sn_kernel<t, CO / 16, CI>), grid, dim3(256), 0, s, P);
+        rc = 0;
+      } else if (psn) {
+        if constexpr (sdf_class_has_T(1, t) && sdf_in(HEAD_SHAPES_PSN, sh)) {
+          SDF_LAUNCH((head_conv_mfma_psn_kernel<t, CI, CO>), mgrid, dim3(256), 0, s, P, tiles);
+          rc = 0;
+        }
+      } else {
+        sdf_dispatch(SdfList<1, 0>{}, fast, [&](auto f) {
+          SDF_LAUNCH((head_conv_mfma_kernel<t, CI, CO, f != 0>), mgrid, dim3(256), 0, s, P, tiles);
+          rc = 0;
+        });
+      }
+    });
+  });
+  return rc ? rc : sdf_launch_rc();
 }
 }  // namespace
 
@@ -460,9 +468,7 @@ extern "C" int sdf_head_conv_sn_fwd(const SdfHeadConvDesc* d, void* stream) {
   if (!d || !d->x || !d->w || !d->out) return SDF_E_NULL;
   if (d->B < 1 || d->H < 1 || d->W < 1 || d->W % 16) return SDF_E_SHAPE;      // whole 16-pixel tiles (16-byte spike stores)
   if (d->alpha && !d->beta) return SDF_E_NULL;
-  if (d->sn_kind != SDF_LIF && d->sn_kind != SDF_PSN && d->sn_kind != SDF_IF) return SDF_E_DTYPE;
-  if (d->sn_kind == SDF_PSN && (!d->psn_w || !d->psn_b)) return SDF_E_NULL;
-  if (!sdf_tau_ok(d->sn_kind, d->tau)) return SDF_E_SHAPE;
+  if (const int rc = sdf_neuron_cfg_rc(d->sn_kind, d->tau, d->psn_w, d->psn_b)) return rc;
   if (!sdf_aligned(d->out, 16)) return SDF_E_ALIGN;
   HeadParams P;
   P.d = *d;
@@ -477,37 +483,16 @@ extern "C" int sdf_head_conv_sn_fwd(const SdfHeadConvDesc* d, void* stream) {
     for (int ci = 0; ci < 4; ++ci) P.d.x_sc[ci] = ci;
   }
   // fp32 matrix-pipe kernel: LIF / IF, 32-pixel tiles, 31-bit byte offsets into the voxel
-  const char* e_hm = sdf_sw(SW_HEAD_MFMA);                        // (read per call)
-  const bool no_mfma = e_hm && e_hm[0] == '0';
+  const bool no_mfma = sdf_sw_is(SW_HEAD_MFMA, '0');                // (read per call)
   int64_t span = (int64_t)(d->B - 1) * P.d.x_sb + (int64_t)(d->T - 1) * P.d.x_st + (int64_t)(d->H - 1) * P.d.x_sy + (int64_t)(d->W - 1) * P.d.x_sx;
   int64_t scmax = 0;
   for (int ci = 0; ci < d->Cin && ci < 4; ++ci) scmax = P.d.x_sc[ci] > scmax ? P.d.x_sc[ci] : scmax;
-  const bool psn_mfma = d->sn_kind == SDF_PSN && d->T <= 10 && d->Cin == 2 && (d->Cout == 48 || d->Cout == 32);
+  const bool psn_mfma = d->sn_kind == SDF_PSN && sdf_class_has_T(1, d->T) && sdf_in(HEAD_SHAPES_PSN, head_shape(d->Cin, d->Cout));
   const bool mfma_ok = !no_mfma && (d->sn_kind != SDF_PSN || psn_mfma) && d->W % 32 == 0 && (span + scmax + 1) * 4 < (1LL << 31) && d->Cin <= 4 &&
                        (int64_t)d->B * d->T * d->H * d->W * d->Cout < (1LL << 31) &&
                        P.d.x_sb >= 0 && P.d.x_st >= 0 && P.d.x_sy >= 0 && P.d.x_sx >= 0;
-  int rc;
-  if (mfma_ok) {
-    switch (d->T) {
-      case 5: rc = launch_head_mfma<5>(P, s); break;
-      case 10: rc = launch_head_mfma<10>(P, s); break;
-      case 20: rc = launch_head_mfma<20>(P, s); break;
-      default: rc = SDF_E_SHAPE;
-    }
-    if (rc) return rc;
-    SDF_LAUNCH_CHECK();
-    return 0;
-  }
-  P.d = *d;
-  switch (d->T) {
-    case 5: rc = launch_head<5>(P, grid, s); break;
-    case 10: rc = launch_head<10>(P, grid, s); break;
-    case 20: rc = launch_head<20>(P, grid, s); break;
-    default: rc = SDF_E_SHAPE;
-  }
-  if (rc) return rc;
-  SDF_LAUNCH_CHECK();
-  return 0;
+  if (!mfma_ok) P.d = *d;                                               // (the 16-pixel kernel reads the descriptor as the caller gave it)
+  return launch_head(P, mfma_ok, grid, s);
 }
 
 extern "C" int sdf_flow_out_fwd(const float* pred, float* out, int B, int D, int h, int w, int64_t ldp, int C, int H, int W,

@@ -27,6 +27,7 @@
 // Compiled with -ffp-contract=off: neuron arithmetic is the separately-rounded op sequence of neuron.hip.
 #include "spike_mm.h"
 #include "switches.h"
+#include "host_launch.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -443,51 +444,35 @@ __global__ __launch_bounds__(64 * RG * CG * TEAMS, (MlpGeo<NSPLIT, T, C16, CG, N
 #endif
 }
 
-template <int NSPLIT, int T, int C16, int CG, int NB1, int RG, int TEAMS>
-int launch_one(const MlpFusedParams& P, hipStream_t s) {
-  using G = MlpGeo<NSPLIT, T, C16, CG, NB1, RG, TEAMS>;
-  if (P.Ch % G::CH) return SDF_E_SHAPE;
-  const int64_t items = (P.P + G::PPI - 1) / G::PPI, wgs = (items + TEAMS - 1) / TEAMS;
-  if (wgs >= (1LL << 31)) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)wgs), block(G::NTW);
-  const bool keep = P.keep_s1 != nullptr;                             // the parity tape: both spike tensors also go to memory
-#define SDF_MLP_LAUNCH(NK)                                                                                              \
-  if (keep) SDF_LAUNCH((ms_mlp_fused_kernel<NSPLIT, T, C16, CG, NB1, RG, TEAMS, NK, true>), grid, block, 0, s, P);     \
-  else SDF_LAUNCH((ms_mlp_fused_kernel<NSPLIT, T, C16, CG, NB1, RG, TEAMS, NK, false>), grid, block, 0, s, P);
-  switch (neuron_class(P.sn1)) {
-    case 0: SDF_MLP_LAUNCH(0) break;
-    case 1:
-      if constexpr (T <= 10) { SDF_MLP_LAUNCH(1) break; }               // PSN: T x T coefficients in scalar registers
-      return SDF_E_SHAPE;
-    default: SDF_MLP_LAUNCH(2) break;
-  }
-#undef SDF_MLP_LAUNCH
-  return 0;
-}
-
-template <int NSPLIT, int T>
-int launch_c(const MlpFusedParams& P, int C, hipStream_t s) {
-  switch (C) {
-    // C = 96: 2 teams x (2 row groups x 3 column groups) = 12 waves, 3 per SIMD; C = 192: 2 teams x 4 column groups = 8 waves.
-    // Three bf16 planes (the exact mode) need more LDS for the weight chunk: one team (of 4 row groups at C = 96)
-    case 96: return launch_one<NSPLIT, T, 6, 3, 2, NSPLIT == 3 ? 4 : 2, NSPLIT == 3 ? 1 : 2>(P, s);
-    case 192: return launch_one<NSPLIT, T, 12, 4, 1, 1, 1>(P, s);
-    default: return SDF_E_SHAPE;
-  }
-}
-
-// two fp16 planes (the default): T in {5, 10, 20}; one / three bf16 planes (bench.py --planes 1 / 3): the shipped T = 10
+// The instantiations: two fp16 planes (the default) at T in {5, 10, 20}; one / three bf16 planes (bench.py --planes 1 / 3) at the
+// shipped T = 10.  C = 96: 2 teams x (2 row groups x 3 column groups) = 12 waves, 3 per SIMD; C = 192: 2 teams x 4 column groups = 8
+// waves.  Three bf16 planes (the exact mode) need more LDS for the weight chunk: one team (of 4 row groups at C = 96).
 int launch_t(const MlpFusedParams& P, int nsplit, int T, int C, hipStream_t s) {
-  if (nsplit == 2) {
-    switch (T) {
-      case 5: return launch_c<2, 5>(P, C, s);
-      case 10: return launch_c<2, 10>(P, C, s);
-      case 20: return launch_c<2, 20>(P, C, s);
-      default: return SDF_E_SHAPE;
-    }
-  }
-  if (T != 10) return SDF_E_SHAPE;
-  return nsplit == 1 ? launch_c<1, 10>(P, C, s) : launch_c<3, 10>(P, C, s);
+  const bool keep = P.keep_s1 != nullptr;                             // the parity tape: both spike tensors also go to memory
+  int rc = SDF_E_SHAPE;
+  sdf_dispatch(SdfList<2, 1, 3>{}, nsplit, [&](auto ns) {
+    sdf_dispatch(SdfList<5, 10, 20>{}, T, [&](auto t) {
+      if constexpr (ns == 2 || t == 10) {
+        sdf_dispatch(SdfList<96, 192>{}, C, [&](auto c) {
+          constexpr int C16 = c / 16, CG = c == 96 ? 3 : 4, NB1 = c == 96 ? 2 : 1;
+          constexpr int RG = c == 96 ? (ns == 3 ? 4 : 2) : 1, TEAMS = c == 96 && ns != 3 ? 2 : 1;
+          using G = MlpGeo<ns, t, C16, CG, NB1, RG, TEAMS>;
+          const int64_t items = (P.P + G::PPI - 1) / G::PPI, wgs = (items + TEAMS - 1) / TEAMS;
+          if (P.Ch % G::CH || wgs >= (1LL << 31)) return;
+          const dim3 grid((unsigned)wgs), block(G::NTW);
+          sdf_dispatch(SDF_NEURON_CLASSES, neuron_class(P.sn1), [&](auto nk) {
+            if constexpr (sdf_class_has_T(nk, t)) {                   // (PSN: T x T coefficients in scalar registers)
+              sdf_dispatch(SdfList<1, 0>{}, keep, [&](auto kp) {
+                SDF_LAUNCH((ms_mlp_fused_kernel<ns, t, C16, CG, NB1, RG, TEAMS, nk, kp != 0>), grid, block, 0, s, P);
+                rc = 0;
+              });
+            }
+          });
+        });
+      }
+    });
+  });
+  return rc ? rc : sdf_launch_rc();
 }
 
 #ifndef SDF_STAMP
@@ -501,12 +486,8 @@ bool ms_mlp_fused_supports(const SdfMsMlpDesc* d) {
   if (d->Ch % 192 || d->nsplit < 1 || d->nsplit > 3) return false;
   if (d->nsplit != 2 && d->D != 10) return false;
   if (neuron_class(d->sn1) != neuron_class(d->sn2)) return false;
-  if (neuron_class(d->sn1) == 1 && d->D > 10) return false;           // PSN over T = 20: 400 coefficients do not fit the scalar registers
-  for (const SdfNeuronCfg* n : {&d->sn1, &d->sn2}) {
-    if (n->kind != SDF_LIF && n->kind != SDF_IF && n->kind != SDF_PSN) return false;
-    if (n->kind == SDF_PSN && (!n->psn_w || !n->psn_b)) return false;
-    if (!sdf_tau_ok(n->kind, n->tau)) return false;
-  }
+  if (!sdf_class_has_T(neuron_class(d->sn1), d->D)) return false;     // PSN over T = 20: 400 coefficients do not fit the scalar registers
+  if (sdf_neuron_cfg_rc(d->sn1) != 0 || sdf_neuron_cfg_rc(d->sn2) != 0) return false;
   // C = 192 (stage 1): a work item streams 1.2 MB of weights for 8 positions; with few positions (batch 1 at 288 x 384: 1 728) the
   // three-launch form is as fast (measured 65 us both), from a few thousand on the one-launch form wins (config 5: -30 %)
   if (d->C == 192 && (int64_t)d->B * d->HW < 4096 && !sdf_sw(SW_MLP_FUSED_ANY)) return false;
@@ -526,10 +507,7 @@ int launch_ms_mlp_fused(const SdfMsMlpDesc* d, uint8_t* keep_s1, uint8_t* keep_s
   P.sn1 = d->sn1; P.sn2 = d->sn2;
   P.inv_tau1 = inv_tau_of(d->sn1); P.inv_tau2 = inv_tau_of(d->sn2);
   P.keep_s1 = keep_s1; P.keep_s2 = keep_s2;
-  const int rc = launch_t(P, d->nsplit, d->D, d->C, s);
-  if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  return launch_t(P, d->nsplit, d->D, d->C, s);
 }
 
 }  // namespace sdfmm

@@ -590,8 +590,7 @@ __global__ __launch_bounds__(64 * NWV) void res_front_kernel(WideFrontParams P) 
 }
 
 bool res_env_off() {
-  const char* e = sdf_sw(SW_RES);                    // A/B: 0 = the kernels these replaced (ms_wide.hip / qk_front / ms_mlp_fused / spike_gemm)
-  return e && e[0] == '0';
+  return sdf_sw_is(SW_RES, '0');                     // A/B: 0 = the kernels these replaced (ms_wide.hip / qk_front / ms_mlp_fused / spike_gemm)
 }
 
 // dynamic LDS above 64 KB needs the attribute, once per kernel function (process-wide, read-only afterwards)
@@ -602,8 +601,7 @@ int res_raise(KernelT kern) {
 }
 
 bool res_strip(const WidePmParams& P) {
-  const char* e = sdf_sw(SW_RES_STRIP);              // A/B: 0 = fragment-shaped loads everywhere
-  if (e && e[0] == '0') return false;
+  if (sdf_sw_is(SW_RES_STRIP, '0')) return false;    // A/B: 0 = fragment-shaped loads everywhere
   return P.cv_Cin != 0 || (!P.a_tiled && !P.zsrc);
 }
 

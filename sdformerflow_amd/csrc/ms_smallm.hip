@@ -466,7 +466,7 @@ static int64_t smallm_conv_rows() {
 bool smallm_conv_plan(const GemmParams& P, SmallmConvPlan& pl) {
   const SdfSpikeGemmDesc& d = P.d;
   const ConvGeom& cv = P.cv;
-  if (const char* e = sdf_sw(SW_SMALLM)) { if (e[0] == '0') return false; }
+  if (sdf_sw_is(SW_SMALLM, '0')) return false;
   const bool bt = d.nsplit == SDF_PLANES_I8X3_TILED;
   if ((d.nsplit != SDF_PLANES_I8X3 && !bt) || !d.col_scale) return false;
   if (!conv_3x3_s1_p1(cv, d.K) || cv.Cin % 64) return false;
@@ -488,7 +488,7 @@ bool smallm_conv_plan(const GemmParams& P, SmallmConvPlan& pl) {
   // 336 workgroups onto 168: with three forwards in flight the headline measured +0.9 % with the narrow tile (three alternating pairs
   // of runs on one box: 687.8 / 683.5 / 685.7 against 680.7 / 677.2 / 679.6 samples/s).  SDF_SMALLM_CB=3 selects the wide tile.
   pl.cb = 2;
-  if (const char* e = sdf_sw(SW_SMALLM_CB)) { if (bt && e[0] == '3' && d.N % 48 == 0) pl.cb = 3; }      // tuning override
+  if (bt && sdf_sw_is(SW_SMALLM_CB, '3') && d.N % 48 == 0) pl.cb = 3;      // tuning override
   return sdf_aligned(d.A, 16) && sdf_aligned(d.Wp, 16) && (!d.out || sdf_aligned(d.out, 16)) && (!d.resid || sdf_aligned(d.resid, 16)) &&
          (!d.out_spike || sdf_aligned(d.out_spike, 16)) && (!d.out || d.ldo == d.N);
 }
@@ -524,16 +524,15 @@ int launch_smallm_conv(const GemmParams& G, const SmallmConvPlan& pl, hipStream_
 // 20.1 -> 24.0 us at stage 2 (4 320 x 384 x 1 536: 648 tiles of 6 steps per wave - two rounds of mostly prologue and reduction), so the
 // form is taken while the tiles fit the chip in one round (<= 512).
 bool smallm_fc2_supports(const SdfMsMlpDesc* d) {
-  if (const char* e = sdf_sw(SW_SMALLM)) { if (e[0] == '0') return false; }
-  if (const char* e = sdf_sw(SW_SMALLM_FC2)) { if (e[0] == '0') return false; }
+  if (sdf_sw_is(SW_SMALLM, '0')) return false;
+  if (sdf_sw_is(SW_SMALLM_FC2, '0')) return false;
   if (!d->fc2_tiled || !d->fc2_cscale || (d->D != 10 && d->D != 20) || d->Ch % 64 || d->C % 32) return false;
   const int64_t tokens = (int64_t)d->B * d->D * d->HW;
   if (tokens > SMALLM_MAX_ROWS || tokens * d->Ch >= (1LL << 31) || tokens * d->C * 4 >= (1LL << 31) || (int64_t)d->C * d->Ch * 3 >= (1LL << 31)) return false;
   if (d->emit_next && !smallm_neuron_ok(d->emit_sn)) return false;
   {
     const int64_t units = pm_units((int64_t)d->B * d->HW, d->D);
-    const char* e = sdf_sw(SW_SMALLM_FC2);
-    if (units * (d->C / 32) > 512 && !(e && e[0] == '2')) return false;       // (SDF_SMALLM_FC2=2: at any size, tests / A/B)
+    if (units * (d->C / 32) > 512 && !sdf_sw_is(SW_SMALLM_FC2, '2')) return false;       // (SDF_SMALLM_FC2=2: at any size, tests / A/B)
   }
   return sdf_aligned(d->fc2_tiled, 16) && sdf_aligned(d->x, 16) && (!d->emit_next || sdf_aligned(d->emit_next, 16));
 }
@@ -557,7 +556,7 @@ int launch_smallm_fc2(const SdfMsMlpDesc* d, const uint8_t* s2, hipStream_t s) {
 // decoder (reference Spiking_modules.py:461-474 as one GEMM, 1 080 rows x 3 456 columns x K = 1 536) and anything else of that shape
 bool smallm_gemm_supports(const GemmParams& P) {
   const SdfSpikeGemmDesc& d = P.d;
-  if (const char* e = sdf_sw(SW_SMALLM)) { if (e[0] == '0') return false; }
+  if (sdf_sw_is(SW_SMALLM, '0')) return false;
   if (d.nsplit != SDF_PLANES_I8X3_TILED || !d.col_scale || d.sn_T > 0 || !d.out) return false;
   if (d.K % 64 || d.K < 64 || d.N % 32 || d.lda != d.K || d.out_rowmap || d.add || d.zg_nH) return false;
   if (d.M % 10 || d.M > smallm_conv_rows()) return false;         // (rows are walked as 10 "steps" x M / 10 "positions": any order serves the fp32 form;
@@ -573,7 +572,7 @@ int launch_smallm_gemm(const GemmParams& G, hipStream_t s) {
   P.alpha = d.alpha; P.beta = d.beta; P.bias = d.bias; P.resid = d.resid; P.out = d.out; P.ldo = (int)d.ldo;
   P.nunits = (int)pm_units(P.P, 10);
   int cb = 2;                                                     // (as the convolution: the narrow tile packs two workgroups per compute unit)
-  if (const char* e = sdf_sw(SW_SMALLM_CB)) { if (e[0] == '3' && d.N % 48 == 0) cb = 3; else if (e[0] == '2') cb = 2; }   // tuning override
+  if (sdf_sw_is(SW_SMALLM_CB, '3') && d.N % 48 == 0) cb = 3;   // tuning override
   P.ncg = d.N / (16 * cb);
   dim3 grid;
   if (int rc = grid8((int64_t)P.ncg * P.nunits, grid)) return rc;

@@ -789,12 +789,10 @@ static int64_t wide_max_rows() {                      // (SDF_WIDE_MAXROWS: tuni
 }
 #define WIDE_MAX_ROWS wide_max_rows()
 bool wide_env_any() {
-  const char* e = sdf_sw(SW_WIDE);
-  return e && e[0] == '2';
+  return sdf_sw_is(SW_WIDE, '2');
 }
 bool wide_env_off() {
-  const char* e = sdf_sw(SW_WIDE);
-  return e && e[0] == '0';
+  return sdf_sw_is(SW_WIDE, '0');
 }
 // narrow stages (C <= 192: swin stages 0 - 1): the weight-resident row-loop kernels of ms_res.hip (SDF_RES=0: off - A/B)
 // Which stages take them is a measured choice, and the measure is CHIP TIME, not latency: bench.py keeps three forwards in flight, so a
@@ -813,8 +811,7 @@ int res_maxc() {                                         // (SDF_RES_MAXC: tunin
   return 768;
 }
 bool res_stage_ok(int C, bool merge = false) {
-  const char* e = sdf_sw(SW_RES);
-  if ((e && e[0] == '0') || C < 64 || C % 32) return false;
+  if (sdf_sw_is(SW_RES, '0') || C < 64 || C % 32) return false;
   // (the merge of a 192-channel stage, K = 768: 24.6 us on 88 compute units against 16.1 us on 168 with the K-ring kernel - slower alone,
   //  less chip time with three forwards in flight; K = 4 C <= 1024 is what the resident image admits)
   if (merge) return C <= 256;
@@ -977,10 +974,7 @@ bool wide_conv_plan(const GemmParams& P, WideConvPlan& pl) {
   // problem, against 50 + 5 us of the streaming ping-pong kernel with its split-K - no gain (four row passes per workgroup each pay
   // the pipeline fill; the reduce pass is latency-bound on 81 workgroups), so the engine does not take it: SDF_WIDE_CONV=1 opts in
   // (tests, A/B).
-  {
-    const char* e = sdf_sw(SW_WIDE_CONV);
-    if (!(e && e[0] == '1')) return false;
-  }
+  if (!sdf_sw_is(SW_WIDE_CONV, '1')) return false;
   if (d.nsplit != SDF_PLANES_I8X3 || !d.col_scale) return false;
   if (!conv_3x3_s1_p1(cv, d.K) || cv.Cin % KCH) return false;
   if (d.N % 32 || d.out_rowmap || d.bias || d.add || d.zg_nH) return false;

@@ -13,6 +13,7 @@
 // accumulates its part of the two dot products; a butterfly over the group's lanes finishes them.
 // Compiled with -ffp-contract=off (neuron arithmetic = the separately-rounded op sequence of neuron.hip).
 #include "spike_mm.h"
+#include "host_launch.h"
 
 namespace {
 using sdfmm::neuron_T;
@@ -148,41 +149,9 @@ __global__ __launch_bounds__(256) void pred_head_kernel(PredParams P) {
   }
 }
 
-template <int T, int LPP>
-int launch_nk(const PredParams& P, int nk, dim3 grid, hipStream_t s) {
-  switch (nk) {
-    case 0: SDF_LAUNCH((pred_head_kernel<T, LPP, 0>), grid, dim3(256), 0, s, P); return 0;
-    case 1:
-      if constexpr (T <= 10) { SDF_LAUNCH((pred_head_kernel<T, LPP, 1>), grid, dim3(256), 0, s, P); return 0; }
-      return SDF_E_SHAPE;
-    default: SDF_LAUNCH((pred_head_kernel<T, LPP, 2>), grid, dim3(256), 0, s, P); return 0;
-  }
-}
-
-template <int T>
-int launch_lpp(const PredParams& P, int nk, hipStream_t s) {
-  const int lpp = P.d.Cin / 12;
-  const int64_t per_wg = 4 * (64 / lpp), wgs = (P.P + per_wg - 1) / per_wg;
-  if (wgs >= (1LL << 31)) return SDF_E_SHAPE;
-  const dim3 grid((unsigned)wgs);
-  switch (lpp) {
-    case 8: return launch_nk<T, 8>(P, nk, grid, s);
-    case 16: return launch_nk<T, 16>(P, nk, grid, s);
-    case 32: return launch_nk<T, 32>(P, nk, grid, s);
-    default: return SDF_E_SHAPE;
-  }
-}
-
 bool same_neuron(const SdfNeuronCfg& a, const SdfNeuronCfg& b) {
   return a.kind == b.kind && a.tau == b.tau && a.v_th == b.v_th && a.v_reset == b.v_reset && a.soft_reset == b.soft_reset &&
          a.psn_w == b.psn_w && a.psn_b == b.psn_b;
-}
-
-int check_neuron(const SdfNeuronCfg& n) {
-  if (n.kind != SDF_LIF && n.kind != SDF_PSN && n.kind != SDF_IF) return SDF_E_DTYPE;
-  if (n.kind == SDF_PSN && (!n.psn_w || !n.psn_b)) return SDF_E_NULL;
-  if (!sdf_tau_ok(n.kind, n.tau)) return SDF_E_SHAPE;
-  return 0;
 }
 }  // namespace
 
@@ -193,13 +162,13 @@ extern "C" int sdf_pred_head_fwd(const SdfPredHeadDesc* d, void* stream) {
   if (d->B < 1 || d->h < 1 || d->w < 1) return SDF_E_SHAPE;
   if (d->Cin != 96 && d->Cin != 192 && d->Cin != 384) return SDF_E_SHAPE;          // 12 channels per lane, 8 / 16 / 32 lanes per position
   if (d->D != 5 && d->D != 10 && d->D != 20) return SDF_E_SHAPE;
-  int rc = check_neuron(d->sn_pred);
+  int rc = sdf_neuron_cfg_rc(d->sn_pred);
   if (rc) return rc;
   const int nk = sdfmm::neuron_class(d->sn_pred);
-  if (nk == 1 && d->D > 10) return SDF_E_SHAPE;
+  if (!sdf_class_has_T(nk, d->D)) return SDF_E_SHAPE;
   if (d->flow && (d->H < d->h || d->W < d->w || d->H % d->h || d->W % d->w)) return SDF_E_SHAPE;   // whole upsampling factors only
   if (d->next_spikes) {
-    rc = check_neuron(d->sn_next);
+    rc = sdf_neuron_cfg_rc(d->sn_next);
     if (rc) return rc;
     if (sdfmm::neuron_class(d->sn_next) != nk) return SDF_E_SHAPE;
     if (d->next_ld < 4 || d->next_ld % 4 || d->next_z_off % 4 || d->next_pred_off % 4 || d->next_zero_off % 4 || d->next_zero_len % 4 ||
@@ -218,12 +187,20 @@ extern "C" int sdf_pred_head_fwd(const SdfPredHeadDesc* d, void* stream) {
   P.P = (int64_t)d->B * d->h * d->w;
   P.same_next = d->next_spikes && same_neuron(d->sn_pred, d->sn_next);
   hipStream_t s = sdf_stream(stream);
-  switch (d->D) {
-    case 5: rc = launch_lpp<5>(P, nk, s); break;
-    case 10: rc = launch_lpp<10>(P, nk, s); break;
-    default: rc = launch_lpp<20>(P, nk, s); break;
-  }
-  if (rc) return rc;
-  SDF_LAUNCH_CHECK();
-  return 0;
+  const int lpp = d->Cin / 12;                                                      // lanes per position: 12 channels per lane
+  const int64_t per_wg = 4 * (64 / lpp), wgs = (P.P + per_wg - 1) / per_wg;
+  if (wgs >= (1LL << 31)) return SDF_E_SHAPE;
+  const dim3 grid((unsigned)wgs);
+  rc = SDF_E_SHAPE;
+  sdf_dispatch(SdfList<5, 10, 20>{}, d->D, [&](auto t) {
+    sdf_dispatch(SdfList<8, 16, 32>{}, lpp, [&](auto l) {
+      sdf_dispatch(SDF_NEURON_CLASSES, nk, [&](auto n) {
+        if constexpr (sdf_class_has_T(n, t)) {
+          SDF_LAUNCH((pred_head_kernel<t, l, n>), grid, dim3(256), 0, s, P);
+          rc = 0;
+        }
+      });
+    });
+  });
+  return rc ? rc : sdf_launch_rc();
 }

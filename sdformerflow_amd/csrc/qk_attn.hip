@@ -42,6 +42,64 @@ void fill_gemm_neuron(SdfSpikeGemmDesc& g, const SdfNeuronCfg& c, int T) {
   g.psn_w = c.psn_w; g.psn_b = c.psn_b;
 }
 
+// proj_sn over the T' frames of every window slice, gathered through the slice map (pad / roll / partition folded in), u8 into `out`
+SdfNeuronDesc slice_neuron(const SdfQkAttnDesc* d, uint8_t* out) {
+  const int64_t rows = d->B_ * d->N1;
+  SdfNeuronDesc n = {};
+  n.x = d->x; n.out = out; n.T = d->Tq; n.out_dtype = SDF_U8;
+  n.nb = 1; n.ni = rows * d->C; n.x_sb = 0; n.x_st = 0; n.o_sb = 0; n.o_st = rows * d->C;
+  n.rowmap = d->slice_map; n.rowlen = d->C;
+  fill_neuron(n, d->sn_proj);
+  return n;
+}
+
+// the MLP's sn1 over the D steps of every (b, hw, c), u8 into `s1`
+SdfNeuronDesc mlp_sn1(const SdfMsMlpDesc* d, uint8_t* s1) {
+  const int64_t hwc = d->HW * d->C;
+  SdfNeuronDesc n = {};
+  n.x = d->x; n.out = s1; n.T = d->D; n.out_dtype = SDF_U8;
+  n.nb = d->B; n.ni = hwc; n.x_sb = d->D * hwc; n.x_st = hwc; n.o_sb = d->D * hwc; n.o_st = hwc;
+  fill_neuron(n, d->sn1);
+  return n;
+}
+
+// Steps 1 - 3 of the attention as three (four with separate q / k weights) launches: xs = proj_sn(slices); q | k spikes into `qk`;
+// E over xs.  The form the one-launch first half (qk_front.hip) replaces where it has an instantiation.
+int qk_front_three_launches(const SdfQkAttnDesc* d, uint8_t* xs, uint8_t* qk, void* stream) {
+  const int C = d->C, Tq = d->Tq;
+  const int64_t rows = d->B_ * d->N1, M = rows * Tq;
+  // 1. proj_sn
+  const SdfNeuronDesc n = slice_neuron(d, xs);
+  int rc = sdf_neuron_fwd(&n, stream);
+  if (rc) return rc;
+  // 2. q = SN(BN(xs Wq^T)), k = SN(BN(xs Wk^T) + PE): the neuron runs in the GEMM epilogue, q / k never exist in fp32
+  auto qk_gemm = [&](const uint16_t* planes, float acc_scale, int N, const float* alpha, const float* beta, const float* add,
+                     const SdfNeuronCfg& sn, uint8_t* out) {
+    SdfSpikeGemmDesc g = {};
+    g.A = xs; g.Wp = planes; g.out_spike = out; g.M = M; g.N = N; g.K = C; g.lda = C; g.ldo = N; g.nsplit = d->nsplit;
+    g.acc_scale = acc_scale; g.alpha = alpha; g.beta = beta; g.add = add; g.add_prows = d->N1;
+    g.pos_count = rows; g.pos_inner = rows; g.pos_ostride = 0; g.t_stride = rows;
+    fill_gemm_neuron(g, sn, Tq);
+    return sdf_spike_gemm_fwd(&g, stream);
+  };
+  int64_t ldq, ldk;
+  const uint8_t *qp, *kp;
+  if (d->qk_planes) {
+    rc = qk_gemm(d->qk_planes, d->qk_acc_scale, 2 * C, d->qk_alpha, d->qk_beta, d->qk_add, d->sn_q, qk);
+    if (rc) return rc;
+    qp = qk; kp = qk + C; ldq = ldk = 2 * C;
+  } else {
+    rc = qk_gemm(d->q_planes, d->q_acc_scale, C, d->q_alpha, d->q_beta, nullptr, d->sn_q, qk);
+    if (rc) return rc;
+    rc = qk_gemm(d->k_planes, d->k_acc_scale, C, d->k_alpha, d->k_beta, d->k_add, d->sn_k, qk + M * C);
+    if (rc) return rc;
+    qp = qk; kp = qk + M * C; ldq = ldk = C;
+  }
+  // 3. token gate: A = sn2_q(sum over each head's 32 channels of q), E = k AND A  (E overwrites xs)
+  return sdf_qk_gate_strided_fwd(qp, kp, xs, Tq, rows, C, ldq, ldk, d->sn2_q.kind, d->sn2_q.tau, d->sn2_q.v_th, d->sn2_q.v_reset,
+                                 d->sn2_q.soft_reset, d->sn2_q.psn_w, d->sn2_q.psn_b, stream);
+}
+
 }  // namespace
 
 extern "C" int sdf_window_slice_map(int32_t* map, int B, int D, int H, int W, int Wd, int Wh, int Ww, int shift_d, int shift_h,
@@ -95,11 +153,7 @@ extern "C" int sdf_qk_attn_fwd(const SdfQkAttnDesc* d, void* stream) {
   if (sdfmm::ms_wide_attn_supports(d)) {
     uint8_t* e = xs;
     uint8_t* xsw = qk + (M * 2 * C + 255) / 256 * 256;
-    SdfNeuronDesc n = {};
-    n.x = d->x; n.out = xsw; n.T = Tq; n.out_dtype = SDF_U8;
-    n.nb = 1; n.ni = rows * C; n.x_sb = 0; n.x_st = 0; n.o_sb = 0; n.o_st = rows * C;
-    n.rowmap = d->slice_map; n.rowlen = C;
-    fill_neuron(n, d->sn_proj);
+    const SdfNeuronDesc n = slice_neuron(d, xsw);
     int rcw = sdf_neuron_fwd(&n, stream);
     if (rcw) return rcw;
     rcw = sdfmm::launch_ms_wide_front(d, xsw, e, qk, (d->flags & SDF_QK_KEEP_SPIKES) != 0, sdf_stream(stream));
@@ -108,57 +162,12 @@ extern "C" int sdf_qk_attn_fwd(const SdfQkAttnDesc* d, void* stream) {
   }
   if (d->emit_s1) return SDF_E_SHAPE;                           // only the wide-stage form emits the next neuron's spikes
 
-  // steps 1 - 3 as one launch where the kernel has an instantiation (SDF_QK_FRONT=0 / SDF_QK_FOUR_LAUNCHES: the A/B reference below)
-  bool front = false;
-  {
-    const char* e_front = sdf_sw(SW_QK_FRONT);                    // (read per call, like SDF_MLP_FUSED)
-    const bool off = e_front && e_front[0] == '0';
-    if (!off && !(d->flags & SDF_QK_FOUR_LAUNCHES) && sdfmm::qk_front_supports(d)) {
-      const int rc0 = sdfmm::launch_qk_front(d, xs, qk, (d->flags & SDF_QK_KEEP_SPIKES) != 0, sdf_stream(stream));
-      if (rc0) return rc0;
-      front = true;
-    }
-  }
-  int rc = 0;
-  if (!front) {
-  // 1. proj_sn over the T' frames of every window slice, gathered through the slice map (pad / roll / partition folded in)
-  SdfNeuronDesc n = {};
-  n.x = d->x; n.out = xs; n.T = Tq; n.out_dtype = SDF_U8;
-  n.nb = 1; n.ni = rows * C; n.x_sb = 0; n.x_st = 0; n.o_sb = 0; n.o_st = rows * C;
-  n.rowmap = d->slice_map; n.rowlen = C;
-  fill_neuron(n, d->sn_proj);
-  rc = sdf_neuron_fwd(&n, stream);
+  // steps 1 - 3 as one launch where the kernel has an instantiation (SDF_QK_FRONT=0 / SDF_QK_FOUR_LAUNCHES: the A/B reference), read
+  // per call like SDF_MLP_FUSED
+  const bool front = !sdf_sw_is(SW_QK_FRONT, '0') && !(d->flags & SDF_QK_FOUR_LAUNCHES) && sdfmm::qk_front_supports(d);
+  const int rc = front ? sdfmm::launch_qk_front(d, xs, qk, (d->flags & SDF_QK_KEEP_SPIKES) != 0, sdf_stream(stream))
+                       : qk_front_three_launches(d, xs, qk, stream);
   if (rc) return rc;
-
-  // 2. q = SN(BN(xs Wq^T)), k = SN(BN(xs Wk^T) + PE): the neuron runs in the GEMM epilogue, q / k never exist in fp32
-  auto qk_gemm = [&](const uint16_t* planes, float acc_scale, int N, const float* alpha, const float* beta, const float* add,
-                     const SdfNeuronCfg& sn, uint8_t* out) {
-    SdfSpikeGemmDesc g = {};
-    g.A = xs; g.Wp = planes; g.out_spike = out; g.M = M; g.N = N; g.K = C; g.lda = C; g.ldo = N; g.nsplit = d->nsplit;
-    g.acc_scale = acc_scale; g.alpha = alpha; g.beta = beta; g.add = add; g.add_prows = d->N1;
-    g.pos_count = rows; g.pos_inner = rows; g.pos_ostride = 0; g.t_stride = rows;
-    fill_gemm_neuron(g, sn, Tq);
-    return sdf_spike_gemm_fwd(&g, stream);
-  };
-  int64_t ldq, ldk;
-  const uint8_t *qp, *kp;
-  if (fused) {
-    rc = qk_gemm(d->qk_planes, d->qk_acc_scale, 2 * C, d->qk_alpha, d->qk_beta, d->qk_add, d->sn_q, qk);
-    if (rc) return rc;
-    qp = qk; kp = qk + C; ldq = ldk = 2 * C;
-  } else {
-    rc = qk_gemm(d->q_planes, d->q_acc_scale, C, d->q_alpha, d->q_beta, nullptr, d->sn_q, qk);
-    if (rc) return rc;
-    rc = qk_gemm(d->k_planes, d->k_acc_scale, C, d->k_alpha, d->k_beta, d->k_add, d->sn_k, qk + M * C);
-    if (rc) return rc;
-    qp = qk; kp = qk + M * C; ldq = ldk = C;
-  }
-
-  // 3. token gate: A = sn2_q(sum over each head's 32 channels of q), E = k AND A  (E overwrites xs)
-  rc = sdf_qk_gate_strided_fwd(qp, kp, xs, Tq, rows, C, ldq, ldk, d->sn2_q.kind, d->sn2_q.tau, d->sn2_q.v_th, d->sn2_q.v_reset,
-                               d->sn2_q.soft_reset, d->sn2_q.psn_w, d->sn2_q.psn_b, stream);
-  if (rc) return rc;
-  }
 
   // 4. x[slice_map] += BN(Z Wp^T + b), Z = E read through the reference's raw head reshape
   SdfSpikeGemmDesc g = {};
@@ -196,10 +205,7 @@ extern "C" int sdf_ms_mlp_fwd(const SdfMsMlpDesc* d, void* stream) {
     const bool tape = (d->flags & SDF_MLP_KEEP_SPIKES) != 0;
     uint8_t* s2w = tape ? s2 : s1 + ((tokens + 80) * C + 255) / 256 * 256;
     if (!d->s1_in) {
-      SdfNeuronDesc n = {};
-      n.x = d->x; n.out = s1; n.T = D; n.out_dtype = SDF_U8;
-      n.nb = d->B; n.ni = hw * C; n.x_sb = (int64_t)D * hw * C; n.x_st = hw * C; n.o_sb = (int64_t)D * hw * C; n.o_st = hw * C;
-      fill_neuron(n, d->sn1);
+      const SdfNeuronDesc n = mlp_sn1(d, s1);
       const int rcw = sdf_neuron_fwd(&n, stream);
       if (rcw) return rcw;
     }
@@ -207,18 +213,12 @@ extern "C" int sdf_ms_mlp_fwd(const SdfMsMlpDesc* d, void* stream) {
   }
   if (d->s1_in || d->emit_next) return SDF_E_SHAPE;            // wide-stage inputs / outputs
   // one launch where the kernel has an instantiation (SDF_MLP_FUSED=0 / SDF_MLP_THREE_LAUNCHES: the A/B reference below)
-  {
-    const char* e = sdf_sw(SW_MLP_FUSED);
-    if (!(d->flags & SDF_MLP_THREE_LAUNCHES) && !(e && e[0] == '0') && sdfmm::ms_mlp_fused_supports(d)) {
-      const bool keep = (d->flags & SDF_MLP_KEEP_SPIKES) != 0;
-      return sdfmm::launch_ms_mlp_fused(d, keep ? s1 : nullptr, keep ? s2 : nullptr, sdf_stream(stream));
-    }
+  if (!(d->flags & SDF_MLP_THREE_LAUNCHES) && !sdf_sw_is(SW_MLP_FUSED, '0') && sdfmm::ms_mlp_fused_supports(d)) {
+    const bool keep = (d->flags & SDF_MLP_KEEP_SPIKES) != 0;
+    return sdfmm::launch_ms_mlp_fused(d, keep ? s1 : nullptr, keep ? s2 : nullptr, sdf_stream(stream));
   }
   // 1. sn1 over the D steps of every (b, hw, c)
-  SdfNeuronDesc n = {};
-  n.x = d->x; n.out = s1; n.T = D; n.out_dtype = SDF_U8;
-  n.nb = d->B; n.ni = hw * C; n.x_sb = (int64_t)D * hw * C; n.x_st = hw * C; n.o_sb = (int64_t)D * hw * C; n.o_st = hw * C;
-  fill_neuron(n, d->sn1);
+  const SdfNeuronDesc n = mlp_sn1(d, s1);
   int rc = sdf_neuron_fwd(&n, stream);
   if (rc) return rc;
   // 2. s2 = SN2(BN1(s1 W1^T)): neuron fused into the GEMM epilogue, the 4C hidden tensor never exists in fp32

@@ -23,6 +23,7 @@
 // Compiled with -ffp-contract=off (the neuron arithmetic is the separately-rounded op sequence of neuron.hip).
 #include "spike_mm.h"
 #include "switches.h"
+#include "host_launch.h"
 #include <stdlib.h>
 
 namespace sdfmm {
@@ -256,15 +257,6 @@ __global__ __launch_bounds__(256, 3) void qk_front_kernel(QkFrontParams P) {
   }
 }
 
-template <bool KEEP>
-int launch_nk(const QkFrontParams& P, int nk, dim3 grid, hipStream_t s) {
-  switch (nk) {
-    case 0: SDF_LAUNCH((qk_front_kernel<0, KEEP>), grid, dim3(256), 0, s, P); return 0;
-    case 1: SDF_LAUNCH((qk_front_kernel<1, KEEP>), grid, dim3(256), 0, s, P); return 0;
-    default: SDF_LAUNCH((qk_front_kernel<2, KEEP>), grid, dim3(256), 0, s, P); return 0;
-  }
-}
-
 }  // namespace
 
 // Shapes and settings the one-launch first half is built for; everything else keeps the three launches.
@@ -274,16 +266,11 @@ bool qk_front_supports(const SdfQkAttnDesc* d) {
   // chunks on (C >= 288: few pairs, every head's workgroup repeats the pair's SN_proj, a chain of chunk latencies per workgroup)
   // the three pipelined launches are as fast or faster (stage 2: 32 vs 32 us, stage 3: 33 vs 55 us) and stay.  SDF_QK_FRONT_ANY=1
   // lifts the limit (tests).
-  const char* e_any = sdf_sw(SW_QK_FRONT_ANY);                     // (read per call: a test may scope it)
-  const bool any = e_any && e_any[0] == '1';
-  if (!any && d->C / QF_KC > 2) return false;
+  if (!sdf_sw_is(SW_QK_FRONT_ANY, '1') && d->C / QF_KC > 2) return false;      // (read per call: a test may scope it)
   const SdfNeuronCfg* ns[4] = {&d->sn_proj, &d->sn_q, &d->sn_k, &d->sn2_q};
   const int nk = neuron_class(*ns[0]);
   for (const SdfNeuronCfg* n : ns) {
-    if (n->kind != SDF_LIF && n->kind != SDF_IF && n->kind != SDF_PSN) return false;
-    if (n->kind == SDF_PSN && (!n->psn_w || !n->psn_b)) return false;
-    if (!sdf_tau_ok(n->kind, n->tau)) return false;
-    if (neuron_class(*n) != nk) return false;
+    if (sdf_neuron_cfg_rc(*n) != 0 || neuron_class(*n) != nk) return false;
   }
   if (d->B_ * d->nH >= (1LL << 31) || d->B_ * 2 * d->N1 >= (1LL << 31)) return false;
   const bool fused = d->qk_planes != nullptr;
@@ -319,11 +306,11 @@ int launch_qk_front(const SdfQkAttnDesc* d, uint8_t* e, uint8_t* qk, bool keep, 
   P.it_proj = inv_tau_of(d->sn_proj); P.it_q = inv_tau_of(d->sn_q); P.it_k = inv_tau_of(d->sn_k); P.it_2 = inv_tau_of(d->sn2_q);
   P.e = e;
   const dim3 grid((unsigned)(d->B_ * d->nH));
-  const int nk = neuron_class(d->sn_proj);
-  const int rc = keep ? launch_nk<true>(P, nk, grid, s) : launch_nk<false>(P, nk, grid, s);
-  if (rc) return rc;
-  hipError_t err = hipGetLastError();
-  return err != hipSuccess ? (int)err : 0;
+  bool built = false;
+  sdf_dispatch(SdfList<1, 0>{}, keep, [&](auto kp) {
+    built = sdf_dispatch(SDF_NEURON_CLASSES, neuron_class(d->sn_proj), [&](auto nk) { SDF_LAUNCH((qk_front_kernel<nk, kp != 0>), grid, dim3(256), 0, s, P); });
+  });
+  return built ? sdf_launch_rc() : SDF_E_SHAPE;
 }
 
 }  // namespace sdfmm

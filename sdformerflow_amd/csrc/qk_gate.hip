@@ -5,6 +5,7 @@
 // One lane per (row, 32-channel group): 32 B of q and k per step, all byte traffic.
 // Compiled with -ffp-contract=off (LIF ops are separately rounded; PSN uses explicit fmaf).
 #include "common.h"
+#include "host_launch.h"
 #include "neuron_step.h"
 
 namespace {
@@ -83,9 +84,7 @@ extern "C" int sdf_qk_gate_strided_fwd(const uint8_t* q, const uint8_t* k, uint8
   if (!q || !k || !e) return SDF_E_NULL;
   if (Tq < 1 || Tq > TQ_MAX || rows < 1 || C < 32 || C % 32) return SDF_E_SHAPE;
   if (ldq < C || ldk < C || ldq % 16 || ldk % 16) return SDF_E_SHAPE;
-  if (kind != SDF_LIF && kind != SDF_PSN && kind != SDF_IF) return SDF_E_DTYPE;
-  if (kind == SDF_PSN && (!psn_w || !psn_b)) return SDF_E_NULL;
-  if (!sdf_tau_ok(kind, tau)) return SDF_E_SHAPE;
+  if (const int rc = sdf_neuron_cfg_rc(kind, tau, psn_w, psn_b)) return rc;
   if (!sdf_aligned(q, 16) || !sdf_aligned(k, 16) || !sdf_aligned(e, 16)) return SDF_E_ALIGN;
   GateParams P;
   P.q = q; P.k = k; P.e = e; P.Tq = Tq; P.rows = rows; P.C = C; P.G = C / 32;

@@ -858,8 +858,7 @@ bool spike_conv_wres_plan(const GemmParams& P, bool any_size, ConvWresPlan& pl) 
     if (ntiles >= 64) pl.grid = (ntiles + per - 1) / per;
     // column blocks of a tile range side by side on one XCD (see the kernel): the grid becomes a multiple of 8 * tiles_n, or of
     // tiles_n with every workgroup's share still `per` items
-    const char* ecb = sdf_sw(SW_CONV_WRES_CB_INNER);
-    if ((!ecb || ecb[0] != '0') && ntiles >= 64) {
+    if (!sdf_sw_is(SW_CONV_WRES_CB_INNER, '0') && ntiles >= 64) {
       int nr = (pl.tiles_m + per - 1) / per;                          // tile ranges of at most `per` items ...
       while (nr * pl.tiles_n <= 256 && (nr * pl.tiles_n) % 8) ++nr;   // ... a few more of them where that makes the grid a multiple of 8
       const int g2 = nr * pl.tiles_n;                                 // (the kernel splits tiles_m evenly over the ranges)

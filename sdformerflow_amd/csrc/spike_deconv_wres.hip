@@ -291,8 +291,7 @@ __global__ __launch_bounds__(NT) void spike_deconv_wres_kernel(DeconvParams P) {
 }  // namespace
 
 bool spike_deconv_wres_supports(int imgs, int H, int W, int Cin, int Cout) {
-  const char* e = sdf_sw(SW_DECONV_WRES);                   // A/B: 0 = the row-loop kernel's form (ms_res.hip)
-  if (e && e[0] == '0') return false;
+  if (sdf_sw_is(SW_DECONV_WRES, '0')) return false;         // A/B: 0 = the row-loop kernel's form (ms_res.hip)
   if (Cin != CIN || Cout < 8 || Cout % 4 || (4 * Cout) % 4) return false;
   const int64_t rows = (int64_t)imgs * H * W;
   return rows * CIN < (1LL << 31) && rows * 16 * Cout < (1LL << 31) && rows >= 4096;
@@ -307,8 +306,7 @@ int launch_spike_deconv_wres(const uint8_t* A, const int8_t* Wd, const float* cs
   P.tiles_n = (P.N + NB - 1) / NB;
   P.ntiles = P.tiles_m * P.tiles_n;
   int grid;
-  const char* eb = sdf_sw(SW_DECONV_BALANCE);           // A/B: 0 = every column block multiplies all four quadrants
-  if (Cout % NB == 0 && P.tiles_m >= 64 && !(eb && eb[0] == '0')) {
+  if (Cout % NB == 0 && P.tiles_m >= 64 && !sdf_sw_is(SW_DECONV_BALANCE, '0')) {      // A/B: 0 = every column block multiplies all four quadrants
     // class-balanced: ranges per class in proportion to a tile's cost in that class - its K steps plus the part every tile pays (halo,
     // epilogue, stores: 16 K steps' worth measured best; SDF_DECONV_EPI: tuning override) - 250 - 256 workgroups in all
     const int cbc = Cout / NB, budget = 256 / cbc;

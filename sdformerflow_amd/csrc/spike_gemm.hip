@@ -415,32 +415,24 @@ __global__ __launch_bounds__(256) void split_weight_f16_kernel(const float* __re
   planes[n + i] = __builtin_bit_cast(uint16_t, lo);
 }
 
-template <int NSPLIT, int NB, int RB, int WAVES, bool CONV = false>
-int launch(const GemmParams& P, dim3 grid, hipStream_t s) {
-#define SDF_GEMM_T(TT)                                                                                      \
-  case TT:                                                                                                  \
-    if constexpr (TT == 0 || (16 * RB) / (TT ? TT : 1) >= 1) {                                              \
-      SDF_LAUNCH((spike_gemm_kernel<NSPLIT, NB, RB, TT, WAVES, CONV>), grid, dim3(64 * WAVES), 0, s, P);  \
-      return 0;                                                                                             \
-    }                                                                                                       \
-    return SDF_E_SHAPE;
-  switch (P.d.sn_T) {
-    SDF_GEMM_T(0) SDF_GEMM_T(2) SDF_GEMM_T(4) SDF_GEMM_T(5) SDF_GEMM_T(10) SDF_GEMM_T(20)
-    default: return SDF_E_SHAPE;
-  }
-#undef SDF_GEMM_T
-}
+// Tile configurations built: 0 = 512 x 96 (8 waves, 2 row blocks), 1 = 256 x 96 (8 waves), 2 = 256 x 32 (4 waves), 3 = 128 x 32 (4 waves).
+// 96-wide tiles reuse every A fragment 3x; the fused neuron needs 16 RB >= T accumulator slots per lane (T = 20: two row blocks).
+constexpr int CFG_NB[4] = {3, 3, 1, 1}, CFG_RB[4] = {2, 1, 2, 1}, CFG_WAVES[4] = {8, 8, 4, 4};
 
-// configurations built: big = 8 waves x (RB=2, NB=3) [512 x 96 tiles]; mid = 8 waves x (RB=1, NB=3) [256 x 96];
-// small = 4 waves x (RB=2 | 1, NB=1) [256|128 x 32]
-template <int NSPLIT>
-int launch_cfg(const GemmParams& P, int cfg, dim3 grid, hipStream_t s) {
-  switch (cfg) {
-    case 0: return launch<NSPLIT, 3, 2, 8>(P, grid, s);
-    case 1: return launch<NSPLIT, 3, 1, 8>(P, grid, s);
-    case 2: return launch<NSPLIT, 1, 2, 4>(P, grid, s);
-    default: return launch<NSPLIT, 1, 1, 4>(P, grid, s);
-  }
+int launch(const GemmParams& P, int cfg, dim3 grid, hipStream_t s) {
+  int rc = SDF_E_SHAPE;
+  sdf_dispatch(SdfList<1, 2, 3>{}, P.d.nsplit, [&](auto ns) {
+    sdf_dispatch(SdfList<0, 1, 2, 3>{}, cfg, [&](auto c) {
+      sdf_dispatch(SdfList<0, 2, 4, 5, 10, 20>{}, P.d.sn_T, [&](auto t) {
+        constexpr int NB = CFG_NB[c], RB = CFG_RB[c], WAVES = CFG_WAVES[c];
+        if constexpr (t == 0 || (16 * RB) / (t ? t : 1) >= 1) {
+          SDF_LAUNCH((spike_gemm_kernel<ns, NB, RB, t, WAVES, false>), grid, dim3(64 * WAVES), 0, s, P);
+          rc = 0;
+        }
+      });
+    });
+  });
+  return rc ? rc : sdf_launch_rc();
 }
 
 // acc_scale: only the fp16 planes carry a weight scale; it must be a power of two (exact rescaling of the accumulator)
@@ -491,9 +483,7 @@ extern "C" int sdf_spike_gemm_fwd(const SdfSpikeGemmDesc* d, void* stream) {
   P.acc_scale = sdf_acc_scale(d);
   if (spike) {
     if (d->pos_count < 1 || d->pos_inner < 1 || d->pos_count * d->sn_T != d->M) return SDF_E_SHAPE;
-    if (d->sn_kind != SDF_LIF && d->sn_kind != SDF_PSN && d->sn_kind != SDF_IF) return SDF_E_DTYPE;
-    if (d->sn_kind == SDF_PSN && (!d->psn_w || !d->psn_b)) return SDF_E_NULL;
-    if (!sdf_tau_ok(d->sn_kind, d->tau)) return SDF_E_SHAPE;
+    if (const int rc = sdf_neuron_cfg_rc(d->sn_kind, d->tau, d->psn_w, d->psn_b)) return rc;
     if (d->add && d->add_prows < 1) return SDF_E_SHAPE;
     if (d->zg_nH > 0 || d->out_rowmap || d->resid || d->bias) return SDF_E_SHAPE;   // F32-only features
     if (!sdf_aligned(d->out_spike, 16) || d->N % 16) return SDF_E_ALIGN;
@@ -509,9 +499,6 @@ extern "C" int sdf_spike_gemm_fwd(const SdfSpikeGemmDesc* d, void* stream) {
     return SDF_E_ALIGN;                                          // the fp32 epilogue moves 16 bytes per lane
 
   // ---- tile configuration ----
-  // cfg 0: 512x96 (8 waves, 2 row blocks)   cfg 1: 256x96 (8 waves)   cfg 2: 256x32 (4 waves)   cfg 3: 128x32 (4 waves)
-  // 96-wide tiles reuse every A fragment 3x; the fused neuron needs 2 row blocks when T > 8 (16*RB slots per lane).
-  static const int CFG_NB[4] = {3, 3, 1, 1}, CFG_RB[4] = {2, 1, 2, 1}, CFG_WAVES[4] = {8, 8, 4, 4};
   auto ok = [&](int c) { return (CFG_NB[c] == 1 || d->N % 96 == 0) && (!spike || (16 * CFG_RB[c]) / d->sn_T >= 1); };
   auto ntiles_for = [&](int c) -> int64_t {
     const int64_t per = spike ? 2 * CFG_WAVES[c] * ((16 * CFG_RB[c]) / d->sn_T) : 32 * CFG_RB[c] * CFG_WAVES[c];
@@ -541,12 +528,11 @@ extern "C" int sdf_spike_gemm_fwd(const SdfSpikeGemmDesc* d, void* stream) {
   // epilogues that the other consumer group hides) and fp32 epilogues with a long K loop over many rows, a very
   // long one, or many column tiles per row tile (the decoders' stacked tap matrices).  SDF_GEMM_WS: 0 = never, 2 = whenever legal.
   {
-    const char* e = sdf_sw(SW_GEMM_WS);
     const bool legal = d->N % 96 == 0 && spike_mm_pp_supports(P, false);
     bool use_pp = legal && ((spike && (d->sn_T == 10 || d->sn_T == 20)) ||
                            (!spike && ((d->K >= 384 && d->M >= 32768) || d->K >= 2048 || (d->K >= 384 && d->N >= 864))));
-    if (e && e[0] == '0') use_pp = false;
-    if (e && e[0] == '2') use_pp = legal;
+    if (sdf_sw_is(SW_GEMM_WS, '0')) use_pp = false;
+    if (sdf_sw_is(SW_GEMM_WS, '2')) use_pp = legal;
     if (use_pp) return launch_spike_mm_pp(P, false, sdf_stream(stream));
   }
   if (!ok(cfg)) return SDF_E_SHAPE;
@@ -561,11 +547,7 @@ extern "C" int sdf_spike_gemm_fwd(const SdfSpikeGemmDesc* d, void* stream) {
   if (const char* e = sdf_sw(SW_GEMM_WGS)) { const int v = atoi(e); if (v >= 1 && v <= 8) wg_per_cu = v; }   // tuning override
   const int G = P.ntiles < 256 * wg_per_cu ? P.ntiles : 256 * wg_per_cu;
   dim3 grid((unsigned)G);
-  hipStream_t s = sdf_stream(stream);
-  const int rc = d->nsplit == 1 ? launch_cfg<1>(P, cfg, grid, s) : (d->nsplit == 2 ? launch_cfg<2>(P, cfg, grid, s) : launch_cfg<3>(P, cfg, grid, s));
-  if (rc) return rc;
-  SDF_LAUNCH_CHECK();
-  return 0;
+  return launch(P, cfg, grid, sdf_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -595,9 +577,7 @@ static int conv2d_build(const SdfSpikeConvDesc* c, GemmParams& P, bool& i8x3, bo
   if (spike) {
     if ((d->sn_T != 10 && !(i8x3 && (d->sn_T == 5 || d->sn_T == 20))) || d->pos_count < 1 || d->pos_inner < 1 ||
         d->pos_count * d->sn_T != d->M) return SDF_E_SHAPE;          // streaming kernels: T = 10; the digit kernel rolls its time loop
-    if (d->sn_kind != SDF_LIF && d->sn_kind != SDF_PSN && d->sn_kind != SDF_IF) return SDF_E_DTYPE;
-    if (d->sn_kind == SDF_PSN && (!d->psn_w || !d->psn_b)) return SDF_E_NULL;
-    if (!sdf_tau_ok(d->sn_kind, d->tau)) return SDF_E_SHAPE;
+    if (const int rc = sdf_neuron_cfg_rc(d->sn_kind, d->tau, d->psn_w, d->psn_b)) return rc;
     if (d->out_rowmap || d->bias || d->add) return SDF_E_SHAPE;
     if (d->resid && !d->out) return SDF_E_NULL;                   // a residual only exists for the membrane output
     if (d->out && (d->ldo < d->N || !sdf_aligned(d->out, 4))) return SDF_E_SHAPE;
@@ -648,8 +628,8 @@ static ConvRoute conv2d_route(const GemmParams& P, bool i8x3, bool tiled, ConvPl
   if (i8x3 && smallm_conv_plan(P, pl.smallm)) return CONV_SMALLM;
   if (tiled) return CONV_REST;
   // 3x3 / stride 1 on 96 channels with enough tiles to fill the chip: weights resident in LDS, halo tiles instead of im2col
-  const char* ewr = sdf_sw(SW_CONV_WRES);                  // A/B override: 0 = always the streaming kernels below, 2 = at any size
-  if (!(ewr && ewr[0] == '0') && spike_conv_wres_plan(P, i8x3 || (ewr && ewr[0] == '2'), pl.wres)) return CONV_WRES;
+  // SDF_CONV_WRES, A/B override: 0 = always the streaming kernels below, 2 = at any size
+  if (!sdf_sw_is(SW_CONV_WRES, '0') && spike_conv_wres_plan(P, i8x3 || sdf_sw_is(SW_CONV_WRES, '2'), pl.wres)) return CONV_WRES;
   if (i8x3) return CONV_REST;                                   // digit planes have no streaming-kernel form: the caller packs per shape
   // 256 x 96 tiles, producer waves do the im2col addressing; the ping-pong kernel overlaps epilogues with the MFMAs
   return spike_mm_pp_supports(P, true) ? CONV_PP : CONV_REST;
@@ -707,8 +687,7 @@ extern "C" int sdf_spike_conv2d_fwd(const SdfSpikeConvDesc* c, void* stream) {
 extern "C" int sdf_spike_conv2d_multi_fwd(const SdfSpikeConvDesc* cs, int n, void* stream) {
   if (!cs) return SDF_E_NULL;
   if (n < 1) return SDF_E_SHAPE;
-  const char* emu = sdf_sw(SW_CONV_MULTI);                 // A/B override: 0 = one launch per convolution
-  if (n >= 2 && n <= 4 && !(emu && emu[0] == '0')) {
+  if (n >= 2 && n <= 4 && !sdf_sw_is(SW_CONV_MULTI, '0')) {      // (SDF_CONV_MULTI=0, A/B override: one launch per convolution)
     GemmParams Ps[4];
     bool one = true;
     for (int i = 0; i < n; ++i) {

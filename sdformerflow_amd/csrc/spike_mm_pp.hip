@@ -676,7 +676,7 @@ static int pp_plan(GemmParams& P) {
   // same duration, and the other in-flight forwards' kernels get the compute units this launch does not need
   // A workgroup's two consumer groups alternate items, so a workgroup wants an EVEN number of items: with one item per workgroup
   // half of its matrix-pipe time is idle.  SDF_PP_PAIR=0: the round-2 rule (one item per workgroup up to 256 workgroups).
-  const bool pair = !(sdf_sw(SW_PP_PAIR) && sdf_sw(SW_PP_PAIR)[0] == '0');
+  const bool pair = !sdf_sw_is(SW_PP_PAIR, '0');
   int G;
   if (pair && nitems >= 16) {
     const int rounds = (nitems + 511) / 512;                     // items per workgroup = 2 * rounds

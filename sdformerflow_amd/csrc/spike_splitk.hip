@@ -1,5 +1,6 @@
 // Split-K plan and its deterministic second pass, shared by the spike matrix-multiply kernels (spike_mm_pp.hip, spike_gemm.hip).
 #include "spike_mm.h"
+#include "host_launch.h"
 #include "switches.h"
 #include <stdlib.h>
 
@@ -75,8 +76,7 @@ int launch_splitk_reduce(const GemmParams& P, hipStream_t s) {
   const int64_t quads = d.M * (d.N / 4);
   SDF_LAUNCH(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, P.partial, P.ksplit, d.M,
                      d.N, P.acc_scale, d.bias, d.alpha, d.beta, d.resid, d.out_rowmap, d.out, d.ldo);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? (int)e : 0;
+  return sdf_launch_rc();
 }
 
 }  // namespace sdfmm

@@ -17,3 +17,8 @@ enum SdfSwitch {
 };
 // Value of SDF_<name> as it stood when the table was (re)built, or nullptr when unset: a drop-in for getenv("SDF_<name>").
 const char* sdf_sw(SdfSwitch s);
+// The test most sites make of a switch: set, and its first character is `c` (sites that parse a number keep sdf_sw).
+static inline bool sdf_sw_is(SdfSwitch s, char c) {
+  const char* e = sdf_sw(s);
+  return e && e[0] == c;
+}

@@ -18,6 +18,7 @@
 // (4 consecutive keys) from L2-resident tables.
 #include "device_prims.h"
 #include "switches.h"
+#include "host_launch.h"
 
 namespace {
 
@@ -834,30 +835,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
   }
 }
 
-template <int MODE, int NTC>
-int launch_tiled_f16(const AttnParams& P, hipStream_t s) {
-  constexpr size_t lds = (size_t)(2 * NTC * 16 * KRS + (NTC * 4) * HD * 16);
-  dim3 grid((unsigned)(P.d.B_ * P.d.nH)), block(256);
-  if (P.d.mask) {
-    SDF_LAUNCH((win_attn_tiled_f16_kernel<MODE, NTC, true>), grid, block, lds, s, P);
-  } else {
-    SDF_LAUNCH((win_attn_tiled_f16_kernel<MODE, NTC, false>), grid, block, lds, s, P);
-  }
-  SDF_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int MODE, int NTC>
-int launch_tiled(const AttnParams& P, hipStream_t s) {
-  constexpr size_t lds = (size_t)(NTC * 16 * LDW + HD * (NTC * 16 + 4)) * sizeof(float);
-  dim3 grid((unsigned)(P.d.B_ * P.d.nH)), block(256);
-  if (P.d.mask) {
-    SDF_LAUNCH((win_attn_tiled_kernel<MODE, NTC, true>), grid, block, lds, s, P);
-  } else {
-    SDF_LAUNCH((win_attn_tiled_kernel<MODE, NTC, false>), grid, block, lds, s, P);
-  }
-  SDF_LAUNCH_CHECK();
-  return 0;
+// The tiled kernels, compiled for the tile counts of the windows (2,8,8) and (2,9,9): mode x tiles x mask; pipe16 = the 16-bit-pipe
+// kernel, else the fp32-pipe one.  false: no kernel for `nt` tiles (nothing launched).
+bool launch_tiled(const AttnParams& P, bool pipe16, int nt, hipStream_t s) {
+  const dim3 grid((unsigned)(P.d.B_ * P.d.nH)), block(256);
+  bool built = false;
+  sdf_dispatch(SdfList<SDF_ATTN_ANN, SDF_ATTN_SEW>{}, P.d.mode, [&](auto mode) {
+    sdf_dispatch(SdfList<8, 11>{}, nt, [&](auto ntc) {
+      built = sdf_dispatch(SdfList<1, 0>{}, P.d.mask != nullptr, [&](auto mask) {
+        if (pipe16) {
+          constexpr size_t lds = (size_t)(2 * ntc * 16 * KRS + (ntc * 4) * HD * 16);
+          SDF_LAUNCH((win_attn_tiled_f16_kernel<mode, ntc, mask != 0>), grid, block, lds, s, P);
+        } else {
+          constexpr size_t lds = (size_t)(ntc * 16 * LDW + HD * (ntc * 16 + 4)) * sizeof(float);
+          SDF_LAUNCH((win_attn_tiled_kernel<mode, ntc, mask != 0>), grid, block, lds, s, P);
+        }
+      });
+    });
+  });
+  return built;
 }
 
 }  // namespace
@@ -879,23 +875,11 @@ extern "C" int sdf_win_attn_fwd(const SdfWinAttnDesc* d, void* stream) {
   dim3 grid((unsigned)(d->B_ * d->nH)), block(256);
   hipStream_t s = sdf_stream(stream);
   // even N that fits a compiled tile count: the MFMA-paced kernel (8-byte bias / mask loads need N % 2 == 0)
-  const char* ge = sdf_sw(SW_ATTN_GENERIC);                 // A/B override: 1 = always the general kernel
-  if (d->N % 2 == 0 && (int64_t)d->N * d->N * 4 < (1LL << 31) && !(ge && ge[0] == '1')) {
-    const int nt = (d->N + 15) / 16;                         // compiled tile counts: windows (2,8,8) and (2,9,9)
-    const char* f32 = sdf_sw(SW_ATTN_F32);                // A/B override: 1 = the fp32-pipe kernels
+  // (SDF_ATTN_GENERIC=1, A/B override: always the general kernel; SDF_ATTN_F32=1: the fp32-pipe kernels)
+  if (d->N % 2 == 0 && (int64_t)d->N * d->N * 4 < (1LL << 31) && !sdf_sw_is(SW_ATTN_GENERIC, '1')) {
     // (the 16-bit-pipe kernels address the output and the row map with 32-bit byte offsets)
-    const bool pipe16 = !(f32 && f32[0] == '1') && (int64_t)d->B_ * d->N * d->nH * HD * 4 < (1LL << 31);
-    if (d->mode == SDF_ATTN_ANN) {
-      if (pipe16 && nt == 8) return launch_tiled_f16<SDF_ATTN_ANN, 8>(P, s);
-      if (pipe16 && nt == 11) return launch_tiled_f16<SDF_ATTN_ANN, 11>(P, s);
-      if (nt == 8) return launch_tiled<SDF_ATTN_ANN, 8>(P, s);
-      if (nt == 11) return launch_tiled<SDF_ATTN_ANN, 11>(P, s);
-    } else {
-      if (pipe16 && nt == 8) return launch_tiled_f16<SDF_ATTN_SEW, 8>(P, s);
-      if (pipe16 && nt == 11) return launch_tiled_f16<SDF_ATTN_SEW, 11>(P, s);
-      if (nt == 8) return launch_tiled<SDF_ATTN_SEW, 8>(P, s);
-      if (nt == 11) return launch_tiled<SDF_ATTN_SEW, 11>(P, s);
-    }
+    const bool pipe16 = !sdf_sw_is(SW_ATTN_F32, '1') && (int64_t)d->B_ * d->N * d->nH * HD * 4 < (1LL << 31);
+    if (launch_tiled(P, pipe16, (d->N + 15) / 16, s)) return sdf_launch_rc();
   }
   static std::atomic<uint64_t> opt_ann{0}, opt_sew{0};      // > 64 KiB of dynamic LDS: opt-in once per kernel and device
   if (const int e1 = sdf_lds_opt_in(opt_ann, reinterpret_cast<const void*>(win_attn_kernel<SDF_ATTN_ANN>), 3 * 16 * NT_MAX * LDW * 4)) return e1;

@@ -8,21 +8,16 @@ column blocks and epilogues 1 / 2 / 3 (and its patch-merging form); wide_front_k
 convolution, fc2 and plain product; T = 10 and 20; the neuron classes 0 (LIF, soft reset), 1 (PSN) and 2 (hard reset / IF).
 
 No numeric comparison: parity is covered by test_ms_wide_gpu.py, test_smallm_gpu.py and the route tests.  Outputs go to fresh buffers."""
-import re
-
 import pytest
 import torch
 
+import routes_common
+from routes_common import DEV, neuron, rnd
 from sdformerflow_amd import hip
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SWITCHES = ("SDF_RES", "SDF_RES_MINC", "SDF_RES_MAXC", "SDF_RES_UPW", "SDF_RES_RMUL", "SDF_RES_STRIP", "SDF_WIDE", "SDF_WIDE_CB",
             "SDF_WIDE_PASSES", "SDF_WIDE_MAXROWS", "SDF_WIDE_CONV", "SDF_SMALLM", "SDF_SMALLM_FC2", "SDF_SMALLM_CB", "SDF_SMALLM_CONV_ROWS")
-
-
-def rnd(shape, lo=-0.1, hi=0.1):
-    return torch.rand(shape, device=DEV) * (hi - lo) + lo
 
 
 def spikes(shape):
@@ -41,26 +36,8 @@ class _L:
         self.bias = rnd((N,)) if bias else None
 
 
-def neuron(name, T):
-    """class 0: LIF with a soft reset; class 1: PSN (its own T x T matrix); class 2: hard reset, IF"""
-    if name == "psn":
-        return hip.NeuronParams("psn", psn_w=(torch.eye(T, device=DEV) * 0.8).contiguous(), psn_b=torch.full((T,), -0.1, device=DEV))
-    return {"lif": hip.NeuronParams("lif", 2.0, 0.1, None), "lif_hard": hip.NeuronParams("lif", 2.0, 0.1, 0.0),
-            "if": hip.NeuronParams("if", 2.0, 0.1, None)}[name]
-
-
-def short(name):
-    name = re.sub(r"^void ", "", name)
-    name = re.sub(r"\b(sdfmm|sdf)::", "", name)
-    name = re.sub(r"\(anonymous namespace\)::", "", name)
-    return re.sub(r"\(.*$", "", name)
-
-
 def logged(call):
-    with hip.launch_log() as log:
-        call()
-    torch.cuda.synchronize()
-    return [f"{wgs} {thr} {lds} {short(k)}" for k, wgs, thr, lds, _ in log.rows]
+    return routes_common.logged(call)[0]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the calls
