@@ -15,9 +15,11 @@ SDF_HIP_LIB naming a build of the commit before the refactor: `PYTHONPATH=. pyth
     three bf16 planes at T = 10; sn1 / sn2 of different classes take the three-launch form;
   * layer norm: 3 rows of C = 64 ... 512 in steps of 64 (1 ... 8 float4 per lane at 16 lanes per row) and C = 576, 1024, 2048 (64 lanes).
 
-Every case runs twice into fresh buffers: the same launches and bit-equal outputs.  No numeric comparison: parity is covered by
-test_head_conv_gpu.py, test_pred_head_gpu.py, test_qk_attn_gpu.py, test_ms_mlp_gpu.py and test_dense_linear_gpu.py.  The streaming GEMM
-and the window attention are pinned by test_spike_gemm_routes_gpu.py and test_win_attn_fwd_gpu.py."""
+Every case runs twice into fresh buffers: the same launches and bit-equal outputs.  No numeric comparison: parity of the head
+convolution, the prediction head, the one-launch QK front, the one-launch MLP and the token gate is test_stage0_parity_gpu.py's, every
+instantiation listed here against the oracle (with test_hip_kernels.py::test_head_conv_bn_neuron, test_pred_head_gpu.py,
+test_qk_front_gpu.py and test_ms_mlp_fused_gpu.py at the workload's shapes); the layer norm's is test_dense_linear_gpu.py's.  The
+streaming GEMM and the window attention are pinned by test_spike_gemm_routes_gpu.py and test_win_attn_fwd_gpu.py."""
 import json
 import os
 
