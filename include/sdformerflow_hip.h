@@ -1139,6 +1139,31 @@ typedef struct SdfPrepareChunkDesc {
 int64_t sdf_prepare_chunk_workspace_bytes(int B);
 int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * u8 spikes -> spike counts per time step: the numerator of the firing rate the reference's output monitor records for a neuron call,
+ * `cal_firing_rate(s_seq) = s_seq.flatten(1).mean(1)` (eval_DSEC_flow_SNN.py:22-24, 140-143, `vis.monitor_fr`).
+ * Element (o, t, r, c) is the byte at spikes + ((o * T + t) * rows + r) * row_stride + c; the call computes
+ *   counts[t] += sum over o, r, c            (t = 0 .. T - 1; 64-bit integers; the CALLER zeroes them)
+ * One addressing form for a contiguous (T, rows, C) tensor (outer 1), a channel-last (B, D, h, w, C) activation (outer B, T = D), a
+ * channel slice [..., c0:c1] of a wider activation (row_stride = its channel count, spikes moved by c0 - any alignment) and the halves
+ * of a stacked (M, 2C) q | k buffer (row_stride 2C).  Nothing outside the addressed bytes is read.  row_stride == C (one run of
+ * rows * C bytes per (o, t)) is the fast path: 16 bytes per lane, byte-wise in front of the first and behind the last 16-byte
+ * boundary; row_stride > C walks the rows and is meant for small tensors.  Sums are integers, added lane -> wave -> workgroup and then
+ * with one 64-bit atomic per workgroup and step: the same bits on every run.  Added to SDF_VERSION 107 (no existing entry changed).
+ * SDF_E_NULL: d, spikes or counts NULL; SDF_E_SHAPE: outer, rows or C < 1, T outside 1 .. 64, row_stride < C (or sizes beyond 2^62
+ * bytes / 2^31 workgroups); SDF_E_ALIGN: counts not 8-byte aligned. */
+typedef struct SdfSpikeCountDesc {
+  const uint8_t* spikes;
+  int64_t outer;
+  int T;
+  int64_t rows;
+  int C;
+  int64_t row_stride;
+  int64_t* counts;
+} SdfSpikeCountDesc;
+
+int sdf_spike_count_fwd(const SdfSpikeCountDesc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,7 @@ class MS_SpikingformerFlowNet(nn.Module):
                             "use_upsample_conv": unet_kwargs.get("use_upsample_conv", True)})
         self.sttmultires_unet = self.unet_type(unet_kwargs, dict(stt_kwargs))
         self._engine, self._stamp_tensors = None, None
+        self._fr_monitor = None       # a monitor.FiringRateMonitor while it is enabled (it lives here, not on the engine: rebuilds keep it)
         # Weight planes of the spike GEMMs / convolutions (binary spikes are exact in 16-bit floats, accumulation is fp32):
         #   2 = fp16 hi + lo of the power-of-two-scaled weight: 22 of the 24 significand bits at 2/3 of the matrix work.
         #       Measured against fp64 the layer outputs are as close as torch's own fp32 convolution, and every
@@ -210,13 +211,24 @@ class MS_SpikingformerFlowNet(nn.Module):
         """reference :310-311."""
         return self.sttmultires_unet.record_flops()
 
+    def _no_monitor(self, what, instead):
+        if self._fr_monitor is not None:
+            raise RuntimeError(f"a firing-rate monitor is enabled on this model and {what}: {instead}")
+
+    def _engine_forward(self, x, scores=None):
+        """The eval forward on the packed plan - through the firing-rate monitor while one is enabled (monitor.FiringRateMonitor)."""
+        if self._fr_monitor is not None:
+            return self._fr_monitor.forward(x, scores)          # (asks for self.engine() itself, behind its refusals)
+        return self.engine().forward(x, scores)
+
     def forward(self, x, log=False):
         if self.training:                     # train-mode forward under autograd (batch-stat BN, HIP neurons both ways)
+            self._no_monitor("the model is in training mode", "rates are counted on the eval forward - call model.eval(), or disable() the monitor")
             from ..train import forward_train
             return {"flow": forward_train(self, x), "attn": None}
         with torch.no_grad():
             scores = [] if log else None          # reference :283-284; see engine.forward for what the reference's own chain does
-            flows = self.engine().forward(x, scores)
+            flows = self._engine_forward(x, scores)
         return {"flow": flows, "attn": scores}
 
     def forward_replicas(self, x):
@@ -226,6 +238,7 @@ class MS_SpikingformerFlowNet(nn.Module):
         couples the samples through `window_partition_v2`'s raw view.)  Eval mode only."""
         if self.training:
             raise RuntimeError("forward_replicas is an inference entry point: call model.eval()")
+        self._no_monitor("forward_replicas was called", "a record set follows ONE reference forward - call model(x[i:i+1]) per sample, or disable() the monitor")
         from .. import hip
 
         def one_by_one():
@@ -263,6 +276,7 @@ class SpikingformerFlowNet(MS_SpikingformerFlowNet):
 
     def forward(self, x, log=False):
         if self.training:                     # train-mode forward under autograd (the SEW attention backward: csrc/win_attn_sew_bwd.hip)
+            self._no_monitor("the model is in training mode", "rates are counted on the eval forward - call model.eval(), or disable() the monitor")
             from ..train import forward_train_sew
             return {"flow": forward_train_sew(self, x), "attn": None}
         if log:
@@ -275,6 +289,7 @@ class SpikingformerFlowNet(MS_SpikingformerFlowNet):
         samples go one by one - same contract as the MS models' call, flow[i] == self(x[i:i+1])["flow"]."""
         if self.training:
             raise RuntimeError("forward_replicas is an inference entry point: call model.eval()")
+        self._no_monitor("forward_replicas was called", "a record set follows ONE reference forward - call model(x[i:i+1]) per sample, or disable() the monitor")
         with torch.no_grad():
             outs = [self.engine().forward(x[i:i + 1], None) for i in range(x.shape[0])]
         return {"flow": [torch.cat([o[lvl] for o in outs], 0) for lvl in range(len(outs[0]))], "attn": None}

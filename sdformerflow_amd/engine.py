@@ -12,7 +12,8 @@ Turns the module tree (state_dict holder) into a flat schedule of C-ABI kernel l
     spike convolutions with the BN / residual / neuron epilogues fused; the large 96-channel 3x3 launches take int8 digit
     planes and the weight-resident kernel (csrc/spike_conv_wres.hip); no library kernel is left in the SNN forward
   * `forward(x, replicas=True)`: the B samples are B independent batch-1 forwards in one launch sequence (round 6; the route functions, `_slice_map`)
-  * `tape` (tests only) keeps every neuron layer's spikes for the spike-forced oracle replay (tests/replay.py)
+  * `tape` (tests only) keeps every neuron layer's spikes for the spike-forced oracle replay (tests/replay.py); a firing-rate
+    monitor (monitor.py) takes the same recording route and counts the spikes instead of keeping them
 
 Reference schedule being replaced: models/STSwinNet_SNN/Spiking_STSwinNet.py:161-182,278-305 and the
 call tree of SURVEY.md 3.2.  No CPU fallback: everything here raises off-GPU.
@@ -447,12 +448,44 @@ class MSFlowEngine:
             raise hip.SdfError(f"expected a contiguous fp32 (B,D,h,w,C) tensor, got shape {tuple(x.shape)} strides {x.stride()} "
                                f"{x.dtype}; call .contiguous() (the update is in place)")
 
-    def _rec(self, name, spikes, layout):
-        """Parity tape (tests only; `self.tape = []` switches it on, never during graph capture): a copy of the u8 spikes of
-        neuron layer `name` (the state_dict prefix of its Spiking_neuron); `layout` says how the copy maps onto the reference's
-        tensor at that call: "flat" = same memory order (reshape), "BDHWC->TBCHW" / "BDHWC->TBHWC" = permute."""
+    # A firing-rate monitor (monitor.FiringRateMonitor) while one of its forwards runs, else None: the model's forward sets and clears it.
+    monitor = None
+
+    @property
+    def taped(self):
+        """Whether this forward takes the recording route - the kernels that leave every neuron layer's spikes in memory (bit-equal
+        to the plain route, tests/test_replay_gpu.py): the parity tape or a firing-rate monitor asks for it.  Every site that
+        chooses between the two routes asks HERE."""
+        return self.tape is not None or self.monitor is not None
+
+    def _rec(self, name, spikes, layout, steps=None):
+        """The u8 spikes of neuron layer `name` (the state_dict prefix of its Spiking_neuron) on the recording route; `layout` says how
+        they map onto the reference's tensor at that call: "flat" = same memory order (reshape; the time steps are the leading
+        blocks - dim 0, or `steps` of them where the record is a (steps * rows, C) matrix), "BDHWC->TBCHW" / "BDHWC->TBHWC" =
+        permute (time steps on dim 1).  The parity tape (tests only; `self.tape = []` switches it on, never during graph capture)
+        keeps a copy; a firing-rate monitor counts them where they lie and keeps nothing."""
         if self.tape is not None:
             self.tape.append((name, spikes.clone(), layout))
+        if self.monitor is not None:
+            self.monitor.record(name, spikes if steps is None else spikes.view(steps, -1, spikes.shape[-1]), layout)
+
+    def _rec_gates(self, blk, q, e, Tq, B_, N1):
+        """Firing-rate monitor only: the two neuron calls of Spiking_QK_WindowAttention3D.forward whose spikes no kernel stores.
+        `attn.sn2_q`, the token gate `self.sn2_q(q.sum(-1, keepdim=True))` on (T', B_, nH, N, 1) (reference :687-693), is RECOMPUTED
+        here from the recorded q spikes - the head sums are exact small integers, the block's sn2_q runs over T' in the neuron kernel
+        - and is not a read-out of the fused kernel's gate; that the two agree is what the replay suite establishes through the gated
+        spikes.  `attn.attn_sn`, the dead attention score (:709-711), is `attention_score` on the gated spikes e."""
+        Cc, nH = q.shape[-1], blk.nH
+        rows = B_ * N1
+        n = rows * nH
+        n4 = (n + 3) // 4 * 4                           # (the neuron kernel moves 4 neurons per lane; the padding is not counted)
+        a = torch.zeros((Tq, n4), dtype=torch.float32, device=q.device)
+        a[:, :n] = q.reshape(Tq, rows, nH, Cc // nH).sum(-1, dtype=torch.float32).view(Tq, n)
+        g = torch.empty((Tq, n4), dtype=torch.uint8, device=q.device)
+        hip.neuron_fwd(a, g, Tq, 1, n4, 0, n4, 0, n4, blk.sn2_q)
+        self.monitor.record(blk.name + "attn.sn2_q.spiking_neuron.", g[:, :n], "flat")
+        s = attention_score(e, blk.attn_sn, nH, Tq, B_, N1)
+        self.monitor.record(blk.name + "attn.attn_sn.spiking_neuron.", s.to(torch.uint8), "flat")
 
     def _neuron_bd(self, x, p, bn=None, out_dtype=torch.uint8, out=None):
         """Neuron over D of a channel-last (B,D,h,w,C) activation, BN fused when given."""
@@ -617,12 +650,12 @@ class MSFlowEngine:
         rowmap, B_ = self._slice_map(B, D, H, W, ws, ss)
         Tq, N1 = ws[0], ws[1] * ws[2]
         rep_windows = B_ // B if self.replicas and B > 1 else 0
-        if rep_windows and (self.tape is not None or score_out is not None):
+        if rep_windows and (self.taped or score_out is not None):
             raise hip.SdfError("the parity tape and log=True follow one forward: run them without replicas")
         # one C-ABI call: neuron over the gathered slices -> q|k spike GEMM (+BN, +PE, neurons fused) -> token gate ->
         # projection spike GEMM through the head scramble with bias + BN + scatter + residual (csrc/qk_attn.hip)
         keep = [] if score_out is not None else None
-        if self.tape is not None:
+        if self.taped:
             # the slice spikes are overwritten by the gate inside the call: the tape runs the same kernel on the same input first
             rows, keep = B_ * N1, []
             xs = torch.empty((Tq, rows, Cc), dtype=torch.uint8, device=x.device)
@@ -637,12 +670,14 @@ class MSFlowEngine:
             # the gate's output replaced the slice spikes at the head of the workspace (csrc/qk_attn.hip)
             e = keep[0][:Tq * B_ * N1 * Cc].view(Tq, B_ * N1, Cc)
             score_out.append(attention_score(e, blk.attn_sn, blk.nH, Tq, B_, N1).view(Tq, B_, ws[1], ws[2], Cc))
-        if keep and self.tape is not None:
+        if keep and self.taped:
             M = Tq * B_ * N1
             qk = keep[0][(M * Cc + 255) // 256 * 256:][:M * 2 * Cc]
             q, k = (qk.view(M, 2 * Cc)[:, :Cc], qk.view(M, 2 * Cc)[:, Cc:]) if blk.qk is not None else (qk[:M * Cc], qk[M * Cc:])
             self._rec(blk.name + "attn.sn_q.spiking_neuron.", q.reshape(Tq, B_ * N1, Cc), "flat")
             self._rec(blk.name + "attn.sn_k.spiking_neuron.", k.reshape(Tq, B_ * N1, Cc), "flat")
+            if self.monitor is not None:
+                self._rec_gates(blk, q.reshape(Tq, B_ * N1, Cc), keep[0][:M * Cc].view(Tq, B_ * N1, Cc), Tq, B_, N1)
         self._emitted = bool(info.get("emitted"))
         return x
 
@@ -651,7 +686,7 @@ class MSFlowEngine:
         workspace with SN1's spikes already at its head (wide stages: left there by the attention's projection); `emit_next`: see
         _next_spikes."""
         self._check_cl(x)
-        keep = [] if self.tape is not None else None
+        keep = [] if self.taped else None
         hip.ms_mlp(x, blk.fc1, blk.fc2, blk.sn1, blk.sn2, keep_ws=keep, ws=ws, s1_ready=s1_ready, emit_next=emit_next)      # one C-ABI call (csrc/qk_attn.hip: sdf_ms_mlp_fwd)
         if keep:
             B, D, H, W, Cc = x.shape
@@ -665,7 +700,7 @@ class MSFlowEngine:
         last = self.scores is not None and i == len(self.stages[s]) - 1          # log=True: the last block of every stage (:1090-1105)
         # wide stages: the projection emits the MLP's first spikes (tiled hand-over layout; the tape / score paths keep row-major spikes
         # and let the MLP run its own first neuron)
-        ws = hip.ms_mlp_workspace(x, blk.fc1.N) if x.shape[-1] >= _WIDE_MINC and self.tape is None and not last else None
+        ws = hip.ms_mlp_workspace(x, blk.fc1.N) if x.shape[-1] >= _WIDE_MINC and not self.taped and not last else None
         self.attention(x, blk, self.scores if last else None, emit=(ws, blk.sn1) if ws is not None else None)
         return self.mlp(x, blk, ws=ws, s1_ready=self._emitted, emit_next=emit_next)
 
@@ -695,7 +730,7 @@ class MSFlowEngine:
         if spikes is not None:
             out = hip.ms_patch_merge(spikes, lin)
             if out is not None:
-                if self.tape is not None:                   # the tape holds the reference's (T, B, H/2, W/2, 4C) concatenation
+                if self.taped:                   # the tape holds the reference's (T, B, H/2, W/2, 4C) concatenation
                     src, H2, W2 = merge_row_map(B, D, H, W)
                     idx = torch.from_numpy(src.reshape(-1).astype("int64")).to(x.device)
                     flat = torch.cat([spikes.view(-1, Cc), spikes.new_zeros(1, Cc)], 0)
@@ -823,7 +858,7 @@ class MSFlowEngine:
             for b in range(B):
                 hip.neuron_fwd(src[b], s[b].view(-1)[c0:], D, hw, take, pitch, hw * pitch, cp, hw * cp, sn)
             c0 += take
-        if self.tape is not None:                                         # the reference's channel order is [prediction | y | skip]
+        if self.taped:                                         # the reference's channel order is [prediction | y | skip]
             npred = self.preds[i - 1].nout if i > 0 else 0
             self._rec(name, torch.cat([s[..., C1 + C2:C1 + C2 + npred], s[..., :C1 + C2]], -1), "BDHWC->TBCHW")
         return s, "perm"
@@ -884,8 +919,8 @@ class MSFlowEngine:
             carried = ready[i + 1] if ready is not None else torch.empty((B, D, H2, W2, cp_n), dtype=torch.uint8, device=z.device)
             nxt = (carried, self.decoders[i + 1].sn, 0, cin_n - 4, (cin_n, cp_n - cin_n))
         pred, self._flows[i], sp = hip.pred_head(z, pr.w, pr.b, pr.sn, fs[0] if fs else None, fs[1] if fs else None,
-                                                 want_pred=self.tape is not None or fs is None or (i + 1 < E and nxt is None),
-                                                 nxt=nxt, keep=self.tape is not None)
+                                                 want_pred=self.taped or fs is None or (i + 1 < E and nxt is None),
+                                                 nxt=nxt, keep=self.taped)
         if sp is not None:
             self._rec(name, sp, "BDHWC->TBCHW")
         return pred, carried
@@ -907,7 +942,7 @@ class MSFlowEngine:
         # Regular pyramid (every level twice the size of the one before, every prediction head on its one-launch kernel): the
         # spike images of ALL levels are laid out now and the decoders' neuron on the four skip tensors - four small launches
         # before - is ONE launch (sdf_neuron_multi_fwd); the [y | prediction] slices arrive from the level above's head.
-        ready = self._prepare_decoder_images(feats, y, out_size, levels) if self.tape is None else None
+        ready = self._prepare_decoder_images(feats, y, out_size, levels) if not self.taped else None
         carried = None          # this level's spike image with the [y | prediction] slices already written by the previous level's head
         for i, level in enumerate(levels):
             skip = feats[E - 1 - i]

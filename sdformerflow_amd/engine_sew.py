@@ -105,8 +105,8 @@ class SEWFlowEngine(MSFlowEngine):
         out = torch.empty((M, Cc), dtype=out_dtype, device=y.device)
         n = M // T * Cc
         hip.neuron_fwd(y, out, T, 1, n, 0, n, 0, n, p, alpha=bn[0], beta=bn[1], Cch=Cc, inner=1)
-        if self.tape is not None:                     # (the byte copy is the tape's: not made when nothing records it)
-            self._rec(name, out.to(torch.uint8) if out_dtype != torch.uint8 else out, "flat")
+        if self.taped:                     # (the byte copy is the tape's: not made when nothing records it)
+            self._rec(name, out.to(torch.uint8) if out_dtype != torch.uint8 else out, "flat", steps=T)
         return out
 
     # ------------------------------------------------------------------ stages
@@ -133,7 +133,7 @@ class SEWFlowEngine(MSFlowEngine):
             spk[n] = torch.empty((M, Cc), dtype=torch.uint8, device=x.device)
             hip.neuron_fwd(y, spk[n], Tq, 1, M // Tq * Cc, 0, 0, 0, M // Tq * Cc, blk.sn[n], rowmap=rowmap, rowlen=Cc,
                            alpha=blk.bn[n][0], beta=blk.bn[n][1], Cch=Cc, inner=1)
-            self._rec(blk.name + f"attn.sn_{n}.spiking_neuron.", spk[n], "flat")
+            self._rec(blk.name + f"attn.sn_{n}.spiking_neuron.", spk[n], "flat", steps=Tq)
         mask = self._mask(D, H, W, ws, ss) if any(s > 0 for s in ss) else None
         z = hip.win_attn_sew(spk["q"], spk["k"], spk["v"], blk.scale, blk.bias(Tq * N1), mask, blk.nH, Tq, B_, N1)
         y = hip.dense_linear(z.view(M, Cc), blk.wp, blk.bp)
@@ -149,7 +149,7 @@ class SEWFlowEngine(MSFlowEngine):
         y = torch.empty((B, D, H, W, Cc), dtype=torch.float32, device=x.device)
         hip.spike_gemm(s1, blk.fc2.Wp, y, B * D * H * W, Cc, blk.fc2.K, alpha=blk.fc2.alpha, beta=blk.fc2.beta)
         s2 = self._neuron_bd(y, blk.sn2, out_dtype=torch.float32)
-        if self.tape is not None:
+        if self.taped:
             self._rec(blk.name + "mlp.sn2.spiking_neuron.", s2.to(torch.uint8), "BDHWC->TBHWC")
         return s2
 
@@ -200,7 +200,7 @@ class SEWFlowEngine(MSFlowEngine):
         s1 = self._neuron_bd(y, rb.sn1, bn=rb.bn1)
         self._rec(rb.name + "sn1.spiking_neuron.", s1, "BDHWC->TBCHW")
         s2 = self._neuron_bd(self._conv3x3(s1, rb.w2, rb.C, bn=rb.bn2), rb.sn2, out_dtype=torch.float32)
-        if self.tape is not None:
+        if self.taped:
             self._rec(rb.name + "sn2.spiking_neuron.", s2.to(torch.uint8), "BDHWC->TBCHW")
         return s2 + x
 

@@ -120,7 +120,36 @@ def event_pairs_to_chunk(pairs, num_frames, sensor_size, crop, norm_input, spike
     return (chunk, chunk.sum(1).sum(1, keepdim=True).bool().float()) if want_event_mask else chunk
 
 
-def evaluate_mv(model, samples, config, device="cuda"):
+def _with_firing_rates(loop, model, samples, config, device, monitor):
+    """`loop(model, samples, config, device)` - and, when `vis.monitor_fr` is true (the reference's key, eval_DSEC_flow_SNN.py:140-143),
+    its forwards under a monitor.FiringRateMonitor (the caller's `monitor`, or a new one; left as enabled or disabled as it came) and
+    two more entries in the dict: "firing_rate" (what the reference prints, :223-227) and "firing_rates" (call name -> its T rates,
+    averaged over the forwards).  Key false or absent: the loop alone."""
+    if not (config.get("vis") or {}).get("monitor_fr"):
+        return loop(model, samples, config, device)
+    if monitor is None:
+        from .monitor import FiringRateMonitor
+        monitor = FiringRateMonitor(model)
+    elif monitor.model is not model:
+        raise ValueError("monitor= belongs to another model: it would record nothing here - pass a FiringRateMonitor of this model, or none")
+    was_on = monitor.enabled
+    monitor.enable()
+    try:
+        result = loop(model, samples, config, device)
+    finally:
+        if not was_on:
+            monitor.disable()
+    result["firing_rate"], result["firing_rates"] = monitor.mean(), monitor.rates()
+    return result
+
+
+def evaluate_mv(model, samples, config, device="cuda", monitor=None):
+    """harness.evaluate's counterpart for the MVSEC / MDR sample dicts (`_evaluate_mv`: the loop itself); `vis.monitor_fr` true: the
+    forwards run under a FiringRateMonitor (`monitor`, or a new one) and the dict also has "firing_rate" and "firing_rates"."""
+    return _with_firing_rates(_evaluate_mv, model, samples, config, device, monitor)
+
+
+def _evaluate_mv(model, samples, config, device="cuda"):
     """The model-facing loop of eval_MV_flow_SNN.py:157-249 over an iterable of sample dicts, either the reference loader's
     ('event_volume_old', 'event_volume_new' (B, num_frames, h, w), 'flow' (B, 2, h, w), 'valid' (B, h, w)) or the raw form
     ('events_old', 'events_new': event dicts, or lists of B of them; 'flow', 'valid' at the sensor's or the crop's size, with or without
@@ -182,7 +211,14 @@ def evaluate_mv(model, samples, config, device="cuda"):
     return {k: v / max(it, 1) for k, v in tot.items()}
 
 
-def evaluate(model, samples, config, device="cuda"):
+def evaluate(model, samples, config, device="cuda", monitor=None):
+    """The evaluation loop (`_evaluate`); `vis.monitor_fr` true: its forwards run under a FiringRateMonitor (`monitor`, or a new one) and
+    the dict also has "firing_rate" (its mean()) and "firing_rates" (name -> T rates averaged over the forwards); false or absent:
+    nothing changes."""
+    return _with_firing_rates(_evaluate, model, samples, config, device, monitor)
+
+
+def _evaluate(model, samples, config, device="cuda"):
     """Run `model` over an iterable of (chunk (B,bins,H,W), mask (B,H,W), label (B,2,H,W)) like
     valid_test does and return the running-mean metrics dict (AEE, PE1-3, outliers) (:253-271, :283-305).
     `chunk` may also be the raw event dict {'ts', 'x', 'y', 'p'} DSECDatasetLite yields when data.preprocessed is false (one sample;
@@ -255,6 +291,9 @@ class StreamEvaluator:
     def __init__(self, model, config, device="cuda", replicas=10, streams=2, graphs=True):
         if replicas < 1 or streams < 1:
             raise ValueError("replicas and streams are at least 1")
+        if (config.get("vis") or {}).get("monitor_fr"):
+            raise RuntimeError("vis.monitor_fr is set: firing rates are counted on single eager forwards, not under replicas and captured "
+                               "graphs - use harness.evaluate / evaluate_mv for the rates, or clear the key for the throughput scheme")
         self.model, self.config, self.device = model, config, torch.device(device)
         self.R, self.F, self.graphs = int(replicas), int(streams), bool(graphs)
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.F)]

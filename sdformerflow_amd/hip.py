@@ -282,6 +282,11 @@ class PrepareChunkDesc(C.Structure):
                 ("per_sample", C.c_int32), ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
 
 
+class SpikeCountDesc(C.Structure):
+    _fields_ = [("spikes", C.c_void_p), ("outer", C.c_int64), ("T", C.c_int), ("rows", C.c_int64), ("C", C.c_int),
+                ("row_stride", C.c_int64), ("counts", C.c_void_p)]
+
+
 # The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
 # plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
 # still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
@@ -348,6 +353,7 @@ SIGNATURES = {
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
     "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
     "sdf_prepare_chunk_workspace_bytes": (_i64, (_i,)), "sdf_prepare_chunk_fwd": (_i, (_P(PrepareChunkDesc), _p)),
+    "sdf_spike_count_fwd": (_i, (_P(SpikeCountDesc), _p)),
 }
 
 
@@ -2124,3 +2130,56 @@ def prepare_chunk(voxel, crop=None, norm_input="minmax", spike_th=None, per_samp
     _note(bytes=B * bins * h * w * 4 * (1 + 2 + 4 * (norm == 1 or spike_th is not None)), shape=shape)
     _check(lib().sdf_prepare_chunk_fwd(C.byref(d), _stream()), "sdf_prepare_chunk_fwd")
     return out
+
+
+def spike_count_form(spikes, t_dim):
+    """(outer, T, rows, C, row_stride) of a u8 tensor or view in sdf_spike_count_fwd's addressing form - element (o, t, r, c) at byte
+    ((o T + t) rows + r) row_stride + c behind its first element - with the time steps on dim `t_dim`: 0 (T outermost, outer = 1) or
+    1 (a batch in front).  The last dim is the counted run C when it is dense, the dims between it and the step axis must nest into
+    ONE row index.  SdfError for everything else (host arithmetic on shapes and strides: no tensor is touched)."""
+    if t_dim not in (0, 1) or spikes.dim() <= t_dim:
+        raise SdfError(f"spike_count: the step axis is dim 0 or 1 of the tensor, got t_dim {t_dim} for shape {tuple(spikes.shape)}")
+    if spikes.numel() == 0:
+        raise SdfError(f"spike_count: empty tensor {tuple(spikes.shape)}", rc=E_SHAPE)
+    shape, st = list(spikes.shape), list(spikes.stride())
+    outer, s_o = (shape[0], st[0]) if t_dim == 1 else (1, 0)
+    T, s_t = shape[t_dim], st[t_dim]
+    dims = [(n, s) for n, s in zip(shape[t_dim + 1:], st[t_dim + 1:]) if n > 1]
+    Cc = dims.pop()[0] if dims and dims[-1][1] == 1 else 1
+    rows, rs = 1, None
+    for n, s in reversed(dims):
+        if rs is None:
+            rs = s
+        elif s != rows * rs:
+            raise SdfError(f"spike_count: shape {tuple(spikes.shape)} with strides {tuple(spikes.stride())} is not (outer, T, rows, C) with "
+                           "one row stride; count the parts one by one")
+        rows *= n
+    if rs is None:                                  # a single row per (o, t): the blocks' own distance is its stride
+        rs = s_t if T > 1 else (s_o if outer > 1 else Cc)
+    if rs < Cc or (T > 1 and s_t != rows * rs) or (outer > 1 and s_o != T * rows * rs):
+        raise SdfError(f"spike_count: shape {tuple(spikes.shape)} with strides {tuple(spikes.stride())} is not (outer, T, rows, C) with "
+                       "(o, t) blocks rows x row stride apart; count the parts one by one")
+    return outer, T, rows, Cc, rs
+
+
+def spike_count(spikes, t_dim, counts=None):
+    """Spikes per time step of a u8 tensor or view (sdf_spike_count_fwd): counts[t] += the sum over everything but dim `t_dim` (0, or
+    1 behind a batch dim).  `counts`: a contiguous int64 tensor of T entries on the same device that is ADDED to (default: a new,
+    zeroed one).  Views are counted in place - channel slices, halves of a stacked buffer, slices of a workspace (spike_count_form);
+    there is no .contiguous() and no torch fallback: a layout outside that form raises SdfError."""
+    if not torch.is_tensor(spikes) or not spikes.is_cuda:
+        raise SdfError("spike_count: HIP path needs a device tensor (no CPU fallback)")
+    if spikes.dtype != torch.uint8:
+        raise SdfError(f"spike_count: spikes are u8, got {spikes.dtype}", rc=E_DTYPE)
+    outer, T, rows, Cc, rs = spike_count_form(spikes, t_dim)
+    if counts is None:
+        counts = torch.zeros(T, dtype=torch.int64, device=spikes.device)
+    elif not (torch.is_tensor(counts) and counts.is_cuda and counts.device == spikes.device and counts.dtype == torch.int64
+              and counts.dim() == 1 and counts.numel() == T and counts.is_contiguous()):
+        raise SdfError(f"spike_count: counts must be a contiguous int64 tensor of T = {T} entries on {spikes.device}")
+    d = SpikeCountDesc()
+    d.spikes, d.counts = spikes.data_ptr(), counts.data_ptr()
+    d.outer, d.T, d.rows, d.C, d.row_stride = outer, T, rows, Cc, rs
+    _note(bytes=outer * T * rows * Cc, shape=(outer, T, rows, Cc))
+    _check(lib().sdf_spike_count_fwd(C.byref(d), _stream()), "sdf_spike_count_fwd")
+    return counts
