@@ -240,6 +240,12 @@ int sdf_neuron_fwd(const SdfNeuronDesc* d, void* stream);
 /* n independent neuron calls as ONE launch when they share T in {2, 4, 5, 10, 20} and n <= 6 (otherwise one launch each): the
  * U-Net decoders' skip inputs - four small tensors that each paid a launch of their own (reference Spiking_modules.py:467-474). */
 int sdf_neuron_multi_fwd(const SdfNeuronDesc* descs, int n, void* stream);
+/* The general launch with the GLIF recurrence (the reference's GatedLIFNode, sdf_glif_fwd's arithmetic from v = 0, s = 0): the addressing
+ * contract of sdf_neuron_fwd field for field - dense strides, rowmap gather, alpha / beta, add, nrep, out_dtype - and `tab` =
+ * [L, Dk, g, R, th, c_0 .. c_{T-1}] in DEVICE memory as sdf_glif_fwd takes it.  kind, tau, v_th, v_reset, soft_reset and psn_* are not
+ * read; v_last must be NULL and T in {2, 4, 5, 10, 20} (SDF_E_SHAPE), tab not NULL (SDF_E_NULL); every other check, and their order,
+ * are sdf_neuron_fwd's.  What an eval forward of a GLIF model launches at every neuron call (no fused epilogue has a GLIF form). */
+int sdf_glif_neuron_fwd(const SdfNeuronDesc* d, const float* tab, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Spike GEMM:  out[M,N] = epilogue( A[M,K] (binary, u8) x W[N,K]^T ).
@@ -589,6 +595,10 @@ int sdf_qk_gate_fwd(const uint8_t* q, const uint8_t* k, uint8_t* e, int Tq, int6
 int sdf_qk_gate_strided_fwd(const uint8_t* q, const uint8_t* k, uint8_t* e, int Tq, int64_t rows, int C,
                             int64_t ldq, int64_t ldk, int kind, float tau, float v_th, float v_reset,
                             int soft_reset, const float* psn_w, const float* psn_b, void* stream);
+/* The strided gate with a GLIF gate node: A = GLIF_T'(a) from v = 0, s = 0 with `tab` = [L, Dk, g, R, th, c_0 .. c_{Tq-1}] in DEVICE
+ * memory; Tq in {2, 4}.  `gate` (Tq, rows, C / 32) u8, when not NULL, also receives A itself.  C, ldq, ldk and alignment as above. */
+int sdf_qk_gate_glif_fwd(const uint8_t* q, const uint8_t* k, uint8_t* e, uint8_t* gate, const float* tab, int Tq, int64_t rows,
+                         int C, int64_t ldq, int64_t ldk, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Head of the patch embedding: conv3x3 / pad 1 (no bias) on the real-valued event voxel -> eval BatchNorm -> neuron over T,

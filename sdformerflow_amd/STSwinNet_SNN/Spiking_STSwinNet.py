@@ -137,6 +137,7 @@ class MS_SpikingformerFlowNet(nn.Module):
                             "use_upsample_conv": unet_kwargs.get("use_upsample_conv", True)})
         self.sttmultires_unet = self.unet_type(unet_kwargs, dict(stt_kwargs))
         self._engine, self._stamp_tensors = None, None
+        self._glif_engine = None      # the unfused eval plan of a GLIF model (eval_engine)
         self._fr_monitor = None       # a monitor.FiringRateMonitor while it is enabled (it lives here, not on the engine: rebuilds keep it)
         # Weight planes of the spike GEMMs / convolutions (binary spikes are exact in 16-bit floats, accumulation is fp32):
         #   2 = fp16 hi + lo of the power-of-two-scaled weight: 22 of the 24 significand bits at 2/3 of the matrix work.
@@ -158,14 +159,14 @@ class MS_SpikingformerFlowNet(nn.Module):
             elif isinstance(m, nn.Conv2d):
                 nn.init.xavier_uniform_(m.weight)
         self.apply(_init)
-        self._engine = None
+        self._engine = self._glif_engine = None
 
     def load_state_dict(self, *a, **k):
-        self._engine = None
+        self._engine = self._glif_engine = None
         return super().load_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):
-        self._engine, self._stamp_tensors = None, None
+        self._engine, self._glif_engine, self._stamp_tensors = None, None, None
         return super()._apply(fn, *a, **k)
 
     def _weights_stamp(self):
@@ -181,12 +182,12 @@ class MS_SpikingformerFlowNet(nn.Module):
 
     def invalidate_engine(self):
         """For callers that swap tensors out behind the module's back (`p.data = ...`), which no version counter sees."""
-        self._engine, self._stamp_tensors = None, None
+        self._engine, self._glif_engine, self._stamp_tensors = None, None, None
 
     def train(self, mode=True):
         """Entering training invalidates the packed inference plan (weights and BN statistics are about to change)."""
         if mode:
-            self._engine = None
+            self._engine = self._glif_engine = None
         return super().train(mode)
 
     def engine(self):
@@ -203,6 +204,18 @@ class MS_SpikingformerFlowNet(nn.Module):
         from ..engine import MSFlowEngine
         return MSFlowEngine(self)
 
+    def eval_engine(self):
+        """The plan an eval forward runs on: `engine()`, except for a model built with GLIF neurons - no fused kernel has a GLIF
+        form and `engine()` keeps refusing it - whose forward runs unfused on `engine_glif.GLIFFlowEngine`.  Rebuilt on the same
+        weight stamp as `engine()` (the gate tables and planes are packed copies)."""
+        if self.sttmultires_unet.spiking_kwargs.get("neuron_type") != "glif":
+            return self.engine()
+        stamp = self._weights_stamp()
+        if self._glif_engine is None or self._glif_stamp != stamp:
+            from ..engine_glif import GLIFFlowEngine
+            self._glif_engine, self._glif_stamp = GLIFFlowEngine(self), stamp
+        return self._glif_engine
+
     def flops(self):
         """reference :307-308."""
         return self.sttmultires_unet.flops()
@@ -218,8 +231,8 @@ class MS_SpikingformerFlowNet(nn.Module):
     def _engine_forward(self, x, scores=None):
         """The eval forward on the packed plan - through the firing-rate monitor while one is enabled (monitor.FiringRateMonitor)."""
         if self._fr_monitor is not None:
-            return self._fr_monitor.forward(x, scores)          # (asks for self.engine() itself, behind its refusals)
-        return self.engine().forward(x, scores)
+            return self._fr_monitor.forward(x, scores)          # (asks for self.eval_engine() itself, behind its refusals)
+        return self.eval_engine().forward(x, scores)
 
     def forward(self, x, log=False):
         if self.training:                     # train-mode forward under autograd (batch-stat BN, HIP neurons both ways)
@@ -242,7 +255,7 @@ class MS_SpikingformerFlowNet(nn.Module):
         from .. import hip
 
         def one_by_one():
-            outs = [self.engine().forward(x[i:i + 1], None) for i in range(x.shape[0])]
+            outs = [self.eval_engine().forward(x[i:i + 1], None) for i in range(x.shape[0])]
             return [torch.cat([o[lvl] for o in outs], 0) for lvl in range(len(outs[0]))]
         with torch.no_grad():
             if self.gemm_nsplit != 2 and x.shape[0] > 1:
@@ -251,10 +264,11 @@ class MS_SpikingformerFlowNet(nn.Module):
                 flows = one_by_one()
             else:
                 try:
-                    flows = self.engine().forward(x, None, replicas=True)
+                    flows = self.eval_engine().forward(x, None, replicas=True)
                 except hip.ReplicaGeometryError:
                     # an odd window count per sample at some stage (e.g. 256 x 320: 175 windows at stage 0): the replica tables cannot
-                    # keep a sample's head scramble inside one attention step - one by one (nothing persistent was touched before the raise)
+                    # keep a sample's head scramble inside one attention step - or a GLIF model, whose plan has no replica form -
+                    # one by one (nothing persistent was touched before the raise)
                     flows = one_by_one()
         return {"flow": flows, "attn": None}
 
@@ -273,6 +287,10 @@ class SpikingformerFlowNet(MS_SpikingformerFlowNet):
     def _make_engine(self):
         from ..engine_sew import SEWFlowEngine
         return SEWFlowEngine(self)
+
+    def eval_engine(self):
+        """The SEW plan; a SEW model built with GLIF neurons is refused by it ("no fused kernel": the unfused GLIF plan is the MS family's)."""
+        return self.engine()
 
     def forward(self, x, log=False):
         if self.training:                     # train-mode forward under autograd (the SEW attention backward: csrc/win_attn_sew_bwd.hip)

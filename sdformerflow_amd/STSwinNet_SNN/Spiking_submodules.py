@@ -118,7 +118,8 @@ class GatedLIFNode(nn.Module):
     Spiking_modules.py:84-92).  The recurrence runs on csrc/glif.hip: one launch in eval mode, `autograd.GLIFFunction` (forward +
     BPTT with the gradients of all 7 + T gate logits) in train mode.  The kernels take the gates as the derived table `table()`
     builds on the device.  Every call starts from v = 0, s = 0 (the harness resets the net before every forward).  The fused
-    engines refuse a model built with it (no shipped configuration uses it)."""
+    engines refuse a model built with it (no shipped configuration uses it); an MS model's eval forward runs unfused on
+    `engine_glif.GLIFFlowEngine`, which forms the table on the host at pack time (`engine_glif.gate_table`)."""
     kind = "glif"
     supported_backends = ("torch", "hip")
 

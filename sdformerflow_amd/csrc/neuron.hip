@@ -60,11 +60,15 @@ __device__ __forceinline__ float4 prologue(const NeuronParams& P, float4 x, int 
   return x;
 }
 
-// T is a compile-time constant (register-resident x) when TT > 0, else runtime (streaming, LIF/IF only).
-template <int TT>
-__device__ __forceinline__ void neuron_body(const NeuronParams& P, int64_t q) {
-  if (q >= P.quads) return;
-  const int T = TT > 0 ? TT : P.d.T;
+// Where quad q of a launch lies: element e of its problem (batch element b, offset r), the problem's offset in x, the quad's offset
+// in out at step 0, and the BN affine of its four channels.
+struct Quad {
+  int64_t e, xrep, b, r, obase;
+  float4 al, be;
+};
+
+__device__ __forceinline__ Quad quad_of(const NeuronParams& P, int64_t q) {
+  Quad Q;
   int64_t e = q * 4, xrep = 0, orep = 0;
   if (P.d.nrep > 1) {                                            // outermost dimension: nrep equally laid out problems (dense mode)
     const int64_t per = P.d.nb * P.d.ni, rp = e / per;
@@ -74,21 +78,33 @@ __device__ __forceinline__ void neuron_body(const NeuronParams& P, int64_t q) {
   }
   const int64_t b = e / P.d.ni;
   const int64_t r = e - b * P.d.ni;
-  const int64_t obase = orep + b * P.d.o_sb + r;
-
-  float4 al = make_float4(1.f, 1.f, 1.f, 1.f), be = make_float4(0.f, 0.f, 0.f, 0.f);
+  Q.e = e; Q.xrep = xrep; Q.b = b; Q.r = r;
+  Q.obase = orep + b * P.d.o_sb + r;
+  Q.al = make_float4(1.f, 1.f, 1.f, 1.f);
+  Q.be = make_float4(0.f, 0.f, 0.f, 0.f);
   if (P.d.alpha) {
     if (P.d.inner == 1) {
       int c = (int)(r % P.d.C);
-      al = load4(P.d.alpha + c);
-      be = load4(P.d.beta + c);
+      Q.al = load4(P.d.alpha + c);
+      Q.be = load4(P.d.beta + c);
     } else {
       int c = (int)((r / P.d.inner) % P.d.C);
       float a = P.d.alpha[c], bb = P.d.beta[c];
-      al = make_float4(a, a, a, a);
-      be = make_float4(bb, bb, bb, bb);
+      Q.al = make_float4(a, a, a, a);
+      Q.be = make_float4(bb, bb, bb, bb);
     }
   }
+  return Q;
+}
+
+// T is a compile-time constant (register-resident x) when TT > 0, else runtime (streaming, LIF/IF only).
+template <int TT>
+__device__ __forceinline__ void neuron_body(const NeuronParams& P, int64_t q) {
+  if (q >= P.quads) return;
+  const int T = TT > 0 ? TT : P.d.T;
+  const Quad Q = quad_of(P, q);
+  const int64_t e = Q.e, xrep = Q.xrep, b = Q.b, r = Q.r, obase = Q.obase;
+  const float4 al = Q.al, be = Q.be;
 
   if constexpr (TT > 0) {
     float4 xv[TT];
@@ -172,6 +188,35 @@ __global__ __launch_bounds__(256) void neuron_kernel(NeuronParams P) {
   neuron_body<TT>(P, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
+// GLIF (neuron_step.h glif_step, from v = 0, s = 0) behind the same addressing, prologue and spike store: a kernel of its own, so
+// that neuron_body keeps its registers.  `tab` = [L, Dk, g, R, th, c_0 .. c_{T-1}] in device memory, as glif.hip takes it.
+template <int TT>
+__global__ __launch_bounds__(256) void glif_neuron_kernel(NeuronParams P, const float* __restrict__ tab) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= P.quads) return;
+  const Quad Q = quad_of(P, q);
+  float4 xv[TT];
+#pragma unroll
+  for (int t = 0; t < TT; ++t) {
+    const float* p = x_addr(P, t, Q.e, Q.b, Q.r, Q.xrep);
+    xv[t] = p ? load4(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+#pragma unroll
+  for (int t = 0; t < TT; ++t) xv[t] = prologue(P, xv[t], t, Q.r, Q.al, Q.be);
+  GlifGates G;
+  G.L = tab[0]; G.Dk = tab[1]; G.g = tab[2]; G.R = tab[3]; G.th = tab[4];
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f), s = v;
+#pragma unroll
+  for (int t = 0; t < TT; ++t) {
+    const float c = tab[5 + t];
+    glif_step(v.x, s.x, xv[t].x, c, G);
+    glif_step(v.y, s.y, xv[t].y, c, G);
+    glif_step(v.z, s.z, xv[t].z, c, G);
+    glif_step(v.w, s.w, xv[t].w, c, G);
+    store_spikes(P, Q.obase + (int64_t)t * P.d.o_st, s);
+  }
+}
+
 // Several independent neuron calls of the same T as ONE launch (the decoders' skip inputs: four small tensors, each a launch of
 // its own before): workgroup ranges are dealt to the descriptors by `first[]`
 constexpr int MULTI_MAX = 6;
@@ -239,11 +284,13 @@ int launch_scalar(const float* x, void* spike, float* v_last, int T, int64_t N, 
   return 0;
 }
 
-int validate(const SdfNeuronDesc& d) {
+// `glif`: the descriptor of sdf_glif_neuron_fwd - its T list, no v_last, and none of the neuron fields (kind, tau, psn_*) is read
+int validate(const SdfNeuronDesc& d, bool glif = false) {
   if (!d.x || !d.out) return SDF_E_NULL;
   if (d.T < 1 || d.nb < 1 || d.ni < 4) return SDF_E_SHAPE;
+  if (glif && (!sdf_in(SDF_T_GLIF, d.T) || d.v_last)) return SDF_E_SHAPE;
   if (d.out_dtype != SDF_F32 && d.out_dtype != SDF_U8) return SDF_E_DTYPE;
-  if (d.kind != SDF_LIF && d.kind != SDF_PSN && d.kind != SDF_IF) return SDF_E_DTYPE;
+  if (!glif && d.kind != SDF_LIF && d.kind != SDF_PSN && d.kind != SDF_IF) return SDF_E_DTYPE;
   if (d.ni % 4 || d.o_sb % 4 || d.o_st % 4) return SDF_E_SHAPE;
   if (!sdf_aligned(d.x, 16) || !sdf_aligned(d.out, d.out_dtype == SDF_F32 ? 16 : 4)) return SDF_E_ALIGN;
   if (d.nrep < 0 || (d.nrep > 1 && (d.rowmap || d.x_srep % 4 || d.o_srep % 4))) return SDF_E_SHAPE;      // (the outer dimension is a dense-mode feature)
@@ -259,6 +306,7 @@ int validate(const SdfNeuronDesc& d) {
     if (d.inner == 1 && (!sdf_aligned(d.alpha, 16) || !sdf_aligned(d.beta, 16))) return SDF_E_ALIGN;
   }
   if (d.add && (d.add_period < 4 || d.add_period % 4 || d.add_st % 4 || !sdf_aligned(d.add, 16))) return SDF_E_SHAPE;
+  if (glif) return 0;
   if (d.kind == SDF_PSN) {
     if (!d.psn_w || !d.psn_b) return SDF_E_NULL;
     if (d.v_last) return SDF_E_SHAPE;
@@ -291,6 +339,20 @@ extern "C" int sdf_neuron_fwd(const SdfNeuronDesc* dp, void* stream) {
     if (dp->kind == SDF_PSN) return SDF_E_SHAPE;
     SDF_LAUNCH(neuron_kernel<0>, grid, block, 0, s, P);            // any other T: the runtime-T kernel
   }
+  SDF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sdf_glif_neuron_fwd(const SdfNeuronDesc* dp, const float* tab, void* stream) {
+  if (!dp || !tab) return SDF_E_NULL;
+  int rc = validate(*dp, true);
+  if (rc) return rc;
+  if (!sdf_aligned(tab, 4)) return SDF_E_ALIGN;
+  NeuronParams P = neuron_params(*dp);
+  if (sdf_quad_blocks(P.quads * 4) >= (1LL << 31)) return SDF_E_SHAPE;
+  dim3 grid((unsigned)sdf_quad_blocks(P.quads * 4)), block(256);
+  hipStream_t s = sdf_stream(stream);
+  sdf_dispatch(SDF_T_GLIF, dp->T, [&](auto tt) { SDF_LAUNCH(glif_neuron_kernel<tt>, grid, block, 0, s, P, tab); });   // (validated: T is in the list)
   SDF_LAUNCH_CHECK();
   return 0;
 }

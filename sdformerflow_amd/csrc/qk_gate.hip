@@ -76,6 +76,45 @@ __global__ __launch_bounds__(256) void qk_gate_kernel(GateParams P) {
     }
   }
 }
+
+// The same gate with a GLIF gate node (neuron_step.h glif_step from v = 0, s = 0; `tab` = [L, Dk, g, R, th, c_0 .. c_{Tq-1}] in
+// device memory): a kernel of its own, the LIF / PSN kernel above keeps its registers.  `gate` (Tq, rows, G) u8 also receives the
+// gate's own spikes when it is not NULL.
+template <int TQ>
+__global__ __launch_bounds__(256) void qk_gate_glif_kernel(const uint8_t* __restrict__ q, const uint8_t* __restrict__ k, uint8_t* __restrict__ e,
+                                                           uint8_t* __restrict__ gate, const float* __restrict__ tab, int64_t rows, int C,
+                                                           int G, int64_t ldq, int64_t ldk) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * G) return;
+  const int64_t step = rows * (int64_t)C;
+  const int64_t off = i * 32;                       // (row*G + g)*32 == row*C + g*32
+  const int64_t row = i / G;
+  const int g32 = (int)(i - row * G) * 32;
+  const int64_t qoff = row * ldq + g32, koff = row * ldk + g32;
+  float a[TQ];
+  uint4 k0[TQ], k1[TQ];
+#pragma unroll
+  for (int t = 0; t < TQ; ++t) {
+    const uint4* qp = reinterpret_cast<const uint4*>(q + t * rows * ldq + qoff);
+    const uint4 x0 = qp[0], x1 = qp[1];
+    a[t] = (float)(__popc(x0.x) + __popc(x0.y) + __popc(x0.z) + __popc(x0.w) + __popc(x1.x) + __popc(x1.y) + __popc(x1.z) + __popc(x1.w));
+    const uint4* kp = reinterpret_cast<const uint4*>(k + t * rows * ldk + koff);
+    k0[t] = kp[0];
+    k1[t] = kp[1];
+  }
+  GlifGates Gt;
+  Gt.L = tab[0]; Gt.Dk = tab[1]; Gt.g = tab[2]; Gt.R = tab[3]; Gt.th = tab[4];
+  float v = 0.f, s = 0.f;
+#pragma unroll
+  for (int t = 0; t < TQ; ++t) {
+    glif_step(v, s, a[t], tab[5 + t], Gt);
+    const uint32_t msk = s != 0.f ? 0xFFFFFFFFu : 0u;
+    uint4* ep = reinterpret_cast<uint4*>(e + t * step + off);
+    ep[0] = make_uint4(k0[t].x & msk, k0[t].y & msk, k0[t].z & msk, k0[t].w & msk);
+    ep[1] = make_uint4(k1[t].x & msk, k1[t].y & msk, k1[t].z & msk, k1[t].w & msk);
+    if (gate) gate[t * rows * G + i] = (uint8_t)(msk & 1u);
+  }
+}
 }  // namespace
 
 extern "C" int sdf_qk_gate_strided_fwd(const uint8_t* q, const uint8_t* k, uint8_t* e, int Tq, int64_t rows, int C, int64_t ldq,
@@ -102,4 +141,21 @@ extern "C" int sdf_qk_gate_fwd(const uint8_t* q, const uint8_t* k, uint8_t* e, i
                                float tau, float v_th, float v_reset, int soft_reset, const float* psn_w,
                                const float* psn_b, void* stream) {
   return sdf_qk_gate_strided_fwd(q, k, e, Tq, rows, C, C, C, kind, tau, v_th, v_reset, soft_reset, psn_w, psn_b, stream);
+}
+
+extern "C" int sdf_qk_gate_glif_fwd(const uint8_t* q, const uint8_t* k, uint8_t* e, uint8_t* gate, const float* tab, int Tq,
+                                    int64_t rows, int C, int64_t ldq, int64_t ldk, void* stream) {
+  if (!q || !k || !e || !tab) return SDF_E_NULL;
+  if ((Tq != 2 && Tq != 4) || rows < 1 || C < 32 || C % 32) return SDF_E_SHAPE;
+  if (ldq < C || ldk < C || ldq % 16 || ldk % 16) return SDF_E_SHAPE;
+  if (!sdf_aligned(q, 16) || !sdf_aligned(k, 16) || !sdf_aligned(e, 16) || !sdf_aligned(tab, 4)) return SDF_E_ALIGN;
+  const int G = C / 32;
+  const int64_t n = rows * G;
+  if ((n + 255) / 256 >= (1LL << 31)) return SDF_E_SHAPE;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipStream_t s = sdf_stream(stream);
+  if (Tq == 2) SDF_LAUNCH(qk_gate_glif_kernel<2>, grid, block, 0, s, q, k, e, gate, tab, rows, C, G, ldq, ldk);
+  else SDF_LAUNCH(qk_gate_glif_kernel<4>, grid, block, 0, s, q, k, e, gate, tab, rows, C, G, ldq, ldk);
+  SDF_LAUNCH_CHECK();
+  return 0;
 }

@@ -64,8 +64,9 @@ def _np(sn_module, device):
     """NeuronParams of a Spiking_neuron wrapper, PSN weights moved to the device."""
     n = sn_module.spiking_neuron
     if n.kind not in hip.KIND:
-        raise hip.SdfError(f"neuron {type(n).__name__}: no fused kernel (lif / if / psn / plif / SLTTlif have one); it only runs as a "
-                           "stand-alone module (reference Spiking_modules.py:84-92)")
+        raise hip.SdfError(f"neuron {type(n).__name__}: no fused kernel (lif / if / psn / plif / SLTTlif have one); it runs as a stand-alone "
+                           "module (reference Spiking_modules.py:84-92), and a whole MS model in eval mode on the unfused plan "
+                           "(model.eval_engine(): engine_glif.GLIFFlowEngine)")
     if n.kind == "psn":
         return hip.NeuronParams("psn", psn_w=n.weight.detach().float().to(device).contiguous(),
                                 psn_b=n.bias.detach().float().reshape(-1).to(device).contiguous())
@@ -86,21 +87,21 @@ def attention_score(e, sn, nH, Tq, B_, N1):
 
 
 class _Block:
-    def __init__(self, blk, device, nsplit, name=""):
+    def __init__(self, blk, device, nsplit, name="", np=_np):
         self.name = name
         a = blk.attn
-        self.attn_sn = _np(a.attn_sn, device)
+        self.attn_sn = np(a.attn_sn, device)
         self.nH, self.window_size, self.shift_size = a.num_heads, blk.window_size, blk.shift_size
         self.q = _Lin(a.linear_q, a.bn_q.norm_layer, device, nsplit)
         self.k = _Lin(a.linear_k, a.bn_k.norm_layer, device, nsplit)
         self.p = _Lin(a.proj, a.proj_bn.norm_layer, device, nsplit)
         self.pe = a.positional_encoding.detach().float().to(device).contiguous()
-        self.sn_proj, self.sn_q, self.sn_k, self.sn2_q = (_np(m, device) for m in (a.proj_sn, a.sn_q, a.sn_k, a.sn2_q))
+        self.sn_proj, self.sn_q, self.sn_k, self.sn2_q = (np(m, device) for m in (a.proj_sn, a.sn_q, a.sn_k, a.sn2_q))
         # q and k read the same spikes: with parameter-free neurons of equal settings (LIF / IF) they run as ONE fused GEMM
         # over the stacked weights [Wq; Wk]; the positional term only exists for the k half (q adds zeros)
         self.qk = None
         sq, sk = self.sn_q, self.sn_k
-        if sq.kind != "psn" and (sq.kind, sq.tau, sq.v_th, sq.v_reset) == (sk.kind, sk.tau, sk.v_th, sk.v_reset):
+        if sq.kind in ("lif", "if") and (sq.kind, sq.tau, sq.v_th, sq.v_reset) == (sk.kind, sk.tau, sk.v_th, sk.v_reset):
             w = torch.cat([a.linear_q.weight.detach().float(), a.linear_k.weight.detach().float()], 0).to(device).contiguous()
             self.qk = {"Wp": hip.split_weight(w, nsplit), "digits": hip.split_weight_i8x3(w) if self.q.digits is not None else None,
                        "alpha": torch.cat([self.q.alpha, self.k.alpha]).contiguous(),
@@ -113,7 +114,7 @@ class _Block:
         self.fc2 = _Lin(m.fc2, m.bn2.norm_layer, device, nsplit)
         if self.fc2.digits is not None and self.fc2.K >= 1536:      # wide stages: fc2 (K = 4 C against few tokens) runs on the small-M kernel
             self.fc2.digits_tiled = hip.tile_weight_i8x3(self.fc2.digits)
-        self.sn1, self.sn2 = _np(m.sn1, device), _np(m.sn2, device)
+        self.sn1, self.sn2 = np(m.sn1, device), np(m.sn2, device)
 
 
 def _conv_planes(w, nsplit, cin_pad=None):
@@ -132,13 +133,13 @@ def _conv_digits(w, nsplit):
 class _ResBlock:
     """MS_ResBlock weights for the spike-convolution path (3x3, pad 1, NHWC)."""
 
-    def __init__(self, rb, device, nsplit, name=""):
+    def __init__(self, rb, device, nsplit, name="", np=_np):
         self.name = name
         self.C = rb.conv1[0].weight.shape[0]
         self.w1, self.w2 = _conv_planes(rb.conv1[0].weight, nsplit), _conv_planes(rb.conv2[0].weight, nsplit)
         self.w1.digits, self.w2.digits = _conv_digits(rb.conv1[0].weight, nsplit), _conv_digits(rb.conv2[0].weight, nsplit)
         self.bn1, self.bn2 = bn_affine(rb.norm1.norm_layer, device), bn_affine(rb.norm2.norm_layer, device)
-        self.sn1, self.sn2 = _np(rb.sn1, device), _np(rb.sn2, device)
+        self.sn1, self.sn2 = np(rb.sn1, device), np(rb.sn2, device)
 
 
 _DECONV_ROWMAPS = {}
@@ -348,6 +349,8 @@ def deconv_route(B, D, h, w, cin, cout, nsplit, replicas=False):
 
 
 class MSFlowEngine:
+    _np = staticmethod(_np)         # how a Spiking_neuron wrapper is packed (engine_glif.GLIFFlowEngine packs gate tables)
+
     @classmethod
     def bare(cls, device, nsplit=2):
         """An engine without a model: the helpers (index maps, kernels, tape) for module-level `forward()` calls - the
@@ -374,18 +377,18 @@ class MSFlowEngine:
         self.num_bins, self.num_steps = pe.num_bins, pe.num_steps
         self.head_w = pe.head.conv[0].weight.detach().contiguous(memory_format=torch.channels_last)
         self.head_w_oihw = pe.head.conv[0].weight.detach().float().contiguous()
-        self.head_bn, self.head_sn = bn_affine(pe.head.norm_layer.norm_layer, dev), _np(pe.head.sn, dev)
+        self.head_bn, self.head_sn = bn_affine(pe.head.norm_layer.norm_layer, dev), self._np(pe.head.sn, dev)
         self.conv_w, self.conv_bn = _conv_planes(pe.conv.conv[0].weight, ns), bn_affine(pe.conv.norm_layer.norm_layer, dev)
         self.conv_w.digits = _conv_digits(pe.conv.conv[0].weight, ns)      # 48 -> 96 at stride 2: the digit kernel's even / odd halo form
         U = "sttmultires_unet."
         self.pe_name = U + "encoders.swin3d.patch_embed."
-        self.pe_res = [_ResBlock(rb, dev, ns, self.pe_name + f"residual_encoding.resblocks.{i}.") for i, rb in enumerate(pe.residual_encoding.resblocks)]
+        self.pe_res = [_ResBlock(rb, dev, ns, self.pe_name + f"residual_encoding.resblocks.{i}.", self._np) for i, rb in enumerate(pe.residual_encoding.resblocks)]
         self.proj_res_w = pe.proj.conv_res.weight.detach().contiguous(memory_format=torch.channels_last)
         self.proj_res_w2 = pe.proj.conv_res.weight.detach().float().reshape(pe.proj.conv_res.weight.shape[0], -1).contiguous()
         self.proj_res_b = None if pe.proj.conv_res.bias is None else pe.proj.conv_res.bias.detach().float().contiguous()
         self.proj_w = _conv_planes(pe.proj.conv.weight, ns)
         self.proj_w.digits = _conv_digits(pe.proj.conv.weight, ns)         # 96 -> C at stride 2: the digit kernel's two-channel-pass form
-        self.proj_bn, self.proj_sn = bn_affine(pe.proj.norm_layer, dev), _np(pe.proj.sn, dev)
+        self.proj_bn, self.proj_sn = bn_affine(pe.proj.norm_layer, dev), self._np(pe.proj.sn, dev)
         self._maps, self._deconv = {}, {}
         self.tape = None            # parity tests set a list: every neuron layer's spikes are recorded (see _rec)
         self.scores = None          # `log=True`: a list that receives the attention score of the last block of every stage
@@ -396,16 +399,16 @@ class MSFlowEngine:
         """Everything behind the patch embedding (the SEW engine packs its own: engine_sew.SEWFlowEngine)."""
         self.stages, self.merges = [], []
         for li, layer in enumerate(sw.layers):
-            self.stages.append([_Block(b, dev, ns, U + f"encoders.swin3d.layers.{li}.swin_blocks.{bi}.") for bi, b in enumerate(layer.swin_blocks)])
+            self.stages.append([_Block(b, dev, ns, U + f"encoders.swin3d.layers.{li}.swin_blocks.{bi}.", self._np) for bi, b in enumerate(layer.swin_blocks)])
             if layer.downsample is not None:
                 d = layer.downsample
-                self.merges.append((_Lin(d.reduction, d.norm.norm_layer, dev, ns), _np(d.sn, dev)))
-        self.unet_res = [_ResBlock(rb, dev, ns, U + f"resblocks.{i}.") for i, rb in enumerate(unet.resblocks)]
-        self.decoders = [_Decoder(d.deconv[0].weight.detach(), bn_affine(d.norm_layer.norm_layer, dev), _np(d.sn, dev)) for d in unet.decoders]
+                self.merges.append((_Lin(d.reduction, d.norm.norm_layer, dev, ns), self._np(d.sn, dev)))
+        self.unet_res = [_ResBlock(rb, dev, ns, U + f"resblocks.{i}.", self._np) for i, rb in enumerate(unet.resblocks)]
+        self.decoders = [_Decoder(d.deconv[0].weight.detach(), bn_affine(d.norm_layer.norm_layer, dev), self._np(d.sn, dev)) for d in unet.decoders]
         self.preds = []
         for p in unet.preds:
             planes, bp, w2 = _pred_planes(p.conv[0], dev, ns)
-            self.preds.append(_Pred(planes, bp, w2.shape[0], _np(p.sn, dev), w2.to(dev).contiguous(), p.conv[0].bias.detach().float().to(dev).contiguous()))
+            self.preds.append(_Pred(planes, bp, w2.shape[0], self._np(p.sn, dev), w2.to(dev).contiguous(), p.conv[0].bias.detach().float().to(dev).contiguous()))
 
     # ------------------------------------------------------------------ helpers
     def _slice_map(self, B, D, H, W, ws, ss):
@@ -590,7 +593,7 @@ class MSFlowEngine:
         # head: real-valued 2-channel input -> conv + BN + SN as one kernel that reads the voxel in place (channel ci of step t is
         # polarity ci % 2 of bin (ci // 2) * T + t; shapes outside its build: re-layout + library convolution, then BN + SN
         # fused in the neuron kernel)
-        if hip.head_conv_sn_supported(T, H, W, num_ch, self.head_w_oihw.shape[0]) and xv.is_contiguous():
+        if self._head_fused(T, H, W, num_ch) and xv.is_contiguous():
             s = hip.head_conv_sn(xv, self.head_w_oihw, B, T, H, W, self.head_sn, alpha=self.head_bn[0], beta=self.head_bn[1],
                                  voxel_bins=xv.shape[1])
         else:
@@ -620,6 +623,10 @@ class MSFlowEngine:
             res = F.conv2d(m.view(B * T, h, w, Cc).permute(0, 3, 1, 2), self.proj_res_w, self.proj_res_b, 2)
             res = res.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
         return self._conv3x3(s1, self.proj_w, self.proj_w.shape[1], stride=2, bn=self.proj_bn, resid=res)
+
+    def _head_fused(self, T, H, W, num_ch):
+        """Whether the head convolution runs with BN and its neuron as one kernel (else: library convolution, then BN + neuron)."""
+        return hip.head_conv_sn_supported(T, H, W, num_ch, self.head_w_oihw.shape[0])
 
     def _zsrc_map(self, rowmap, B_, Tq, N1, nH, x_rows, key):
         key = ("zsrc", nH, self.replicas) + key
@@ -853,15 +860,20 @@ class MSFlowEngine:
         else:
             s = (torch.zeros if cp != cin else torch.empty)((B, D, h, w, cp), dtype=torch.uint8, device=y.device)
             srcs, c0 = [(y, C1, C1), (skip, C2, C2)] + ([(preds[-1], 4, preds[-1].shape[-1])] if i > 0 else []), 0
-        hw = h * w
         for src, take, pitch in srcs:                                     # (tensor, channels taken, pitch)
-            for b in range(B):
-                hip.neuron_fwd(src[b], s[b].view(-1)[c0:], D, hw, take, pitch, hw * pitch, cp, hw * cp, sn)
+            self._slice_neuron(src, take, pitch, s, c0, sn)
             c0 += take
         if self.taped:                                         # the reference's channel order is [prediction | y | skip]
             npred = self.preds[i - 1].nout if i > 0 else 0
             self._rec(name, torch.cat([s[..., C1 + C2:C1 + C2 + npred], s[..., :C1 + C2]], -1), "BDHWC->TBCHW")
         return s, "perm"
+
+    def _slice_neuron(self, src, take, pitch, s, c0, sn):
+        """Spikes of `sn` over D on the first `take` channels of src (B,D,h,w,pitch) fp32, into channels c0.. of the image s (B,D,h,w,cp) u8."""
+        B, D, h, w, cp = s.shape
+        hw = h * w
+        for b in range(B):
+            hip.neuron_fwd(src[b], s[b].view(-1)[c0:], D, hw, take, pitch, hw * pitch, cp, hw * cp, sn)
 
     def _transposed_conv(self, i, route, s, wkey, wuse):
         """z (B,D,2h,2w,cout) fp32 = BN(ConvTranspose2d(k 3, s 2, p 1, op 1)(s)) of decoder level i, launched as deconv_route decided."""

@@ -316,6 +316,7 @@ SIGNATURES = {
     "sdf_qk_gate_plif_bwd_workspace_bytes": (_i64, (_i, _i64, _i)),
     "sdf_qk_gate_plif_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i, _f, _i, _f, _i, _i, _f, _p)),
     "sdf_neuron_fwd": (_i, (_P(NeuronDesc), _p)), "sdf_neuron_multi_fwd": (_i, (_P(NeuronDesc), _i, _p)),
+    "sdf_glif_neuron_fwd": (_i, (_P(NeuronDesc), _p, _p)),
     "sdf_split_weight_i8x3": (_i, (_p, _p, _p, _i, _i, _p)), "sdf_tile_weight_i8x3": (_i, (_p, _p, _i, _i, _p)),
     "sdf_spike_gemm_fwd": (_i, (_P(SpikeGemmDesc), _p)),
     "sdf_spike_gemm_bn_fwd": (_i, (_p, _p, _i, _f, _p, _p, _p, _i64, _i, _i, _p)),
@@ -330,6 +331,7 @@ SIGNATURES = {
     "sdf_split_weight_bf16": (_i, (_p, _p, _i64, _i, _p)), "sdf_split_weight_f16x2": (_i, (_p, _p, _i64, _f, _p)),
     "sdf_qk_gate_fwd": (_i, (_p, _p, _p, _i, _i64, _i, _i, _f, _f, _f, _i, _p, _p, _p)),
     "sdf_qk_gate_strided_fwd": (_i, (_p, _p, _p, _i, _i64, _i, _i64, _i64, _i, _f, _f, _f, _i, _p, _p, _p)),
+    "sdf_qk_gate_glif_fwd": (_i, (_p, _p, _p, _p, _p, _i, _i64, _i, _i64, _i64, _p)),
     "sdf_head_conv_sn_fwd": (_i, (_P(HeadConvDesc), _p)), "sdf_pointwise_conv_f32_fwd": (_i, (_P(PointwiseConvDesc), _p)),
     "sdf_deconv_col2im_fwd": (_i, (_p, _p, _p, _p, _i, _i, _i, _i, _p)),
     "sdf_flow_out_fwd": (_i, (_p, _p, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _p)),
@@ -501,6 +503,15 @@ class NeuronParams:
         self.psn_w, self.psn_b = psn_w, psn_b
 
 
+class GlifParams(NeuronParams):
+    """A GLIF node (the reference's GatedLIFNode) as the kernels take it: `tab` = [L, Dk, g, R, th, c_0 .. c_{T-1}], 5 + T fp32 on the
+    device.  No fused epilogue has a GLIF form: `neuron_fwd` sends it to the general GLIF launch, every fused entry point refuses it."""
+
+    def __init__(self, tab):
+        super().__init__("glif")
+        self.tab = tab
+
+
 def _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, rowmap=None, rowlen=0,
                  alpha=None, beta=None, Cch=0, inner=1, add=None, add_st=0, add_period=0, v_last=None, rep=None):
     d = NeuronDesc()
@@ -525,9 +536,25 @@ def _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, row
 def neuron_fwd(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, rowmap=None, rowlen=0,
                alpha=None, beta=None, Cch=0, inner=1, add=None, add_st=0, add_period=0, v_last=None):
     """sdf_neuron_fwd: see include/sdformerflow_hip.h for the addressing contract."""
+    if p.kind == "glif":
+        return glif_neuron_fwd(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p.tab, rowmap, rowlen, alpha, beta, Cch, inner, add, add_st,
+                               add_period, v_last)
     d = _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p, rowmap, rowlen, alpha, beta, Cch, inner, add, add_st, add_period, v_last)
     _note(bytes=T * nb * ni * (4 + out.element_size()), shape=(T, nb * ni))
     _check(lib().sdf_neuron_fwd(C.byref(d), _stream()), "sdf_neuron_fwd")
+    return out
+
+
+def glif_neuron_fwd(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, tab, rowmap=None, rowlen=0, alpha=None, beta=None, Cch=0, inner=1,
+                    add=None, add_st=0, add_period=0, v_last=None, rep=None):
+    """sdf_glif_neuron_fwd: neuron_fwd's addressing with the GLIF recurrence from v = 0, s = 0; `tab` = the node's 5 + T gate table on
+    the device; `rep` = (count, stride in x, stride in out) of the descriptor's outermost dimension."""
+    if tab.numel() != 5 + T:
+        raise SdfError(f"glif_neuron_fwd: the gate table has {tab.numel()} entries, T = {T} needs {5 + T}")
+    d = _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, NeuronParams(), rowmap, rowlen, alpha, beta, Cch, inner, add, add_st,
+                     add_period, v_last, rep)
+    _note(bytes=T * nb * ni * (4 + out.element_size()), shape=(T, nb * ni))
+    _check(lib().sdf_glif_neuron_fwd(C.byref(d), _ptr(tab, torch.float32), _stream()), "sdf_glif_neuron_fwd")
     return out
 
 
@@ -869,6 +896,20 @@ def qk_gate(q, k, e, Tq, rows, Cch, p: NeuronParams, ldq=None, ldk=None):
                                        Cch if ldq is None else ldq, Cch if ldk is None else ldk, KIND[p.kind], p.tau, p.v_th,
                                        v_reset, soft_reset, _ptr(p.psn_w, torch.float32), _ptr(p.psn_b, torch.float32), _stream())
     _check(rc, "sdf_qk_gate_strided_fwd")
+    return e
+
+
+def qk_gate_glif(q, k, e, Tq, rows, Cch, tab, ldq=None, ldk=None, gate=None):
+    """sdf_qk_gate_glif_fwd: qk_gate with a GLIF gate node (`tab` = its 5 + Tq gate table on the device); `gate` (Tq, rows, C / 32) u8
+    also receives the gate's own spikes."""
+    if tab.numel() != 5 + Tq:
+        raise SdfError(f"qk_gate_glif: the gate table has {tab.numel()} entries, T' = {Tq} needs {5 + Tq}")
+    if gate is not None and (not gate.is_contiguous() or gate.numel() != Tq * rows * (Cch // 32)):
+        raise SdfError("qk_gate_glif: `gate` must be a contiguous (Tq, rows, C / 32) u8 tensor")
+    rc = lib().sdf_qk_gate_glif_fwd(_ptr(q, torch.uint8), _ptr(k, torch.uint8), _ptr(e, torch.uint8), _ptr(gate, torch.uint8),
+                                    _ptr(tab, torch.float32), Tq, rows, Cch, Cch if ldq is None else ldq, Cch if ldk is None else ldk,
+                                    _stream())
+    _check(rc, "sdf_qk_gate_glif_fwd")
     return e
 
 
@@ -1824,6 +1865,8 @@ def pointwise_conv_f32(x, w, stride, bias=None):
 def pred_head_supported(D, Cin, H, W, h, w, sn, sn_next=None):
     """Mirror of sdf_pred_head_fwd's shape rules (csrc/pred_head.hip): the caller keeps the three-launch form otherwise."""
     if Cin not in (96, 192, 384) or D not in (5, 10, 20) or H % h or W % w:
+        return False
+    if sn.kind not in KIND or (sn_next is not None and sn_next.kind not in KIND):       # (GLIF: the general launch only)
         return False
     if sn.kind == "psn" and D > 10:
         return False

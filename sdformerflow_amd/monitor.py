@@ -20,7 +20,8 @@ copy is kept and the host does not synchronise per forward.  The denominator is 
 call, the zero rows it concatenates itself (odd sizes in front of a patch merging, padded window rows) included.  The two calls of
 the MS attention whose spikes no kernel stores - the token gate `attn.sn2_q` and the dead score `attn.attn_sn` - are recomputed from
 the recorded q spikes and the gated spikes (engine.MSFlowEngine._rec_gates): the gate's record is a recomputation, not a read-out of
-the fused kernel.  Eval mode, eager, one forward at a time: training mode, `forward_replicas` and graph capture are refused.
+the fused kernel.  (A GLIF model runs on the unfused plan, engine_glif.py: there the gate's record IS the gate kernel's own output.)
+Eval mode, eager, one forward at a time: training mode, `forward_replicas` and graph capture are refused.
 """
 import csv
 
@@ -117,7 +118,7 @@ class FiringRateMonitor:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("a firing-rate monitor is enabled during graph capture: its forward takes the eager recording route and "
                                "grows a table - disable() the monitor around the capture, or run the monitored forwards eagerly")
-        engine = self.model.engine()
+        engine = self.model.eval_engine()
         self._room(x.device)
         self._seen = [None] * len(self.names)
         engine.monitor = self
