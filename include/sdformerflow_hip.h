@@ -723,6 +723,7 @@ int sdf_affine_resid_fwd(const float* x, const float* alpha, const float* beta, 
  *     raw head view (B_, nH, N, 32) of the (T', B_, N1, C) buffers; (q*scale[g]) k^T + bias[g] (+ mask), NO
  *     softmax, @ v; out fp32 (T', B_, N1, C) through the (B_,nH,T',N1,hd) -> (T',B_,N1,C) scramble.
  * bias is (nH, N, N) fp32, mask (nW, N, N) fp32 or NULL.  All matrix products run on the exact fp32 MFMA.
+ * More than 192 tokens per window: sdf_win_attn_large_fwd.
  */
 enum { SDF_ATTN_ANN = 0, SDF_ATTN_SEW = 1 };
 typedef struct SdfWinAttnDesc {
@@ -746,6 +747,14 @@ typedef struct SdfWinAttnDesc {
 } SdfWinAttnDesc;
 
 int sdf_win_attn_fwd(const SdfWinAttnDesc* d, void* stream);
+
+/* ---- the same attention for larger windows: 192 < N <= 1024 tokens (up to window (2,22,22)) ------------------------------------
+ * Descriptor, modes, layouts and arithmetic of sdf_win_attn_fwd (exact fp32 MFMA for both products, the score rounded as
+ * (acc * scale + bias) + mask), with the keys walked in blocks of 64: the ANN mode keeps a running row maximum and sum (online
+ * softmax), the SEW mode only accumulates.  Argument checks are those of sdf_win_attn_fwd in the same order, except the range:
+ * N <= 192 or N > 1024 is SDF_E_SHAPE.  Everything is refused before any launch; one launch; no atomics, two calls give bit-equal
+ * results.  Forward only: the backward entry points below serve N <= 192. */
+int sdf_win_attn_large_fwd(const SdfWinAttnDesc* d, void* stream);
 
 /* ---- backward of the SDF_ATTN_ANN core of sdf_win_attn_fwd (training of the ANN model) -------------------------------------
  * Per window b and head g: q^ = q / max(|q|, 1e-12), k^ likewise, S = q^ k^T * scale[g] + bias[g] (+ mask[b % nW]),

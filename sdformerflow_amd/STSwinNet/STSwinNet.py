@@ -220,6 +220,9 @@ class STTFlowNet(nn.Module):
             raise hip.SdfError("STTFlowNet runs on the GPU only (no CPU fallback)")
         if log:
             raise NotImplementedError("attention-score logging is analysis tooling outside the forward path")
+        if self.training:                                      # (before the first launch, not in the first swin block)
+            ws = self.sttmultires_unet.encoders.swin3d.layers[0].window_size
+            hip.check_attn_bwd_window(ws[0] * ws[1] * ws[2], "SDF_ANN_ATTN_BWD")
         # training: under autograd (train.train_step); eval: no graph, the fused inference kernels
         with contextlib.nullcontext() if self.training else torch.no_grad():
             if x.size(1) != self.num_bins:                     # DSEC double-chunk input: last block of chunk 1 + chunk 2

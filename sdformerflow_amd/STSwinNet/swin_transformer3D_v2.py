@@ -139,10 +139,11 @@ class WindowAttention3D(nn.Module):
         """Training form of `forward_rows` (no shortcut): proj(attention(qkv(y2))) on un-partitioned rows y2 (rows, C) under autograd.
         The core is `WinAttnAnnFunction` (HIP forward and backward); a padding token reads the qkv bias, so its gradient reaches
         `qkv.bias` through the Function's `pad_qkv` input.  `SDF_ANN_ATTN_BWD=0`: the same attention as a torch composition."""
+        N = self.window_size[0] * self.window_size[1] * self.window_size[2]
+        hip.check_attn_bwd_window(N, "SDF_ANN_ATTN_BWD")
         qkv = F.linear(y2, self.qkv.weight, self.qkv.bias)
         pad = self.qkv.bias if self.qkv.bias is not None else torch.zeros(3 * self.dim, device=y2.device)
         bias, scale = self._bias_and_scale()
-        N = self.window_size[0] * self.window_size[1] * self.window_size[2]
         if hip.sw("SDF_ANN_ATTN_BWD", "1") == "0":
             o = attention_rows_torch(qkv, row_map, B_, N, pad, scale, bias, mask, self.num_heads)
         else:

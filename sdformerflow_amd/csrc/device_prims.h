@@ -1,10 +1,12 @@
-// Device primitives the kernel files share, each stated once: raw buffer access, the LDS hand-over counters of the role-split
-// kernels and the quad transpose.  Includes common.h only and defines no matrix-operand type (bf16x8 is `short` x 8 in spike_mm.h
-// and `__bf16` x 8 in bf16_split.h), so every kernel file may include it.
+// Device primitives the kernel files share, each stated once: the MFMA accumulator, raw buffer access, the LDS hand-over counters of
+// the role-split kernels and the quad transpose.  Includes common.h only and defines no 16-bit matrix-operand type (bf16x8 is `short` x 8
+// in spike_mm.h and `__bf16` x 8 in bf16_split.h), so every kernel file may include it.
 #pragma once
 #include "common.h"
 
 namespace {
+
+typedef __attribute__((ext_vector_type(4))) float f32x4;   // accumulator of a 16 x 16 MFMA: four fp32 per lane
 
 // Raw buffer access (32-bit byte offset against a wave-uniform descriptor of 2^31 records): an offset with bit 31 set is
 // out of range, so the hardware returns zeros for such a load and drops such a store - row / tap / K bounds become an

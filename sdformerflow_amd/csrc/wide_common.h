@@ -71,8 +71,6 @@ int launch_res_front(WideFrontParams& P, bool keep, int nk, hipStream_t s);
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 // 4 bits -> 4 bytes {0, 1}: bit i lands in byte i (i + 7 i = 8 i; the cross terms i + 7 k, k != i, miss every byte's bit 0)
 __device__ __forceinline__ uint32_t spread4(uint32_t nib) { return __umul24(nib & 0xFu, 0x204081u) & 0x01010101u; }
 

@@ -16,30 +16,13 @@
 // LDS round trip and no shuffle between the two matrix products.  Row max / sum reduce in-lane over the 4*NT
 // registers and across the 4 lane groups with two DPP-free shuffles.  Bias and mask are read as float4
 // (4 consecutive keys) from L2-resident tables.
-#include "device_prims.h"
+#include "win_attn_common.h"
 #include "switches.h"
 #include "host_launch.h"
 
 namespace {
 
-constexpr int HD = 32;
-constexpr int NT_MAX = 12;            // up to 192 tokens per window
-constexpr int LDW = HD + 4;           // padded LDS row (floats)
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-struct AttnParams {
-  SdfWinAttnDesc d;
-};
-
-// ANN mode: first float of the q | k | v row of token r of window b.  With a row map the window partition (pad, roll, reshape)
-// is this lookup; a padding token reads the qkv Linear's image of a zero row.
-__device__ __forceinline__ const float* qkv_row(const SdfWinAttnDesc& d, int b, int r, int C) {
-  const float* q = reinterpret_cast<const float*>(d.q);
-  if (!d.row_map) return q + ((int64_t)b * d.N + r) * 3 * C;
-  const int row = d.row_map[(int64_t)b * d.N + r];
-  return row >= 0 ? q + (int64_t)row * 3 * C : d.pad_qkv;
-}
+constexpr int NT_MAX = 12;            // up to 192 tokens per window (beyond: win_attn_large.hip)
 
 template <int MODE>
 __global__ __launch_bounds__(256) void win_attn_kernel(AttnParams P) {

@@ -336,7 +336,7 @@ SIGNATURES = {
     "sdf_deconv_col2im_fwd": (_i, (_p, _p, _p, _p, _i, _i, _i, _i, _p)),
     "sdf_flow_out_fwd": (_i, (_p, _p, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _p)),
     "sdf_pred_head_fwd": (_i, (_P(PredHeadDesc), _p)), "sdf_affine_resid_fwd": (_i, (_p, _p, _p, _p, _p, _i64, _i, _i64, _p)),
-    "sdf_win_attn_fwd": (_i, (_P(WinAttnDesc), _p)),
+    "sdf_win_attn_fwd": (_i, (_P(WinAttnDesc), _p)), "sdf_win_attn_large_fwd": (_i, (_P(WinAttnDesc), _p)),
     "sdf_win_attn_ann_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_ann_bwd": (_i, (_P(WinAttnBwdDesc), _p)),
     "sdf_win_attn_sew_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_sew_bwd": (_i, (_P(WinAttnSewBwdDesc), _p)),
     "sdf_ann_attn_block_supported": (_i, (_i, _i, _i)), "sdf_ann_attn_block_fwd": (_i, (_P(AnnAttnBlockDesc), _p)),
@@ -1273,6 +1273,25 @@ def affine_resid(x, alpha, beta, Cch, inner, resid=None, out=None):
     return out
 
 
+ATTN_BWD_MAX_N = 192          # tokens per window the attention backward kernels stage in LDS (sdf_win_attn_ann_bwd / _sew_bwd)
+
+
+def check_attn_bwd_window(N, switch):
+    """Training at a window the HIP attention backward does not serve is refused before any kernel runs (the forward would succeed on
+    sdf_win_attn_large_fwd and `backward` would fail); `switch` = SDF_ANN_ATTN_BWD / SDF_SEW_ATTN_BWD, whose value 0 selects the
+    torch composition of the attention, which trains at any window."""
+    if N > ATTN_BWD_MAX_N and sw(switch, "1") != "0":
+        raise NotImplementedError(f"training with {N}-token windows: the HIP window-attention backward serves at most {ATTN_BWD_MAX_N} tokens "
+                                  f"per window; set {switch}=0 to train on the torch composition of the attention instead")
+
+
+def _win_attn_fwd(d):
+    """The forward entry point by window size: sdf_win_attn_fwd up to 192 tokens, sdf_win_attn_large_fwd beyond (which refuses more
+    than 1024 with the library's code)."""
+    name = "sdf_win_attn_fwd" if d.N <= 192 else "sdf_win_attn_large_fwd"
+    _check(getattr(lib(), name)(C.byref(d), _stream()), name)
+
+
 def win_attn_ann_windowed(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH):
     """The same with the window partition / reverse INSIDE the kernel: qkv (rows, 3C) fp32 in the activation's own row order,
     row_map (B_*N,) int32 from `window_slice_map` (pad + roll + partition; -1 = padding token, which reads `pad_qkv` (3C) and
@@ -1284,7 +1303,7 @@ def win_attn_ann_windowed(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH):
     d.B_, d.nW, d.nH, d.N, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, N, C3 // 3 // nH
     d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
     d.row_map, d.pad_qkv = _ptr(row_map, torch.int32), _ptr(pad_qkv, torch.float32)
-    _check(lib().sdf_win_attn_fwd(C.byref(d), _stream()), "sdf_win_attn_fwd")
+    _win_attn_fwd(d)
     return out
 
 
@@ -1403,7 +1422,7 @@ def win_attn_ann(qkv, scale, bias, mask, nH):
     d.mode, d.q, d.k, d.v, d.out = 0, _ptr(qkv, torch.float32), _ptr(qkv), _ptr(qkv), _ptr(out)
     d.B_, d.nW, d.nH, d.N, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, N, C3 // 3 // nH
     d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
-    _check(lib().sdf_win_attn_fwd(C.byref(d), _stream()), "sdf_win_attn_fwd")
+    _win_attn_fwd(d)
     return out
 
 
@@ -1416,7 +1435,7 @@ def win_attn_sew(q, k, v, scale, bias, mask, nH, Tq, B_, N1):
     d.B_, d.nW, d.nH, d.N, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, Tq * N1, Cc // nH
     d.Tq, d.N1 = Tq, N1
     d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
-    _check(lib().sdf_win_attn_fwd(C.byref(d), _stream()), "sdf_win_attn_fwd")
+    _win_attn_fwd(d)
     return out
 
 

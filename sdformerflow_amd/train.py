@@ -301,6 +301,7 @@ def sew_attention(xw, attn, mask):
     the torch composition); the relative-position bias is the table gathered under autograd; proj (with bias) -> BN -> SN."""
     Tq, B_, N1, Cc = xw.shape
     nH, N = attn.num_heads, Tq * N1
+    hip.check_attn_bwd_window(N, "SDF_SEW_ATTN_BWD")
     q, k, v = (getattr(attn, f"sn_{n}")(_bn_last(_linear(xw, getattr(attn, f"linear_{n}"), spikes=False), getattr(attn, f"bn_{n}").norm_layer))
                for n in ("q", "k", "v"))
     bias = attn.relative_position_bias_table[attn.relative_position_index[:N, :N].reshape(-1)].reshape(N, N, nH).permute(2, 0, 1)
@@ -366,6 +367,8 @@ def forward_train_sew(model, x):
     H, W = x.shape[-2:]
     unet = model.sttmultires_unet
     sw = unet.encoders.swin3d
+    ws = sw.layers[0].swin_blocks[0].attn.window_size
+    hip.check_attn_bwd_window(ws[0] * ws[1] * ws[2], "SDF_SEW_ATTN_BWD")                    # (before the first launch, not in block 0)
     y = patch_embed(x.float(), sw.patch_embed).permute(1, 0, 3, 4, 2).contiguous()          # (B, D, h, w, C)
     blocks = []
     for i, layer in enumerate(sw.layers):
