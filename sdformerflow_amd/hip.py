@@ -981,13 +981,14 @@ def window_zsrc_map(slice_map, B_, Tq, N1, nH, x_rows):
 
 
 def qk_attn(x, slice_map, B_, Tq, N1, nH, p_lin, sn_proj, sn_q, sn_k, sn2_q, qk=None, q_lin=None, k_lin=None, pe=None, keep_ws=None,
-            four_launches=False, x_src=None, emit=None, narrow=False, info=None, rep_windows=0):
+            four_launches=False, x_src=None, emit=None, narrow=False, info=None, rep_windows=0, ws=None):
     """sdf_qk_attn_fwd: x (B,D,H,W,C) fp32 channel-last += SSA(x), in place.  `qk` = {"Wp", "alpha", "beta", "add"} for the
     stacked projection, or q_lin / k_lin (objects with Wp / alpha / beta) + pe for separate ones; p_lin has Wp / bias / alpha / beta.
     `x_src` (window_zsrc_map) lets the library take its wide-stage kernels; `emit` = (u8 buffer, NeuronParams): the projection
     also writes SN(x after the update) over D there (the MLP's first neuron) when the call runs on the wide-stage kernels - `info`
     (a dict) then receives "emitted": True; `narrow` forces the general kernels (A/B).  `rep_windows` > 0: the B_ windows are
-    B_ / rep_windows independent batch-1 problems and `slice_map` / `x_src` their concatenated tables (replica_slice_map, replica_zsrc_map)."""
+    B_ / rep_windows independent batch-1 problems and `slice_map` / `x_src` their concatenated tables (replica_slice_map, replica_zsrc_map).
+    `ws`: the caller's workspace, a 256-byte aligned u8 buffer of at least sdf_qk_attn_workspace_bytes (as ms_mlp's `ws`); default: allocated here."""
     Cc = x.shape[-1]
     d = QkAttnDesc()
     d.rep_windows = rep_windows
@@ -1006,8 +1007,11 @@ def qk_attn(x, slice_map, B_, Tq, N1, nH, p_lin, sn_proj, sn_q, sn_k, sn2_q, qk=
     for c, p in ((d.sn_proj, sn_proj), (d.sn_q, sn_q), (d.sn_k, sn_k), (d.sn2_q, sn2_q)):
         _ncfg(c, p)
     nbytes = lib().sdf_qk_attn_workspace_bytes(B_, Tq, N1, Cc)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)          # intermediates: caller-owned, caching allocator
-    d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
+    if ws is None:
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)      # intermediates: caller-owned, caching allocator
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % 256:
+        raise SdfError(f"qk_attn: `ws` must be a contiguous, 256-byte aligned u8 buffer of at least {nbytes} bytes")
+    d.workspace, d.workspace_bytes = _ptr(ws, torch.uint8), ws.numel()
     gws = workspace(x.device)
     d.gemm_workspace, d.gemm_workspace_bytes = gws.data_ptr(), gws.numel()
     d.flags = (SDF_QK_KEEP_SPIKES if keep_ws is not None else 0) | (SDF_QK_FOUR_LAUNCHES if four_launches else 0) | \
