@@ -7,7 +7,8 @@ call goes through the C ABI and
   * writes into a slice of a larger buffer, 64 guard elements on each side, NaN (fp32) or the byte 7 (spikes) everywhere
     beforehand: the guards hold the same bits afterwards and nothing of the fill is left where a result belongs;
   * runs twice: bit-equal, parameter gradients included.
-No numeric tolerance: parity with the oracle stays with test_hip_kernels.py and the *_train_gpu.py suites."""
+No numeric tolerance: parity with the oracle stays with test_hip_kernels.py and the *_train_gpu.py suites, and every one of these
+instantiations is compared by value with an fp64 autograd reference in test_neuron_parity_gpu.py (cases: neuron_train_cases.py)."""
 import ctypes as C
 
 import pytest
