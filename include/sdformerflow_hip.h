@@ -753,7 +753,8 @@ int sdf_win_attn_fwd(const SdfWinAttnDesc* d, void* stream);
  * (acc * scale + bias) + mask), with the keys walked in blocks of 64: the ANN mode keeps a running row maximum and sum (online
  * softmax), the SEW mode only accumulates.  Argument checks are those of sdf_win_attn_fwd in the same order, except the range:
  * N <= 192 or N > 1024 is SDF_E_SHAPE.  Everything is refused before any launch; one launch; no atomics, two calls give bit-equal
- * results.  Forward only: the backward entry points below serve N <= 192. */
+ * results.  Its backward: sdf_win_attn_large_ann_bwd / sdf_win_attn_large_sew_bwd below (the first two backward entry points serve
+ * N <= 192). */
 int sdf_win_attn_large_fwd(const SdfWinAttnDesc* d, void* stream);
 
 /* ---- backward of the SDF_ATTN_ANN core of sdf_win_attn_fwd (training of the ANN model) -------------------------------------
@@ -816,6 +817,24 @@ typedef struct SdfWinAttnSewBwdDesc {
 
 int64_t sdf_win_attn_sew_bwd_workspace_bytes(int B_, int nH, int N);   /* 0 for an unsupported shape */
 int sdf_win_attn_sew_bwd(const SdfWinAttnSewBwdDesc* d, void* stream);
+
+/* ---- the two backward passes for larger windows: 192 < N <= 1024 tokens (the backward of sdf_win_attn_large_fwd) ---------------------
+ * Descriptors, layouts and arithmetic of sdf_win_attn_ann_bwd / sdf_win_attn_sew_bwd, with keys and queries walked in blocks of 64
+ * tokens: neither LDS nor registers depend on N.  Argument checks are those of the first two in the same order, except the range:
+ * N <= 192 or N > 1024 is SDF_E_SHAPE (workspace queries: 0).  Everything is refused before any launch.
+ *   ANN: a flash-style backward - a query-major kernel walks the keys twice (online softmax -> row maximum, 1 / row sum and
+ *     D = rowsum(P o dP) per query, kept in the workspace; then dS, dq^ and the d_scale term), a key-major kernel walks the queries
+ *     (dv, dk^), and d_bias is split-K over fixed runs of windows that recompute dS from the stored row statistics.  Exact fp32 MFMA
+ *     products, the score rounded as (acc * scale + bias) + mask, a key past N contributes nothing; bias and mask must be finite.
+ *   SEW: the Gram form of sdf_win_attn_sew_bwd with the Grams, dq / dk and the (bias + mask)^T dO walk streaming 64-token blocks, and
+ *     the d_bias kernel staging V per 256-key block.
+ * The workspace holds per-query row statistics, per-workgroup d_pad / d_scale partials and the d_bias run partials (a number of
+ * runs bounded by the shape of one window, not by B_): no buffer grows as B_ * nH * N^2.  No atomics; d_pad, d_scale and d_bias are
+ * summed in a fixed order: two calls give bit-equal results. */
+int64_t sdf_win_attn_large_ann_bwd_workspace_bytes(int B_, int nH, int N);   /* 0 for an unsupported shape */
+int sdf_win_attn_large_ann_bwd(const SdfWinAttnBwdDesc* d, void* stream);
+int64_t sdf_win_attn_large_sew_bwd_workspace_bytes(int B_, int nH, int N);   /* 0 for an unsupported shape */
+int sdf_win_attn_large_sew_bwd(const SdfWinAttnSewBwdDesc* d, void* stream);
 
 /* ---- the attention half of an ANN video-swin block as one launch (BASELINE config 3, first stage) -----------------
  * Replaces `SwinTransformerBlock3D.forward_part1` + the shortcut (reference models/STSwinNet/swin_transformer3D_v2.py:272-310, :331)

@@ -383,8 +383,8 @@ class SpikeLinearFunction(torch.autograd.Function):
 class WinAttnAnnFunction(torch.autograd.Function):
     """The cosine window attention core of the ANN WindowAttention3D with the window partition inside the kernels (reference
     models/STSwinNet/swin_transformer3D_v2.py:176-202): forward `hip.win_attn_ann_windowed` (csrc/win_attn.hip), backward
-    `hip.win_attn_ann_bwd` (csrc/win_attn_bwd.hip).  Gradients for qkv (rows, 3C), scale (nH), bias (nH, N, N) and pad_qkv (3C:
-    the padding tokens read it - pass the qkv Linear's bias); scale = exp(clamp(logit_scale)) and bias = 16 sigmoid(cpb_mlp(...))
+    `hip.win_attn_ann_bwd` (csrc/win_attn_bwd.hip; above 192 tokens `hip.win_attn_ann_bwd_large`, csrc/win_attn_large_bwd.hip).
+    Gradients for qkv (rows, 3C), scale (nH), bias (nH, N, N) and pad_qkv (3C: the padding tokens read it - pass the qkv Linear's bias); scale = exp(clamp(logit_scale)) and bias = 16 sigmoid(cpb_mlp(...))
     stay torch autograd upstream.  Saves its inputs only (the backward recomputes the scores); no (N, N) tensor outlives a call."""
 
     @staticmethod
@@ -399,7 +399,8 @@ class WinAttnAnnFunction(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, scale, bias, pad = ctx.saved_tensors
         row_map, B_, N, mask, nH = ctx.cfg
-        dqkv, d_pad, d_scale, d_bias = hip.win_attn_ann_bwd(qkv, row_map, B_, N, pad, scale, bias, mask, nH, dout.contiguous())
+        bwd = hip.win_attn_ann_bwd if N <= hip.ATTN_BWD_MAX_N else hip.win_attn_ann_bwd_large    # as hip._win_attn_fwd picks the forward
+        dqkv, d_pad, d_scale, d_bias = bwd(qkv, row_map, B_, N, pad, scale, bias, mask, nH, dout.contiguous())
         return dqkv, d_scale, d_bias, d_pad, None, None, None, None, None
 
 
@@ -407,7 +408,8 @@ class WinAttnSewFunction(torch.autograd.Function):
     """The softmax-free core of the SEW Spiking_BN_WindowAttention3D (reference Spiking_swin_transformer3D.py:320-363): q, k, v
     (T', B_, N1, C) spikes in the reference's raw head view, bias (nH, N, N) = table[index[:N, :N]] (autograd carries its gradient on to
     the table), scale (nH), mask (nW, N, N) or None -> (T', B_, N1, C) fp32 through the reference's scramble.  Forward
-    `hip.win_attn_sew` on the spikes as bytes (exact), backward `hip.win_attn_sew_bwd` (csrc/win_attn_sew_bwd.hip).  Saves the three
+    `hip.win_attn_sew` on the spikes as bytes (exact), backward `hip.win_attn_sew_bwd` (csrc/win_attn_sew_bwd.hip; above 192
+    tokens `hip.win_attn_sew_bwd_large`, csrc/win_attn_large_bwd.hip).  Saves the three
     byte tensors and the bias; no (N, N) tensor per window exists in either direction.  fp32 under autocast too."""
 
     @staticmethod
@@ -425,5 +427,6 @@ class WinAttnSewFunction(torch.autograd.Function):
         qu, ku, vu, b = ctx.saved_tensors
         scale, mask, nH, dtype = ctx.cfg
         Tq, B_, N1, _ = qu.shape
-        dq, dk, dv, d_bias = hip.win_attn_sew_bwd(qu, ku, vu, scale, b, mask, nH, Tq, B_, N1, dout.float().contiguous())
+        bwd = hip.win_attn_sew_bwd if Tq * N1 <= hip.ATTN_BWD_MAX_N else hip.win_attn_sew_bwd_large
+        dq, dk, dv, d_bias = bwd(qu, ku, vu, scale, b, mask, nH, Tq, B_, N1, dout.float().contiguous())
         return dq.to(dtype), dk.to(dtype), dv.to(dtype), d_bias, None, None, None

@@ -1,5 +1,5 @@
 // What the window-attention forward files (win_attn.hip, win_attn_large.hip) share: the head dimension, the padded LDS row, the kernel
-// parameter block and the ANN mode's row lookup.
+// parameter block and the ANN mode's row lookup.  win_attn_large_bwd.hip takes the head dimension and the padded row from here.
 #pragma once
 #include "device_prims.h"
 

@@ -339,6 +339,8 @@ SIGNATURES = {
     "sdf_win_attn_fwd": (_i, (_P(WinAttnDesc), _p)), "sdf_win_attn_large_fwd": (_i, (_P(WinAttnDesc), _p)),
     "sdf_win_attn_ann_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_ann_bwd": (_i, (_P(WinAttnBwdDesc), _p)),
     "sdf_win_attn_sew_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_sew_bwd": (_i, (_P(WinAttnSewBwdDesc), _p)),
+    "sdf_win_attn_large_ann_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_large_ann_bwd": (_i, (_P(WinAttnBwdDesc), _p)),
+    "sdf_win_attn_large_sew_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_large_sew_bwd": (_i, (_P(WinAttnSewBwdDesc), _p)),
     "sdf_ann_attn_block_supported": (_i, (_i, _i, _i)), "sdf_ann_attn_block_fwd": (_i, (_P(AnnAttnBlockDesc), _p)),
     "sdf_ann_mlp_block_supported": (_i, (_i, _i)), "sdf_ann_mlp_block_fwd": (_i, (_P(AnnMlpBlockDesc), _p)),
     "sdf_dense_conv3x3_fwd": (_i, (_P(DenseConvDesc), _p)),
@@ -1278,15 +1280,23 @@ def affine_resid(x, alpha, beta, Cch, inner, resid=None, out=None):
 
 
 ATTN_BWD_MAX_N = 192          # tokens per window the attention backward kernels stage in LDS (sdf_win_attn_ann_bwd / _sew_bwd)
+ATTN_BWD_LARGE_MAX_N = 1024   # ... and the key-blocked ones serve beyond (sdf_win_attn_large_ann_bwd / _sew_bwd), at switch value 2
 
 
 def check_attn_bwd_window(N, switch):
     """Training at a window the HIP attention backward does not serve is refused before any kernel runs (the forward would succeed on
     sdf_win_attn_large_fwd and `backward` would fail); `switch` = SDF_ANN_ATTN_BWD / SDF_SEW_ATTN_BWD, whose value 0 selects the
-    torch composition of the attention, which trains at any window."""
-    if N > ATTN_BWD_MAX_N and sw(switch, "1") != "0":
+    torch composition of the attention, which trains at any window, and whose value 2 opts in to the key-blocked HIP backward
+    (csrc/win_attn_large_bwd.hip), which trains at every window up to 1024 tokens."""
+    value = sw(switch, "1")
+    if value == "2":
+        if N > ATTN_BWD_LARGE_MAX_N:
+            raise NotImplementedError(f"training with {N}-token windows: the HIP window-attention kernels serve at most {ATTN_BWD_LARGE_MAX_N} "
+                                      f"tokens per window; set {switch}=0 to train on the torch composition of the attention instead")
+    elif N > ATTN_BWD_MAX_N and value != "0":
         raise NotImplementedError(f"training with {N}-token windows: the HIP window-attention backward serves at most {ATTN_BWD_MAX_N} tokens "
-                                  f"per window; set {switch}=0 to train on the torch composition of the attention instead")
+                                  f"per window; set {switch}=0 to train on the torch composition of the attention instead, or {switch}=2 "
+                                  f"for the key-blocked HIP backward (up to {ATTN_BWD_LARGE_MAX_N} tokens)")
 
 
 def _win_attn_fwd(d):
@@ -1311,16 +1321,15 @@ def win_attn_ann_windowed(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH):
     return out
 
 
-def win_attn_ann_bwd(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout):
-    """Backward of `win_attn_ann_windowed` (sdf_win_attn_ann_bwd): qkv (rows, 3C), row_map (B_*N,) int32, pad_qkv (3C), scale (nH),
-    bias (nH, N, N), mask (nW, N, N) or None as the forward took them; dout = dL/d(output) (rows, C).  -> (dqkv (rows, 3C), d_pad (3C), d_scale (nH), d_bias (nH, N, N)); deterministic (fixed-order window sums)."""
+def _win_attn_ann_bwd(entry, qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout):
+    """`win_attn_ann_bwd` / `win_attn_ann_bwd_large` on their entry point (same descriptor, `<entry>_workspace_bytes` beside it)."""
     rows, C3 = qkv.shape
     dev = qkv.device
     dqkv = torch.empty_like(qkv)                                 # every real row lies in exactly one window: all of it is written
     d_pad = torch.empty((C3,), dtype=torch.float32, device=dev)
     d_scale = torch.empty((nH,), dtype=torch.float32, device=dev)
     d_bias = torch.empty((nH, N, N), dtype=torch.float32, device=dev)
-    nbytes = lib().sdf_win_attn_ann_bwd_workspace_bytes(B_, nH, N)
+    nbytes = getattr(lib(), entry + "_workspace_bytes")(B_, nH, N)
     ws = torch.empty((max(nbytes, 256) // 4,), dtype=torch.float32, device=dev)
     d = WinAttnBwdDesc()
     d.qkv, d.row_map, d.pad_qkv = _ptr(qkv, torch.float32), _ptr(row_map, torch.int32), _ptr(pad_qkv, torch.float32)
@@ -1329,8 +1338,20 @@ def win_attn_ann_bwd(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout):
     d.dqkv, d.d_pad, d.d_scale, d.d_bias = _ptr(dqkv), _ptr(d_pad), _ptr(d_scale), _ptr(d_bias)
     d.workspace, d.workspace_bytes = _ptr(ws), nbytes
     d.B_, d.nW, d.nH, d.N, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, N, C3 // 3 // nH
-    _check(lib().sdf_win_attn_ann_bwd(C.byref(d), _stream()), "sdf_win_attn_ann_bwd")
+    _check(getattr(lib(), entry)(C.byref(d), _stream()), entry)
     return dqkv, d_pad, d_scale, d_bias
+
+
+def win_attn_ann_bwd(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout):
+    """Backward of `win_attn_ann_windowed` (sdf_win_attn_ann_bwd): qkv (rows, 3C), row_map (B_*N,) int32, pad_qkv (3C), scale (nH),
+    bias (nH, N, N), mask (nW, N, N) or None as the forward took them; dout = dL/d(output) (rows, C).  -> (dqkv (rows, 3C), d_pad (3C), d_scale (nH), d_bias (nH, N, N)); deterministic (fixed-order window sums)."""
+    return _win_attn_ann_bwd("sdf_win_attn_ann_bwd", qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout)
+
+
+def win_attn_ann_bwd_large(qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout):
+    """The same for windows of 193 .. 1024 tokens (sdf_win_attn_large_ann_bwd, csrc/win_attn_large_bwd.hip: keys and queries walked
+    in blocks, no (B_, nH, N, N) buffer): arguments and returns of `win_attn_ann_bwd`."""
+    return _win_attn_ann_bwd("sdf_win_attn_large_ann_bwd", qkv, row_map, B_, N, pad_qkv, scale, bias, mask, nH, dout)
 
 
 def ann_attn_block_supported(Cc, nH, N):
@@ -1443,15 +1464,13 @@ def win_attn_sew(q, k, v, scale, bias, mask, nH, Tq, B_, N1):
     return out
 
 
-def win_attn_sew_bwd(q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout):
-    """Backward of `win_attn_sew` (sdf_win_attn_sew_bwd): q, k, v u8 (T',B_,N1,C), scale (nH), bias (nH,N,N), mask (nW,N,N) or None as
-    the forward took them; dout = dL/d(output) (T',B_,N1,C) fp32.  -> (dq, dk, dv (T',B_,N1,C) fp32, d_bias (nH,N,N)); deterministic
-    (fixed-order split-K sum over windows for d_bias)."""
+def _win_attn_sew_bwd(entry, q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout):
+    """`win_attn_sew_bwd` / `win_attn_sew_bwd_large` on their entry point (same descriptor, `<entry>_workspace_bytes` beside it)."""
     Cc, N = q.shape[-1], Tq * N1
     dev = q.device
     dq, dk, dv = (torch.empty((Tq, B_, N1, Cc), dtype=torch.float32, device=dev) for _ in range(3))
     d_bias = torch.empty((nH, N, N), dtype=torch.float32, device=dev)
-    nbytes = lib().sdf_win_attn_sew_bwd_workspace_bytes(B_, nH, N)
+    nbytes = getattr(lib(), entry + "_workspace_bytes")(B_, nH, N)
     ws = torch.empty((max(nbytes, 256) // 4,), dtype=torch.float32, device=dev)
     d = WinAttnSewBwdDesc()
     d.q, d.k, d.v, d.dout = _ptr(q, torch.uint8), _ptr(k, torch.uint8), _ptr(v, torch.uint8), _ptr(dout, torch.float32)
@@ -1459,8 +1478,21 @@ def win_attn_sew_bwd(q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout):
     d.dq, d.dk, d.dv, d.d_bias = _ptr(dq), _ptr(dk), _ptr(dv), _ptr(d_bias)
     d.workspace, d.workspace_bytes = _ptr(ws), nbytes
     d.B_, d.nW, d.nH, d.Tq, d.N1, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, Tq, N1, Cc // nH
-    _check(lib().sdf_win_attn_sew_bwd(C.byref(d), _stream()), "sdf_win_attn_sew_bwd")
+    _check(getattr(lib(), entry)(C.byref(d), _stream()), entry)
     return dq, dk, dv, d_bias
+
+
+def win_attn_sew_bwd(q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout):
+    """Backward of `win_attn_sew` (sdf_win_attn_sew_bwd): q, k, v u8 (T',B_,N1,C), scale (nH), bias (nH,N,N), mask (nW,N,N) or None as
+    the forward took them; dout = dL/d(output) (T',B_,N1,C) fp32.  -> (dq, dk, dv (T',B_,N1,C) fp32, d_bias (nH,N,N)); deterministic
+    (fixed-order split-K sum over windows for d_bias)."""
+    return _win_attn_sew_bwd("sdf_win_attn_sew_bwd", q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout)
+
+
+def win_attn_sew_bwd_large(q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout):
+    """The same for windows of 193 .. 1024 tokens (sdf_win_attn_large_sew_bwd, csrc/win_attn_large_bwd.hip: token blocks streamed
+    through LDS): arguments and returns of `win_attn_sew_bwd`."""
+    return _win_attn_sew_bwd("sdf_win_attn_large_sew_bwd", q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout)
 
 
 # ---- dense 3x3 convolution of real-valued activations (ANN patch embedding; csrc/dense_conv_wres.hip) ----
