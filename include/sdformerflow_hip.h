@@ -757,6 +757,22 @@ int sdf_win_attn_fwd(const SdfWinAttnDesc* d, void* stream);
  * N <= 192). */
 int sdf_win_attn_large_fwd(const SdfWinAttnDesc* d, void* stream);
 
+/* ---- the attention map of the same attention: 1 <= N <= 1024 tokens (`return_attention=True`, `log=True`) --------------------------
+ * What the reference's attention modules return as their second value, scores (B_, nH, N, N) fp32, window-major:
+ * scores[((b * nH + g) * N + i) * N + j].  Descriptor, modes, operand layouts and arithmetic of sdf_win_attn_fwd (exact fp32 MFMA,
+ * the score rounded as (acc * scale + bias) + mask); d->v and d->out are ignored and may be NULL.
+ *   SDF_ATTN_ANN: softmax over the keys of normalize(q) normalize(k)^T * scale[g] + bias[g] (+ mask[b % nW]) (reference
+ *     swin_transformer3D_v2.py:176-202), through row_map / pad_qkv as sdf_win_attn_fwd reads them: a padding token is a row and a
+ *     column of the map.  The keys are walked twice (row maximum and sum, then exp(s - max) / sum); no workspace.
+ *   SDF_ATTN_SEW: (q * scale[g]) k^T + bias[g] (+ mask), no softmax (Spiking_swin_transformer3D.py:320-360): the accumulator is the
+ *     exact count c of common spikes and the element is fp32(fp32(c * scale[g]) + bias) (+ mask).
+ * One kernel for every N, keys in blocks of 64, one launch; no atomics, two calls give bit-equal results.  Checks, before any
+ * launch, in sdf_win_attn_fwd's order: NULL d, q, k (SEW), scale, bias, row_map without pad_qkv -> SDF_E_NULL; unknown mode ->
+ * SDF_E_DTYPE; hd != 32, B_ / nH / N < 1, N > 1024, SEW Tq * N1 != N, a mask with nW < 1 or B_ % nW != 0, SEW with a row_map ->
+ * SDF_E_SHAPE; then scores NULL -> SDF_E_NULL, scores not 4-byte aligned (or q / k / pad_qkv not aligned as sdf_win_attn_fwd
+ * needs them) -> SDF_E_ALIGN.  Added to SDF_VERSION 107 (no existing entry changed). */
+int sdf_win_attn_scores_fwd(const SdfWinAttnDesc* d, float* scores, void* stream);
+
 /* ---- backward of the SDF_ATTN_ANN core of sdf_win_attn_fwd (training of the ANN model) -------------------------------------
  * Per window b and head g: q^ = q / max(|q|, 1e-12), k^ likewise, S = q^ k^T * scale[g] + bias[g] (+ mask[b % nW]),
  * P = softmax(S), O = P v.  Given dout = dL/dO (rows, C) through the same row map (D = rowsum(dO o O) is formed as

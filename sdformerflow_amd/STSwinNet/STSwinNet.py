@@ -113,8 +113,8 @@ class STT_encoder(nn.Module):
             nn.ModuleList([nn.Conv2d(embed_dim * 2 ** i, embed_dim * 2 ** i // self.num_blocks, 1) for _ in range(self.num_blocks)])
             for i in range(len(depths))])
 
-    def forward(self, x):
-        feats = self.swin3d(x)
+    def forward(self, x, scores=None):
+        feats = self.swin3d(x, scores)
         outs = []
         for f, ps in zip(feats, self.projections):
             B, _, _, h, w = f.shape
@@ -149,8 +149,8 @@ class STT_MultiResUNet(nn.Module):
             self.decoders.append(UpsampleConvLayer(2 * ci + (0 if i == 0 else n_out), co, k))
             self.preds.append(ConvLayer(co, n_out, 1, activation=None))
 
-    def forward(self, x):
-        blocks = self.encoders(x)
+    def forward(self, x, scores=None):
+        blocks = self.encoders(x, scores)
         y = blocks[-1]
         for rb in self.resblocks:
             y = rb(y)
@@ -163,12 +163,13 @@ class STT_MultiResUNet(nn.Module):
             parts = [_fit_to(y, skip), skip] + ([_fit_to(preds[-1], skip)] if i > 0 else [])
             y = dec.forward_parts(parts, [2, 0, 1] if i > 0 else [0, 1])
             preds.append(pred(y))
-        return preds, None
+        return preds, scores
 
 
 class STTFlowNet(nn.Module):
-    """forward(event_voxel (B,num_bins,H,W), event_cnt, log=False) -> {"flow": [..(B,2,H,W)], "attn": None,
-    "spiking_rates": None}; same constructor dictionaries as the reference (`model:` and `swin_transformer:` yaml blocks)."""
+    """forward(event_voxel (B,num_bins,H,W), event_cnt, log=False) -> {"flow": [..(B,2,H,W)], "attn": None (log=True, eval mode:
+    the attention map (B * nW_s, nH_s, N, N) of the last block of every stage), "spiking_rates": None}; same constructor
+    dictionaries as the reference (`model:` and `swin_transformer:` yaml blocks)."""
     num_en = 3
 
     def __init__(self, unet_kwargs, stt_kwargs):
@@ -218,8 +219,8 @@ class STTFlowNet(nn.Module):
             if self.training:
                 raise NotImplementedError("training runs on the GPU only: the attention backward is a HIP kernel (no CPU fallback)")
             raise hip.SdfError("STTFlowNet runs on the GPU only (no CPU fallback)")
-        if log:
-            raise NotImplementedError("attention-score logging is analysis tooling outside the forward path")
+        if log and self.training:
+            raise NotImplementedError("log=True is built for eval mode: training keeps no attention map (call model.eval())")
         if self.training:                                      # (before the first launch, not in the first swin block)
             ws = self.sttmultires_unet.encoders.swin3d.layers[0].window_size
             hip.check_attn_bwd_window(ws[0] * ws[1] * ws[2], "SDF_ANN_ATTN_BWD")
@@ -236,9 +237,11 @@ class STTFlowNet(nn.Module):
             H, W = x.shape[-2:]
             if H % 2 or W % 2:
                 x = F.pad(x, (0, W % 2, 0, H % 2))
-            flows, _ = self.sttmultires_unet(x)
+            # log=True (reference :448-450): the attention map (B * nW_s, nH_s, N, N) of the last block of every stage, taken during
+            # this one forward (swin_transformer3D_v2.Swin_BasicLayer.forward) - the reference runs the encoder a second time for them
+            flows, attns = self.sttmultires_unet(x, [] if log else None)
             flow_list = [F.interpolate(f, scale_factor=(H / f.shape[2], W / f.shape[3])) for f in flows]
-        return {"flow": flow_list, "attn": None, "spiking_rates": None}
+        return {"flow": flow_list, "attn": attns, "spiking_rates": None}
 
 
 class STTFlowNet_4en(STTFlowNet):

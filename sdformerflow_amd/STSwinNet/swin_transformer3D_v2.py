@@ -270,12 +270,31 @@ class SwinTransformerBlock3D(nn.Module):
         x = x + drop_path(a, self.drop_path, True)
         return x + drop_path(self.mlp(self.norm2(x)), self.drop_path, True)
 
-    def forward(self, x, mask_matrix=None):
+    def attention_map(self, x, mask):
+        """`return_attention=True` (reference :296-297, :327-328): the softmax probabilities (B_, nH, N, N) fp32 of this block's
+        windows, padding tokens as rows and columns, INSTEAD of the block's output.  The forward kernels never store them, so they
+        come from a kernel of their own (hip.win_attn_ann_scores, csrc/win_attn_scores.hip) on LayerNorm and the qkv projection of the
+        un-partitioned rows, read through the block's row map.  (Always the unfused LayerNorm and qkv: the first stage's one-launch
+        half block never has qkv in memory.)"""
+        B, D, H, W, C = x.shape
+        ws, ss = get_window_size((D, H, W), self.window_size, self.shift_size)
+        a = self.attn
+        with torch.no_grad():
+            row_map, B_ = self._row_map(B, D, H, W, ws, ss, x.device)
+            qkv = linear_rows(a.qkv, layer_norm(self.norm1, x).reshape(-1, C))
+            pad = a.qkv.bias.detach().float().contiguous() if a.qkv.bias is not None else torch.zeros(3 * C, device=x.device)
+            bias, scale = a._bias_and_scale()
+            return hip.win_attn_ann_scores(qkv, scale, bias, mask, a.num_heads, row_map, B_, ws[0] * ws[1] * ws[2], pad)
+
+    def forward(self, x, mask_matrix=None, return_attention=False):
         """forward_part1 + forward_part2 (reference :272-313).  The reference pads, rolls and partitions LN(x) into windows and
         reverses all of that behind the attention (:286-310); here the qkv projection runs on the un-partitioned rows and the
         attention kernel reads / writes them through the slice map (index arithmetic inside the kernel, nothing materialised):
         the projection is row-wise, so it commutes with the permutation; a padding token is a zero row, whose q | k | v is the
-        qkv bias.  `SDF_ATTN_MATERIALISE=1` keeps the reference's sequence as the A/B path."""
+        qkv bias.  `SDF_ATTN_MATERIALISE=1` keeps the reference's sequence as the A/B path.
+        `return_attention=True` (eval mode): the block's attention map instead of its output, see `attention_map`."""
+        if return_attention and self.training:
+            raise NotImplementedError("return_attention=True is built for eval mode: training keeps no attention map (call model.eval())")
         B, D, H, W, C = x.shape
         ws, ss = get_window_size((D, H, W), self.window_size, self.shift_size)
         if tuple(ws) != tuple(self.window_size):
@@ -288,6 +307,8 @@ class SwinTransformerBlock3D(nn.Module):
         mask = (mask_matrix if mask_matrix is not None else compute_mask(Dp, Hp, Wp, ws, ss, x.device)) if shifted else None
         if self.training:
             return self.forward_train(x, None if mask is None else mask.contiguous())
+        if return_attention:
+            return self.attention_map(x, None if mask is None else mask.contiguous())
         materialise = hip.sw("SDF_ATTN_MATERIALISE") == "1"
         # first stage (C = 96, three heads, 162-token windows): LayerNorm -> qkv -> attention -> proj -> + x is ONE launch that reads x
         # through the slice map (csrc/ann_block.hip); elsewhere the norm runs here and forward_rows takes its output
@@ -356,10 +377,23 @@ class Swin_BasicLayer(nn.Module):
             for i in range(depth)])
         self.downsample = downsample(dim) if downsample is not None else None
 
-    def forward(self, x):
-        for blk in self.swin_blocks:
+    def forward(self, x, scores=None):
+        """`scores` (a list, `log=True`): the last block also appends its attention map, from the input its own forward then takes -
+        every other launch is that of a plain forward."""
+        for i, blk in enumerate(self.swin_blocks):
+            if scores is not None and i == len(self.swin_blocks) - 1:
+                scores.append(blk(x, None, return_attention=True))
             x = blk(x)
         return x, (self.downsample(x) if self.downsample is not None else x)
+
+    def get_lst_block_attention_scores(self, x):
+        """The attention map (B_, nH, N, N) of the stage's last block (reference :515-530); x in the layout `forward` takes here,
+        (B,D,H,W,C).  Eval mode only."""
+        if self.training:
+            raise NotImplementedError("attention maps are built for eval mode (call model.eval())")
+        for blk in self.swin_blocks[:-1]:
+            x = blk(x)
+        return self.swin_blocks[-1](x, None, return_attention=True)
 
 
 class SwinTransformer3D_v2(nn.Module):
@@ -382,11 +416,20 @@ class SwinTransformer3D_v2(nn.Module):
         for i in self.out_indices:
             self.add_module(f"norm{i}", nn.LayerNorm(self.num_features[i]))
 
-    def forward(self, x):
+    def forward(self, x, scores=None):
         x = self.patch_embed(x).permute(0, 2, 3, 4, 1).contiguous()                 # (B,D,h,w,C)
         outs = []
         for i, layer in enumerate(self.layers):
-            o, x = layer(x)
+            o, x = layer(x, scores)
             if i in self.out_indices:
                 outs.append(layer_norm(getattr(self, f"norm{i}"), o).permute(0, 4, 1, 2, 3))
         return outs
+
+    def get_layer_attention_scores(self, x):
+        """[attention map (B * nW_s, nH_s, N, N) of the last block of stage s] (reference :765-778), x as `forward` takes it.  One
+        pass: the maps are taken during the forward that also makes the features (the reference runs the stages again)."""
+        if self.training:
+            raise NotImplementedError("attention maps are built for eval mode (call model.eval())")
+        scores = []
+        self.forward(x, scores)
+        return scores

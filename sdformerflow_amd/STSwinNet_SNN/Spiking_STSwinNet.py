@@ -294,12 +294,12 @@ class SpikingformerFlowNet(MS_SpikingformerFlowNet):
 
     def forward(self, x, log=False):
         if self.training:                     # train-mode forward under autograd (the SEW attention backward: csrc/win_attn_sew_bwd.hip)
+            if log:
+                raise NotImplementedError("log=True is built for eval mode: training keeps no attention map (call model.eval())")
             self._no_monitor("the model is in training mode", "rates are counted on the eval forward - call model.eval(), or disable() the monitor")
             from ..train import forward_train_sew
             return {"flow": forward_train_sew(self, x), "attn": None}
-        if log:
-            raise NotImplementedError("SEW attention maps (B_, nH, N, N) live in registers of the fused window-attention kernel and "
-                                      "are never materialised; log=True is built for the MS (QK token-gate) family")
+        # log=True: "attn" = the attention map (B_, nH, N, N) of the last block of every stage (engine_sew.SEWFlowEngine.swin_block)
         return super().forward(x, log)
 
     def forward_replicas(self, x):

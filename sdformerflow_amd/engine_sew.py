@@ -110,8 +110,11 @@ class SEWFlowEngine(MSFlowEngine):
         return out
 
     # ------------------------------------------------------------------ stages
-    def attention(self, x, blk: _SewBlock):
-        """SSA(x) (reference Spiking_swin_transformer3D.py:781-821 around :300-370): spikes, (B,D,H,W,C) fp32."""
+    def attention(self, x, blk: _SewBlock, score_out=None):
+        """SSA(x) (reference Spiking_swin_transformer3D.py:781-821 around :300-370): spikes, (B,D,H,W,C) fp32.  `score_out` (a list)
+        also receives the block's attention map (B_, nH, N, N) fp32 - `return_attention=True` (:807-808) without abandoning x: the
+        fused kernel keeps the map in registers, so it comes from a launch of its own on the same q and k spikes
+        (hip.win_attn_sew_scores, csrc/win_attn_scores.hip)."""
         self._check_cl(x)
         B, D, H, W, Cc = x.shape
         ws, ss = get_window_size((D, H, W), blk.window_size, blk.shift_size)
@@ -135,6 +138,8 @@ class SEWFlowEngine(MSFlowEngine):
                            alpha=blk.bn[n][0], beta=blk.bn[n][1], Cch=Cc, inner=1)
             self._rec(blk.name + f"attn.sn_{n}.spiking_neuron.", spk[n], "flat", steps=Tq)
         mask = self._mask(D, H, W, ws, ss) if any(s > 0 for s in ss) else None
+        if score_out is not None:
+            score_out.append(hip.win_attn_sew_scores(spk["q"], spk["k"], blk.scale, blk.bias(Tq * N1), mask, blk.nH, Tq, B_, N1))
         z = hip.win_attn_sew(spk["q"], spk["k"], spk["v"], blk.scale, blk.bias(Tq * N1), mask, blk.nH, Tq, B_, N1)
         y = hip.dense_linear(z.view(M, Cc), blk.wp, blk.bp)
         s = self._sn_rows(y, Tq, blk.proj_sn, blk.proj_bn, blk.name + "attn.proj_sn.spiking_neuron.")
@@ -155,7 +160,8 @@ class SEWFlowEngine(MSFlowEngine):
 
     def swin_block(self, x, s, i):
         blk = self.stages[s][i]
-        x = self.attention(x, blk) + x                                            # SEW ADD (:840)
+        last = self.scores is not None and i == len(self.stages[s]) - 1          # log=True: the last block of every stage (:1090-1105)
+        x = self.attention(x, blk, self.scores if last else None) + x            # SEW ADD (:840)
         return self.mlp(x, blk) + x                                               # (:845)
 
     def _tail_kwargs(self):

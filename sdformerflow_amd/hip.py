@@ -337,6 +337,7 @@ SIGNATURES = {
     "sdf_flow_out_fwd": (_i, (_p, _p, _i, _i, _i, _i, _i64, _i, _i, _i, _f, _f, _p)),
     "sdf_pred_head_fwd": (_i, (_P(PredHeadDesc), _p)), "sdf_affine_resid_fwd": (_i, (_p, _p, _p, _p, _p, _i64, _i, _i64, _p)),
     "sdf_win_attn_fwd": (_i, (_P(WinAttnDesc), _p)), "sdf_win_attn_large_fwd": (_i, (_P(WinAttnDesc), _p)),
+    "sdf_win_attn_scores_fwd": (_i, (_P(WinAttnDesc), _p, _p)),
     "sdf_win_attn_ann_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_ann_bwd": (_i, (_P(WinAttnBwdDesc), _p)),
     "sdf_win_attn_sew_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_sew_bwd": (_i, (_P(WinAttnSewBwdDesc), _p)),
     "sdf_win_attn_large_ann_bwd_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_win_attn_large_ann_bwd": (_i, (_P(WinAttnBwdDesc), _p)),
@@ -1462,6 +1463,42 @@ def win_attn_sew(q, k, v, scale, bias, mask, nH, Tq, B_, N1):
     d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
     _win_attn_fwd(d)
     return out
+
+
+def _win_attn_scores(d, device):
+    """The attention map of the descriptor's attention (sdf_win_attn_scores_fwd: one kernel for 1 .. 1024 tokens per window, more
+    are refused with the library's code) -> (B_, nH, N, N) fp32, window-major."""
+    scores = torch.empty((d.B_, d.nH, d.N, d.N), dtype=torch.float32, device=device)
+    _check(lib().sdf_win_attn_scores_fwd(C.byref(d), _ptr(scores), _stream()), "sdf_win_attn_scores_fwd")
+    return scores
+
+
+def win_attn_ann_scores(qkv, scale, bias, mask, nH, row_map=None, B_=None, N=None, pad_qkv=None):
+    """The softmax probabilities `win_attn_ann` / `win_attn_ann_windowed` multiply v with, which they never store (SDF_ATTN_ANN of
+    sdf_win_attn_scores_fwd): qkv (B_,N,3C) fp32, or with `row_map` (B_*N,) int32 qkv (rows, 3C), B_, N and pad_qkv (3C) as
+    `win_attn_ann_windowed` takes them (a padding token is a row and a column of the map) -> (B_, nH, N, N) fp32."""
+    if row_map is None:
+        B_, N = qkv.shape[:2]
+    C3 = qkv.shape[-1]
+    d = WinAttnDesc()
+    d.mode, d.q = 0, _ptr(qkv, torch.float32)
+    d.B_, d.nW, d.nH, d.N, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, N, C3 // 3 // nH
+    d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
+    if row_map is not None:
+        d.row_map, d.pad_qkv = _ptr(row_map, torch.int32), _ptr(pad_qkv, torch.float32)
+    return _win_attn_scores(d, qkv.device)
+
+
+def win_attn_sew_scores(q, k, scale, bias, mask, nH, Tq, B_, N1):
+    """The score matrix `win_attn_sew` multiplies v with (SDF_ATTN_SEW of sdf_win_attn_scores_fwd, no softmax): q, k u8
+    (T',B_,N1,C) -> (B_, nH, N, N) fp32 on the reference's raw head view, N = T' * N1."""
+    Cc = q.shape[-1]
+    d = WinAttnDesc()
+    d.mode, d.q, d.k = 1, _ptr(q, torch.uint8), _ptr(k, torch.uint8)
+    d.B_, d.nW, d.nH, d.N, d.hd = B_, (mask.shape[0] if mask is not None else 1), nH, Tq * N1, Cc // nH
+    d.Tq, d.N1 = Tq, N1
+    d.scale, d.bias, d.mask = _ptr(scale, torch.float32), _ptr(bias, torch.float32), _ptr(mask, torch.float32)
+    return _win_attn_scores(d, q.device)
 
 
 def _win_attn_sew_bwd(entry, q, k, v, scale, bias, mask, nH, Tq, B_, N1, dout):

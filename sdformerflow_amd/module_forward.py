@@ -143,13 +143,16 @@ def _sew(mod_block):
 
 def sew_block_forward(mod, x, mask_matrix=None, return_attention=False):
     """`Spiking_SwinTransformerBlock3D.forward` (reference :824-847): x (B,D,H,W,C) -> SSA(x) + x, then MLP(.) + (.).  The shift
-    mask is derived from the shape like the layer does (:1070-1076); a passed `mask_matrix` is accepted for the signature."""
+    mask is derived from the shape like the layer does (:1070-1076); a passed `mask_matrix` is accepted for the signature.
+    `return_attention=True` (:836-837): the attention map (B_, nH, N, N) of the block's windows instead of its output."""
     _eval_only(mod)
-    if return_attention:
-        raise NotImplementedError("return_attention is not built")
     eng, blk = _sew(mod)
     with torch.no_grad():
         x = _cl(x)
+        if return_attention:
+            score = []
+            eng.attention(x, blk, score)
+            return score[0]
         x = eng.attention(x, blk) + x
         return eng.mlp(x, blk) + x
 
