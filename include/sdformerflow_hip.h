@@ -246,6 +246,16 @@ int sdf_neuron_multi_fwd(const SdfNeuronDesc* descs, int n, void* stream);
  * read; v_last must be NULL and T in {2, 4, 5, 10, 20} (SDF_E_SHAPE), tab not NULL (SDF_E_NULL); every other check, and their order,
  * are sdf_neuron_fwd's.  What an eval forward of a GLIF model launches at every neuron call (no fused epilogue has a GLIF form). */
 int sdf_glif_neuron_fwd(const SdfNeuronDesc* d, const float* tab, void* stream);
+/* The general launch that also keeps the membrane (the reference's `store_v_seq = True`, eval_DSEC_flow_SNN.py:145-149, `vis.monitor_v`):
+ * sdf_neuron_fwd's contract field for field - dense strides, rowmap gather with negative entries, alpha / beta with inner == 1 and
+ * inner > 1, add, nrep, out_dtype, v_last, T in {2, 4, 5, 10, 20} compiled in and any other T at run time - and the same spikes bit for
+ * bit, plus the membrane AFTER the reset of step t (spikingjelly's v_seq[t]) as fp32 at
+ *     v_seq + b*o_sb + t*o_st + r        (+ p*o_srep for problem p of nrep)
+ * i.e. `out`'s own addressing in fp32 elements: a v_seq tensor has the shape and strides of the spike tensor.  Nothing else of v_seq is
+ * written.  Kinds SDF_LIF and SDF_IF; SDF_PSN has no membrane and is refused with SDF_E_DTYPE where the kind is checked.  v_seq NULL ->
+ * SDF_E_NULL (with d), v_seq not 16-byte aligned -> SDF_E_ALIGN (behind the descriptor's own checks); every other check, and their
+ * order, are sdf_neuron_fwd's.  Added to SDF_VERSION 107 (no existing entry changed). */
+int sdf_neuron_vseq_fwd(const SdfNeuronDesc* d, float* v_seq, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Spike GEMM:  out[M,N] = epilogue( A[M,K] (binary, u8) x W[N,K]^T ).
@@ -1192,6 +1202,37 @@ typedef struct SdfPrepareChunkDesc {
 
 int64_t sdf_prepare_chunk_workspace_bytes(int B);
 int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * fp32 membranes -> per-time-step statistics in integers: what a reader of the reference's `v_seq_monitor.records` (`vis.monitor_v`)
+ * looks at - mean, extremes and a histogram of a neuron call's membrane per step - without keeping the membrane.
+ * sdf_spike_count_fwd's geometry on fp32: element (o, t, r, c) is the float at v + ((o * T + t) * rows + r) * row_stride + c (strides
+ * in elements).  Nothing outside the addressed floats is read: row_stride == C is one run of rows * C floats per (o, t), 16 bytes per
+ * lane between the run's first and last 16-byte boundary and element-wise in front and behind; row_stride > C walks the rows.
+ * Step t ADDS into the record table + t * (4 + bins + 2) of 64-bit integers:
+ *   [0] n_nan    += NaNs (a NaN takes part in nothing else)
+ *   [1] sum_q16  += (int64) rintf(clamp(x, -32768.f, 32768.f) * 65536.f)            (the product is exact in fp32)
+ *   [2] min_key   = min(min_key, key(x)),  [3] max_key = max(max_key, key(x)),  key = bits ^ (sign ? 0xFFFFFFFF : 0x80000000), the
+ *       order-preserving unsigned key of the fp32 bits; the CALLER initialises the slots to 2^32 - 1 and 0 (and the rest to 0)
+ *   [4 + i] hist[i] += 1,  i = x < lo ? 0 : x >= hi ? bins + 1 : 1 + min(bins - 1, (int) floorf((x - lo) * inv_width)), every
+ *       operation rounded separately; inv_width = bins / (hi - lo) is formed once by the caller in fp32
+ * Integer atomics only: the same bits on every run, and restated exactly on the host (sdformerflow_amd/monitor.py membrane_record).
+ * SDF_E_NULL: d, v or table NULL; SDF_E_SHAPE: outer, rows or C < 1, T outside 1 .. 64, row_stride < C, bins outside 1 .. 256, not
+ * lo < hi, inv_width not positive and finite (or sizes beyond 2^60 elements / 2^31 workgroups); SDF_E_ALIGN: v not 4-byte or table not
+ * 8-byte aligned.  Added to SDF_VERSION 107 (no existing entry changed). */
+typedef struct SdfMembraneStatsDesc {
+  const float* v;
+  int64_t outer;
+  int T;
+  int64_t rows;
+  int C;
+  int64_t row_stride;
+  int64_t* table;           /* T records of 4 + bins + 2 */
+  int bins;
+  float lo, hi, inv_width;
+} SdfMembraneStatsDesc;
+
+int sdf_membrane_stats_fwd(const SdfMembraneStatsDesc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * u8 spikes -> spike counts per time step: the numerator of the firing rate the reference's output monitor records for a neuron call,

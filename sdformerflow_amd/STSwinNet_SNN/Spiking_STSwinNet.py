@@ -138,7 +138,10 @@ class MS_SpikingformerFlowNet(nn.Module):
         self.sttmultires_unet = self.unet_type(unet_kwargs, dict(stt_kwargs))
         self._engine, self._stamp_tensors = None, None
         self._glif_engine = None      # the unfused eval plan of a GLIF model (eval_engine)
-        self._fr_monitor = None       # a monitor.FiringRateMonitor while it is enabled (it lives here, not on the engine: rebuilds keep it)
+        self._unfused_engine = None   # the unfused eval plan of a lif / if / plif / SLTTlif model (unfused_engine)
+        # a monitor.FiringRateMonitor or monitor.MembraneMonitor while it is enabled - one at a time (it lives here, not on the engine:
+        # rebuilds keep it)
+        self._fr_monitor = None
         # Weight planes of the spike GEMMs / convolutions (binary spikes are exact in 16-bit floats, accumulation is fp32):
         #   2 = fp16 hi + lo of the power-of-two-scaled weight: 22 of the 24 significand bits at 2/3 of the matrix work.
         #       Measured against fp64 the layer outputs are as close as torch's own fp32 convolution, and every
@@ -159,14 +162,14 @@ class MS_SpikingformerFlowNet(nn.Module):
             elif isinstance(m, nn.Conv2d):
                 nn.init.xavier_uniform_(m.weight)
         self.apply(_init)
-        self._engine = self._glif_engine = None
+        self._engine = self._glif_engine = self._unfused_engine = None
 
     def load_state_dict(self, *a, **k):
-        self._engine = self._glif_engine = None
+        self._engine = self._glif_engine = self._unfused_engine = None
         return super().load_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):
-        self._engine, self._glif_engine, self._stamp_tensors = None, None, None
+        self._engine, self._glif_engine, self._unfused_engine, self._stamp_tensors = None, None, None, None
         return super()._apply(fn, *a, **k)
 
     def _weights_stamp(self):
@@ -182,12 +185,12 @@ class MS_SpikingformerFlowNet(nn.Module):
 
     def invalidate_engine(self):
         """For callers that swap tensors out behind the module's back (`p.data = ...`), which no version counter sees."""
-        self._engine, self._glif_engine, self._stamp_tensors = None, None, None
+        self._engine, self._glif_engine, self._unfused_engine, self._stamp_tensors = None, None, None, None
 
     def train(self, mode=True):
         """Entering training invalidates the packed inference plan (weights and BN statistics are about to change)."""
         if mode:
-            self._engine = self._glif_engine = None
+            self._engine = self._glif_engine = self._unfused_engine = None
         return super().train(mode)
 
     def engine(self):
@@ -216,6 +219,19 @@ class MS_SpikingformerFlowNet(nn.Module):
             self._glif_engine, self._glif_stamp = GLIFFlowEngine(self), stamp
         return self._glif_engine
 
+    def unfused_engine(self):
+        """The unfused plan beside `eval_engine()`: every neuron call as "fp32 pre-activation in memory -> general neuron launch -> u8
+        spikes" (engine_unfused.UnfusedFlowEngine) for a `lif` / `if` / `plif` / `SLTTlif` model - what a membrane monitor runs its
+        forwards on - and the GLIF engine for a glif model.  Rebuilt on the same weight stamp as `engine()`.  The plain forward and
+        `eval_engine()` of a non-glif model never ask for it."""
+        if self.sttmultires_unet.spiking_kwargs.get("neuron_type") == "glif":
+            return self.eval_engine()
+        stamp = self._weights_stamp()
+        if self._unfused_engine is None or self._unfused_stamp != stamp:
+            from ..engine_unfused import UnfusedFlowEngine
+            self._unfused_engine, self._unfused_stamp = UnfusedFlowEngine(self), stamp
+        return self._unfused_engine
+
     def flops(self):
         """reference :307-308."""
         return self.sttmultires_unet.flops()
@@ -226,17 +242,17 @@ class MS_SpikingformerFlowNet(nn.Module):
 
     def _no_monitor(self, what, instead):
         if self._fr_monitor is not None:
-            raise RuntimeError(f"a firing-rate monitor is enabled on this model and {what}: {instead}")
+            raise RuntimeError(f"a {self._fr_monitor.what} is enabled on this model and {what}: {instead}")
 
     def _engine_forward(self, x, scores=None):
-        """The eval forward on the packed plan - through the firing-rate monitor while one is enabled (monitor.FiringRateMonitor)."""
+        """The eval forward on the packed plan - through the firing-rate or membrane monitor while one is enabled (monitor.py)."""
         if self._fr_monitor is not None:
             return self._fr_monitor.forward(x, scores)          # (asks for self.eval_engine() itself, behind its refusals)
         return self.eval_engine().forward(x, scores)
 
     def forward(self, x, log=False):
         if self.training:                     # train-mode forward under autograd (batch-stat BN, HIP neurons both ways)
-            self._no_monitor("the model is in training mode", "rates are counted on the eval forward - call model.eval(), or disable() the monitor")
+            self._no_monitor("the model is in training mode", "it records the eval forward - call model.eval(), or disable() the monitor")
             from ..train import forward_train
             return {"flow": forward_train(self, x), "attn": None}
         with torch.no_grad():
@@ -296,7 +312,7 @@ class SpikingformerFlowNet(MS_SpikingformerFlowNet):
         if self.training:                     # train-mode forward under autograd (the SEW attention backward: csrc/win_attn_sew_bwd.hip)
             if log:
                 raise NotImplementedError("log=True is built for eval mode: training keeps no attention map (call model.eval())")
-            self._no_monitor("the model is in training mode", "rates are counted on the eval forward - call model.eval(), or disable() the monitor")
+            self._no_monitor("the model is in training mode", "it records the eval forward - call model.eval(), or disable() the monitor")
             from ..train import forward_train_sew
             return {"flow": forward_train_sew(self, x), "attn": None}
         # log=True: "attn" = the attention map (B_, nH, N, N) of the last block of every stage (engine_sew.SEWFlowEngine.swin_block)

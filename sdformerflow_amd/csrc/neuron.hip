@@ -217,6 +217,54 @@ __global__ __launch_bounds__(256) void glif_neuron_kernel(NeuronParams P, const 
   }
 }
 
+// The LIF / IF launch that also keeps the membrane: step t's v after the reset (fire_reset's v - spikingjelly's v_seq under
+// store_v_seq) goes to v_seq at the spike's own offset, in fp32 elements.  A kernel of its own, as the GLIF one, so that neuron_body
+// keeps its registers; TT == 0 is the runtime-T form (one load ahead).  Same step, same order: the spikes are sdf_neuron_fwd's.
+template <int TT>
+__global__ __launch_bounds__(256) void neuron_vseq_kernel(NeuronParams P, float* __restrict__ v_seq) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= P.quads) return;
+  const int T = TT > 0 ? TT : P.d.T;
+  const Quad Q = quad_of(P, q);
+  const bool soft = P.d.soft_reset != 0;
+  const bool reset0 = soft || P.d.v_reset == 0.f, is_if = P.d.kind == SDF_IF;
+  const float v0 = soft ? 0.f : P.d.v_reset;
+  float4 v = make_float4(v0, v0, v0, v0);
+  auto step = [&](int t, float4 x) {
+    float4 h, s;
+    h.x = neuron_charge(is_if, v.x, x.x, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+    h.y = neuron_charge(is_if, v.y, x.y, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+    h.z = neuron_charge(is_if, v.z, x.z, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+    h.w = neuron_charge(is_if, v.w, x.w, P.d.tau, P.inv_tau, P.d.v_reset, reset0);
+    s.x = fire_reset(v.x, h.x, P.d.v_th, P.d.v_reset, soft);
+    s.y = fire_reset(v.y, h.y, P.d.v_th, P.d.v_reset, soft);
+    s.z = fire_reset(v.z, h.z, P.d.v_th, P.d.v_reset, soft);
+    s.w = fire_reset(v.w, h.w, P.d.v_th, P.d.v_reset, soft);
+    const int64_t off = Q.obase + (int64_t)t * P.d.o_st;
+    store_spikes(P, off, s);
+    *reinterpret_cast<float4*>(v_seq + off) = v;
+  };
+  auto load = [&](int t) {
+    const float* p = x_addr(P, t, Q.e, Q.b, Q.r, Q.xrep);
+    return p ? load4(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  if constexpr (TT > 0) {
+    float4 xv[TT];
+#pragma unroll
+    for (int t = 0; t < TT; ++t) xv[t] = load(t);
+#pragma unroll
+    for (int t = 0; t < TT; ++t) step(t, prologue(P, xv[t], t, Q.r, Q.al, Q.be));
+  } else {
+    float4 nxt = load(0);
+    for (int t = 0; t < T; ++t) {
+      const float4 x = nxt;
+      if (t + 1 < T) nxt = load(t + 1);
+      step(t, prologue(P, x, t, Q.r, Q.al, Q.be));
+    }
+  }
+  if (P.d.v_last) *reinterpret_cast<float4*>(P.d.v_last + q * 4) = v;
+}
+
 // Several independent neuron calls of the same T as ONE launch (the decoders' skip inputs: four small tensors, each a launch of
 // its own before): workgroup ranges are dealt to the descriptors by `first[]`
 constexpr int MULTI_MAX = 6;
@@ -285,12 +333,14 @@ int launch_scalar(const float* x, void* spike, float* v_last, int T, int64_t N, 
 }
 
 // `glif`: the descriptor of sdf_glif_neuron_fwd - its T list, no v_last, and none of the neuron fields (kind, tau, psn_*) is read
-int validate(const SdfNeuronDesc& d, bool glif = false) {
+// `vseq`: the descriptor of sdf_neuron_vseq_fwd - a PSN has no membrane and is refused where the kind is checked
+int validate(const SdfNeuronDesc& d, bool glif = false, bool vseq = false) {
   if (!d.x || !d.out) return SDF_E_NULL;
   if (d.T < 1 || d.nb < 1 || d.ni < 4) return SDF_E_SHAPE;
   if (glif && (!sdf_in(SDF_T_GLIF, d.T) || d.v_last)) return SDF_E_SHAPE;
   if (d.out_dtype != SDF_F32 && d.out_dtype != SDF_U8) return SDF_E_DTYPE;
   if (!glif && d.kind != SDF_LIF && d.kind != SDF_PSN && d.kind != SDF_IF) return SDF_E_DTYPE;
+  if (vseq && d.kind == SDF_PSN) return SDF_E_DTYPE;
   if (d.ni % 4 || d.o_sb % 4 || d.o_st % 4) return SDF_E_SHAPE;
   if (!sdf_aligned(d.x, 16) || !sdf_aligned(d.out, d.out_dtype == SDF_F32 ? 16 : 4)) return SDF_E_ALIGN;
   if (d.nrep < 0 || (d.nrep > 1 && (d.rowmap || d.x_srep % 4 || d.o_srep % 4))) return SDF_E_SHAPE;      // (the outer dimension is a dense-mode feature)
@@ -353,6 +403,21 @@ extern "C" int sdf_glif_neuron_fwd(const SdfNeuronDesc* dp, const float* tab, vo
   dim3 grid((unsigned)sdf_quad_blocks(P.quads * 4)), block(256);
   hipStream_t s = sdf_stream(stream);
   sdf_dispatch(SDF_T_GLIF, dp->T, [&](auto tt) { SDF_LAUNCH(glif_neuron_kernel<tt>, grid, block, 0, s, P, tab); });   // (validated: T is in the list)
+  SDF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sdf_neuron_vseq_fwd(const SdfNeuronDesc* dp, float* v_seq, void* stream) {
+  if (!dp || !v_seq) return SDF_E_NULL;
+  int rc = validate(*dp, false, true);
+  if (rc) return rc;
+  if (!sdf_aligned(v_seq, 16)) return SDF_E_ALIGN;
+  const NeuronParams P = neuron_params(*dp);
+  if (sdf_quad_blocks(P.quads * 4) >= (1LL << 31)) return SDF_E_SHAPE;
+  dim3 grid((unsigned)sdf_quad_blocks(P.quads * 4)), block(256);
+  hipStream_t s = sdf_stream(stream);
+  if (!sdf_dispatch(SDF_T_GLIF, dp->T, [&](auto tt) { SDF_LAUNCH(neuron_vseq_kernel<tt>, grid, block, 0, s, P, v_seq); }))
+    SDF_LAUNCH(neuron_vseq_kernel<0>, grid, block, 0, s, P, v_seq);   // any other T: the runtime-T form
   SDF_LAUNCH_CHECK();
   return 0;
 }

@@ -73,16 +73,16 @@ def _np(sn_module, device):
     return hip.NeuronParams(n.kind, n.tau, n.v_threshold, n.v_reset)
 
 
-def attention_score(e, sn, nH, Tq, B_, N1):
+def attention_score(e, sn, nH, Tq, B_, N1, launch=None):
     """`attn = self.attn_sn(x)` of `Spiking_QK_WindowAttention3D.forward` (reference Spiking_swin_transformer3D.py:709-711) from the
     gated spikes e (T', B_*N1, C) u8 of one block: the head scramble Z[t,b,n,g,d] = E_flat[((((b nH + g) T' + t) N1 + n) hd + d] as a
-    re-layout (diagnostic path: the score is dead on the forward path, :715-716), then the neuron kernel over T'.
-    -> (T', B_, N1, C) fp32 spikes."""
+    re-layout (diagnostic path: the score is dead on the forward path, :715-716), then the neuron kernel over T' (`launch`: the
+    engine's neuron launch).  -> (T', B_, N1, C) fp32 spikes."""
     Cc = e.shape[-1]
     z = e.reshape(B_, nH, Tq, N1, Cc // nH).permute(2, 0, 3, 1, 4).reshape(Tq, B_ * N1 * Cc).float().contiguous()
     out = torch.empty_like(z)
     n = z.shape[1]
-    hip.neuron_fwd(z, out, Tq, 1, n, 0, n, 0, n, sn)
+    (launch or hip.neuron_fwd)(z, out, Tq, 1, n, 0, n, 0, n, sn)
     return out.view(Tq, B_, N1, Cc)
 
 
@@ -350,6 +350,10 @@ def deconv_route(B, D, h, w, cin, cout, nsplit, replicas=False):
 
 class MSFlowEngine:
     _np = staticmethod(_np)         # how a Spiking_neuron wrapper is packed (engine_glif.GLIFFlowEngine packs gate tables)
+    # the general neuron launch of every method below (engine_unfused.UnfusedFlowEngine's also keeps the membrane for a monitor)
+    @staticmethod
+    def _neuron_fwd(*a, **kw):
+        return hip.neuron_fwd(*a, **kw)
 
     @classmethod
     def bare(cls, device, nsplit=2):
@@ -485,10 +489,14 @@ class MSFlowEngine:
         a = torch.zeros((Tq, n4), dtype=torch.float32, device=q.device)
         a[:, :n] = q.reshape(Tq, rows, nH, Cc // nH).sum(-1, dtype=torch.float32).view(Tq, n)
         g = torch.empty((Tq, n4), dtype=torch.uint8, device=q.device)
-        hip.neuron_fwd(a, g, Tq, 1, n4, 0, n4, 0, n4, blk.sn2_q)
-        self.monitor.record(blk.name + "attn.sn2_q.spiking_neuron.", g[:, :n], "flat")
-        s = attention_score(e, blk.attn_sn, nH, Tq, B_, N1)
-        self.monitor.record(blk.name + "attn.attn_sn.spiking_neuron.", s.to(torch.uint8), "flat")
+        self._neuron_fwd(a, g, Tq, 1, n4, 0, n4, 0, n4, blk.sn2_q)
+        self._rec_monitor(blk.name + "attn.sn2_q.spiking_neuron.", g[:, :n], "flat")
+        s = attention_score(e, blk.attn_sn, nH, Tq, B_, N1, self._neuron_fwd)
+        self._rec_monitor(blk.name + "attn.attn_sn.spiking_neuron.", s, "flat")
+
+    def _rec_monitor(self, name, spikes, layout):
+        """A record that goes to the monitor alone (the parity tape does not hold it): u8 spikes, or fp32 ones that are counted as u8."""
+        self.monitor.record(name, spikes if spikes.dtype == torch.uint8 else spikes.to(torch.uint8), layout)
 
     def _neuron_bd(self, x, p, bn=None, out_dtype=torch.uint8, out=None):
         """Neuron over D of a channel-last (B,D,h,w,C) activation, BN fused when given."""
@@ -498,7 +506,7 @@ class MSFlowEngine:
             out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
         a, b = bn if bn is not None else (None, None)
         n = h * w * Cc
-        hip.neuron_fwd(x, out, D, B, n, D * n, n, D * n, n, p, alpha=a, beta=b, Cch=Cc, inner=1)
+        self._neuron_fwd(x, out, D, B, n, D * n, n, D * n, n, p, alpha=a, beta=b, Cch=Cc, inner=1)
         return out
 
     def _conv3x3(self, s, Wp, Cout, stride=1, bn=None, resid=None, sn=None, membrane=False):
@@ -666,7 +674,7 @@ class MSFlowEngine:
             # the slice spikes are overwritten by the gate inside the call: the tape runs the same kernel on the same input first
             rows, keep = B_ * N1, []
             xs = torch.empty((Tq, rows, Cc), dtype=torch.uint8, device=x.device)
-            hip.neuron_fwd(x, xs, Tq, 1, rows * Cc, 0, 0, 0, rows * Cc, blk.sn_proj, rowmap=rowmap, rowlen=Cc)
+            self._neuron_fwd(x, xs, Tq, 1, rows * Cc, 0, 0, 0, rows * Cc, blk.sn_proj, rowmap=rowmap, rowlen=Cc)
             self._rec(blk.name + "attn.proj_sn.spiking_neuron.", xs, "flat")
         info = {}
         zsrc = self._zsrc_map(rowmap, B_, Tq, N1, blk.nH, B * D * H * W, (B, D, H, W, tuple(ws), tuple(ss))) if Cc >= _WIDE_MINC and Tq == 2 else None
@@ -743,10 +751,16 @@ class MSFlowEngine:
                     flat = torch.cat([spikes.view(-1, Cc), spikes.new_zeros(1, Cc)], 0)
                     self._rec(name, flat[idx].view(D, B, H2, W2, 4 * Cc), "flat")
                 return out
+        return self._patch_merge_gathered(x, lin, sn, name)
+
+    def _patch_merge_gathered(self, x, lin, sn, name):
+        """The merge as the reference lays it out: the neuron over the gathered 2x2 concatenation (a zero row where the size is odd),
+        then the reduction product with BN."""
+        B, D, H, W, Cc = x.shape
         rowmap, H2, W2, out_map = self._merge_map(B, D, H, W)
         rows = B * H2 * W2
         sp = torch.empty((D * rows, 4 * Cc), dtype=torch.uint8, device=x.device)
-        hip.neuron_fwd(x, sp, D, 1, rows * 4 * Cc, 0, 0, 0, rows * 4 * Cc, sn, rowmap=rowmap, rowlen=Cc)
+        self._neuron_fwd(x, sp, D, 1, rows * 4 * Cc, 0, 0, 0, rows * 4 * Cc, sn, rowmap=rowmap, rowlen=Cc)
         self._rec(name, sp.view(D, B, H2, W2, 4 * Cc), "flat")
         out = torch.empty((B, D, H2, W2, lin.N), dtype=torch.float32, device=x.device)
         hip.spike_gemm(sp, lin.Wp, out, D * rows, lin.N, 4 * Cc, alpha=lin.alpha, beta=lin.beta, out_rowmap=out_map)
@@ -873,7 +887,7 @@ class MSFlowEngine:
         B, D, h, w, cp = s.shape
         hw = h * w
         for b in range(B):
-            hip.neuron_fwd(src[b], s[b].view(-1)[c0:], D, hw, take, pitch, hw * pitch, cp, hw * cp, sn)
+            self._neuron_fwd(src[b], s[b].view(-1)[c0:], D, hw, take, pitch, hw * pitch, cp, hw * cp, sn)
 
     def _transposed_conv(self, i, route, s, wkey, wuse):
         """z (B,D,2h,2w,cout) fp32 = BN(ConvTranspose2d(k 3, s 2, p 1, op 1)(s)) of decoder level i, launched as deconv_route decided."""
@@ -916,8 +930,8 @@ class MSFlowEngine:
         pr, E, name = self.preds[i], len(feats), f"sttmultires_unet.preds.{i}.sn.spiking_neuron."
         nxt_skip = feats[E - 2 - i] if i + 1 < E else None
         fs = out_size if out_size is not None and out_size[0] % H2 == 0 and out_size[1] % W2 == 0 else None
-        if not (pr.nout == 2 and hip.pred_head_supported(D, cout, fs[0] if fs else H2, fs[1] if fs else W2, H2, W2, pr.sn,
-                                                         self.decoders[i + 1].sn if nxt_skip is not None else None)
+        if not (pr.nout == 2 and self._pred_head_fused(D, cout, fs[0] if fs else H2, fs[1] if fs else W2, H2, W2, pr.sn,
+                                                       self.decoders[i + 1].sn if nxt_skip is not None else None)
                 and B * D * H2 * W2 * max(cout, 16) * 4 < 1 << 40):
             sp = self._neuron_bd(z, pr.sn)
             self._rec(name, sp, "BDHWC->TBCHW")
@@ -936,6 +950,11 @@ class MSFlowEngine:
         if sp is not None:
             self._rec(name, sp, "BDHWC->TBCHW")
         return pred, carried
+
+    # whether a level's prediction head runs as one launch with its neuron inside (the unfused plan answers no)
+    @staticmethod
+    def _pred_head_fused(*a):
+        return hip.pred_head_supported(*a)
 
     def unet_tail(self, feats, out_size=None, s1=None):
         """res-blocks + decoders + per-scale predictions on channel-last (B,D,h,w,C) features

@@ -124,14 +124,26 @@ def _with_firing_rates(loop, model, samples, config, device, monitor):
     """`loop(model, samples, config, device)` - and, when `vis.monitor_fr` is true (the reference's key, eval_DSEC_flow_SNN.py:140-143),
     its forwards under a monitor.FiringRateMonitor (the caller's `monitor`, or a new one; left as enabled or disabled as it came) and
     two more entries in the dict: "firing_rate" (what the reference prints, :223-227) and "firing_rates" (call name -> its T rates,
-    averaged over the forwards).  Key false or absent: the loop alone."""
-    if not (config.get("vis") or {}).get("monitor_fr"):
+    averaged over the forwards).  Key false or absent: the loop alone.
+    `vis.monitor_v` true (the reference's other key, :145-149, 228-230): the same under a monitor.MembraneMonitor, and ONE more entry,
+    "membrane": call name -> {"mean", "min", "max": T floats, "hist": T lists of bins + 2 counts, "n_nan"} over the forwards (mean
+    averaged, extremes over all, histogram summed; the bin edges are the monitor's `.edges`).  Both keys true is refused: a forward
+    takes one recording route."""
+    vis = config.get("vis") or {}
+    want_fr, want_v = bool(vis.get("monitor_fr")), bool(vis.get("monitor_v"))
+    if want_fr and want_v:
+        raise RuntimeError("vis.monitor_fr and vis.monitor_v are both set: one monitor at a time (the rates are counted on the fused "
+                           "plan's recording route, the membranes kept on the unfused plan) - run the evaluation once per key")
+    if not (want_fr or want_v):
         return loop(model, samples, config, device)
+    from .monitor import FiringRateMonitor, MembraneMonitor
+    cls = MembraneMonitor if want_v else FiringRateMonitor
     if monitor is None:
-        from .monitor import FiringRateMonitor
-        monitor = FiringRateMonitor(model)
+        monitor = cls(model)
     elif monitor.model is not model:
-        raise ValueError("monitor= belongs to another model: it would record nothing here - pass a FiringRateMonitor of this model, or none")
+        raise ValueError(f"monitor= belongs to another model: it would record nothing here - pass a {cls.__name__} of this model, or none")
+    elif type(monitor) is not cls:
+        raise ValueError(f"monitor= is a {type(monitor).__name__}, vis.monitor_{'v' if want_v else 'fr'} asks for a {cls.__name__}: pass one, or none")
     was_on = monitor.enabled
     monitor.enable()
     try:
@@ -139,7 +151,10 @@ def _with_firing_rates(loop, model, samples, config, device, monitor):
     finally:
         if not was_on:
             monitor.disable()
-    result["firing_rate"], result["firing_rates"] = monitor.mean(), monitor.rates()
+    if want_v:
+        result["membrane"] = monitor.summary()
+    else:
+        result["firing_rate"], result["firing_rates"] = monitor.mean(), monitor.rates()
     return result
 
 
@@ -294,6 +309,9 @@ class StreamEvaluator:
         if (config.get("vis") or {}).get("monitor_fr"):
             raise RuntimeError("vis.monitor_fr is set: firing rates are counted on single eager forwards, not under replicas and captured "
                                "graphs - use harness.evaluate / evaluate_mv for the rates, or clear the key for the throughput scheme")
+        if (config.get("vis") or {}).get("monitor_v"):
+            raise RuntimeError("vis.monitor_v is set: membranes are recorded on single eager forwards of the unfused plan, not under "
+                               "replicas and captured graphs - use harness.evaluate / evaluate_mv, or clear the key for the throughput scheme")
         self.model, self.config, self.device = model, config, torch.device(device)
         self.R, self.F, self.graphs = int(replicas), int(streams), bool(graphs)
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.F)]

@@ -287,6 +287,12 @@ class SpikeCountDesc(C.Structure):
                 ("row_stride", C.c_int64), ("counts", C.c_void_p)]
 
 
+class MembraneStatsDesc(C.Structure):
+    _fields_ = [("v", C.c_void_p), ("outer", C.c_int64), ("T", C.c_int), ("rows", C.c_int64), ("C", C.c_int),
+                ("row_stride", C.c_int64), ("table", C.c_void_p), ("bins", C.c_int), ("lo", C.c_float), ("hi", C.c_float),
+                ("inv_width", C.c_float)]
+
+
 # The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
 # plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
 # still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
@@ -316,7 +322,7 @@ SIGNATURES = {
     "sdf_qk_gate_plif_bwd_workspace_bytes": (_i64, (_i, _i64, _i)),
     "sdf_qk_gate_plif_bwd": (_i, (_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i, _f, _i, _f, _i, _i, _f, _p)),
     "sdf_neuron_fwd": (_i, (_P(NeuronDesc), _p)), "sdf_neuron_multi_fwd": (_i, (_P(NeuronDesc), _i, _p)),
-    "sdf_glif_neuron_fwd": (_i, (_P(NeuronDesc), _p, _p)),
+    "sdf_glif_neuron_fwd": (_i, (_P(NeuronDesc), _p, _p)), "sdf_neuron_vseq_fwd": (_i, (_P(NeuronDesc), _p, _p)),
     "sdf_split_weight_i8x3": (_i, (_p, _p, _p, _i, _i, _p)), "sdf_tile_weight_i8x3": (_i, (_p, _p, _i, _i, _p)),
     "sdf_spike_gemm_fwd": (_i, (_P(SpikeGemmDesc), _p)),
     "sdf_spike_gemm_bn_fwd": (_i, (_p, _p, _i, _f, _p, _p, _p, _i64, _i, _i, _p)),
@@ -358,6 +364,7 @@ SIGNATURES = {
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
     "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
     "sdf_prepare_chunk_workspace_bytes": (_i64, (_i,)), "sdf_prepare_chunk_fwd": (_i, (_P(PrepareChunkDesc), _p)),
+    "sdf_membrane_stats_fwd": (_i, (_P(MembraneStatsDesc), _p)),
     "sdf_spike_count_fwd": (_i, (_P(SpikeCountDesc), _p)),
 }
 
@@ -537,12 +544,21 @@ def _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, row
 
 
 def neuron_fwd(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p: NeuronParams, rowmap=None, rowlen=0,
-               alpha=None, beta=None, Cch=0, inner=1, add=None, add_st=0, add_period=0, v_last=None):
-    """sdf_neuron_fwd: see include/sdformerflow_hip.h for the addressing contract."""
+               alpha=None, beta=None, Cch=0, inner=1, add=None, add_st=0, add_period=0, v_last=None, rep=None, v_seq=None):
+    """sdf_neuron_fwd: see include/sdformerflow_hip.h for the addressing contract.  `rep` = (count, stride in x, stride in out) of the
+    descriptor's outermost dimension.  `v_seq` (fp32, addressed as `out` is, in elements): the call goes to sdf_neuron_vseq_fwd, which
+    also writes the membrane after the reset of every step there (LIF / IF; a PSN or GLIF node has no such record)."""
     if p.kind == "glif":
+        if v_seq is not None:
+            raise SdfError("neuron_fwd: a GLIF node has no v_seq (the reference's GatedLIFNode keeps none either)", rc=E_DTYPE)
         return glif_neuron_fwd(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p.tab, rowmap, rowlen, alpha, beta, Cch, inner, add, add_st,
-                               add_period, v_last)
-    d = _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p, rowmap, rowlen, alpha, beta, Cch, inner, add, add_st, add_period, v_last)
+                               add_period, v_last, rep)
+    d = _neuron_desc(x, out, T, nb, ni, x_sb, x_st, o_sb, o_st, p, rowmap, rowlen, alpha, beta, Cch, inner, add, add_st, add_period, v_last,
+                     rep)
+    if v_seq is not None:
+        _note(bytes=T * nb * ni * (8 + out.element_size()), shape=(T, nb * ni))
+        _check(lib().sdf_neuron_vseq_fwd(C.byref(d), _ptr(v_seq, torch.float32), _stream()), "sdf_neuron_vseq_fwd")
+        return out
     _note(bytes=T * nb * ni * (4 + out.element_size()), shape=(T, nb * ni))
     _check(lib().sdf_neuron_fwd(C.byref(d), _stream()), "sdf_neuron_fwd")
     return out
@@ -2318,3 +2334,47 @@ def spike_count(spikes, t_dim, counts=None):
     _note(bytes=outer * T * rows * Cc, shape=(outer, T, rows, Cc))
     _check(lib().sdf_spike_count_fwd(C.byref(d), _stream()), "sdf_spike_count_fwd")
     return counts
+
+
+MEMBRANE_HEAD = 4                                   # [n_nan, sum_q16, min_key, max_key] in front of a record's histogram
+MEMBRANE_KEY_INIT = (0xFFFFFFFF, 0)                 # what the caller puts into min_key / max_key before the first call
+
+
+def membrane_inv_width(lo, hi, bins):
+    """(lo, hi, inv_width) as sdf_membrane_stats_fwd takes them: fp32 bounds and bins / (hi - lo) formed ONCE in fp32 on the host."""
+    lo32, hi32 = torch.tensor(float(lo), dtype=torch.float32), torch.tensor(float(hi), dtype=torch.float32)
+    return lo32.item(), hi32.item(), (torch.tensor(float(bins), dtype=torch.float32) / (hi32 - lo32)).item()
+
+
+def membrane_table(T, bins, device):
+    """A fresh (T, 4 + bins + 2) int64 record table: zeros, min_key = 2^32 - 1, max_key = 0."""
+    table = torch.zeros((T, MEMBRANE_HEAD + bins + 2), dtype=torch.int64, device=device)
+    table[:, 2] = MEMBRANE_KEY_INIT[0]
+    return table
+
+
+def membrane_stats(v, t_dim, table=None, lo=-2.0, hi=2.0, bins=64):
+    """Per-step statistics of an fp32 membrane tensor or view (sdf_membrane_stats_fwd): record t of `table` - (T, 4 + bins + 2) int64,
+    contiguous, same device - takes [n_nan, sum_q16, min_key, max_key, hist] over everything but dim `t_dim` (0, or 1 behind a batch
+    dim) and is ADDED to (default: a fresh membrane_table).  Views are read in place (spike_count_form's addressing, in elements);
+    there is no .contiguous() and no torch fallback: a layout outside that form raises SdfError."""
+    if not torch.is_tensor(v) or not v.is_cuda:
+        raise SdfError("membrane_stats: HIP path needs a device tensor (no CPU fallback)")
+    if v.dtype != torch.float32:
+        raise SdfError(f"membrane_stats: membranes are fp32, got {v.dtype}", rc=E_DTYPE)
+    bins = int(bins)
+    if not 1 <= bins <= 256:
+        raise SdfError(f"membrane_stats: {bins} bins; the kernel's LDS histogram takes 1 to 256", rc=E_SHAPE)
+    outer, T, rows, Cc, rs = spike_count_form(v, t_dim)
+    if table is None:
+        table = membrane_table(T, bins, v.device)
+    elif not (torch.is_tensor(table) and table.is_cuda and table.device == v.device and table.dtype == torch.int64
+              and tuple(table.shape) == (T, MEMBRANE_HEAD + bins + 2) and table.is_contiguous()):
+        raise SdfError(f"membrane_stats: table must be a contiguous int64 tensor of shape ({T}, {MEMBRANE_HEAD + bins + 2}) on {v.device}")
+    d = MembraneStatsDesc()
+    d.v, d.table = v.data_ptr(), table.data_ptr()
+    d.outer, d.T, d.rows, d.C, d.row_stride, d.bins = outer, T, rows, Cc, rs, bins
+    d.lo, d.hi, d.inv_width = membrane_inv_width(lo, hi, bins)
+    _note(bytes=outer * T * rows * Cc * 4, shape=(outer, T, rows, Cc))
+    _check(lib().sdf_membrane_stats_fwd(C.byref(d), _stream()), "sdf_membrane_stats_fwd")
+    return table

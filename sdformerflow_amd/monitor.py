@@ -22,6 +22,11 @@ the MS attention whose spikes no kernel stores - the token gate `attn.sn2_q` and
 the recorded q spikes and the gated spikes (engine.MSFlowEngine._rec_gates): the gate's record is a recomputation, not a read-out of
 the fused kernel.  (A GLIF model runs on the unfused plan, engine_glif.py: there the gate's record IS the gate kernel's own output.)
 Eval mode, eager, one forward at a time: training mode, `forward_replicas` and graph capture are refused.
+
+The reference's other diagnostic, `vis.monitor_v` (eval_DSEC_flow_SNN.py:145-149, 228-230: `v_seq`, the membrane after reset at every
+time step of every neuron call), is `MembraneMonitor` below: the same names, the same switching, the forward on the unfused plan
+(engine_unfused.py), per-step statistics in integers on the device (csrc/membrane_stats.hip, restated here in numpy: membrane_record).
+One monitor of either kind at a time on a model.
 """
 import csv
 
@@ -60,9 +65,61 @@ def neuron_call_names(model):
     return [n + _SUFFIX for n in names]
 
 
+# ---------------------------------------------------------------------- the membrane record, restated on the host
+# csrc/membrane_stats.hip adds, per time step, [n_nan, sum_q16, min_key, max_key, hist[0 .. bins + 1]] into 64-bit integers.  The same
+# arithmetic in numpy - fp32 operations rounded one by one, integers from there on - is what the tests compare the kernel's table with,
+# integer for integer, and what the monitor's reading side decodes with.
+def membrane_keys(v):
+    """Order-preserving unsigned keys of fp32 values: bits ^ (sign ? 0xFFFFFFFF : 0x80000000), as int64."""
+    import numpy as np
+    bits = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    return (bits ^ np.where(bits >> 31, np.uint32(0xFFFFFFFF), np.uint32(0x80000000))).astype(np.int64)
+
+
+def membrane_unkey(key):
+    """The exact fp32 value (as a numpy float32 array) of membrane_keys' keys."""
+    import numpy as np
+    key = np.asarray(key, dtype=np.int64).astype(np.uint32)
+    return (key ^ np.where(key >> 31, np.uint32(0x80000000), np.uint32(0xFFFFFFFF))).view(np.float32)
+
+
+def membrane_edges(lo, hi, bins):
+    """The bins + 1 edges of the histogram's inner bins, float64, from the fp32 bounds the kernel takes."""
+    import numpy as np
+    lo32, hi32, _ = hip.membrane_inv_width(lo, hi, bins)
+    return lo32 + (hi32 - lo32) * np.arange(bins + 1, dtype=np.float64) / bins
+
+
+def membrane_record(v, lo, hi, bins):
+    """v (T, ...) fp32 (numpy) -> the (T, 4 + bins + 2) int64 records sdf_membrane_stats_fwd leaves in a fresh table."""
+    import numpy as np
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    v = v.reshape(v.shape[0], -1)
+    lo32, hi32, inv = (np.float32(a) for a in hip.membrane_inv_width(lo, hi, bins))
+    table = np.zeros((v.shape[0], hip.MEMBRANE_HEAD + bins + 2), dtype=np.int64)
+    table[:, 2] = hip.MEMBRANE_KEY_INIT[0]
+    for t, row in enumerate(v):
+        nan = np.isnan(row)
+        x = row[~nan]
+        table[t, 0] = int(nan.sum())
+        with np.errstate(over="ignore", invalid="ignore"):
+            table[t, 1] = int(np.rint(np.clip(x, np.float32(-32768.0), np.float32(32768.0)) * np.float32(65536.0)).astype(np.int64).sum())
+            if x.size:
+                keys = membrane_keys(x)
+                table[t, 2], table[t, 3] = int(keys.min()), int(keys.max())
+            inner = (x >= lo32) & (x < hi32)
+            p = (x[inner] - lo32) * inv                                    # (fp32 subtraction, then fp32 product: two roundings)
+            idx = 1 + np.minimum(bins - 1, np.floor(p).astype(np.int64))
+        hist = np.bincount(idx, minlength=bins + 2)
+        hist[0], hist[bins + 1] = int((x < lo32).sum()), int((x >= hi32).sum())
+        table[t, hip.MEMBRANE_HEAD:] = hist
+    return table
+
+
 class FiringRateMonitor:
     """Per-step spike counts of every neuron call of `model`'s eval forwards while enabled (see the module's text).  `forwards`: rows
     the count table starts with; it doubles when they run out."""
+    what = "firing-rate monitor"      # how the model's refusals name the enabled monitor
 
     def __init__(self, model, forwards=16):
         from .STSwinNet_SNN.Spiking_STSwinNet import MS_SpikingformerFlowNet
@@ -83,7 +140,8 @@ class FiringRateMonitor:
     def enable(self):
         other = getattr(self.model, "_fr_monitor", None)
         if other is not None and other is not self:
-            raise RuntimeError("another FiringRateMonitor is enabled on this model: disable() it first")
+            raise RuntimeError(f"another {type(other).__name__} is enabled on this model (one monitor at a time: a forward takes one "
+                               "recording route): disable() it first")
         self.model._fr_monitor = self
         return self
 
@@ -219,3 +277,223 @@ class FiringRateMonitor:
             for k, fwd in enumerate(host):
                 for name, r in zip(self.names, fwd):
                     w.writerow([k, name] + r)
+
+
+def membrane_summary(records, elements):
+    """Host arithmetic of the membrane monitor, float64: records (forwards, T, 4 + bins + 2) int64 of ONE call (numpy), `elements` per
+    step and forward -> {"n_nan" (T,), "mean" (T,), "min" (T,), "max" (T,), "hist" (T, bins + 2)} over the forwards together:
+    mean = sum_q16 / 65536 / (elements - n_nan) (good to 2^-17), min / max = the keys decoded back to the exact floats (NaN where a step
+    held no number), hist summed."""
+    import numpy as np
+    records = np.asarray(records, dtype=np.int64)
+    n_nan, total = records[:, :, 0].sum(0), records.shape[0] * int(elements)
+    count = total - n_nan
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = records[:, :, 1].sum(0).astype(np.float64) / 65536.0 / count
+    kmin, kmax = records[:, :, 2].min(0), records[:, :, 3].max(0)
+    seen = kmin <= kmax
+    lo = np.where(seen, membrane_unkey(np.where(seen, kmin, 0x80000000)).astype(np.float64), np.nan)
+    hi = np.where(seen, membrane_unkey(np.where(seen, kmax, 0x80000000)).astype(np.float64), np.nan)
+    return {"n_nan": n_nan, "mean": mean, "min": lo, "max": hi, "hist": records[:, :, hip.MEMBRANE_HEAD:].sum(0)}
+
+
+_TO_REFERENCE = {"flat": None, "BDHWC->TBCHW": (1, 0, 4, 2, 3), "BDHWC->TBHWC": (1, 0, 2, 3, 4)}
+
+
+class MembraneMonitor(FiringRateMonitor):
+    """Per-step membrane statistics of every neuron call of `model`'s eval forwards while enabled: the reference's `vis.monitor_v`
+    (eval_DSEC_flow_SNN.py:145-149, 228-230: `store_v_seq = True` on every neuron, `v_seq` - the membrane after reset at every time
+    step - recorded per call).
+
+        mon = MembraneMonitor(model, bins=64, range=(-2.0, 2.0), keep=())     # range in multiples of v_th
+        with mon: model(x)
+        mon.names                  # neuron_call_names(model): shared with the firing-rate monitor
+        mon.table()                # (forwards, calls, Tmax, 4 + bins + 2) int64 on the device (csrc/membrane_stats.hip's records)
+        mon.elements, mon.mean(), mon.min(), mon.max(), mon.hist(), mon.edges  # one read-back, formed on the host in float64
+        mon.v_seq(name)            # names listed in `keep` ("all" allowed): the LAST forward's fp32 membrane in the reference's
+                                   # tensor order (the record's layout tag applied) - what `v_seq_monitor.records` holds
+        mon.to_csv(path); mon.reset()
+
+    While enabled, the model's eval forward runs on `model.unfused_engine()` (engine_unfused.py): every neuron call allocates a v_seq
+    with the spike buffer's addressing, launches `sdf_neuron_vseq_fwd` and one `sdf_membrane_stats_fwd` into this forward's records,
+    and releases the buffer unless the call is kept.  The host does not synchronise per forward; the table doubles as the firing-rate
+    table does.  The token gate's call `attn.sn2_q` and the dead score `attn.attn_sn` are RECOMPUTED through the general launch
+    (engine.MSFlowEngine._rec_gates): the gate's record is a recomputation, not a read-out of the gate kernel.
+    MS models with `lif` / `if` / `plif` / `SLTTlif` neurons, eval mode, eager, one forward at a time, one monitor at a time."""
+    what = "membrane monitor"
+
+    def __init__(self, model, bins=64, range=(-2.0, 2.0), keep=(), forwards=16):
+        from .STSwinNet_SNN.Spiking_STSwinNet import MS_SpikingformerFlowNet, SpikingformerFlowNet
+        if not isinstance(model, MS_SpikingformerFlowNet):
+            raise hip.SdfError(f"MembraneMonitor records membranes: {type(model).__name__} is not a spiking model of this package (the ANN "
+                               "model STTFlowNet has no neuron calls); use MS_SpikingformerFlowNet(_en4)")
+        if isinstance(model, SpikingformerFlowNet):
+            raise hip.SdfError("MembraneMonitor is not built for the SEW family (SpikingformerFlowNet): use an MS model "
+                               "(MS_SpikingformerFlowNet(_en4)), or FiringRateMonitor for this model's firing rates")
+        kind = model.sttmultires_unet.spiking_kwargs.get("neuron_type")
+        if kind in ("psn", "glif"):
+            raise hip.SdfError(f"MembraneMonitor: a {kind} neuron keeps no membrane sequence (the reference's node has no v_seq either): "
+                               "build the model with lif / if / plif / SLTTlif neurons, or use FiringRateMonitor for its firing rates")
+        bins = int(bins)
+        if not 1 <= bins <= 256:
+            raise hip.SdfError(f"MembraneMonitor: {bins} histogram bins; the statistics kernel takes 1 to 256")
+        if not float(range[0]) < float(range[1]):
+            raise hip.SdfError(f"MembraneMonitor: range {tuple(range)} is empty; give (lo, hi) in multiples of v_th with lo < hi")
+        self.model = model
+        self.names = neuron_call_names(model)
+        self._index = {n: i for i, n in enumerate(self.names)}
+        unet = model.sttmultires_unet
+        self.Tmax = max(int(unet.steps), int(unet.window_size[0]))
+        if self.Tmax > 64:
+            raise hip.SdfError(f"MembraneMonitor: {self.Tmax} time steps; the statistics kernel takes at most 64 - monitor a model "
+                               "with fewer steps")
+        self.v_th = float(unet.spiking_kwargs["v_th"])
+        self.bins, self.lo, self.hi = bins, float(range[0]) * self.v_th, float(range[1]) * self.v_th
+        self.edges = membrane_edges(self.lo, self.hi, bins)
+        keep = self.names if keep == "all" else [k if k.endswith(_SUFFIX) else k + _SUFFIX for k in ([keep] if isinstance(keep, str) else keep)]
+        unknown = [k for k in keep if k not in self._index]
+        if unknown:
+            raise hip.SdfError(f"MembraneMonitor: keep= names {unknown[:3]}, which are not neuron calls of this model (see .names)")
+        self.keep = frozenset(keep)
+        self._reserve = max(int(forwards), 1)
+        self.reset()
+
+    def reset(self):
+        super().reset()
+        self._kept = {}
+
+    # ------------------------------------------------------------------ the forward (called by the model)
+    def _fresh(self, shape, device):
+        table = torch.zeros(tuple(shape) + (hip.MEMBRANE_HEAD + self.bins + 2,), dtype=torch.int64, device=device)
+        table[..., 2] = hip.MEMBRANE_KEY_INIT[0]
+        return table
+
+    def _room(self, device):
+        shape = (len(self.names), self.Tmax)
+        if self._table is None or self._table.device != device:
+            if self._n:
+                raise hip.SdfError(f"membrane monitor: records so far are on {self._table.device}, this forward on {device}; reset() first")
+            self._table = self._fresh((self._reserve,) + shape, device)
+        elif self._n == self._table.shape[0]:
+            table = self._fresh((2 * self._n,) + shape, device)
+            table[:self._n] = self._table
+            self._table = table
+
+    def forward(self, x, scores=None):
+        """One monitored forward on the model's unfused plan.  The refusals come first: nothing is packed or launched for a forward
+        that is refused."""
+        if not x.is_cuda:
+            raise hip.SdfError("input must be a GPU tensor (no CPU fallback)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a membrane monitor is enabled during graph capture: its forward allocates a membrane per neuron call and "
+                               "grows a table - disable() the monitor around the capture, or run the monitored forwards eagerly")
+        if scores is not None:
+            raise NotImplementedError("a membrane monitor is enabled and log=True was asked for: the unfused plan computes no attention "
+                                      "score - call model(x) without log, or disable() the monitor")
+        engine = self.model.unfused_engine()
+        self._room(x.device)
+        self._seen, kept = [None] * len(self.names), {}
+        engine.monitor, engine._membranes, self._keeping = self, True, kept
+        try:
+            flows = engine.forward(x)
+            missing = [n for n, s in zip(self.names, self._seen) if s is None]
+            if missing:
+                raise hip.SdfError(f"membrane monitor: {len(missing)} neuron calls were not recorded by this forward, e.g. {missing[:3]}")
+        except BaseException:
+            self._table[self._n] = self._fresh(self._table.shape[1:3], x.device)      # (a forward that failed leaves no record)
+            raise
+        finally:
+            engine.monitor, engine._membranes, self._keeping = None, False, None
+        self._steps.append([s[0] for s in self._seen])
+        self._elements.append([s[1] for s in self._seen])
+        self._seen, self._kept = None, kept
+        self._n += 1
+        return flows
+
+    def record(self, name, v, layout):
+        """The unfused engine's sink: the statistics of the fp32 membrane `v` of neuron call `name` where it lies, with the spikes'
+        own shape, strides and layout tag ("flat": steps on dim 0, "BDHWC->...": on dim 1)."""
+        name = name.rstrip(".")
+        i = self._index.get(name)
+        if i is None:
+            raise hip.SdfError(f"membrane monitor: the forward recorded {name!r}, which is not a neuron call of this model")
+        if self._seen[i] is not None:
+            raise hip.SdfError(f"membrane monitor: neuron call {name!r} recorded twice in one forward")
+        if v.dtype != torch.float32:
+            raise hip.SdfError(f"membrane monitor: {name!r} handed over {v.dtype}, not its fp32 membrane (is the forward on the unfused plan?)")
+        t_dim = 0 if layout == "flat" else 1
+        T = v.shape[t_dim]
+        if T > self.Tmax:
+            raise hip.SdfError(f"membrane monitor: {name!r} has {T} time steps, the table {self.Tmax}")
+        hip.membrane_stats(v, t_dim, self._table[self._n, i, :T], self.lo, self.hi, self.bins)
+        self._seen[i] = (T, v.numel() // T)
+        if name in self.keep:
+            self._keeping[name] = (v, layout)
+
+    # ------------------------------------------------------------------ reading
+    def table(self):
+        """(forwards, calls, Tmax, 4 + bins + 2) int64 on the device: [n_nan, sum_q16, min_key, max_key, hist] per forward, call and
+        step; steps beyond a call's T keep their initial record.  (Reading it synchronises.)"""
+        if self._table is None:
+            return self._fresh((0, len(self.names), self.Tmax), next(self.model.parameters()).device)
+        return self._table[:self._n]
+
+    counts = table
+
+    def _host(self):
+        """name -> membrane_summary over the forwards; ONE synchronising copy of the table."""
+        if not self._n:
+            return {}
+        tab = self._table[:self._n].cpu().numpy()
+        out = {}
+        for i, name in enumerate(self.names):
+            T, el = self._steps[-1][i], self._elements[-1][i]
+            if any(s[i] != T or e[i] != el for s, e in zip(self._steps, self._elements)):
+                raise hip.SdfError(f"membrane monitor: {name!r} changed its size between the forwards; reset() between input sizes")
+            out[name] = membrane_summary(tab[:, i, :T], el)
+        return out
+
+    def mean(self):
+        """name -> (T,) float64: the mean membrane per step over the forwards (NaNs left out)."""
+        return {n: s["mean"] for n, s in self._host().items()}
+
+    def min(self):
+        return {n: s["min"] for n, s in self._host().items()}
+
+    def max(self):
+        return {n: s["max"] for n, s in self._host().items()}
+
+    def hist(self):
+        """name -> (T, bins + 2) int64 summed over the forwards: underflow, the bins between .edges, overflow."""
+        return {n: s["hist"] for n, s in self._host().items()}
+
+    def summary(self):
+        """name -> {"mean", "min", "max": T floats, "hist": T lists of bins + 2 counts, "n_nan": T counts} as plain Python values."""
+        return {n: {k: v.tolist() for k, v in s.items()} for n, s in self._host().items()}
+
+    records = property(lambda self: self.summary())
+    rates = summary
+
+    def v_seq(self, name):
+        """The last forward's fp32 membrane of a kept call in the reference's tensor order (time steps first)."""
+        name = name if name.endswith(_SUFFIX) else name + _SUFFIX
+        if name not in self._kept:
+            raise hip.SdfError(f"membrane monitor: no membrane kept for {name!r}: list it in keep= (or keep='all') and run a forward")
+        v, layout = self._kept[name]
+        perm = _TO_REFERENCE[layout]
+        return v if perm is None else v.permute(*perm)
+
+    def to_csv(self, path):
+        """Append one row per forward, call and step: forward, name, step, elements, n_nan, mean, min, max, the bins + 2 counts."""
+        if not self._n:
+            return
+        tab = self._table[:self._n].cpu().numpy()
+        with open(path, "a", newline="") as f:
+            w = csv.writer(f)
+            for k in range(self._n):
+                for i, name in enumerate(self.names):
+                    T, el = self._steps[k][i], self._elements[k][i]
+                    s = membrane_summary(tab[k:k + 1, i, :T], el)
+                    for t in range(T):
+                        w.writerow([k, name, t, el, int(s["n_nan"][t]), repr(float(s["mean"][t])), repr(float(s["min"][t])),
+                                    repr(float(s["max"][t]))] + s["hist"][t].tolist())
