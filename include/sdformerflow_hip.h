@@ -1204,6 +1204,76 @@ int64_t sdf_prepare_chunk_workspace_bytes(int B);
 int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * What was evaluated, as images (reference utils/visualization.py Visualization_DSEC, `vis.store`): bytes into a caller's buffer on
+ * the stream, no read-back, nothing allocated.  Added to SDF_VERSION 107 (no existing entry changed).
+ *
+ * sdf_flow_image_fwd: flow (B, 2, H, W) fp32 [* mask (B, 1, H, W) fp32, multiplied in first; may be NULL] -> out (B, H, W, 3) u8, the
+ * reference's flow_to_image of every sample on its own.  Two launches:
+ *   1  mag = sqrtf(fx * fx + fy * fy) (np.linalg.norm in fp32: two products, one add, a correctly rounded root); mag >= 0, so its bits
+ *      order as unsigned integers: per-sample min / max lane -> wave -> workgroup -> one atomicMin / atomicMax per workgroup into the
+ *      sample's two workspace words, which the call itself initialises on the stream.  Order-independent: the same bits on every run.
+ *   2  h = (atan2f(fy, fx) + (float)pi) * (float)(1 / pi / 2);  v = (double)(mag - min) / (double)(max - min) (undivided when
+ *      max == min);  matplotlib's hsv_to_rgb with s = 1 in fp64 - i = (int)(h * 6), f = h * 6 - i, the six cases of i % 6 (h may be
+ *      exactly 1: i = 6 is case 0);  byte = (uint8)(255 * c), truncated.
+ * Only atan2f is not bit-equal to numpy's; a byte can differ by one where 255 * c lies within that error of an integer.  NaN flows:
+ * the bytes are unspecified, and nothing faults.
+ * Loads are 16 bytes per lane where the planes of a sample share their alignment, element-wise in front of the first and behind the
+ * last 16-byte boundary and everywhere otherwise; nothing outside the addressed floats is read.  A pixel's three bytes are written by
+ * one lane.
+ * workspace: sdf_flow_image_workspace_bytes(B, H, W) bytes, 4-byte aligned (0: refused geometry).
+ * SDF_E_NULL: d, flow, out or workspace NULL; SDF_E_SHAPE: B, H or W < 1, B > 65535, H W >= 2^30, workspace too small;
+ * SDF_E_ALIGN: flow, mask or workspace not 4-byte aligned. */
+typedef struct SdfFlowImageDesc {
+  const float* flow;
+  const float* mask;
+  uint8_t* out;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t B, H, W;
+} SdfFlowImageDesc;
+
+int64_t sdf_flow_image_workspace_bytes(int B, int H, int W);
+int sdf_flow_image_fwd(const SdfFlowImageDesc* d, void* stream);
+
+/* sdf_flow_submission_fwd: flow (B, 2, H, W) fp32 -> out (B, H, W, 3) u16 in the DSEC benchmark's encoding (the reference's
+ * `flow_test` branch of Visualization_DSEC.store): channels 0 and 1 = (uint16)(f * 128.f + 32768.f) - the product and the sum
+ * rounded one by one in fp32, then truncated - and channel 2 = 0.  Bit-exact for |f| < 256 px; beyond that the reference's numpy cast
+ * is undefined, and here the value clamps to [0, 65535] (NaN: 0).  One launch.
+ * SDF_E_NULL: d, flow or out NULL; SDF_E_SHAPE: as sdf_flow_image_fwd; SDF_E_ALIGN: flow not 4-byte or out not 2-byte aligned. */
+typedef struct SdfFlowSubmissionDesc {
+  const float* flow;
+  void* out;
+  int32_t B, H, W;
+} SdfFlowSubmissionDesc;
+
+int sdf_flow_submission_fwd(const SdfFlowSubmissionDesc* d, void* stream);
+
+/* sdf_event_image_fwd: the loops' `chunk_vis` and the reference's events_to_image (green_red) of it, as the bytes cv2.imwrite stores.
+ * stage 0: src -> chunk_vis (B, 2, h, w) fp32 on the window (crop_h, crop_w) at (crop_oy, crop_ox) (0, 0 at origin 0, 0: all of it).
+ *   mode 0 (signed): src is a signed voxel (B, bins, Hs, Ws): pos = sum over bins of max(v, 0), neg = sum over bins of max(-v, 0)
+ *                    (eval_DSEC_flow_SNN.py:182-188, eval_MV_flow_SNN.py:184)
+ *   mode 1 (split):  src is the model's input (B, bins, 2, Hs, Ws): pos / neg = channel 0 / 1 summed over bins
+ *   both added in bin order in fp32.
+ * stage 1: chunk_vis and bounds (B, 4) fp32 = {pos_min, pos_max, neg_min, neg_max}, the 1st and 99th percentiles of each polarity of
+ *   the sample (the caller's: any quantile routine on the stream) -> out (B, h, w, 3) u8.  In fp32: m = max(pos_max, neg_max);
+ *   pos' = clip((pos - pos_min) / (m - pos_min), 0, 1) when pos_min != m, else clip(pos, 0, 1); neg' alike.  The reference's image is
+ *   (0, pos', neg') and cv2.imwrite reads it as BGR, so the stored file's RGB is out = (neg', pos', 0), each byte rint(255 * x) in
+ *   fp64 with halves to even: OpenCV's documented saturate_cast<uchar>(double) (taken from its documentation, not checked against cv2).
+ * SDF_E_NULL: d, chunk_vis, src (stage 0), bounds or out (stage 1) NULL; SDF_E_DTYPE: mode or stage not 0 / 1; SDF_E_SHAPE: B, bins,
+ * Hs or Ws < 1, B > 65535, a window outside the source, h w >= 2^30 or a source beyond 2^60 elements; SDF_E_ALIGN: a float pointer not
+ * 4-byte aligned. */
+typedef struct SdfEventImageDesc {
+  const float* src;
+  float* chunk_vis;
+  const float* bounds;
+  uint8_t* out;
+  int32_t B, bins, Hs, Ws, crop_h, crop_w, crop_oy, crop_ox;
+  int32_t mode, stage;
+} SdfEventImageDesc;
+
+int sdf_event_image_fwd(const SdfEventImageDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * fp32 membranes -> per-time-step statistics in integers: what a reader of the reference's `v_seq_monitor.records` (`vis.monitor_v`)
  * looks at - mean, extremes and a histogram of a neuron call's membrane per step - without keeping the membrane.
  * sdf_spike_count_fwd's geometry on fp32: element (o, t, r, c) is the float at v + ((o * T + t) * rows + r) * row_stride + c (strides

@@ -158,13 +158,46 @@ def _with_firing_rates(loop, model, samples, config, device, monitor):
     return result
 
 
-def evaluate_mv(model, samples, config, device="cuda", monitor=None):
+class _Storer:
+    """`vis.store` of the two loops (the reference's key, eval_DSEC_flow_SNN.py:278-280, eval_MV_flow_SNN.py:256-258): every sample's
+    event image, flow and ground-truth flow - and, with `submission`, the flow in the DSEC benchmark's 16-bit encoding - through
+    utils.visualization.Visualization_DSEC into <store_dir>/results/eval_0/<sequence>/... (flow_test/<sequence>/ for the submission)."""
+
+    def __init__(self, config, store_dir, sequence, submission):
+        from .utils.visualization import Visualization_DSEC
+        self.vis = Visualization_DSEC(config, eval_id=0, path_results=store_dir)
+        self.sequence, self.submission, self.count = sequence, bool(submission), 0
+
+    def __call__(self, source, label, pred, mask=None):
+        """`source`: the signed voxel (B, bins, h, w) on the scored window ("signed" sums) or the model's input (B, bins, 2, h, w)
+        ("split" sums: of the NORMALISED input); `mask`: multiplied into both flows first (the MV loop's), None: stored as they are."""
+        from . import hip
+        if mask is not None:
+            label, pred = label * mask, pred * mask
+        self.vis.store(hip.event_counts(source), label, mask, pred, self.sequence, flow_test=pred if self.submission else None,
+                       idx=self.count)
+        self.count += pred.shape[0]
+
+
+def _storing(loop, config, store_dir, sequence, submission):
+    """`loop` with its `store=` bound when `vis.store` is true (refused without a `store_dir`, before any forward); else `loop`."""
+    if not (config.get("vis") or {}).get("store"):
+        return loop
+    if store_dir is None:
+        raise ValueError("vis.store is set: pass store_dir= (the images go to <store_dir>/results/eval_0/<sequence>/), or clear the key")
+    store = _Storer(config, store_dir, sequence, submission)
+    return lambda model, samples, config, device: loop(model, samples, config, device, store=store)
+
+
+def evaluate_mv(model, samples, config, device="cuda", monitor=None, store_dir=None, sequence="eval", submission=False):
     """harness.evaluate's counterpart for the MVSEC / MDR sample dicts (`_evaluate_mv`: the loop itself); `vis.monitor_fr` true: the
-    forwards run under a FiringRateMonitor (`monitor`, or a new one) and the dict also has "firing_rate" and "firing_rates"."""
-    return _with_firing_rates(_evaluate_mv, model, samples, config, device, monitor)
+    forwards run under a FiringRateMonitor (`monitor`, or a new one) and the dict also has "firing_rate" and "firing_rates".
+    `vis.store` true: every sample's events, flow * mask and label * mask are stored as harness.evaluate stores them (`store_dir`,
+    `sequence`, `submission`)."""
+    return _with_firing_rates(_storing(_evaluate_mv, config, store_dir, sequence, submission), model, samples, config, device, monitor)
 
 
-def _evaluate_mv(model, samples, config, device="cuda"):
+def _evaluate_mv(model, samples, config, device="cuda", store=None):
     """The model-facing loop of eval_MV_flow_SNN.py:157-249 over an iterable of sample dicts, either the reference loader's
     ('event_volume_old', 'event_volume_new' (B, num_frames, h, w), 'flow' (B, 2, h, w), 'valid' (B, h, w)) or the raw form
     ('events_old', 'events_new': event dicts, or lists of B of them; 'flow', 'valid' at the sensor's or the crop's size, with or without
@@ -213,6 +246,8 @@ def _evaluate_mv(model, samples, config, device="cuda"):
             pred = model(x)["flow"][-1]
         if mask_events:
             mask = mask * event_mask
+        if store is not None:
+            store(x if "events_new" in data else chunk, label, pred, mask)
         results = {n: getattr(flow_supervised, n)(pred, label, mask, config["metrics"]["flow_scaling"])() for n in names}
         for b in range(pred.shape[0]):
             it += 1
@@ -226,14 +261,19 @@ def _evaluate_mv(model, samples, config, device="cuda"):
     return {k: v / max(it, 1) for k, v in tot.items()}
 
 
-def evaluate(model, samples, config, device="cuda", monitor=None):
+def evaluate(model, samples, config, device="cuda", monitor=None, store_dir=None, sequence="eval", submission=False):
     """The evaluation loop (`_evaluate`); `vis.monitor_fr` true: its forwards run under a FiringRateMonitor (`monitor`, or a new one) and
     the dict also has "firing_rate" (its mean()) and "firing_rates" (name -> T rates averaged over the forwards); false or absent:
-    nothing changes."""
-    return _with_firing_rates(_evaluate, model, samples, config, device, monitor)
+    nothing changes.
+    `vis.store` true (the reference's key): every sample's event image, flow and ground-truth flow, unmasked as the reference stores
+    them, are rendered on the GPU and written as PNGs to <store_dir>/results/eval_0/<sequence>/{events, flow, gtflow}/%09d.png, and with
+    `submission` the flow in the DSEC benchmark's 16-bit encoding to .../flow_test/<sequence>/%06d.png (utils.visualization); without
+    a `store_dir` the key is refused before any forward.  False or absent: nothing changes and no render kernel is launched.
+    `vis.enabled` (the live window) is ignored."""
+    return _with_firing_rates(_storing(_evaluate, config, store_dir, sequence, submission), model, samples, config, device, monitor)
 
 
-def _evaluate(model, samples, config, device="cuda"):
+def _evaluate(model, samples, config, device="cuda", store=None):
     """Run `model` over an iterable of (chunk (B,bins,H,W), mask (B,H,W), label (B,2,H,W)) like
     valid_test does and return the running-mean metrics dict (AEE, PE1-3, outliers) (:253-271, :283-305).
     `chunk` may also be the raw event dict {'ts', 'x', 'y', 'p'} DSECDatasetLite yields when data.preprocessed is false (one sample;
@@ -269,6 +309,8 @@ def _evaluate(model, samples, config, device="cuda"):
             pred = model(x)["flow"][-1]
         if config["metrics"].get("mask_events"):
             mask = mask * x.sum(1).sum(1, keepdim=True).bool()
+        if store is not None:
+            store(x if chunk is None else chunk, label, pred)
         m = AEE(pred, label, mask, config["metrics"]["flow_scaling"])()
         for b in range(pred.shape[0]):
             it += 1
@@ -309,6 +351,9 @@ class StreamEvaluator:
         if (config.get("vis") or {}).get("monitor_fr"):
             raise RuntimeError("vis.monitor_fr is set: firing rates are counted on single eager forwards, not under replicas and captured "
                                "graphs - use harness.evaluate / evaluate_mv for the rates, or clear the key for the throughput scheme")
+        if (config.get("vis") or {}).get("store"):
+            raise RuntimeError("vis.store is set: files are written by harness.evaluate / evaluate_mv (store_dir=) - under the throughput "
+                               "scheme pass renders_out= to run() for the rendered bytes on the device, and clear the key")
         if (config.get("vis") or {}).get("monitor_v"):
             raise RuntimeError("vis.monitor_v is set: membranes are recorded on single eager forwards of the unfused plan, not under "
                                "replicas and captured graphs - use harness.evaluate / evaluate_mv, or clear the key for the throughput scheme")
@@ -422,7 +467,31 @@ class StreamEvaluator:
                                  "em": z(self.R, 1, *hw) if self.mask_events else None, "fwd": {}}
         return s
 
-    def _issue(self, j, k, units, flows_out):
+    def _render(self, k, units, s, flow, renders_out):
+        """The group's rendered bytes into rows k .. of the caller's buffers, on the current stream: the flows as the loop of the
+        samples' form stores them (DSEC forms unmasked, MV forms * mask), the events from the signed voxel where the sample came as
+        one ("signed" sums on the scored window) and from the model's input otherwise ("split" sums)."""
+        from . import hip
+        n, dev = len(units), self.device
+        m = None
+        if units[0][0] in ("volume", "pairs"):
+            m = s["msk"][:n] * s["em"][:n] if self.mask_events else s["msk"][:n]
+        if "flow" in renders_out:
+            hip.flow_image(flow, m, out=renders_out["flow"][k:k + n])
+        if "gtflow" in renders_out:
+            hip.flow_image(s["lab"][:n], m, out=renders_out["gtflow"][k:k + n])
+        if "submission" in renders_out:
+            hip.flow_submission(flow, out=renders_out["submission"][k:k + n])
+        if "events" in renders_out:
+            counts = torch.empty((n, 2) + tuple(flow.shape[-2:]), dtype=torch.float32, device=dev)
+            for i, (kind, payload, _, _) in enumerate(units):
+                if kind in ("voxel", "volume"):
+                    hip.event_counts(payload.to(dev, torch.float32), self.crop if kind == "voxel" else None, out=counts[i:i + 1])
+                else:
+                    hip.event_counts(s["x"][i:i + 1], out=counts[i:i + 1])
+            hip.event_counts_image(counts, out=renders_out["events"][k:k + n])
+
+    def _issue(self, j, k, units, flows_out, renders_out=None):
         """Group of len(units) samples numbered from k, on stream j."""
         from .spikingjelly_compat import functional
         n, st = len(units), self.streams[j]
@@ -454,11 +523,19 @@ class StreamEvaluator:
                                 self.config["metrics"]["flow_scaling"], row=k)
             if flows_out is not None:
                 flows_out[k:k + n].copy_(flow, non_blocking=True)
+            if renders_out:
+                self._render(k, units, s, flow, renders_out)
 
-    def run(self, samples, flows_out=None):
+    def run(self, samples, flows_out=None, renders_out=None):
         """Evaluate the iterable `samples` (the forms of harness.evaluate, or of harness.evaluate_mv when an item is a dict) and return
-        the running-mean metrics dict.  `flows_out` (n, 2, h, w): receives every sample's last flow level, in iteration order."""
+        the running-mean metrics dict.  `flows_out` (n, 2, h, w): receives every sample's last flow level, in iteration order.
+        `renders_out`: a dict of device tensors with any of "flow", "gtflow", "events" ((n, h, w, 3) uint8 RGB) and "submission"
+        ((n, h, w, 3) uint16) that receive every sample's rendered images (hip.flow_image / event_image / flow_submission), filled
+        on the group's stream right after the metrics: no file is written and no synchronisation added."""
         from .loss.flow_supervised import FlowMetrics
+        unknown = set(renders_out or ()) - {"flow", "gtflow", "events", "submission"}
+        if unknown:
+            raise ValueError(f"renders_out: unknown keys {sorted(unknown)} (flow, gtflow, events, submission)")
         names, rows = None, 64
         if hasattr(samples, "__len__"):
             rows = max(len(samples), 1)
@@ -470,13 +547,14 @@ class StreamEvaluator:
                     names = self.config["metrics"].get("name", default)
                 if k + len(units) > self.metrics.table.shape[0]:
                     self.metrics.reserve(max(k + len(units), 2 * self.metrics.table.shape[0]))
-                self._issue(j, k, units, flows_out)
+                self._issue(j, k, units, flows_out, renders_out)
         return self.metrics.result(tuple(names or ["AEE"]))
 
 
-def evaluate_stream(model, samples, config, device="cuda", replicas=10, streams=2, graphs=True, flows_out=None):
+def evaluate_stream(model, samples, config, device="cuda", replicas=10, streams=2, graphs=True, flows_out=None, renders_out=None):
     """harness.evaluate / evaluate_mv at the throughput scheme's rate (StreamEvaluator): same sample forms, same config keys
     (loader.crop / polarity, model.norm_input, data.spike_th / num_chunks, metrics.mask_events / flow_scaling / name), every sample a
     batch-1 evaluation (a loader batch of B yields B of them), one host synchronisation at the end.  `flows_out` (n, 2, h, w) receives
-    the last flow level of every sample in iteration order.  graphs=False issues the launch sequences eagerly."""
-    return StreamEvaluator(model, config, device, replicas, streams, graphs).run(samples, flows_out)
+    the last flow level of every sample in iteration order; `renders_out`: StreamEvaluator.run's dict of device buffers for the rendered
+    images (`vis.store` itself is refused here: no files under this scheme).  graphs=False issues the launch sequences eagerly."""
+    return StreamEvaluator(model, config, device, replicas, streams, graphs).run(samples, flows_out, renders_out)

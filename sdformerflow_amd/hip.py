@@ -282,6 +282,21 @@ class PrepareChunkDesc(C.Structure):
                 ("per_sample", C.c_int32), ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
 
 
+class FlowImageDesc(C.Structure):
+    _fields_ = [("flow", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
+class FlowSubmissionDesc(C.Structure):
+    _fields_ = [("flow", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
+class EventImageDesc(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("chunk_vis", C.c_void_p), ("bounds", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int32), ("bins", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32),
+                ("crop_oy", C.c_int32), ("crop_ox", C.c_int32), ("mode", C.c_int32), ("stage", C.c_int32)]
+
+
 class SpikeCountDesc(C.Structure):
     _fields_ = [("spikes", C.c_void_p), ("outer", C.c_int64), ("T", C.c_int), ("rows", C.c_int64), ("C", C.c_int),
                 ("row_stride", C.c_int64), ("counts", C.c_void_p)]
@@ -364,6 +379,8 @@ SIGNATURES = {
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
     "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
     "sdf_prepare_chunk_workspace_bytes": (_i64, (_i,)), "sdf_prepare_chunk_fwd": (_i, (_P(PrepareChunkDesc), _p)),
+    "sdf_flow_image_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_image_fwd": (_i, (_P(FlowImageDesc), _p)),
+    "sdf_flow_submission_fwd": (_i, (_P(FlowSubmissionDesc), _p)), "sdf_event_image_fwd": (_i, (_P(EventImageDesc), _p)),
     "sdf_membrane_stats_fwd": (_i, (_P(MembraneStatsDesc), _p)),
     "sdf_spike_count_fwd": (_i, (_P(SpikeCountDesc), _p)),
 }
@@ -2378,3 +2395,119 @@ def membrane_stats(v, t_dim, table=None, lo=-2.0, hi=2.0, bins=64):
     _note(bytes=outer * T * rows * Cc * 4, shape=(outer, T, rows, Cc))
     _check(lib().sdf_membrane_stats_fwd(C.byref(d), _stream()), "sdf_membrane_stats_fwd")
     return table
+
+
+_FI_WS, _EI_Q = {}, {}
+
+
+def _flow_planes(fn, flow):
+    """(flow contiguous, B, H, W) of a (B, 2, H, W) fp32 device tensor (`fn` prefixes the message)."""
+    _ptr(flow, torch.float32)
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise SdfError(f"{fn}: flow is (B, 2, H, W), got {tuple(flow.shape)}")
+    return (flow.contiguous(),) + tuple(flow.shape[0:1] + flow.shape[2:])
+
+
+def _image_out(fn, out, shape, dtype, dev):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not (torch.is_tensor(out) and out.is_cuda and out.device == dev and out.dtype == dtype and tuple(out.shape) == shape and out.is_contiguous()):
+        raise SdfError(f"{fn}: out must be a contiguous {shape} {dtype} tensor on {dev}")
+    return out
+
+
+def flow_image(flow, mask=None, out=None):
+    """The reference's Visualization_DSEC.flow_to_image of every sample on the GPU (sdf_flow_image_fwd: two launches, no read-back,
+    nothing allocated when `out` is given): flow (B, 2, H, W) fp32 [* mask (B, 1, H, W) or (B, H, W) fp32] -> (B, H, W, 3) u8 RGB.
+    Hue = direction, value = magnitude scaled by the SAMPLE's own min / max (a sample's bytes do not depend on its batch); identical
+    bytes from run to run.  NaN flows give unspecified bytes."""
+    flow, B, H, W = _flow_planes("flow_image", flow)
+    dev = flow.device
+    if mask is not None:
+        _ptr(mask, torch.float32)
+        if mask.numel() != B * H * W or tuple(mask.shape[-2:]) != (H, W):
+            raise SdfError(f"flow_image: mask is (B, 1, H, W) or (B, H, W) at the flow's size, got {tuple(mask.shape)}")
+        mask = mask.contiguous()
+    out = _image_out("flow_image", out, (B, H, W, 3), torch.uint8, dev)
+    need = lib().sdf_flow_image_workspace_bytes(B, H, W)
+    if need <= 0:
+        raise SdfError(f"flow_image: geometry refused (B {B}, {H} x {W})", rc=E_SHAPE)
+    ws = _stream_ws(_FI_WS, dev, max(need, 256))
+    d = FlowImageDesc()
+    d.flow, d.mask, d.out = flow.data_ptr(), _ptr(mask, torch.float32), out.data_ptr()
+    d.workspace, d.workspace_bytes, d.B, d.H, d.W = ws.data_ptr(), ws.numel(), B, H, W
+    _note(bytes=B * H * W * (2 * (8 + 4 * (mask is not None)) + 3), shape=(B, H, W))
+    _check(lib().sdf_flow_image_fwd(C.byref(d), _stream()), "sdf_flow_image_fwd")
+    return out
+
+
+def flow_submission(flow, out=None):
+    """Flow maps in the DSEC benchmark's 16-bit encoding on the GPU (sdf_flow_submission_fwd, the reference's `flow_test` branch of
+    Visualization_DSEC.store): flow (B, 2, H, W) fp32 -> (B, H, W, 3) uint16, channels 0 / 1 = (uint16)(f * 128 + 2 ** 15) in fp32,
+    channel 2 = 0.  Bit-exact for |f| < 256 px.  Beyond that the reference's numpy cast is undefined; here the value CLAMPS to
+    [0, 65535] (NaN: 0)."""
+    flow, B, H, W = _flow_planes("flow_submission", flow)
+    out = _image_out("flow_submission", out, (B, H, W, 3), torch.uint16, flow.device)
+    d = FlowSubmissionDesc()
+    d.flow, d.out, d.B, d.H, d.W = flow.data_ptr(), out.data_ptr(), B, H, W
+    _note(bytes=B * H * W * (8 + 6), shape=(B, H, W))
+    _check(lib().sdf_flow_submission_fwd(C.byref(d), _stream()), "sdf_flow_submission_fwd")
+    return out
+
+
+def event_counts(voxel_or_input, crop=None, crop_origin=None, out=None):
+    """The loops' `chunk_vis` on the GPU (stage 0 of sdf_event_image_fwd): per pixel the positive and the negative event sums over the
+    bins, added in bin order -> (B, 2, h, w) fp32.  A 4-D tensor is a signed voxel (B, bins, Hs, Ws) ("signed" mode: sums of relu(v) /
+    relu(-v), eval_DSEC_flow_SNN.py:182-188); a 5-D one is the model's input (B, bins, 2, Hs, Ws) ("split" mode: channels 0 / 1
+    summed).  `crop` (h, w) at `crop_origin` (default harness.center_crop's)."""
+    src = voxel_or_input
+    _ptr(src, torch.float32)
+    if src.dim() not in (4, 5) or (src.dim() == 5 and src.shape[2] != 2):
+        raise SdfError(f"event_counts: a signed voxel (B, bins, H, W) or the model's input (B, bins, 2, H, W), got {tuple(src.shape)}")
+    src = src.contiguous()
+    B, bins, (Hs, Ws) = src.shape[0], src.shape[1], src.shape[-2:]
+    h, w = crop if crop else (Hs, Ws)
+    oy, ox = crop_origin if crop_origin is not None else (((Hs - h) // 2, (Ws - w) // 2) if crop else (0, 0))
+    if out is None:
+        out = torch.empty((B, 2, h, w), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (B, 2, h, w) or not out.is_contiguous():
+        raise SdfError(f"event_counts: out must be a contiguous {(B, 2, h, w)} tensor")
+    d = EventImageDesc()
+    d.src, d.chunk_vis = src.data_ptr(), _ptr(out, torch.float32)
+    d.B, d.bins, d.Hs, d.Ws = B, bins, Hs, Ws
+    d.crop_h, d.crop_w, d.crop_oy, d.crop_ox = (h if crop else 0), (w if crop else 0), oy, ox
+    d.mode, d.stage = int(src.dim() == 5), 0
+    _note(bytes=B * bins * h * w * 4 + B * h * w * 8, shape=(B, bins, h, w))
+    _check(lib().sdf_event_image_fwd(C.byref(d), _stream()), "sdf_event_image_fwd")
+    return out
+
+
+def event_image(voxel_or_input, crop=None, crop_origin=None, out=None):
+    """The stored event image of every sample on the GPU: event_counts (the loops' `chunk_vis`) rendered as the reference's
+    events_to_image (green_red) and byte-ordered as cv2.imwrite stores it: (B, h, w, 3) u8 RGB = (neg', pos', 0), each polarity scaled
+    between its 1st percentile and the larger 99th percentile of the two, per sample.  Stage 0 of sdf_event_image_fwd |
+    torch.quantile on the stream (linear interpolation, numpy's default) | stage 1; no read-back.  The byte is rint(255 x) with halves
+    to even - OpenCV's documented saturate_cast, not checked against cv2 itself."""
+    return event_counts_image(event_counts(voxel_or_input, crop, crop_origin), out=out)
+
+
+def event_counts_image(counts, out=None):
+    """event_image's second half on its own: counts (B, 2, h, w) fp32 - a sample's positive and negative event sums, the loops'
+    `chunk_vis` - -> (B, h, w, 3) u8 RGB as stored (percentiles by torch.quantile on the stream, then stage 1 of sdf_event_image_fwd)."""
+    _ptr(counts, torch.float32)
+    if counts.dim() != 4 or counts.shape[1] != 2:
+        raise SdfError(f"event_counts_image: counts are (B, 2, h, w), got {tuple(counts.shape)}")
+    vis = counts.contiguous()
+    B, _, h, w = vis.shape
+    dev = vis.device
+    out = _image_out("event_counts_image", out, (B, h, w, 3), torch.uint8, dev)
+    if str(dev) not in _EI_Q:
+        _EI_Q[str(dev)] = torch.tensor([0.01, 0.99], dtype=torch.float32, device=dev)
+    # plumbing: (2, B * 2) percentiles [q][sample, polarity] -> (B, 4) {pos_min, pos_max, neg_min, neg_max}
+    bounds = torch.quantile(vis.view(B * 2, h * w), _EI_Q[str(dev)], dim=1).view(2, B, 2).permute(1, 2, 0).reshape(B, 4).contiguous()
+    d = EventImageDesc()
+    d.chunk_vis, d.bounds, d.out = vis.data_ptr(), bounds.data_ptr(), out.data_ptr()
+    d.B, d.bins, d.Hs, d.Ws, d.stage = B, 1, h, w, 1
+    _note(bytes=B * h * w * (8 + 3), shape=(B, h, w))
+    _check(lib().sdf_event_image_fwd(C.byref(d), _stream()), "sdf_event_image_fwd")
+    return out
