@@ -1305,6 +1305,83 @@ typedef struct SdfMembraneStatsDesc {
 int sdf_membrane_stats_fwd(const SdfMembraneStatsDesc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The tail of a training step on flat fp32 gradient buckets (train.GradientBuckets): per-parameter gradient statistics (the
+ * reference's `vis.store_grads`, utils/gradients.py), the clip coefficient of torch.nn.utils.clip_grad_norm_, and the AdamW update.
+ * A parameter is a SEGMENT [offset, offset + length) of the flat buffer (in floats); segments are packed at any element offset, so
+ * every kernel reads a segment's floats one by one in front of its first and behind its last 16-byte boundary and 16 bytes per lane
+ * between them; nothing outside a segment is touched.  No host synchronisation and no float atomics anywhere.
+ *
+ * The segment tables are given TWICE, with the same contents: on the host (`*_host`: read by the entry point's checks before any
+ * launch) and on the device (read by the kernels).  Checks shared by the three entry points, in this order: SDF_E_NULL: a required
+ * pointer NULL; SDF_E_SHAPE: no segment or more than 65535, a buffer beyond 2^40 floats, an offset < 0, a length < 1, a segment that
+ * starts in front of its predecessor's end (segments ascend and do not overlap) or ends behind the buffer, rows outside the table, a
+ * workspace that is too small; SDF_E_ALIGN: a pointer not aligned as stated below; SDF_E_DTYPE: a pointer the kernels would
+ * dereference is not device (or managed) memory as far as hipPointerGetAttributes can tell - a host pointer never reaches a launch.
+ * Added to SDF_VERSION 107 (no existing entry changed).
+ *
+ * sdf_grad_stats_fwd: segment s of `flat` (n floats) writes row row0 + s of `table` (double[rows][5]; other rows are left alone):
+ *   {sum_abs = sum |g|, sum_sq = sum g * g, min_abs, max_abs, nonfinite = #(inf, -inf, NaN)}
+ * over the FINITE elements, |g| and g * g formed and added in fp64 (both exact), the count exact.  A segment without a finite element
+ * has sum 0, min_abs +inf, max_abs 0.  Two launches: 128 workgroups per segment own fixed, interleaved 16 KiB chunks of it and write
+ * one partial record each to the workspace (lane -> wave -> workgroup); a second kernel combines a segment's 128 partials in a fixed
+ * order.  Two runs on the same bytes give the same bytes.
+ * flat 4-byte aligned (any position within 16 bytes, the segments too), table / workspace 8-byte aligned, seg: int64[nseg][2] = {offset, length}.
+ * workspace: sdf_grad_stats_workspace_bytes(nseg) bytes (0: refused nseg). */
+typedef struct SdfGradStatsDesc {
+  const float* flat;
+  int64_t n;
+  const int64_t* seg_host;
+  const int64_t* seg;
+  int32_t nseg, row0, rows;
+  double* table;
+  void* workspace;
+  int64_t workspace_bytes;
+} SdfGradStatsDesc;
+
+int64_t sdf_grad_stats_workspace_bytes(int nseg);
+int sdf_grad_stats_fwd(const SdfGradStatsDesc* d, void* stream);
+
+/* sdf_grad_clip_coef: over the rows r of a sdf_grad_stats_fwd table (double[rows][5], every bucket's rows in one table) with
+ * mask[r] != 0 (mask: rows bytes on the device, or NULL: every row), in fp64 and in a fixed order:
+ *   total = sqrt(sum sum_sq[r]);   record[0] = total;   record[1] = sum nonfinite[r];
+ *   coef[0] = (float) min(1, (double) max_norm / (total + 1e-6))
+ * - clip_grad_norm_'s formula with the norm taken in fp64; max_norm +inf gives coef 1 (no clip).  One launch of one workgroup.
+ * SDF_E_SHAPE: rows < 1 or > 2^24, max_norm NaN or < 0; table / record 8-byte, coef 4-byte aligned. */
+int sdf_grad_clip_coef(const double* table, int rows, const uint8_t* mask, float max_norm, float* coef, double* record, void* stream);
+
+/* sdf_adamw_step: torch.optim.AdamW(foreach=False)'s update of every ACTIVE segment, one read of g, m, v, p and one write of m, v, p.
+ * Row s of `rows` names the parameter (its own fp32 storage, `length` contiguous floats), its segment of grad / exp_avg / exp_avg_sq
+ * (three flat buffers of n floats with the same layout) and the step's scalars, rounded to fp32 as torch rounds the Python doubles:
+ *   decay = 1 - lr * weight_decay, w1 = 1 - beta1, beta2, w2 = 1 - beta2, neg_step_size = -lr / (1 - beta1^step),
+ *   bc2_sqrt = sqrt(1 - beta2^step), eps.
+ * Per element, every operation rounded on its own in fp32, c = coef ? coef[0] : 1:
+ *   g = grad * c;  p = p * decay;  m = w1 < 0.5 ? m + w1 * (g - m) : g - (g - m) * (1 - w1)  (torch's lerp);
+ *   v = v * beta2;  v = v + (w2 * g) * g;  p = p + (neg_step_size * m) / (sqrt(v) / bc2_sqrt + eps)
+ * grad itself is not written.  A row with active == 0 is not touched: not p, not the moments.  p is accessed 16 bytes per lane where it
+ * shares the segment's position within 16 bytes, 4 bytes per lane otherwise.
+ * grad / exp_avg / exp_avg_sq 4-byte aligned and at ONE position within 16 bytes, every param and coef 4-byte aligned, rows 8-byte
+ * aligned; SDF_E_NULL also for a NULL param of an active row; SDF_E_DTYPE also for a param of an active row that is not device memory. */
+typedef struct SdfAdamwRow {
+  void* param;
+  int64_t offset, length;
+  float decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps;
+  int32_t active;
+} SdfAdamwRow;
+
+typedef struct SdfAdamwDesc {
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t n;
+  const SdfAdamwRow* rows_host;
+  const SdfAdamwRow* rows;
+  int32_t nseg;
+  const float* coef;
+} SdfAdamwDesc;
+
+int sdf_adamw_step(const SdfAdamwDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * u8 spikes -> spike counts per time step: the numerator of the firing rate the reference's output monitor records for a neuron call,
  * `cal_firing_rate(s_seq) = s_seq.flatten(1).mean(1)` (eval_DSEC_flow_SNN.py:22-24, 140-143, `vis.monitor_fr`).
  * Element (o, t, r, c) is the byte at spikes + ((o * T + t) * rows + r) * row_stride + c; the call computes

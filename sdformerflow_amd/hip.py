@@ -308,6 +308,22 @@ class MembraneStatsDesc(C.Structure):
                 ("inv_width", C.c_float)]
 
 
+class GradStatsDesc(C.Structure):
+    _fields_ = [("flat", C.c_void_p), ("n", C.c_int64), ("seg_host", C.c_void_p), ("seg", C.c_void_p), ("nseg", C.c_int32),
+                ("row0", C.c_int32), ("rows", C.c_int32), ("table", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class AdamwRow(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("length", C.c_int64), ("decay", C.c_float), ("w1", C.c_float),
+                ("beta2", C.c_float), ("w2", C.c_float), ("neg_step_size", C.c_float), ("bc2_sqrt", C.c_float), ("eps", C.c_float),
+                ("active", C.c_int32)]
+
+
+class AdamwDesc(C.Structure):
+    _fields_ = [("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64), ("rows_host", C.c_void_p),
+                ("rows", C.c_void_p), ("nseg", C.c_int32), ("coef", C.c_void_p)]
+
+
 # The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
 # plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
 # still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
@@ -382,6 +398,8 @@ SIGNATURES = {
     "sdf_flow_image_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_image_fwd": (_i, (_P(FlowImageDesc), _p)),
     "sdf_flow_submission_fwd": (_i, (_P(FlowSubmissionDesc), _p)), "sdf_event_image_fwd": (_i, (_P(EventImageDesc), _p)),
     "sdf_membrane_stats_fwd": (_i, (_P(MembraneStatsDesc), _p)),
+    "sdf_grad_stats_workspace_bytes": (_i64, (_i,)), "sdf_grad_stats_fwd": (_i, (_P(GradStatsDesc), _p)),
+    "sdf_grad_clip_coef": (_i, (_p, _i, _p, _f, _p, _p, _p)), "sdf_adamw_step": (_i, (_P(AdamwDesc), _p)),
     "sdf_spike_count_fwd": (_i, (_P(SpikeCountDesc), _p)),
 }
 
@@ -2395,6 +2413,107 @@ def membrane_stats(v, t_dim, table=None, lo=-2.0, hi=2.0, bins=64):
     _note(bytes=outer * T * rows * Cc * 4, shape=(outer, T, rows, Cc))
     _check(lib().sdf_membrane_stats_fwd(C.byref(d), _stream()), "sdf_membrane_stats_fwd")
     return table
+
+
+GRAD_STATS_FIELDS = ("sum_abs", "sum_sq", "min_abs", "max_abs", "nonfinite")
+_GS_WS = {}
+
+
+class GradSegments:
+    """The parameters of one flat fp32 buffer as the grad-step entry points take them: (offset, length) pairs in floats, ascending and
+    not overlapping, once on the host (the entry points' checks) and once on `device` (the kernels)."""
+
+    def __init__(self, pairs, device):
+        import numpy as np
+        self.host = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.int64).reshape(-1, 2))
+        self.n = int(self.host.shape[0])
+        self.dev = torch.from_numpy(self.host).to(device)
+
+
+def adamw_rows(n):
+    """A host table of n SdfAdamwRow as a numpy structured array (fill it by field; `hip.adamw_step` takes it as it is)."""
+    import numpy as np
+    dt = np.dtype([("param", np.uint64), ("offset", np.int64), ("length", np.int64), ("decay", np.float32), ("w1", np.float32),
+                   ("beta2", np.float32), ("w2", np.float32), ("neg_step_size", np.float32), ("bc2_sqrt", np.float32),
+                   ("eps", np.float32), ("active", np.int32)], align=True)
+    assert dt.itemsize == C.sizeof(AdamwRow) and all(dt.fields[f][1] == getattr(AdamwRow, f).offset for f, _ in AdamwRow._fields_)
+    return np.zeros(n, dtype=dt)
+
+
+def _flat_f32(fn, name, t):
+    _ptr(t, torch.float32)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise SdfError(f"{fn}: {name} is a flat contiguous fp32 tensor, got {tuple(t.shape)}")
+    return t
+
+
+def grad_stats(flat, segments, table=None, row=0):
+    """Per-parameter gradient statistics of a flat fp32 bucket on the GPU (sdf_grad_stats_fwd: two launches, no read-back, no float
+    atomics): segment s of `segments` - a GradSegments, or (offset, length) pairs - writes row `row` + s of `table` (rows, 5) float64 -
+    GRAD_STATS_FIELDS: sum |g|, sum g^2, min |g|, max |g| over the finite elements (fp64, both terms exact) and the count of the
+    others - and leaves the other rows as they are.  `table` None: a new zero table of row + n rows.  Returns the table.  Identical
+    bytes from run to run."""
+    _flat_f32("grad_stats", "flat", flat)
+    dev = flat.device
+    if not isinstance(segments, GradSegments):
+        segments = GradSegments(segments, dev)
+    if table is None:
+        table = torch.zeros((row + segments.n, len(GRAD_STATS_FIELDS)), dtype=torch.float64, device=dev)
+    _ptr(table, torch.float64)
+    if table.dim() != 2 or table.shape[1] != len(GRAD_STATS_FIELDS) or not table.is_contiguous():
+        raise SdfError(f"grad_stats: table must be a contiguous (rows, {len(GRAD_STATS_FIELDS)}) float64 tensor")
+    need = lib().sdf_grad_stats_workspace_bytes(segments.n)
+    if need <= 0:
+        raise SdfError(f"grad_stats: {segments.n} segments; the entry point takes 1 to 65535", rc=E_SHAPE)
+    ws = _stream_ws(_GS_WS, dev, need)
+    d = GradStatsDesc()
+    d.flat, d.n, d.seg_host, d.seg, d.nseg = flat.data_ptr(), flat.numel(), segments.host.ctypes.data, segments.dev.data_ptr(), segments.n
+    d.row0, d.rows, d.table, d.workspace, d.workspace_bytes = row, table.shape[0], table.data_ptr(), ws.data_ptr(), ws.numel()
+    _check(lib().sdf_grad_stats_fwd(C.byref(d), _stream()), "sdf_grad_stats_fwd")
+    return table
+
+
+def grad_clip_coef(table, max_norm, mask=None, coef=None, record=None):
+    """torch.nn.utils.clip_grad_norm_'s coefficient from a grad_stats table, on the GPU (sdf_grad_clip_coef: one launch, no read-back):
+    total = sqrt(sum of sum_sq over the rows with mask != 0 (`mask`: (rows,) uint8 or None: all)) in fp64, coef = min(1, max_norm /
+    (total + 1e-6)) as one fp32.  max_norm is taken as fp32; inf gives coef 1.  Returns (coef (1,) float32, record (2,) float64 =
+    [total, non-finite count]), both device tensors - `coef` / `record` when given."""
+    _ptr(table, torch.float64)
+    if table.dim() != 2 or table.shape[1] != len(GRAD_STATS_FIELDS) or not table.is_contiguous():
+        raise SdfError(f"grad_clip_coef: table must be a contiguous (rows, {len(GRAD_STATS_FIELDS)}) float64 tensor")
+    dev = table.device
+    if mask is not None and (_ptr(mask, torch.uint8) is None or mask.shape != (table.shape[0],) or not mask.is_contiguous()):
+        raise SdfError(f"grad_clip_coef: mask is a contiguous ({table.shape[0]},) uint8 tensor")
+    coef = torch.empty(1, dtype=torch.float32, device=dev) if coef is None else coef
+    record = torch.empty(2, dtype=torch.float64, device=dev) if record is None else record
+    if coef.numel() != 1 or record.numel() != 2:
+        raise SdfError("grad_clip_coef: coef holds one float32 and record two float64")
+    _check(lib().sdf_grad_clip_coef(table.data_ptr(), table.shape[0], _ptr(mask), float(max_norm), _ptr(coef, torch.float32),
+                                    _ptr(record, torch.float64), _stream()), "sdf_grad_clip_coef")
+    return coef, record
+
+
+def adamw_step(grad, exp_avg, exp_avg_sq, rows, rows_dev=None, coef=None):
+    """torch.optim.AdamW(foreach=False)'s update of the parameters of one flat bucket (sdf_adamw_step: one launch; one read of g, m, v, p
+    and one write of m, v, p): `rows` is an adamw_rows() table - per parameter its data pointer, its segment of the three flat
+    buffers, the step's scalars and `active` (0: nothing of it is touched); `rows_dev` the same bytes on the device (None: copied
+    here, which waits for the copy).  `coef` (1,) float32 on the device multiplies every gradient as it is read (grad_clip_coef).
+    The parameters are written through their raw pointers: the CALLER moves their version counters."""
+    for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        _flat_f32("adamw_step", name, t)
+    if exp_avg.numel() != grad.numel() or exp_avg_sq.numel() != grad.numel():
+        raise SdfError("adamw_step: the moments mirror the gradient bucket")
+    if rows.dtype.itemsize != C.sizeof(AdamwRow) or not rows.flags["C_CONTIGUOUS"]:
+        raise SdfError("adamw_step: rows is an adamw_rows() table")
+    if rows_dev is None:
+        rows_dev = torch.from_numpy(rows.view("uint8")).to(grad.device)
+    if _ptr(rows_dev, torch.uint8) is None or rows_dev.numel() < rows.nbytes or not rows_dev.is_contiguous():
+        raise SdfError("adamw_step: rows_dev holds the bytes of rows on the device")
+    d = AdamwDesc()
+    d.grad, d.exp_avg, d.exp_avg_sq, d.n = grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.numel()
+    d.rows_host, d.rows, d.nseg, d.coef = rows.ctypes.data, rows_dev.data_ptr(), len(rows), _ptr(coef, torch.float32)
+    _note(bytes=int(rows["length"][rows["active"] != 0].sum()) * 28)
+    _check(lib().sdf_adamw_step(C.byref(d), _stream()), "sdf_adamw_step")
 
 
 _FI_WS, _EI_Q = {}, {}

@@ -7,7 +7,9 @@ since round 5 - ALL THREE products of every Linear layer (`autograd.LinearHipFun
 dW on csrc/linear_dw.hip: 35 ms of library fp32 GEMM -> 13 ms; no rocBLAS GEMM of a Linear layer is left in a step) and the forward and
 weight gradient of the MS_ResBlock convolutions (`autograd.Conv3x3HipFunction`: products over zero-ringed channels-last pixel rows).
 The other dense products - the convolutions' dX, the remaining convolutions' forward and dW - are library work through torch on the
-same stream (MIOpen); their replacements are the next row.  Nothing here touches `oracle/`, and CPU
+same stream (MIOpen); their replacements are the next row.  Behind the backward pass, with a `BucketAdamW`: the per-parameter gradient
+statistics (`vis.store_grads`), the clip coefficient and the AdamW update on the flat buckets (csrc/grad_step.hip), without a host
+synchronisation; with any other optimiser torch's clip_grad_norm_ and step.  Nothing here touches `oracle/`, and CPU
 tensors are refused by the neuron kernels (`SdfError`).
 
 Reference semantics mirrored (file:line under /root/reference):
@@ -465,6 +467,7 @@ class GradientBuckets:
         self._pending = [len(b) for b in self.buckets]
         self._seen, self._works, self._launched = set(), [], set()
         self.log = []                                                   # (event, bucket index, hooks fired so far): test hook
+        self.stats = None                                               # BucketStats, made by its first user (bucket_stats)
 
     def zero(self):
         for buf in self.flat:
@@ -473,6 +476,8 @@ class GradientBuckets:
     def begin(self, dist=None, world=1):
         """Start of a step: zero the buckets, re-attach the `.grad` views, arm the hooks."""
         self.zero()
+        if self.stats is not None:
+            self.stats.valid = self.stats.clipped = False
         for p, v in self._views.items():
             p.grad = v
         self._dist, self._world = (dist, world) if (dist is not None and world > 1) else (None, 1)
@@ -523,8 +528,259 @@ class GradientBuckets:
             buf.div_(world)
 
 
+# ---------------------------------------------------------------------------------------------- the step's tail on the buckets
+class BucketStats:
+    """Per-parameter gradient statistics of a GradientBuckets on the GPU (csrc/grad_step.hip): one (offset, length) table per bucket,
+    ONE statistics table for all of them - row r is parameter `params[r]`, bucket after bucket, hip.GRAD_STATS_FIELDS - and behind it,
+    in the same allocation, the clip record [total norm, non-finite count] and the fp32 clip coefficient, so that one read-back
+    fetches everything.  `compute()` is two launches per bucket, `clip()` one more; nothing waits for the host."""
+
+    def __init__(self, buckets):
+        self.params = [p for b in buckets.buckets for p in b]
+        if not self.params:
+            raise ValueError("BucketStats: the buckets hold no parameter")
+        self.flat, self.segments, self.row0, self.row_of = buckets.flat, [], [], {}
+        for flat, b in zip(buckets.flat, buckets.buckets):
+            pairs = []
+            for p in b:
+                v = buckets._views[p]
+                self.row_of[p] = len(self.row_of)
+                pairs.append(((v.data_ptr() - flat.data_ptr()) // 4, v.numel()))
+            self.row0.append(len(self.row_of) - len(b))
+            self.segments.append(hip.GradSegments(pairs, flat.device))
+        n, dev = len(self.params), buckets.flat[0].device
+        self._buf = torch.zeros(n * 5 + 3, dtype=torch.float64, device=dev)
+        self.table, self.record = self._buf[:n * 5].view(n, 5), self._buf[n * 5:n * 5 + 2]
+        self.coef = self._buf[n * 5 + 2:].view(torch.float32)[:1]
+        self.mask, self._mask_key = torch.ones(n, dtype=torch.uint8, device=dev), None
+        self.lengths = [p.numel() for p in self.params]
+        self.valid = self.clipped = False
+
+    def compute(self):
+        for flat, seg, row0 in zip(self.flat, self.segments, self.row0):
+            hip.grad_stats(flat, seg, self.table, row0)
+        self.valid, self.clipped = True, False
+
+    def clip(self, max_norm, active=None):
+        """The clip coefficient over the rows with active[r] (None: all) into `coef`; max_norm None = inf: coef 1, the norm is recorded."""
+        key = None if active is None else bytes(bytearray(int(bool(a)) for a in active))           # (a few hundred rows)
+        if key != self._mask_key:
+            host = torch.ones(len(self.params), dtype=torch.uint8) if key is None else torch.frombuffer(bytearray(key), dtype=torch.uint8)
+            self.mask.copy_(host.pin_memory(), non_blocking=True)
+            self._mask_key = key
+        hip.grad_clip_coef(self.table, float("inf") if max_norm is None else max_norm, self.mask, self.coef, self.record)
+        self.clipped = True
+
+    def read(self):
+        """ONE read-back: (table (n, 5) float64 numpy, [total norm, non-finite count], coef)."""
+        host = self._buf.cpu()
+        n = len(self.params)
+        return host[:n * 5].view(n, 5).numpy(), host[n * 5:n * 5 + 2].tolist(), float(host[n * 5 + 2:].view(torch.float32)[0])
+
+
+def bucket_stats(buckets):
+    """The buckets' BucketStats, made at the first call."""
+    if buckets.stats is None:
+        buckets.stats = BucketStats(buckets)
+    return buckets.stats
+
+
+def grad_stats_record(named_grads, coef=1.0):
+    """numpy restatement (float64) of the statistics kernel and of get_grads' arithmetic: {name: gradient array or None} ->
+    ({name_mean, name_min, name_max}, rows {name: (sum_abs, sum_sq, min_abs, max_abs, nonfinite)}).  Non-finite elements are counted and
+    left out of the sums and extremes; a parameter holding one records NaN.  `coef` scales to the post-clip values."""
+    import math
+    import numpy as np
+    record, rows = {}, {}
+    for name, g in named_grads.items():
+        a = np.abs(np.asarray(g, dtype=np.float32).reshape(-1)).astype(np.float64)
+        fin = a[np.isfinite(a)]
+        bad = a.size - fin.size
+        rows[name] = (math.fsum(fin), math.fsum(fin * fin), float(fin.min()) if fin.size else math.inf,
+                      float(fin.max()) if fin.size else 0.0, float(bad))
+        nan = bad > 0
+        record[f"{name}_mean"] = math.nan if nan else rows[name][0] / a.size * coef
+        record[f"{name}_min"] = math.nan if nan else rows[name][2] * coef
+        record[f"{name}_max"] = math.nan if nan else rows[name][3] * coef
+    return record, rows
+
+
+def clip_coef_restatement(sum_sq, max_norm):
+    """(coef, total) of sdf_grad_clip_coef in float64: clip_grad_norm_'s formula on the per-parameter sums of squares."""
+    import math
+    total = math.sqrt(math.fsum(sum_sq))
+    return min(1.0, float(max_norm) / (total + 1e-6)), total
+
+
+def adamw_scalars(step, lr, betas, eps, weight_decay):
+    """The scalars of AdamW's step number `step` as Python doubles, formed as torch.optim.AdamW(foreach=False) forms them:
+    (decay, w1, beta2, w2, neg_step_size, bc2_sqrt, eps)."""
+    b1, b2 = betas
+    return (1 - lr * weight_decay, 1 - b1, b2, 1 - b2, -(lr / (1 - b1 ** step)), (1 - b2 ** step) ** 0.5, eps)
+
+
+def adamw_restatement(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, coef=1.0):
+    """numpy restatement (float64 throughout) of one sdf_adamw_step on one parameter: returns the new (p, m, v).  `step` is the number
+    of THIS step (1 for the first); `coef` the clip coefficient the gradient is multiplied by."""
+    import numpy as np
+    decay, w1, beta2, w2, nstep, bc2s, eps = adamw_scalars(step, lr, betas, eps, weight_decay)
+    p, g, m, v = (np.asarray(a, dtype=np.float64) for a in (p, g, m, v))
+    g = g * float(coef)
+    p = p * decay
+    m = m + w1 * (g - m)
+    v = v * beta2 + w2 * g * g
+    return p + nstep * m / (np.sqrt(v) / bc2s + eps), m, v
+
+
+class BucketAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW (decoupled weight decay; no amsgrad, no maximize, one param group) on a GradientBuckets' flat buffers: the
+    moments are two flat buffers per bucket with the buckets' layout - `state[p]["exp_avg"]` / `["exp_avg_sq"]` are views into them,
+    `state[p]["step"]` torch's float32 CPU scalar - and `step(clip_grad)` is gradient statistics -> clip coefficient -> update on
+    csrc/grad_step.hip, on the current stream, without a host synchronisation: the update reads the coefficient from device memory.
+    The gradients themselves are NOT scaled in place (clip_grad_norm_ does); `get_grads` scales what it reports.  A parameter whose
+    `.grad` is None (GradientBuckets.finish) is not touched - not its value, its moments or its step count - as in torch.
+    `state_dict()` / `load_state_dict()` interchange with torch.optim.AdamW over the same parameters."""
+
+    def __init__(self, buckets, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        if not isinstance(buckets, GradientBuckets):
+            raise TypeError("BucketAdamW(buckets, ...): the first argument is the model's GradientBuckets")
+        if not (0.0 <= lr and 0.0 <= eps and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and 0.0 <= weight_decay):
+            raise ValueError(f"BucketAdamW: lr {lr}, betas {betas}, eps {eps}, weight_decay {weight_decay}")
+        for p in buckets.params:
+            if not (p.dtype == torch.float32 and p.is_contiguous() and p.numel() > 0):
+                raise hip.SdfError("BucketAdamW: parameters are non-empty contiguous fp32 tensors")
+        # (torch.optim.AdamW's group keys, so that a state_dict of this class loads into it; only the first four are options here)
+        super().__init__(buckets.params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                                              foreach=None, capturable=False, differentiable=False, fused=None,
+                                              decoupled_weight_decay=True))
+        self.buckets, self.stats = buckets, bucket_stats(buckets)
+        self.exp_avg = [torch.zeros_like(f) for f in buckets.flat]
+        self.exp_avg_sq = [torch.zeros_like(f) for f in buckets.flat]
+        self._rows = hip.adamw_rows(len(self.stats.params))
+        self._rows_dev = torch.zeros(self._rows.nbytes, dtype=torch.uint8, device=buckets.flat[0].device)
+        self._views = {}
+        for bi, (b, seg) in enumerate(zip(buckets.buckets, self.stats.segments)):
+            for p, (off, n) in zip(b, seg.host.tolist()):
+                r = self.stats.row_of[p]
+                self._rows["offset"][r], self._rows["length"][r] = off, n
+                self._views[p] = (self.exp_avg[bi][off:off + n].view_as(p), self.exp_avg_sq[bi][off:off + n].view_as(p))
+        self._attach({})
+
+    def _attach(self, steps):
+        """state[p] = torch's AdamW state over the flat views; `steps`: {p: step tensor to keep}."""
+        import numpy as np
+        for p, (m, v) in self._views.items():
+            step = steps.get(p)
+            self.state[p] = {"step": torch.tensor(0.0, dtype=torch.float32) if step is None else step, "exp_avg": m, "exp_avg_sq": v}
+        self._step_t = [self.state[p]["step"] for p in self.stats.params]                   # row order
+        self._k = np.array([float(t) for t in self._step_t], dtype=np.float64)              # their values, kept in lockstep
+
+    def load_state_dict(self, state_dict):
+        """torch's loading, then the loaded moments are copied INTO the flat views (which stay the state); a parameter the loaded
+        state does not know starts from zero."""
+        super().load_state_dict(state_dict)
+        if len(self.param_groups) != 1:
+            raise ValueError("BucketAdamW: one param group")
+        steps = {}
+        for p, (m, v) in self._views.items():
+            st = self.state.get(p, {})
+            if "exp_avg" in st:
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
+                steps[p] = torch.as_tensor(st["step"]).detach().to("cpu", torch.float32).reshape(()).clone()
+            else:
+                m.zero_()
+                v.zero_()
+        self._attach(steps)
+
+    @torch.no_grad()
+    def step(self, clip_grad=None, closure=None):
+        import numpy as np
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g = self.param_groups[0]
+        if g.get("amsgrad") or g.get("maximize"):
+            raise NotImplementedError("BucketAdamW: amsgrad and maximize are not built")
+        lr, betas, eps, wd = float(g["lr"]), g["betas"], g["eps"], g["weight_decay"]
+        st, rows = self.stats, self._rows
+        act = np.fromiter((p.grad is not None for p in st.params), dtype=bool, count=len(st.params))
+        st.compute()
+        st.clip(clip_grad, act)
+        if not act.any():
+            return loss
+        updated = [p for p, a in zip(st.params, act) if a]
+        torch._foreach_add_([t for t, a in zip(self._step_t, act) if a], 1)
+        self._k[act] += 1
+        rows["active"][:] = act
+        rows["param"][:] = [p.data_ptr() for p in st.params]
+        for k in np.unique(self._k[act]):                                                  # (one value, unless parameters joined late)
+            sel = act & (self._k == k)
+            for name, val in zip(("decay", "w1", "beta2", "w2", "neg_step_size", "bc2_sqrt", "eps"), adamw_scalars(float(k), lr, betas, eps, wd)):
+                rows[name][sel] = val
+        # (a fresh pinned block per step: the host allocator holds it back until the copy has run, so nothing waits here)
+        self._rows_dev.copy_(torch.from_numpy(rows.view("uint8")).pin_memory(), non_blocking=True)
+        for bi, n in enumerate(len(b) for b in self.buckets.buckets):
+            r0 = st.row0[bi]
+            if act[r0:r0 + n].any():
+                hip.adamw_step(self.buckets.flat[bi], self.exp_avg[bi], self.exp_avg_sq[bi], rows[r0:r0 + n],
+                               self._rows_dev[r0 * rows.itemsize:(r0 + n) * rows.itemsize], st.coef)
+        # the kernel wrote through raw pointers: move the version counters, which the packed inference weights are keyed on
+        torch.autograd.graph.increment_version(updated)
+        return loss
+
+
+def get_grads(model, buckets, coef=None, missing="skip"):
+    """The reference's `vis.store_grads` record (utils/gradients.py get_grads, taken after the clip): {name}_mean / _min / _max of
+    |grad| of every `requires_grad` parameter with "weight" in its name, from the buckets' statistics table with ONE read-back
+    instead of three `.item()` per parameter.  The statistics are those of this step (computed here unless BucketAdamW.step already
+    did).  `coef`: what the clip multiplied the gradients by - None: the coefficient of this step's BucketAdamW.step, 1 without one.
+    A parameter holding a non-finite gradient records NaN.  A parameter without a gradient: `missing="skip"` leaves it out,
+    "raise" is the reference's AttributeError."""
+    import math
+    if missing not in ("skip", "raise"):
+        raise ValueError('get_grads: missing is "skip" or "raise"')
+    st = bucket_stats(buckets)
+    if not st.valid:
+        st.compute()
+    table, _, dev_coef = st.read()
+    c = float(coef) if coef is not None else dev_coef if st.clipped else 1.0
+    record = {}
+    for name, p in model.named_parameters():
+        if not (p.requires_grad and "weight" in name):
+            continue
+        if p.grad is None or p not in st.row_of:
+            if missing == "raise":
+                raise AttributeError(f"{name} grad error: gradient returns None")
+            continue
+        r = st.row_of[p]
+        sum_abs, _, mn, mx, bad = table[r]
+        nan = bad > 0
+        record[f"{name}_mean"] = math.nan if nan else float(sum_abs) / st.lengths[r] * c
+        record[f"{name}_min"] = math.nan if nan else float(mn) * c
+        record[f"{name}_max"] = math.nan if nan else float(mx) * c
+    return record
+
+
+def save_grads_csv(records, path):
+    """The reference's save_csv(grads_w, "grads_w.csv") without pandas: a header (an empty index cell, then the keys of the first
+    record) and one row per record, index first; appended WITHOUT a header when the file exists."""
+    import csv
+    if not records:
+        return
+    new = not os.path.isfile(path)
+    keys = list(records[0])
+    with open(path, "a", newline="") as f:
+        w = csv.writer(f)
+        if new:
+            w.writerow([""] + keys)
+        for i, rec in enumerate(records):
+            w.writerow([i] + [repr(float(rec[k])) if k in rec else "" for k in keys])
+
+
 def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, world=1, clip_grad=100.0, flow_scaling=1.0,
-               lambda_mod=1.0, amp=False, forward_fn=None):
+               lambda_mod=1.0, amp=False, forward_fn=None, grads_out=None):
     """One step of train_flow_parallel_supervised_SNN.py's loop body (:233-336) on this rank's shard of the batch; returns the
     loss tensor (this rank's samples' mean of err / n_global; the mean over ranks is the gathered-batch loss).
     `amp`: the reference trains under `torch.cuda.amp.autocast` with fp16 + GradScaler (`optimizer.use_amp: true`,
@@ -533,7 +789,14 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
     An STTFlowNet (the ANN family, `clip_grad=None` as its config has it) trains through its own train-mode forward,
     `model(chunk, None)["flow"]`, in fp32; a SpikingformerFlowNet (the SEW family) through `forward_train_sew`.
     `forward_fn(model, chunk) -> flows` replaces the HIP train-mode forward (the CPU dry run of the N > 1 plumbing, bench.py --train
-    --plumbing: everything else in this function is the code the GPU ranks run)."""
+    --plumbing: everything else in this function is the code the GPU ranks run).
+    With a `BucketAdamW` the tail behind the backward pass - clip and update - is `optimizer.step(clip_grad)` on csrc/grad_step.hip;
+    with any other optimiser it is torch's, as before.  `grads_out`, a list: the reference's `vis.store_grads` - one `get_grads`
+    record of the clipped gradients is appended per step (needs `buckets`)."""
+    if isinstance(optimizer, BucketAdamW) and buckets is not optimizer.buckets:
+        raise ValueError("train_step: a BucketAdamW steps on its GradientBuckets - pass them as buckets=")
+    if grads_out is not None and buckets is None:
+        raise ValueError("train_step: grads_out takes the statistics from the gradient buckets - pass buckets=")
     from .spikingjelly_compat import functional
     from .STSwinNet.STSwinNet import STTFlowNet
     from .STSwinNet_SNN.Spiking_STSwinNet import SpikingformerFlowNet
@@ -562,7 +825,14 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
     loss.backward()                                                  # bucket all-reduces leave from the grad-ready hooks
     if buckets is not None:
         buckets.finish()
+    if isinstance(optimizer, BucketAdamW):
+        optimizer.step(clip_grad)
+        if grads_out is not None:
+            grads_out.append(get_grads(model, buckets))
+        return loss.detach()
     if clip_grad is not None:
         torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], clip_grad)
+    if grads_out is not None:                                        # (the gradients are clipped in place here: coef 1)
+        grads_out.append(get_grads(model, buckets, coef=1.0))
     optimizer.step()
     return loss.detach()
