@@ -1382,6 +1382,69 @@ typedef struct SdfAdamwDesc {
 int sdf_adamw_step(const SdfAdamwDesc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same tail with a loss scaler (torch.amp.GradScaler's arithmetic), a skipped step and gradient accumulation: the decision "this
+ * step is off" and the factor "multiply by this" live in device memory and the update obeys them; the host waits for neither.
+ * Conventions, check order and alignment rules are those of the three entry points above.  Added to SDF_VERSION 107 (no existing
+ * entry changed).
+ *
+ * SdfLossScaleState (device memory, 8-byte aligned): `scale` is what the NEXT loss is multiplied by; `inv_scale`, `found_inf` and
+ * `skipped` are written by sdf_grad_clip_scale_coef: the reciprocal of the scale the gradients of THIS step carry, whether one of
+ * them is not finite, and how many steps were found so since the state was made. */
+typedef struct SdfLossScaleState {
+  float scale;
+  int32_t growth_tracker;
+  float inv_scale;
+  int32_t found_inf;
+  int64_t skipped;
+} SdfLossScaleState;
+
+/* sdf_grad_scale_inplace: g = g * coef[0] over every segment s of `flat` with mask[s] != 0 (mask: nseg bytes on the device, or NULL:
+ * every segment) - clip_grad_norm_'s in-place pass on a running sum, the coefficient read from device memory.  One fp32
+ * multiplication per element (inf and NaN follow IEEE); 16 bytes per lane between a segment's 16-byte boundaries, single floats in
+ * front of and behind them; one launch.  flat / coef 4-byte, seg 8-byte aligned; seg as in SdfGradStatsDesc. */
+typedef struct SdfGradScaleDesc {
+  float* flat;
+  int64_t n;
+  const int64_t* seg_host;
+  const int64_t* seg;
+  int32_t nseg;
+  const uint8_t* mask;
+  const float* coef;
+} SdfGradScaleDesc;
+
+int sdf_grad_scale_inplace(const SdfGradScaleDesc* d, void* stream);
+
+/* sdf_grad_clip_scale_coef: sdf_grad_clip_coef's reduction (the same order, fp64) and, behind it in the same single workgroup, the
+ * scaler.  With s0 = state->scale as it stands (the scale the gradients carry):
+ *   total, record[0], record[1] as sdf_grad_clip_coef;   inv_scale = (float)(1.0 / (double) s0);
+ *   coef[0] = (float) min(1, (double) max_norm / (t + 1e-6)),  t = clip_unscaled ? total * inv_scale : total
+ *     (clip_unscaled 0: the clip bounds the STILL-SCALED norm, as a loop that calls clip_grad_norm_ without scaler.unscale_ does);
+ *   found_inf = record[1] > 0;   skipped += found_inf;
+ *   update != 0 - torch's _amp_update_scale_ on fp32 values:  found_inf: scale = s0 * backoff_factor, growth_tracker = 0;  else
+ *     growth_tracker + 1 == growth_interval: scale = s0 * growth_factor unless that is not finite, growth_tracker = 0;  else
+ *     growth_tracker += 1.   update == 0 leaves scale and growth_tracker alone (a scaler that only provides the skip).
+ * SDF_E_SHAPE: rows < 1 or > 2^24, max_norm NaN or < 0, a factor that is NaN or <= 0, growth_interval < 1; table / record / state
+ * 8-byte, coef 4-byte aligned. */
+typedef struct SdfGradClipScaleDesc {
+  const double* table;
+  int32_t rows;
+  const uint8_t* mask;
+  float max_norm;
+  float* coef;
+  double* record;
+  SdfLossScaleState* state;
+  float growth_factor, backoff_factor;
+  int32_t growth_interval, clip_unscaled, update;
+} SdfGradClipScaleDesc;
+
+int sdf_grad_clip_scale_coef(const SdfGradClipScaleDesc* d, void* stream);
+
+/* sdf_adamw_step_scaled: sdf_adamw_step under a loss scaler.  state->found_inf != 0: no byte of a parameter or a moment is written by
+ * any workgroup.  Otherwise sdf_adamw_step's arithmetic on g = (grad * c) * state->inv_scale - two fp32 multiplications, as
+ * clip_grad_norm_'s in-place pass followed by GradScaler.unscale_ performs.  state: device memory, 8-byte aligned (SDF_E_NULL when NULL). */
+int sdf_adamw_step_scaled(const SdfAdamwDesc* d, const SdfLossScaleState* state, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * u8 spikes -> spike counts per time step: the numerator of the firing rate the reference's output monitor records for a neuron call,
  * `cal_firing_rate(s_seq) = s_seq.flatten(1).mean(1)` (eval_DSEC_flow_SNN.py:22-24, 140-143, `vis.monitor_fr`).
  * Element (o, t, r, c) is the byte at spikes + ((o * T + t) * rows + r) * row_stride + c; the call computes

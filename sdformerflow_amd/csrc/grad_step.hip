@@ -1,5 +1,7 @@
 // The tail of a training step on flat fp32 gradient buckets, gfx950: per-parameter gradient statistics, the clip coefficient and the
-// AdamW update (include/sdformerflow_hip.h: sdf_grad_stats_fwd, sdf_grad_clip_coef, sdf_adamw_step).
+// AdamW update (include/sdformerflow_hip.h: sdf_grad_stats_fwd, sdf_grad_clip_coef, sdf_adamw_step) - and the same tail under a loss
+// scaler, with skipped steps and gradient accumulation (sdf_grad_scale_inplace, sdf_grad_clip_scale_coef, sdf_adamw_step_scaled): a
+// device-resident SdfLossScaleState carries the verdict on a step and the factor to divide out, and the update obeys it unasked.
 //
 // Replaces what train.train_step ran in stock torch behind loss.backward(): clip_grad_norm_'s multi-tensor norm and scale passes,
 // optimizer.step()'s multi-tensor passes over parameters, gradients and moments, and - for `vis.store_grads` - the reference's three
@@ -14,7 +16,8 @@
 // fixed order, so two runs on the same bytes give the same bytes.  Compiled with -ffp-contract=off: every fp32 operation of the
 // update is rounded on its own, in torch.optim.AdamW(foreach=False)'s order.
 //
-// Launch sequences: statistics: partial records (kGsGroups x nseg) | finish (nseg).  coefficient: one workgroup.  update: (kGsGroups x nseg).
+// Launch sequences: statistics: partial records (kGsGroups x nseg) | finish (nseg).  coefficient (with or without the scaler): one
+// workgroup.  update, in-place scale: (kGsGroups x nseg).
 #include "host_launch.h"
 
 namespace {
@@ -138,9 +141,9 @@ __global__ __launch_bounds__(64) void grad_stats_finish_kernel(const double* __r
   }
 }
 
-// one workgroup: lane t adds rows t, t + 256, ... in row order, then wave tree, then the 4 waves in order
-__global__ __launch_bounds__(kGsThreads) void grad_clip_coef_kernel(const double* __restrict__ table, int rows, const uint8_t* __restrict__ mask,
-                                                                    double max_norm, float* __restrict__ coef, double* __restrict__ record) {
+// one workgroup: lane t adds rows t, t + 256, ... in row order, then wave tree, then the 4 waves in order.  True on thread 0 alone,
+// which then holds the sum of squares `s` and the non-finite count `b` of the masked rows.
+__device__ __forceinline__ bool gc_reduce(const double* __restrict__ table, int rows, const uint8_t* __restrict__ mask, double& s, double& b) {
   double ssq = 0.0, bad = 0.0;
   for (int r = threadIdx.x; r < rows; r += kGsThreads) {
     if (mask && !mask[r]) continue;
@@ -158,12 +161,20 @@ __global__ __launch_bounds__(kGsThreads) void grad_clip_coef_kernel(const double
     r_b[threadIdx.x >> 6] = bad;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0, b = 0.0;
-    for (int w = 0; w < W; ++w) {
-      s += r_s[w];
-      b += r_b[w];
-    }
+  if (threadIdx.x != 0) return false;
+  s = 0.0;
+  b = 0.0;
+  for (int w = 0; w < W; ++w) {
+    s += r_s[w];
+    b += r_b[w];
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(kGsThreads) void grad_clip_coef_kernel(const double* __restrict__ table, int rows, const uint8_t* __restrict__ mask,
+                                                                    double max_norm, float* __restrict__ coef, double* __restrict__ record) {
+  double s, b;
+  if (gc_reduce(table, rows, mask, s, b)) {
     const double total = sqrt(s);
     const double c = max_norm / (total + 1e-6);
     record[0] = total;
@@ -172,12 +183,50 @@ __global__ __launch_bounds__(kGsThreads) void grad_clip_coef_kernel(const double
   }
 }
 
+// ... and the loss scaler behind the same reduction: the verdict on this step, the reciprocal of the scale its gradients carry, and
+// then torch's _amp_update_scale_ for the next one
+__global__ __launch_bounds__(kGsThreads) void grad_clip_scale_coef_kernel(const double* __restrict__ table, int rows,
+                                                                          const uint8_t* __restrict__ mask, double max_norm,
+                                                                          float* __restrict__ coef, double* __restrict__ record,
+                                                                          SdfLossScaleState* __restrict__ state, float growth, float backoff,
+                                                                          int growth_interval, int clip_unscaled, int update) {
+  double s, b;
+  if (gc_reduce(table, rows, mask, s, b)) {
+    const double total = sqrt(s);
+    const float scale = state->scale;
+    const float inv = (float)(1.0 / (double)scale);
+    const double c = max_norm / ((clip_unscaled ? total * (double)inv : total) + 1e-6);
+    record[0] = total;
+    record[1] = b;
+    coef[0] = (float)(c < 1.0 ? c : 1.0);
+    const int found = b > 0.0 ? 1 : 0;
+    state->found_inf = found;
+    state->inv_scale = inv;
+    state->skipped += found;
+    if (update) {
+      if (found) {
+        state->scale = scale * backoff;
+        state->growth_tracker = 0;
+      } else if (state->growth_tracker + 1 == growth_interval) {
+        const float grown = scale * growth;
+        if (fabsf(grown) < __builtin_inff()) state->scale = grown;
+        state->growth_tracker = 0;
+      } else {
+        state->growth_tracker += 1;
+      }
+    }
+  }
+}
+
 struct AwScalars {
-  float decay, w1, beta2, w2, nstep, bc2s, eps, c;
+  float decay, w1, beta2, w2, nstep, bc2s, eps, c, inv;
 };
 
+// kScaled: the gradient carries a loss scale - a second multiplication, by its reciprocal, behind the clip's
+template <bool kScaled>
 __device__ __forceinline__ void aw_elem(const AwScalars& S, float g, float& m, float& v, float& p) {
   g = g * S.c;
+  if (kScaled) g = g * S.inv;
   p = p * S.decay;
   const float diff = g - m;
   m = S.w1 < 0.5f ? m + S.w1 * diff : g - diff * (1.0f - S.w1);
@@ -187,15 +236,23 @@ __device__ __forceinline__ void aw_elem(const AwScalars& S, float g, float& m, f
   p = p + (S.nstep * m) / denom;
 }
 
-__global__ __launch_bounds__(kGsThreads) void adamw_step_kernel(const float* __restrict__ grad, float* __restrict__ exp_avg,
-                                                                float* __restrict__ exp_avg_sq, const SdfAdamwRow* __restrict__ rows,
-                                                                const float* __restrict__ coef) {
+// the update of segment blockIdx.y by workgroup blockIdx.x, shared by the two kernels below.  kScaled: `state` decides - a step with a
+// non-finite gradient writes nothing at all, any other one divides the scale out
+template <bool kScaled>
+__device__ __forceinline__ void aw_segment(const float* __restrict__ grad, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                           const SdfAdamwRow* __restrict__ rows, const float* __restrict__ coef,
+                                           const SdfLossScaleState* __restrict__ state) {
   const SdfAdamwRow R = rows[blockIdx.y];
   if (!R.active) return;
   const int x = blockIdx.x;
   AwScalars S;
   S.decay = R.decay; S.w1 = R.w1; S.beta2 = R.beta2; S.w2 = R.w2; S.nstep = R.neg_step_size; S.bc2s = R.bc2_sqrt; S.eps = R.eps;
   S.c = coef ? coef[0] : 1.0f;
+  S.inv = 1.0f;
+  if (kScaled) {
+    if (state->found_inf != 0) return;
+    S.inv = state->inv_scale;
+  }
   const float* g = grad + R.offset;
   float* m = exp_avg + R.offset;
   float* v = exp_avg_sq + R.offset;
@@ -226,10 +283,10 @@ __global__ __launch_bounds__(kGsThreads) void adamw_step_kernel(const float* __r
     for (int k = 0; k < kAwVecs; ++k) {
       const int64_t i = v0 + k * kGsThreads + threadIdx.x;
       if (i < G.nvec) {
-        aw_elem(S, gw[k].x, mw[k].x, vw[k].x, pw[k].x);
-        aw_elem(S, gw[k].y, mw[k].y, vw[k].y, pw[k].y);
-        aw_elem(S, gw[k].z, mw[k].z, vw[k].z, pw[k].z);
-        aw_elem(S, gw[k].w, mw[k].w, vw[k].w, pw[k].w);
+        aw_elem<kScaled>(S, gw[k].x, mw[k].x, vw[k].x, pw[k].x);
+        aw_elem<kScaled>(S, gw[k].y, mw[k].y, vw[k].y, pw[k].y);
+        aw_elem<kScaled>(S, gw[k].z, mw[k].z, vw[k].z, pw[k].z);
+        aw_elem<kScaled>(S, gw[k].w, mw[k].w, vw[k].w, pw[k].w);
         m4[i] = mw[k];
         v4[i] = vw[k];
         if (pvec) {
@@ -249,11 +306,59 @@ __global__ __launch_bounds__(kGsThreads) void adamw_step_kernel(const float* __r
     }
     if (mine) {
       float mm = m[i], vv = v[i], pp = p[i];
-      aw_elem(S, g[i], mm, vv, pp);
+      aw_elem<kScaled>(S, g[i], mm, vv, pp);
       m[i] = mm;
       v[i] = vv;
       p[i] = pp;
     }
+  }
+}
+
+__global__ __launch_bounds__(kGsThreads) void adamw_step_kernel(const float* __restrict__ grad, float* __restrict__ exp_avg,
+                                                                float* __restrict__ exp_avg_sq, const SdfAdamwRow* __restrict__ rows,
+                                                                const float* __restrict__ coef) {
+  aw_segment<false>(grad, exp_avg, exp_avg_sq, rows, coef, nullptr);
+}
+
+__global__ __launch_bounds__(kGsThreads) void adamw_step_scaled_kernel(const float* __restrict__ grad, float* __restrict__ exp_avg,
+                                                                       float* __restrict__ exp_avg_sq, const SdfAdamwRow* __restrict__ rows,
+                                                                       const float* __restrict__ coef,
+                                                                       const SdfLossScaleState* __restrict__ state) {
+  aw_segment<true>(grad, exp_avg, exp_avg_sq, rows, coef, state);
+}
+
+// g *= coef[0] over the active segments: workgroup (x, s) of a (kGsGroups, nseg) grid, the statistics kernel's chunks
+__global__ __launch_bounds__(kGsThreads) void grad_scale_kernel(float* __restrict__ flat, const int64_t* __restrict__ seg,
+                                                                const uint8_t* __restrict__ mask, const float* __restrict__ coef) {
+  const int s = blockIdx.y, x = blockIdx.x;
+  if (mask && !mask[s]) return;
+  const float c = coef[0];
+  const int64_t len = seg[2 * s + 1];
+  float* base = flat + seg[2 * s];
+  const GsSpan S = gs_span(base, len);
+  float4* body = reinterpret_cast<float4*>(base + S.head);
+  for (int64_t v0 = (int64_t)x * (kGsThreads * kGsVecs); v0 < S.nvec; v0 += (int64_t)kGsGroups * (kGsThreads * kGsVecs)) {
+    float4 w[kGsVecs];
+#pragma unroll
+    for (int k = 0; k < kGsVecs; ++k) {                  // every load of the chunk is issued before the first store
+      const int64_t i = v0 + k * kGsThreads + threadIdx.x;
+      if (i < S.nvec) w[k] = body[i];
+    }
+#pragma unroll
+    for (int k = 0; k < kGsVecs; ++k) {
+      const int64_t i = v0 + k * kGsThreads + threadIdx.x;
+      if (i < S.nvec) {
+        w[k].x = w[k].x * c; w[k].y = w[k].y * c; w[k].z = w[k].z * c; w[k].w = w[k].w * c;
+        body[i] = w[k];
+      }
+    }
+  }
+  if (x == 0) {                                          // lanes 0 .. 2: the head floats, lanes 16 .. 18: the tail floats
+    const int64_t i = threadIdx.x;
+    if (i < S.head)
+      base[i] = base[i] * c;
+    else if (i >= 16 && i < 19 && S.tail0 + (i - 16) < len)
+      base[S.tail0 + (i - 16)] = base[S.tail0 + (i - 16)] * c;
   }
 }
 
@@ -319,7 +424,11 @@ extern "C" int sdf_grad_clip_coef(const double* table, int rows, const uint8_t* 
   return sdf_launch_rc();
 }
 
-extern "C" int sdf_adamw_step(const SdfAdamwDesc* d, void* stream) {
+namespace {
+
+// the checks of sdf_adamw_step and of its scaled form (`scaled`: with a loss-scale state), in the family's order: 0, or the refusal
+inline int aw_check(const SdfAdamwDesc* d, const SdfLossScaleState* state, bool scaled) {
+  if (scaled && !state) return SDF_E_NULL;
   if (!d || !d->grad || !d->exp_avg || !d->exp_avg_sq || !d->rows_host || !d->rows) return SDF_E_NULL;
   if (!gs_count_ok(d->nseg, d->n)) return SDF_E_SHAPE;
   for (int i = 0; i < d->nseg; ++i)
@@ -327,15 +436,55 @@ extern "C" int sdf_adamw_step(const SdfAdamwDesc* d, void* stream) {
   if (!gs_segments_ok(d->nseg, d->n, [&](int i, int64_t& off, int64_t& len) { off = d->rows_host[i].offset; len = d->rows_host[i].length; }))
     return SDF_E_SHAPE;
   if (!sdf_aligned(d->grad, 4) || !sdf_aligned(d->rows, 8) || !sdf_aligned(d->coef, 4)) return SDF_E_ALIGN;
+  if (scaled && !sdf_aligned(state, 8)) return SDF_E_ALIGN;
   if (!gs_same_phase(d->grad, d->exp_avg) || !gs_same_phase(d->grad, d->exp_avg_sq)) return SDF_E_ALIGN;
   for (int i = 0; i < d->nseg; ++i)
     if (d->rows_host[i].active && !sdf_aligned(d->rows_host[i].param, 4)) return SDF_E_ALIGN;
   if (!gs_on_device(d->grad) || !gs_on_device(d->exp_avg) || !gs_on_device(d->exp_avg_sq) || !gs_on_device(d->rows) ||
-      (d->coef && !gs_on_device(d->coef)))
+      (d->coef && !gs_on_device(d->coef)) || (scaled && !gs_on_device(state)))
     return SDF_E_DTYPE;
   for (int i = 0; i < d->nseg; ++i)
     if (d->rows_host[i].active && !gs_on_device(d->rows_host[i].param)) return SDF_E_DTYPE;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int sdf_adamw_step(const SdfAdamwDesc* d, void* stream) {
+  if (const int rc = aw_check(d, nullptr, false)) return rc;
   SDF_LAUNCH(adamw_step_kernel, dim3(kGsGroups, d->nseg), dim3(kGsThreads), 0, sdf_stream(stream), d->grad, d->exp_avg, d->exp_avg_sq, d->rows,
              d->coef);
+  return sdf_launch_rc();
+}
+
+extern "C" int sdf_adamw_step_scaled(const SdfAdamwDesc* d, const SdfLossScaleState* state, void* stream) {
+  if (const int rc = aw_check(d, state, true)) return rc;
+  SDF_LAUNCH(adamw_step_scaled_kernel, dim3(kGsGroups, d->nseg), dim3(kGsThreads), 0, sdf_stream(stream), d->grad, d->exp_avg, d->exp_avg_sq,
+             d->rows, d->coef, state);
+  return sdf_launch_rc();
+}
+
+extern "C" int sdf_grad_scale_inplace(const SdfGradScaleDesc* d, void* stream) {
+  if (!d || !d->flat || !d->seg_host || !d->seg || !d->coef) return SDF_E_NULL;
+  if (!gs_count_ok(d->nseg, d->n)) return SDF_E_SHAPE;
+  if (!gs_segments_ok(d->nseg, d->n, [&](int i, int64_t& off, int64_t& len) { off = d->seg_host[2 * i]; len = d->seg_host[2 * i + 1]; }))
+    return SDF_E_SHAPE;
+  if (!sdf_aligned(d->flat, 4) || !sdf_aligned(d->seg, 8) || !sdf_aligned(d->coef, 4)) return SDF_E_ALIGN;
+  if (!gs_on_device(d->flat) || !gs_on_device(d->seg) || (d->mask && !gs_on_device(d->mask)) || !gs_on_device(d->coef)) return SDF_E_DTYPE;
+  SDF_LAUNCH(grad_scale_kernel, dim3(kGsGroups, d->nseg), dim3(kGsThreads), 0, sdf_stream(stream), d->flat, d->seg, d->mask, d->coef);
+  return sdf_launch_rc();
+}
+
+extern "C" int sdf_grad_clip_scale_coef(const SdfGradClipScaleDesc* d, void* stream) {
+  if (!d || !d->table || !d->coef || !d->record || !d->state) return SDF_E_NULL;
+  if (d->rows < 1 || d->rows > (1 << 24) || !(d->max_norm >= 0.f)) return SDF_E_SHAPE;            // (+inf: no clip, coef 1)
+  if (!(d->growth_factor > 0.f) || !(d->backoff_factor > 0.f) || d->growth_interval < 1) return SDF_E_SHAPE;
+  if (!sdf_aligned(d->table, 8) || !sdf_aligned(d->record, 8) || !sdf_aligned(d->coef, 4) || !sdf_aligned(d->state, 8)) return SDF_E_ALIGN;
+  if (!gs_on_device(d->table) || (d->mask && !gs_on_device(d->mask)) || !gs_on_device(d->coef) || !gs_on_device(d->record) ||
+      !gs_on_device(d->state))
+    return SDF_E_DTYPE;
+  SDF_LAUNCH(grad_clip_scale_coef_kernel, dim3(1), dim3(kGsThreads), 0, sdf_stream(stream), d->table, (int)d->rows, d->mask,
+             (double)d->max_norm, d->coef, d->record, d->state, d->growth_factor, d->backoff_factor, (int)d->growth_interval,
+             (int)d->clip_unscaled, (int)d->update);
   return sdf_launch_rc();
 }

@@ -324,6 +324,22 @@ class AdamwDesc(C.Structure):
                 ("rows", C.c_void_p), ("nseg", C.c_int32), ("coef", C.c_void_p)]
 
 
+class LossScaleState(C.Structure):
+    _fields_ = [("scale", C.c_float), ("growth_tracker", C.c_int32), ("inv_scale", C.c_float), ("found_inf", C.c_int32),
+                ("skipped", C.c_int64)]
+
+
+class GradScaleDesc(C.Structure):
+    _fields_ = [("flat", C.c_void_p), ("n", C.c_int64), ("seg_host", C.c_void_p), ("seg", C.c_void_p), ("nseg", C.c_int32),
+                ("mask", C.c_void_p), ("coef", C.c_void_p)]
+
+
+class GradClipScaleDesc(C.Structure):
+    _fields_ = [("table", C.c_void_p), ("rows", C.c_int32), ("mask", C.c_void_p), ("max_norm", C.c_float), ("coef", C.c_void_p),
+                ("record", C.c_void_p), ("state", C.c_void_p), ("growth_factor", C.c_float), ("backoff_factor", C.c_float),
+                ("growth_interval", C.c_int32), ("clip_unscaled", C.c_int32), ("update", C.c_int32)]
+
+
 # The C ABI in header order, a family of entry points per line: name -> (restype, argtypes).  lib() declares every one, so ctypes converts
 # plain Python ints / floats / pointers itself and refuses a wrong argument count or type at the call (an int too wide for its C type is
 # still truncated).  tests/test_abi_cpu.py checks the table and the Structure mirrors against include/sdformerflow_hip.h.
@@ -400,6 +416,8 @@ SIGNATURES = {
     "sdf_membrane_stats_fwd": (_i, (_P(MembraneStatsDesc), _p)),
     "sdf_grad_stats_workspace_bytes": (_i64, (_i,)), "sdf_grad_stats_fwd": (_i, (_P(GradStatsDesc), _p)),
     "sdf_grad_clip_coef": (_i, (_p, _i, _p, _f, _p, _p, _p)), "sdf_adamw_step": (_i, (_P(AdamwDesc), _p)),
+    "sdf_grad_scale_inplace": (_i, (_P(GradScaleDesc), _p)), "sdf_grad_clip_scale_coef": (_i, (_P(GradClipScaleDesc), _p)),
+    "sdf_adamw_step_scaled": (_i, (_P(AdamwDesc), _P(LossScaleState), _p)),
     "sdf_spike_count_fwd": (_i, (_P(SpikeCountDesc), _p)),
 }
 
@@ -2514,6 +2532,110 @@ def adamw_step(grad, exp_avg, exp_avg_sq, rows, rows_dev=None, coef=None):
     d.rows_host, d.rows, d.nseg, d.coef = rows.ctypes.data, rows_dev.data_ptr(), len(rows), _ptr(coef, torch.float32)
     _note(bytes=int(rows["length"][rows["active"] != 0].sum()) * 28)
     _check(lib().sdf_adamw_step(C.byref(d), _stream()), "sdf_adamw_step")
+
+
+def loss_scale_state(scale=65536.0, growth_tracker=0, device="cuda"):
+    """A SdfLossScaleState in device memory as a (3,) int64 tensor (24 bytes, 8-byte aligned): scale, growth_tracker, inv_scale = 1 /
+    scale, found_inf = 0, skipped = 0.  `loss_scale_views(state)` names its members."""
+    import numpy as np
+    host = np.zeros(1, dtype=loss_scale_dtype())
+    host["scale"], host["growth_tracker"] = scale, growth_tracker
+    host["inv_scale"] = np.float32(1.0 / np.float64(host["scale"][0]))
+    return torch.from_numpy(host.view(np.int64).copy()).to(device)
+
+
+def loss_scale_dtype():
+    """SdfLossScaleState as a numpy structured dtype."""
+    import numpy as np
+    dt = np.dtype([("scale", np.float32), ("growth_tracker", np.int32), ("inv_scale", np.float32), ("found_inf", np.int32),
+                   ("skipped", np.int64)], align=True)
+    assert dt.itemsize == C.sizeof(LossScaleState) and all(dt.fields[f][1] == getattr(LossScaleState, f).offset for f, _ in LossScaleState._fields_)
+    return dt
+
+
+def loss_scale_views(state):
+    """{member: one-element view} of a loss_scale_state tensor: scale / inv_scale float32, growth_tracker / found_inf int32, skipped int64."""
+    f, i = state.view(torch.float32), state.view(torch.int32)
+    return {"scale": f[0:1], "growth_tracker": i[1:2], "inv_scale": f[2:3], "found_inf": i[3:4], "skipped": state[2:3]}
+
+
+def loss_scale_read(state):
+    """One read-back of a loss_scale_state: {member: Python number}."""
+    host = state.cpu().numpy().view(loss_scale_dtype())[0]
+    return {k: host[k].item() for k in host.dtype.names}
+
+
+def _loss_scale_ptr(fn, state):
+    if not (torch.is_tensor(state) and state.dtype == torch.int64 and state.numel() == 3 and state.is_contiguous()):
+        raise SdfError(f"{fn}: state is a hip.loss_scale_state() tensor")
+    return _ptr(state, torch.int64)
+
+
+def grad_scale(flat, segments, coef, mask=None):
+    """flat[segment] *= coef[0] in place over every segment of a flat fp32 bucket whose mask byte is non-zero (sdf_grad_scale_inplace:
+    one launch; `coef` (1,) float32 and `mask` (n segments,) uint8 on the device, mask None: every segment) - what clip_grad_norm_
+    does to a running sum of gradients, the coefficient never leaving the device.  Nothing outside an active segment is touched."""
+    _flat_f32("grad_scale", "flat", flat)
+    if not isinstance(segments, GradSegments):
+        segments = GradSegments(segments, flat.device)
+    if _ptr(coef, torch.float32) is None or coef.numel() != 1:
+        raise SdfError("grad_scale: coef holds one float32 on the device")
+    if mask is not None and (_ptr(mask, torch.uint8) is None or mask.shape != (segments.n,) or not mask.is_contiguous()):
+        raise SdfError(f"grad_scale: mask is a contiguous ({segments.n},) uint8 tensor")
+    d = GradScaleDesc()
+    d.flat, d.n, d.seg_host, d.seg, d.nseg = flat.data_ptr(), flat.numel(), segments.host.ctypes.data, segments.dev.data_ptr(), segments.n
+    d.mask, d.coef = _ptr(mask), coef.data_ptr()
+    _note(bytes=int(segments.host[:, 1].sum()) * 8)
+    _check(lib().sdf_grad_scale_inplace(C.byref(d), _stream()), "sdf_grad_scale_inplace")
+    return flat
+
+
+def grad_clip_scale_coef(table, max_norm, state, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, mask=None, coef=None,
+                         record=None, clip_unscaled=False, update=True):
+    """grad_clip_coef and the loss scaler in one launch of one workgroup (sdf_grad_clip_scale_coef): coef and record as grad_clip_coef
+    gives them - with `clip_unscaled` the norm is divided by the scale first, the textbook order - and in `state`
+    (hip.loss_scale_state) found_inf = a non-finite gradient was counted, inv_scale = 1 / the scale these gradients carry, skipped +=
+    found_inf, and then torch's _amp_update_scale_ with the two factors taken as fp32 (`update` False: scale and tracker stay).
+    Returns (coef, record)."""
+    _ptr(table, torch.float64)
+    if table.dim() != 2 or table.shape[1] != len(GRAD_STATS_FIELDS) or not table.is_contiguous():
+        raise SdfError(f"grad_clip_scale_coef: table must be a contiguous (rows, {len(GRAD_STATS_FIELDS)}) float64 tensor")
+    dev = table.device
+    if mask is not None and (_ptr(mask, torch.uint8) is None or mask.shape != (table.shape[0],) or not mask.is_contiguous()):
+        raise SdfError(f"grad_clip_scale_coef: mask is a contiguous ({table.shape[0]},) uint8 tensor")
+    coef = torch.empty(1, dtype=torch.float32, device=dev) if coef is None else coef
+    record = torch.empty(2, dtype=torch.float64, device=dev) if record is None else record
+    if coef.numel() != 1 or record.numel() != 2:
+        raise SdfError("grad_clip_scale_coef: coef holds one float32 and record two float64")
+    d = GradClipScaleDesc()
+    d.table, d.rows, d.mask, d.max_norm = table.data_ptr(), table.shape[0], _ptr(mask), float(max_norm)
+    d.coef, d.record, d.state = _ptr(coef, torch.float32), _ptr(record, torch.float64), _loss_scale_ptr("grad_clip_scale_coef", state)
+    d.growth_factor, d.backoff_factor, d.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+    d.clip_unscaled, d.update = int(bool(clip_unscaled)), int(bool(update))
+    _check(lib().sdf_grad_clip_scale_coef(C.byref(d), _stream()), "sdf_grad_clip_scale_coef")
+    return coef, record
+
+
+def adamw_step_scaled(grad, exp_avg, exp_avg_sq, rows, state, rows_dev=None, coef=None):
+    """adamw_step under a loss scaler (sdf_adamw_step_scaled: one launch): with state.found_inf set no parameter and no moment is
+    written; otherwise the update runs on (grad * coef) * state.inv_scale.  `state`: hip.loss_scale_state, as grad_clip_scale_coef
+    left it.  The other arguments are adamw_step's."""
+    for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        _flat_f32("adamw_step_scaled", name, t)
+    if exp_avg.numel() != grad.numel() or exp_avg_sq.numel() != grad.numel():
+        raise SdfError("adamw_step_scaled: the moments mirror the gradient bucket")
+    if rows.dtype.itemsize != C.sizeof(AdamwRow) or not rows.flags["C_CONTIGUOUS"]:
+        raise SdfError("adamw_step_scaled: rows is an adamw_rows() table")
+    sp = _loss_scale_ptr("adamw_step_scaled", state)
+    if rows_dev is None:
+        rows_dev = torch.from_numpy(rows.view("uint8")).to(grad.device)
+    if _ptr(rows_dev, torch.uint8) is None or rows_dev.numel() < rows.nbytes or not rows_dev.is_contiguous():
+        raise SdfError("adamw_step_scaled: rows_dev holds the bytes of rows on the device")
+    d = AdamwDesc()
+    d.grad, d.exp_avg, d.exp_avg_sq, d.n = grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), grad.numel()
+    d.rows_host, d.rows, d.nseg, d.coef = rows.ctypes.data, rows_dev.data_ptr(), len(rows), _ptr(coef, torch.float32)
+    _note(bytes=int(rows["length"][rows["active"] != 0].sum()) * 28)
+    _check(lib().sdf_adamw_step_scaled(C.byref(d), C.cast(C.c_void_p(sp), C.POINTER(LossScaleState)), _stream()), "sdf_adamw_step_scaled")
 
 
 _FI_WS, _EI_Q = {}, {}

@@ -9,7 +9,9 @@ weight gradient of the MS_ResBlock convolutions (`autograd.Conv3x3HipFunction`: 
 The other dense products - the convolutions' dX, the remaining convolutions' forward and dW - are library work through torch on the
 same stream (MIOpen); their replacements are the next row.  Behind the backward pass, with a `BucketAdamW`: the per-parameter gradient
 statistics (`vis.store_grads`), the clip coefficient and the AdamW update on the flat buckets (csrc/grad_step.hip), without a host
-synchronisation; with any other optimiser torch's clip_grad_norm_ and step.  Nothing here touches `oracle/`, and CPU
+synchronisation - also under fp16 autocast with a `LossScaler` (torch.amp.GradScaler's arithmetic on the device: a step with a
+non-finite gradient is skipped by the kernels) and with gradient accumulation (`num_acc`: the running sum is clipped in place);
+with any other optimiser torch's clip_grad_norm_ and step.  Nothing here touches `oracle/`, and CPU
 tensors are refused by the neuron kernels (`SdfError`).
 
 Reference semantics mirrored (file:line under /root/reference):
@@ -466,6 +468,8 @@ class GradientBuckets:
         self._dist, self._world = None, 1
         self._pending = [len(b) for b in self.buckets]
         self._seen, self._works, self._launched = set(), [], set()
+        self._seen_sum = set()                                          # ... over the micro-steps of a running sum (begin(zero=False))
+        self.accumulating = False                                       # train_step: the buckets hold a running sum the next call keeps
         self.log = []                                                   # (event, bucket index, hooks fired so far): test hook
         self.stats = None                                               # BucketStats, made by its first user (bucket_stats)
 
@@ -473,9 +477,13 @@ class GradientBuckets:
         for buf in self.flat:
             buf.zero_()
 
-    def begin(self, dist=None, world=1):
-        """Start of a step: zero the buckets, re-attach the `.grad` views, arm the hooks."""
-        self.zero()
+    def begin(self, dist=None, world=1, zero=True):
+        """Start of a step: zero the buckets, re-attach the `.grad` views, arm the hooks.  `zero=False` (gradient accumulation) keeps the
+        running sum: the views are re-attached and the hooks re-armed, and a parameter counts as having a gradient if any
+        micro-step since the last zeroing gave it one."""
+        if zero:
+            self.zero()
+            self._seen_sum = set()
         if self.stats is not None:
             self.stats.valid = self.stats.clipped = False
         for p, v in self._views.items():
@@ -512,8 +520,9 @@ class GradientBuckets:
         if self._dist is not None:
             for buf in self.flat:
                 buf.div_(self._world)
+        self._seen_sum |= self._seen
         for p in self.params:
-            if id(p) not in self._seen:
+            if id(p) not in self._seen_sum:
                 p.grad = None
         self._works = []
 
@@ -555,21 +564,33 @@ class BucketStats:
         self.mask, self._mask_key = torch.ones(n, dtype=torch.uint8, device=dev), None
         self.lengths = [p.numel() for p in self.params]
         self.valid = self.clipped = False
+        self.scaled = False                                             # the last clip() ran with a loss scaler
 
     def compute(self):
         for flat, seg, row0 in zip(self.flat, self.segments, self.row0):
             hip.grad_stats(flat, seg, self.table, row0)
         self.valid, self.clipped = True, False
 
-    def clip(self, max_norm, active=None):
-        """The clip coefficient over the rows with active[r] (None: all) into `coef`; max_norm None = inf: coef 1, the norm is recorded."""
+    def clip(self, max_norm, active=None, scaler=None, clip_unscaled=False):
+        """The clip coefficient over the rows with active[r] (None: all) into `coef`; max_norm None = inf: coef 1, the norm is recorded.
+        With a `scaler` (LossScaler) the same launch also gives the verdict on the step and updates the scale (hip.grad_clip_scale_coef)."""
         key = None if active is None else bytes(bytearray(int(bool(a)) for a in active))           # (a few hundred rows)
         if key != self._mask_key:
             host = torch.ones(len(self.params), dtype=torch.uint8) if key is None else torch.frombuffer(bytearray(key), dtype=torch.uint8)
             self.mask.copy_(host.pin_memory(), non_blocking=True)
             self._mask_key = key
-        hip.grad_clip_coef(self.table, float("inf") if max_norm is None else max_norm, self.mask, self.coef, self.record)
-        self.clipped = True
+        if scaler is None:
+            hip.grad_clip_coef(self.table, float("inf") if max_norm is None else max_norm, self.mask, self.coef, self.record)
+        else:
+            hip.grad_clip_scale_coef(self.table, float("inf") if max_norm is None else max_norm, scaler.state, scaler.growth_factor,
+                                     scaler.backoff_factor, scaler.growth_interval, self.mask, self.coef, self.record,
+                                     clip_unscaled=clip_unscaled, update=scaler.enabled)
+        self.clipped, self.scaled = True, scaler is not None
+
+    def scale_inplace(self):
+        """flat *= coef over the rows of the last clip(): clip_grad_norm_'s in-place pass (one launch per bucket)."""
+        for flat, seg, row0 in zip(self.flat, self.segments, self.row0):
+            hip.grad_scale(flat, seg, self.coef, self.mask[row0:row0 + seg.n])
 
     def read(self):
         """ONE read-back: (table (n, 5) float64 numpy, [total norm, non-finite count], coef)."""
@@ -632,6 +653,80 @@ def adamw_restatement(p, g, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, weight
     return p + nstep * m / (np.sqrt(v) / bc2s + eps), m, v
 
 
+def loss_scale_restatement(scale, growth_tracker, found_inf, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+    """numpy restatement of the scale update of sdf_grad_clip_scale_coef - torch's _amp_update_scale_ with the scale and both factors as
+    fp32: (scale, growth_tracker) after a step whose gradients were (`found_inf`) or were not all finite."""
+    import numpy as np
+    scale = np.float32(scale)
+    if found_inf:
+        return float(scale * np.float32(backoff_factor)), 0
+    if growth_tracker + 1 == growth_interval:
+        with np.errstate(over="ignore"):
+            grown = scale * np.float32(growth_factor)
+        return float(grown if np.isfinite(grown) else scale), 0
+    return float(scale), growth_tracker + 1
+
+
+class LossScaler:
+    """torch.amp.GradScaler's dynamic loss scale as a device-resident SdfLossScaleState (csrc/grad_step.hip): `scale(loss)` multiplies
+    by the device scalar, `BucketAdamW.step(..., scaler=this)` finds non-finite gradients, skips the update, divides the scale out
+    and grows or backs the scale off - all in the kernels, without the host waiting for the verdict.  `get_scale()` and `skipped`
+    (steps skipped since construction) are host reads.  `state_dict()` / `load_state_dict()` carry exactly GradScaler's keys and
+    interchange with it.  `enabled=False`: the scale is 1 and stays 1; only the skip of a non-finite step remains."""
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True, device="cuda"):
+        if not (growth_factor > 1.0 and 0.0 < backoff_factor < 1.0 and int(growth_interval) >= 1 and init_scale > 0.0):
+            raise ValueError(f"LossScaler: init_scale {init_scale}, growth_factor {growth_factor} (> 1), backoff_factor {backoff_factor} "
+                             f"(in (0, 1)), growth_interval {growth_interval} (>= 1)")
+        self.enabled = bool(enabled)
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self.device = torch.device(device)
+        self._pending = []                                              # reconciliations of steps whose verdict the host has not read
+        self._set(float(init_scale) if self.enabled else 1.0, 0)
+
+    def _set(self, scale, tracker, skipped=0):
+        self.state = hip.loss_scale_state(scale, tracker, self.device)
+        self._views = hip.loss_scale_views(self.state)
+        self._views["skipped"].fill_(int(skipped))
+        self._scale = self._views["scale"][0]                           # a 0-dim view: what a loss is multiplied by
+
+    def scale(self, loss):
+        """loss * scale, the scale read on the device (no synchronisation); the loss itself when not enabled."""
+        return loss * self._scale if self.enabled else loss
+
+    def reconcile(self):
+        """Read the verdicts of the steps taken so far (BucketAdamW rolls the host's step counts of a skipped one back)."""
+        pending, self._pending = self._pending, []
+        for fn in pending:
+            fn()
+
+    def get_scale(self):
+        return float(self._scale)
+
+    @property
+    def skipped(self):
+        self.reconcile()
+        return int(self._views["skipped"])
+
+    def state_dict(self):
+        """torch.amp.GradScaler.state_dict()'s keys and values; {} when not enabled, as GradScaler's."""
+        if not self.enabled:
+            return {}
+        host = hip.loss_scale_read(self.state)
+        return {"scale": host["scale"], "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": host["growth_tracker"]}
+
+    def load_state_dict(self, state_dict):
+        if not self.enabled:
+            return
+        if len(state_dict) == 0:
+            raise RuntimeError("LossScaler.load_state_dict: the state dict is empty - it was saved from a disabled scaler")
+        self.reconcile()
+        self.growth_factor, self.backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self.growth_interval = int(state_dict["growth_interval"])
+        self._set(float(state_dict["scale"]), int(state_dict["_growth_tracker"]), int(self._views["skipped"]))
+
+
 class BucketAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW (decoupled weight decay; no amsgrad, no maximize, one param group) on a GradientBuckets' flat buffers: the
     moments are two flat buffers per bucket with the buckets' layout - `state[p]["exp_avg"]` / `["exp_avg_sq"]` are views into them,
@@ -639,7 +734,13 @@ class BucketAdamW(torch.optim.Optimizer):
     csrc/grad_step.hip, on the current stream, without a host synchronisation: the update reads the coefficient from device memory.
     The gradients themselves are NOT scaled in place (clip_grad_norm_ does); `get_grads` scales what it reports.  A parameter whose
     `.grad` is None (GradientBuckets.finish) is not touched - not its value, its moments or its step count - as in torch.
-    `state_dict()` / `load_state_dict()` interchange with torch.optim.AdamW over the same parameters."""
+    `state_dict()` / `load_state_dict()` interchange with torch.optim.AdamW over the same parameters.
+    `step(clip_grad, scaler=LossScaler)`: the same number of launches, the coefficient kernel also deciding whether the step is off
+    (a non-finite gradient) and the update obeying it: a skipped step writes no parameter and no moment.  The host does not wait for
+    that verdict: it counts the step, copies the verdict into a pinned slot behind the launches and reads the slot at the start of
+    the next step() (or in state_dict() / LossScaler.skipped), rolling the counts of a skipped step back before they are used again.
+    The clip bounds the STILL-SCALED norm unless `clip_unscaled` (a loop that calls clip_grad_norm_ without scaler.unscale_ does the
+    former)."""
 
     def __init__(self, buckets, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         if not isinstance(buckets, GradientBuckets):
@@ -658,6 +759,8 @@ class BucketAdamW(torch.optim.Optimizer):
         self.exp_avg_sq = [torch.zeros_like(f) for f in buckets.flat]
         self._rows = hip.adamw_rows(len(self.stats.params))
         self._rows_dev = torch.zeros(self._rows.nbytes, dtype=torch.uint8, device=buckets.flat[0].device)
+        self._slot = self._event = None
+        self._verdict = None                                            # (pinned found_inf, event, rows counted) of a scaled step not yet read
         self._views = {}
         for bi, (b, seg) in enumerate(zip(buckets.buckets, self.stats.segments)):
             for p, (off, n) in zip(b, seg.host.tolist()):
@@ -678,6 +781,7 @@ class BucketAdamW(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         """torch's loading, then the loaded moments are copied INTO the flat views (which stay the state); a parameter the loaded
         state does not know starts from zero."""
+        self._reconcile()
         super().load_state_dict(state_dict)
         if len(self.param_groups) != 1:
             raise ValueError("BucketAdamW: one param group")
@@ -693,9 +797,26 @@ class BucketAdamW(torch.optim.Optimizer):
                 v.zero_()
         self._attach(steps)
 
+    def _reconcile(self):
+        """The verdict of the last scaled step, if the host has not read it yet: a skipped step did not happen - its rows' counts go back."""
+        if self._verdict is None:
+            return
+        (slot, event, act), self._verdict = self._verdict, None
+        event.synchronize()
+        if slot.numpy()[0] != 0:
+            torch._foreach_sub_([t for t, a in zip(self._step_t, act) if a], 1)
+            self._k[act] -= 1
+
+    def state_dict(self):
+        self._reconcile()
+        return super().state_dict()
+
     @torch.no_grad()
-    def step(self, clip_grad=None, closure=None):
+    def step(self, clip_grad=None, closure=None, scaler=None, clip_unscaled=False):
         import numpy as np
+        if scaler is not None and not (isinstance(scaler, LossScaler) and scaler.state.is_cuda):
+            raise hip.SdfError("BucketAdamW.step: scaler is a train.LossScaler whose state lives on the GPU (no CPU fallback)")
+        self._reconcile()
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -707,7 +828,7 @@ class BucketAdamW(torch.optim.Optimizer):
         st, rows = self.stats, self._rows
         act = np.fromiter((p.grad is not None for p in st.params), dtype=bool, count=len(st.params))
         st.compute()
-        st.clip(clip_grad, act)
+        st.clip(clip_grad, act, scaler, clip_unscaled)
         if not act.any():
             return loss
         updated = [p for p, a in zip(st.params, act) if a]
@@ -723,29 +844,48 @@ class BucketAdamW(torch.optim.Optimizer):
         self._rows_dev.copy_(torch.from_numpy(rows.view("uint8")).pin_memory(), non_blocking=True)
         for bi, n in enumerate(len(b) for b in self.buckets.buckets):
             r0 = st.row0[bi]
-            if act[r0:r0 + n].any():
+            if not act[r0:r0 + n].any():
+                continue
+            if scaler is None:
                 hip.adamw_step(self.buckets.flat[bi], self.exp_avg[bi], self.exp_avg_sq[bi], rows[r0:r0 + n],
                                self._rows_dev[r0 * rows.itemsize:(r0 + n) * rows.itemsize], st.coef)
+            else:
+                hip.adamw_step_scaled(self.buckets.flat[bi], self.exp_avg[bi], self.exp_avg_sq[bi], rows[r0:r0 + n], scaler.state,
+                                      self._rows_dev[r0 * rows.itemsize:(r0 + n) * rows.itemsize], st.coef)
+        if scaler is not None:                                          # the verdict follows the launches; nobody waits for it here
+            if self._slot is None:
+                self._slot, self._event = torch.zeros(1, dtype=torch.int32).pin_memory(), torch.cuda.Event()
+            self._slot.copy_(scaler._views["found_inf"], non_blocking=True)
+            self._event.record()
+            self._verdict = (self._slot, self._event, act)
+            if self._reconcile not in scaler._pending:
+                scaler._pending.append(self._reconcile)
         # the kernel wrote through raw pointers: move the version counters, which the packed inference weights are keyed on
         torch.autograd.graph.increment_version(updated)
         return loss
 
 
-def get_grads(model, buckets, coef=None, missing="skip"):
+def get_grads(model, buckets, coef=None, missing="skip", unscale=False, scaler=None):
     """The reference's `vis.store_grads` record (utils/gradients.py get_grads, taken after the clip): {name}_mean / _min / _max of
     |grad| of every `requires_grad` parameter with "weight" in its name, from the buckets' statistics table with ONE read-back
     instead of three `.item()` per parameter.  The statistics are those of this step (computed here unless BucketAdamW.step already
     did).  `coef`: what the clip multiplied the gradients by - None: the coefficient of this step's BucketAdamW.step, 1 without one.
     A parameter holding a non-finite gradient records NaN.  A parameter without a gradient: `missing="skip"` leaves it out,
-    "raise" is the reference's AttributeError."""
+    "raise" is the reference's AttributeError.  Under a loss scaler the record is, as the reference's, of the STILL-SCALED gradients;
+    `unscale=True` with the `scaler` divides the scale these gradients carry out (one more host read)."""
     import math
     if missing not in ("skip", "raise"):
         raise ValueError('get_grads: missing is "skip" or "raise"')
+    if unscale and scaler is None:
+        raise ValueError("get_grads: unscale=True divides by a loss scale - pass scaler=")
     st = bucket_stats(buckets)
     if not st.valid:
         st.compute()
     table, _, dev_coef = st.read()
     c = float(coef) if coef is not None else dev_coef if st.clipped else 1.0
+    if unscale:                                                         # (a scaled clip has moved `scale` on; it left the reciprocal of the old one)
+        ls = hip.loss_scale_read(scaler.state)
+        c *= ls["inv_scale"] if st.scaled else 1.0 / ls["scale"]
     record = {}
     for name, p in model.named_parameters():
         if not (p.requires_grad and "weight" in name):
@@ -780,7 +920,7 @@ def save_grads_csv(records, path):
 
 
 def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, world=1, clip_grad=100.0, flow_scaling=1.0,
-               lambda_mod=1.0, amp=False, forward_fn=None, grads_out=None):
+               lambda_mod=1.0, amp=False, forward_fn=None, grads_out=None, scaler=None, num_acc=1, step_now=True, clip_unscaled=False):
     """One step of train_flow_parallel_supervised_SNN.py's loop body (:233-336) on this rank's shard of the batch; returns the
     loss tensor (this rank's samples' mean of err / n_global; the mean over ranks is the gathered-batch loss).
     `amp`: the reference trains under `torch.cuda.amp.autocast` with fp16 + GradScaler (`optimizer.use_amp: true`,
@@ -792,25 +932,50 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
     --plumbing: everything else in this function is the code the GPU ranks run).
     With a `BucketAdamW` the tail behind the backward pass - clip and update - is `optimizer.step(clip_grad)` on csrc/grad_step.hip;
     with any other optimiser it is torch's, as before.  `grads_out`, a list: the reference's `vis.store_grads` - one `get_grads`
-    record of the clipped gradients is appended per step (needs `buckets`)."""
+    record of the clipped gradients is appended per step (needs `buckets`).
+    `amp`: False, True or "bf16" (bf16 autocast, no scaler needed), or "fp16" - the reference's numerics: fp16 autocast with a
+    `scaler` (LossScaler; the loss is multiplied by its device scalar, the step's tail finds non-finite gradients, skips the update and
+    moves the scale, see BucketAdamW.step).  As in the reference's loop the clip bounds the still-scaled norm; `clip_unscaled=True`
+    is the textbook order (unscale, then clip - once, at the step).  `num_acc > 1`: the reference's gradient accumulation - the loss
+    is divided by num_acc, a call with `step_now=False` adds its gradients to the running sum in the buckets and clips that sum IN
+    PLACE (statistics, coefficient, hip.grad_scale), and the call with `step_now=True` steps; the call after it zeroes the buckets.
+    The caller decides: step_now = (sample + 1) % num_acc == 0 or sample + 1 == len(loader).  The returned loss is the divided,
+    unscaled one."""
     if isinstance(optimizer, BucketAdamW) and buckets is not optimizer.buckets:
         raise ValueError("train_step: a BucketAdamW steps on its GradientBuckets - pass them as buckets=")
     if grads_out is not None and buckets is None:
         raise ValueError("train_step: grads_out takes the statistics from the gradient buckets - pass buckets=")
+    if amp not in (False, True, "bf16", "fp16"):
+        raise ValueError(f'train_step: amp is False, True, "bf16" or "fp16", got {amp!r}')
+    num_acc = int(num_acc)
+    if num_acc < 1:
+        raise ValueError(f"train_step: num_acc {num_acc}; it counts the micro-steps of one update (>= 1)")
+    if (scaler is not None or num_acc > 1 or not step_now) and not isinstance(optimizer, BucketAdamW):
+        raise NotImplementedError("train_step: a loss scaler and gradient accumulation live in the HIP tail of the step - use "
+                                  "train.BucketAdamW over train.GradientBuckets as the optimiser (a scaler for the stock optimisers "
+                                  "is not built)")
+    if scaler is not None and not isinstance(scaler, LossScaler):
+        raise TypeError("train_step: scaler is a train.LossScaler (load a torch.amp.GradScaler's state_dict() into one)")
+    if (num_acc > 1 or not step_now) and dist is not None and world > 1:
+        raise NotImplementedError("train_step: num_acc > 1 with world > 1 is not built - the bucket all-reduce would sum running sums; "
+                                  "accumulate on one rank, or raise the per-rank batch instead")
+    if amp == "fp16" and scaler is None:
+        raise ValueError('train_step: amp="fp16" needs a loss scaler - pass scaler=train.LossScaler(), or use amp="bf16"')
     from .spikingjelly_compat import functional
     from .STSwinNet.STSwinNet import STTFlowNet
     from .STSwinNet_SNN.Spiking_STSwinNet import SpikingformerFlowNet
     ann = isinstance(model, STTFlowNet)             # the ANN family (train_flow_parallel_supervised.py): model(voxel, cnt)["flow"]
     if ann and amp:
-        raise NotImplementedError("the ANN model trains in fp32 (configs/train_DSEC_supervised_STT_voxel.yml: use_amp False)")
+        raise NotImplementedError("the ANN model trains in fp32 (configs/train_DSEC_supervised_STT_voxel.yml: use_amp False) - "
+                                  "pass amp=False; fp16 for STTFlowNet is not built")
     model.train()
     if not ann:
         functional.reset_net(model)
     if buckets is not None:
-        buckets.begin(dist, world)
+        buckets.begin(dist, world, zero=not buckets.accumulating)
     else:
         optimizer.zero_grad(set_to_none=True)
-    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+    with torch.autocast("cuda", dtype=torch.float16 if amp == "fp16" else torch.bfloat16, enabled=bool(amp)):
         if forward_fn is not None:
             flows = forward_fn(model, chunk)
         elif ann:
@@ -822,11 +987,25 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
     n_valid = global_valid_count(mask, dist, world)
     # local mean over B_local of err_i / n_global, times 1 / world from the gradient average = the gathered-batch mean
     loss = flow_loss_supervised([f.float() for f in flows], label, mask, flow_scaling, lambda_mod, n_valid=n_valid)
-    loss.backward()                                                  # bucket all-reduces leave from the grad-ready hooks
+    if num_acc > 1:
+        loss = loss / num_acc
+    (loss if scaler is None else scaler.scale(loss)).backward()      # bucket all-reduces leave from the grad-ready hooks
     if buckets is not None:
         buckets.finish()
     if isinstance(optimizer, BucketAdamW):
-        optimizer.step(clip_grad)
+        buckets.accumulating = not step_now
+        if not step_now:                                             # the reference's clip of the running sum, in place; nothing is zeroed
+            st = optimizer.stats
+            clip_sum = clip_grad is not None and not clip_unscaled   # (the textbook order clips once, at the step)
+            if clip_sum or grads_out is not None:
+                st.compute()
+            if clip_sum:
+                st.clip(clip_grad, [p.grad is not None for p in st.params])
+                st.scale_inplace()
+        elif scaler is None:
+            optimizer.step(clip_grad)
+        else:
+            optimizer.step(clip_grad, scaler=scaler, clip_unscaled=clip_unscaled)
         if grads_out is not None:
             grads_out.append(get_grads(model, buckets))
         return loss.detach()
