@@ -1180,6 +1180,52 @@ int64_t sdf_flow_metrics_workspace_bytes(int B, int H, int W);
 int sdf_flow_metrics_fwd(const SdfFlowMetricsDesc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A loader item -> the training step's (input, label, mask): the reference loops' Compose([RandomCrop, Random_horizontal_flip,
+ * Random_vertical_flip, Random_event_drop]) (DSEC_dataloader/data_augmentation.py) followed by the preparation below
+ * (train_flow_parallel_supervised_SNN.py:241-308), with the random decisions drawn by the caller and every operation IEEE fp32: the
+ * outputs equal the torch composition bit for bit.  Added to SDF_VERSION 107 (no existing entry changed).
+ * voxel (B, bins, Hs, Ws) fp32 signed; label (B, 2, Hs, Ws) fp32 and valid (B, 1, Hs, Ws) fp32 or, with valid_is_u8, one byte per
+ * element - each may be NULL together with its output.  Per sample b (host arrays, B <= SDF_AUGMENT_MAX_B entries used): the window
+ * origin oy[b], ox[b] of the (crop_h, crop_w) window (0, 0: the whole volume, origins 0); flags[b] bit 0 horizontal, bit 1 vertical
+ * flip; drop_q[b], negative = no drop.  Order: crop, flips, drop, preparation.
+ *   output pixel (y, x) reads the source at (oy + (vflip ? h-1-y : y), ox + (hflip ? w-1-x : x));
+ *   label_out (B, 2, h, w): the gathered flow, its x component negated under a horizontal, its y component under a vertical flip;
+ *   mask_out (B, 1, h, w) fp32: the gathered valid != 0 as 0.f / 1.f;
+ *   drop: v = v * (u > q ? 1.f : 0.f), u = drop_u[cell] when drop_u (B, bins, h, w; output coordinates) is given, else Philox4x32-10
+ *     at the cell's linear index i in (B, bins, h, w): key = seed, counter = {i >> 2 (two words), offset (two words)}, the word taken is
+ *     number i & 3, u = (word >> 8) * 2^-24;
+ *   out (B, bins, 2, h, w) = relu(v) | relu(-v), then norm / per_sample / use_spike_th / event_mask as SdfPrepareChunkDesc;
+ *   mask_events: mask_out is multiplied by the event mask (the loops' mask * event_mask, metrics.mask_events).
+ * Launches: [clear the min / max pairs] | gather + split | [finish]; nothing is allocated, nothing waits for the host.
+ * workspace: sdf_augment_chunk_workspace_bytes(B) bytes, 8-byte aligned (0: refused B).
+ * SDF_E_SHAPE: B outside 1 .. SDF_AUGMENT_MAX_B, a dimension < 1, half a crop, a crop larger than the volume, an origin outside
+ * [0, Hs - h] x [0, Ws - w] (checked for every sample before anything is launched), a short workspace; SDF_E_DTYPE: norm outside 0 | 1,
+ * a flags word with other bits; SDF_E_NULL: d, voxel, out or workspace NULL, label / valid without its output or the reverse,
+ * mask_events without mask_out; SDF_E_ALIGN: an fp32 pointer not 4-byte or the workspace not 8-byte aligned. */
+#define SDF_AUGMENT_MAX_B 64
+
+typedef struct SdfAugmentChunkDesc {
+  const float* voxel;
+  const float* label;
+  const void* valid;
+  const float* drop_u;
+  float* out;
+  float* label_out;
+  float* mask_out;
+  float* event_mask;
+  void* workspace;
+  int64_t workspace_bytes, seed, offset;
+  int32_t B, bins, Hs, Ws, crop_h, crop_w;
+  int32_t valid_is_u8, norm, per_sample, use_spike_th, mask_events;
+  float spike_th;
+  int32_t oy[64], ox[64], flags[64];
+  float drop_q[64];
+} SdfAugmentChunkDesc;
+
+int64_t sdf_augment_chunk_workspace_bytes(int B);
+int sdf_augment_chunk_fwd(const SdfAugmentChunkDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Signed voxel volume -> the model's input: harness.prepare_chunk(center_crop(voxel, crop), norm_input, spike_th, polarity=True)
  * (reference eval_DSEC_flow_SNN.py:179-217) with every decision on the device; the output equals the torch composition bit for bit.
  * voxel (B, bins, Hs, Ws) fp32 -> out (B, bins, 2, h, w) = relu(v) | relu(-v) on the window (crop_h, crop_w) at (crop_oy, crop_ox)

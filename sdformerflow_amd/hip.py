@@ -282,6 +282,19 @@ class PrepareChunkDesc(C.Structure):
                 ("per_sample", C.c_int32), ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
 
 
+AUGMENT_MAX_B = 64                       # SDF_AUGMENT_MAX_B
+
+
+class AugmentChunkDesc(C.Structure):
+    _fields_ = [("voxel", C.c_void_p), ("label", C.c_void_p), ("valid", C.c_void_p), ("drop_u", C.c_void_p), ("out", C.c_void_p),
+                ("label_out", C.c_void_p), ("mask_out", C.c_void_p), ("event_mask", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("seed", C.c_int64), ("offset", C.c_int64),
+                ("B", C.c_int32), ("bins", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32),
+                ("valid_is_u8", C.c_int32), ("norm", C.c_int32), ("per_sample", C.c_int32), ("use_spike_th", C.c_int32),
+                ("mask_events", C.c_int32), ("spike_th", C.c_float),
+                ("oy", C.c_int32 * 64), ("ox", C.c_int32 * 64), ("flags", C.c_int32 * 64), ("drop_q", C.c_float * 64)]
+
+
 class FlowImageDesc(C.Structure):
     _fields_ = [("flow", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_int64), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
@@ -410,6 +423,7 @@ SIGNATURES = {
     "sdf_event_voxel_tb_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i, _i, _i, _i)),
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
     "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
+    "sdf_augment_chunk_workspace_bytes": (_i64, (_i,)), "sdf_augment_chunk_fwd": (_i, (_P(AugmentChunkDesc), _p)),
     "sdf_prepare_chunk_workspace_bytes": (_i64, (_i,)), "sdf_prepare_chunk_fwd": (_i, (_P(PrepareChunkDesc), _p)),
     "sdf_flow_image_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_image_fwd": (_i, (_P(FlowImageDesc), _p)),
     "sdf_flow_submission_fwd": (_i, (_P(FlowSubmissionDesc), _p)), "sdf_event_image_fwd": (_i, (_P(EventImageDesc), _p)),
@@ -2334,6 +2348,96 @@ def prepare_chunk(voxel, crop=None, norm_input="minmax", spike_th=None, per_samp
     _note(bytes=B * bins * h * w * 4 * (1 + 2 + 4 * (norm == 1 or spike_th is not None)), shape=shape)
     _check(lib().sdf_prepare_chunk_fwd(C.byref(d), _stream()), "sdf_prepare_chunk_fwd")
     return out
+
+
+def _per_sample(fn, name, value, B, width):
+    """`value` - one entry for every sample or a sequence of B - as a list of B entries (`width` > 1: each a tuple of that many)."""
+    one = not isinstance(value, (list, tuple)) or (width > 1 and len(value) == width and not isinstance(value[0], (list, tuple)))
+    rows = [value] * B if one else list(value)
+    if len(rows) != B or (width > 1 and any(not isinstance(r, (list, tuple)) or len(r) != width for r in rows)):
+        raise SdfError(f"{fn}: {name} is one entry or {B} of them (one per sample), got {value!r}")
+    return rows
+
+
+def augment_chunk(voxel, label, valid, crop, origins, flips, drop_q=None, drop_u=None, seed=0, offset=0, norm_input="minmax",
+                  spike_th=None, per_sample=False, mask_events=False, out=None, label_out=None, mask_out=None, event_mask=None):
+    """A loader item -> the training step's (input, label, mask) on the GPU without a host round trip (sdf_augment_chunk_fwd): the
+    reference loops' crop, flips and event drop (DSEC_dataloader.data_augmentation), then harness.prepare_chunk and, with `mask_events`,
+    mask * event_mask - bit for bit what that composition gives.  voxel (B, bins, Hs, Ws) fp32 signed; label (B, 2, Hs, Ws) fp32 and valid
+    (B, 1, Hs, Ws) or (B, Hs, Ws), fp32 / uint8 / bool - either may be None, and so is its output.  `crop` (h, w) or None (the whole
+    volume); `origins` one (oy, ox) or B of them; `flips` one flag word or B (bit 0 horizontal, bit 1 vertical); `drop_q` None, one
+    value or B (None / negative: that sample keeps its events).  A dropped sample takes its uniform field from `drop_u` (B, bins, h, w)
+    fp32 in output coordinates when given, else from the kernel's Philox4x32-10 keyed by `seed` at `offset` (64-bit each; the same pair
+    gives the same field, a caller advances `offset` per step).  norm_input / spike_th / per_sample / event_mask as hip.prepare_chunk.
+    Returns (out (B, bins, 2, h, w), label_out (B, 2, h, w) or None, mask_out (B, 1, h, w) fp32 or None); `out`, `label_out`,
+    `mask_out`: contiguous tensors of those shapes to write into."""
+    _ptr(voxel, torch.float32)
+    if voxel.dim() != 4:
+        raise SdfError(f"augment_chunk: voxel is (B, bins, H, W), got {tuple(voxel.shape)}")
+    voxel = voxel.contiguous()
+    B, bins, Hs, Ws = voxel.shape
+    if B > AUGMENT_MAX_B:
+        raise SdfError(f"augment_chunk: batch of {B} refused (at most {AUGMENT_MAX_B} per call)", rc=E_SHAPE)
+    h, w = crop if crop else (Hs, Ws)
+    dev = voxel.device
+    if label is not None:
+        _ptr(label, torch.float32)
+        if tuple(label.shape) != (B, 2, Hs, Ws):
+            raise SdfError(f"augment_chunk: label is {(B, 2, Hs, Ws)}, got {tuple(label.shape)}")
+        label = label.contiguous()
+    if valid is not None:
+        _ptr(valid)
+        if valid.numel() != B * Hs * Ws or tuple(valid.shape[-2:]) != (Hs, Ws):
+            raise SdfError(f"augment_chunk: valid is (B, H, W) or (B, 1, H, W) at the voxel's size, got {tuple(valid.shape)}")
+        if valid.dtype == torch.bool:
+            valid = valid.contiguous().view(torch.uint8)
+        elif valid.dtype not in (torch.float32, torch.uint8):
+            raise SdfError(f"augment_chunk: valid is fp32, uint8 or bool, got {valid.dtype}")
+        valid = valid.contiguous()
+    if drop_u is not None:
+        _ptr(drop_u, torch.float32)
+        if tuple(drop_u.shape) != (B, bins, h, w) or not drop_u.is_contiguous():
+            raise SdfError(f"augment_chunk: drop_u must be a contiguous {(B, bins, h, w)} tensor (output coordinates)")
+
+    def buffer(t, shape, name, wanted=True):
+        if not wanted:
+            if t is not None:
+                raise SdfError(f"augment_chunk: {name} given without its input")
+            return None
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise SdfError(f"augment_chunk: {name} must be a contiguous {shape} tensor")
+        return t
+    out = buffer(out, (B, bins, 2, h, w), "out")
+    label_out = buffer(label_out, (B, 2, h, w), "label_out", label is not None)
+    mask_out = buffer(mask_out, (B, 1, h, w), "mask_out", valid is not None)
+    if event_mask is not None and (tuple(event_mask.shape) != (B, 1, h, w) or not event_mask.is_contiguous()):
+        raise SdfError(f"augment_chunk: event_mask must be a contiguous {(B, 1, h, w)} tensor")
+    if mask_events and mask_out is None:
+        raise SdfError("augment_chunk: mask_events multiplies the valid mask - pass valid")
+    need = lib().sdf_augment_chunk_workspace_bytes(B)
+    if need <= 0:
+        raise SdfError(f"augment_chunk: batch of {B} refused", rc=E_SHAPE)
+    ws = _stream_ws(_PC_WS, dev, max(need, 256))
+    d = AugmentChunkDesc()
+    d.voxel, d.label, d.valid, d.drop_u = voxel.data_ptr(), _ptr(label), _ptr(valid), _ptr(drop_u)
+    d.out, d.label_out, d.mask_out = _ptr(out, torch.float32), _ptr(label_out, torch.float32), _ptr(mask_out, torch.float32)
+    d.event_mask, d.workspace, d.workspace_bytes = _ptr(event_mask, torch.float32), ws.data_ptr(), ws.numel()
+    d.seed, d.offset = (C.c_int64(int(v) & (2 ** 64 - 1)).value for v in (seed, offset))
+    d.B, d.bins, d.Hs, d.Ws, d.crop_h, d.crop_w = B, bins, Hs, Ws, (h if crop else 0), (w if crop else 0)
+    d.valid_is_u8 = int(valid is not None and valid.dtype == torch.uint8)
+    d.norm, d.per_sample = {None: 0, "minmax": 1}.get(norm_input, 2), int(bool(per_sample))   # (anything else is the library's to refuse)
+    d.use_spike_th, d.spike_th, d.mask_events = int(spike_th is not None), float(spike_th or 0.0), int(bool(mask_events))
+    qs = _per_sample("augment_chunk", "drop_q", drop_q, B, 1)
+    rows = zip(_per_sample("augment_chunk", "origins", origins, B, 2), _per_sample("augment_chunk", "flips", flips, B, 1), qs)
+    for b, ((oy, ox), f, q) in enumerate(rows):
+        d.oy[b], d.ox[b], d.flags[b], d.drop_q[b] = int(oy), int(ox), int(f), (-1.0 if q is None else float(q))
+    # the window read once (+ drop_u), input / label / mask written once, the finish's read-modify-write of the input
+    planes = bins * (3 + (drop_u is not None)) + 4 * (label is not None) + (valid is not None) + 4 * bins * (d.norm == 1 or spike_th is not None)
+    _note(bytes=B * h * w * (4 * planes + (valid.element_size() if valid is not None else 0)), shape=(B, bins, 2, h, w))
+    _check(lib().sdf_augment_chunk_fwd(C.byref(d), _stream()), "sdf_augment_chunk_fwd")
+    return out, label_out, mask_out
 
 
 def spike_count_form(spikes, t_dim):

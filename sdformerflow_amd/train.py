@@ -24,6 +24,8 @@ Reference semantics mirrored (file:line under /root/reference):
   DropPath                timm 0.6.13 `drop_path` (per-sample Bernoulli keep mask / keep_prob), SSA branch only (:840)
   loss                    loss/flow_supervised.py:80-105 (gamma None), :14-30
   step                    train_flow_parallel_supervised_SNN.py:233-336 (reset, forward, loss, backward, clip 100, AdamW)
+  loader item -> step     ...:155-171, :241-308 (crop, flips, drop, split, min-max, threshold, mask * event_mask): `prepare_train_item`
+                          on csrc/prepare_chunk.hip (hip.augment_chunk), `train_step_from_item`
   data parallelism        the reference wraps the model in DataParallel: replicas, local batch statistics, summed
                           gradients; here one process per GPU and ONE bucketed all-reduce(sum)/world per step (RCCL)
 """
@@ -1015,3 +1017,69 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
         grads_out.append(get_grads(model, buckets, coef=1.0))
     optimizer.step()
     return loss.detach()
+
+
+# ---------------------------------------------------------------------------------------------- from a loader item to the step
+def train_transform(config, finetune=False):
+    """The loops' `transform_train` (train_flow_parallel_supervised_SNN.py:155-171): RandomCrop(loader.crop) - not when fine-tuning -
+    then the two flips with loader.augment_prob[0] and [1]."""
+    from .DSEC_dataloader.data_augmentation import Compose, RandomCrop, Random_horizontal_flip, Random_vertical_flip
+    p = config["loader"]["augment_prob"]
+    crop = [] if finetune else [RandomCrop(tuple(config["loader"]["crop"]))]
+    return Compose(crop + [Random_horizontal_flip(p[0]), Random_vertical_flip(p[1])])
+
+
+def _item_transform(config, transform):
+    """`transform`, or for None the loops' `transform_valid`: CenterCrop(loader.crop) (nothing when the config has no crop)."""
+    from .DSEC_dataloader.data_augmentation import CenterCrop, Compose
+    if transform is not None:
+        return transform
+    crop = config["loader"].get("crop")
+    return Compose([CenterCrop(tuple(crop))] if crop else [])
+
+
+def prepare_train_item_torch(chunk, label, mask, config, transform, drop_u=None):
+    """The loop's own sequence in torch (train_flow_parallel_supervised_SNN.py:241-308): the transforms on (chunk, label, mask), the
+    polarity split / normalisation / threshold (harness.prepare_chunk) and, with metrics.mask_events, mask * event_mask.  What
+    `prepare_train_item` is compared with, and what serves the configurations its kernel does not.  `drop_u`: the drop's uniform field
+    in place of torch.rand_like.  Returns (x, label, mask (B, 1, h, w) fp32)."""
+    from . import harness
+    mask = mask.reshape(mask.shape[0], 1, *mask.shape[-2:]).float()
+    chunk, label, mask = _item_transform(config, transform)((chunk, label, mask), drop_u)
+    voxel = config["model"].get("encoding", "voxel") == "voxel"
+    polarity = bool(config["loader"].get("polarity", True))
+    if not voxel and polarity and chunk.dim() == 5:
+        chunk = chunk.reshape(chunk.shape[0], -1, *chunk.shape[3:])
+    x = harness.prepare_chunk(chunk, config["model"].get("norm_input"), config["data"].get("spike_th"), voxel and polarity)
+    mask = mask.float()
+    if config.get("metrics", {}).get("mask_events"):
+        mask = mask * x.reshape(x.shape[0], -1, *x.shape[-2:]).sum(1, keepdim=True).bool()
+    return x.contiguous(), label.contiguous(), mask.contiguous()
+
+
+def prepare_train_item(chunk, label, mask, config, transform, step=0):
+    """A loader item - signed voxel (B, bins, Hs, Ws), flow (B, 2, Hs, Ws), valid mask (B, Hs, Ws) or (B, 1, Hs, Ws), on the GPU - to
+    `train_step`'s (x, label, mask): `transform.sample` draws the batch's crop origin, flips and drop rate as the reference's Compose
+    does, and hip.augment_chunk (csrc/prepare_chunk.hip) applies them together with the loop's preparation in at most three launches,
+    without asking the host; bit for bit `prepare_train_item_torch` given the same uniform field.  `transform` None: the loops'
+    validation transform, CenterCrop(loader.crop).  Read from `config`: loader.crop (that case), model.norm_input, data.spike_th,
+    metrics.mask_events, and for the drop's Philox stream loader.seed as the key and `step` as the offset (pass the iteration count: a
+    step's field is then reproducible and no two steps share one).  `norm_input: std`, `loader.polarity: false` and the `cnt` encoding
+    run the torch sequence."""
+    norm = config["model"].get("norm_input")
+    if norm not in (None, "minmax") or not config["loader"].get("polarity", True) or config["model"].get("encoding", "voxel") != "voxel":
+        return prepare_train_item_torch(chunk, label, mask, config, transform)
+    B = chunk.shape[0]
+    p = _item_transform(config, transform).sample(chunk.shape)
+    origins, flips, drop_q = p.per_sample(B)
+    crop = None if tuple(p.crop) == tuple(chunk.shape[-2:]) else p.crop
+    return hip.augment_chunk(chunk, label, mask, crop, origins, flips, drop_q=drop_q, seed=int(config["loader"].get("seed", 0)),
+                             offset=int(step), norm_input=norm, spike_th=config["data"].get("spike_th"),
+                             mask_events=bool(config.get("metrics", {}).get("mask_events")))
+
+
+def train_step_from_item(model, optimizer, item, config, transform, step=0, **train_step_kwargs):
+    """`train_step` on a loader item (chunk, label, mask): `prepare_train_item`, then the step unchanged.  Returns its loss."""
+    chunk, label, mask = item
+    x, label, mask = prepare_train_item(chunk, label, mask, config, transform, step=step)
+    return train_step(model, optimizer, x, label, mask, **train_step_kwargs)
