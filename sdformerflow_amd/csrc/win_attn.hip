@@ -16,6 +16,9 @@
 // LDS round trip and no shuffle between the two matrix products.  Row max / sum reduce in-lane over the 4*NT
 // registers and across the 4 lane groups with two DPP-free shuffles.  Bias and mask are read as float4
 // (4 consecutive keys) from L2-resident tables.
+// Shared with the other window-attention files and stated in win_attn_common.h: the spike unpack, the query fragment and the K / V
+// piece with their F.normalize, the eight-step MFMA chain over an LDS row, the score rounding and the output offset.  One site keeps
+// its text: win_attn_tiled_kernel's load_q (the function moves two instantiations' VGPR counts).
 #include "win_attn_common.h"
 #include "switches.h"
 #include "host_launch.h"
@@ -52,14 +55,14 @@ __global__ __launch_bounds__(256) void win_attn_kernel(AttnParams P) {
           kv[i] = *reinterpret_cast<const float4*>(base + C + 4 * i);
           vv[i] = *reinterpret_cast<const float4*>(base + 2 * C + 4 * i);
         }
-        // F.normalize(x, dim=-1): x / max(||x||_2, 1e-12)
+        // F.normalize(x, dim=-1): x / max(||x||_2, eps)
         float sq = 0.f, sk = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           sq += qv[i].x * qv[i].x + qv[i].y * qv[i].y + qv[i].z * qv[i].z + qv[i].w * qv[i].w;
           sk += kv[i].x * kv[i].x + kv[i].y * kv[i].y + kv[i].z * kv[i].z + kv[i].w * kv[i].w;
         }
-        const float iq = 1.f / fmaxf(sqrtf(sq), 1e-12f), ik = 1.f / fmaxf(sqrtf(sk), 1e-12f);
+        const float iq = 1.f / fmaxf(sqrtf(sq), NEPS), ik = 1.f / fmaxf(sqrtf(sk), NEPS);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           qv[i].x *= iq; qv[i].y *= iq; qv[i].z *= iq; qv[i].w *= iq;
@@ -73,13 +76,9 @@ __global__ __launch_bounds__(256) void win_attn_kernel(AttnParams P) {
         const float sc = d.scale[g];                      // q * scale (reference :26)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          uint32_t wq = *reinterpret_cast<const uint32_t*>(qp + 4 * i);
-          uint32_t wk = *reinterpret_cast<const uint32_t*>(kp + 4 * i);
-          uint32_t wv = *reinterpret_cast<const uint32_t*>(vp + 4 * i);
-          qv[i] = make_float4((wq & 0xff) ? sc : 0.f, ((wq >> 8) & 0xff) ? sc : 0.f, ((wq >> 16) & 0xff) ? sc : 0.f,
-                              (wq >> 24) ? sc : 0.f);
-          kv[i] = make_float4((float)(wk & 0xff), (float)((wk >> 8) & 0xff), (float)((wk >> 16) & 0xff), (float)(wk >> 24));
-          vv[i] = make_float4((float)(wv & 0xff), (float)((wv >> 8) & 0xff), (float)((wv >> 16) & 0xff), (float)(wv >> 24));
+          qv[i] = u8x4_on(*reinterpret_cast<const uint32_t*>(qp + 4 * i), sc);
+          kv[i] = u8x4_f(*reinterpret_cast<const uint32_t*>(kp + 4 * i));
+          vv[i] = u8x4_f(*reinterpret_cast<const uint32_t*>(vp + 4 * i));
         }
       }
     }
@@ -101,28 +100,12 @@ __global__ __launch_bounds__(256) void win_attn_kernel(AttnParams P) {
     const int qi = qt * 16 + l15;                          // this lane's query
     // B operand of S^T = K Q^T: Q[qi][8*lg + s], s = 0..7
     float qreg[8];
-    {
-      float4 a = *reinterpret_cast<const float4*>(&Qs[qi * LDW + 8 * lg]);
-      float4 c = *reinterpret_cast<const float4*>(&Qs[qi * LDW + 8 * lg + 4]);
-      qreg[0] = a.x; qreg[1] = a.y; qreg[2] = a.z; qreg[3] = a.w;
-      qreg[4] = c.x; qreg[5] = c.y; qreg[6] = c.z; qreg[7] = c.w;
-    }
+    load_row8(&Qs[qi * LDW + 8 * lg], qreg);
     f32x4 st[NT_MAX];
 #pragma unroll
     for (int jt = 0; jt < NT_MAX; ++jt) {
       if (jt < NT) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        const int kj = jt * 16 + l15;                      // A operand row: key
-        float4 a = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg]);
-        float4 c = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg + 4]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, qreg[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, qreg[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, qreg[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, qreg[3], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.x, qreg[4], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.y, qreg[5], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.z, qreg[6], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.w, qreg[7], acc, 0, 0, 0);
+        f32x4 acc = mfma_row8(&Ks[(jt * 16 + l15) * LDW + 8 * lg], qreg);   // A operand row: key
         // lane holds S[qi][kb + r], kb = 16*jt + 4*lg : scale, bias, mask
         const int kb = jt * 16 + 4 * lg;
         float4 bv = make_float4(0.f, 0.f, 0.f, 0.f), mv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -140,12 +123,10 @@ __global__ __launch_bounds__(256) void win_attn_kernel(AttnParams P) {
             if (kb + 3 < N) mv.w = mp[3];
           }
         }
-        const float NEG = (MODE == SDF_ATTN_ANN) ? -INFINITY : 0.f;
-        // attn = qk * logit_scale + bias (+ mask): separately rounded, as the reference computes it
-        acc[0] = (kb + 0 < N) ? (acc[0] * ls + bv.x) + mv.x : NEG;
-        acc[1] = (kb + 1 < N) ? (acc[1] * ls + bv.y) + mv.y : NEG;
-        acc[2] = (kb + 2 < N) ? (acc[2] * ls + bv.z) + mv.z : NEG;
-        acc[3] = (kb + 3 < N) ? (acc[3] * ls + bv.w) + mv.w : NEG;
+        acc[0] = attn_score(acc[0], ls, bv.x, mv.x, kb + 0 < N, key_past_n<MODE>());
+        acc[1] = attn_score(acc[1], ls, bv.y, mv.y, kb + 1 < N, key_past_n<MODE>());
+        acc[2] = attn_score(acc[2], ls, bv.z, mv.z, kb + 2 < N, key_past_n<MODE>());
+        acc[3] = attn_score(acc[3], ls, bv.w, mv.w, kb + 3 < N, key_past_n<MODE>());
         st[jt] = acc;
       }
     }
@@ -196,14 +177,7 @@ __global__ __launch_bounds__(256) void win_attn_kernel(AttnParams P) {
       const int i = qt * 16 + 4 * lg + r;
       if (i < N) {
         int64_t off;
-        if (MODE == SDF_ATTN_ANN) {
-          const int64_t orow = d.row_map ? d.row_map[(int64_t)b * N + i] : (int64_t)b * N + i;
-          if (orow < 0) continue;                                            // padding token: cropped away by the reference
-          off = orow * C + g * HD;                                           // (attn@v).transpose(1,2).reshape(B_,N,C) [+ window reverse]
-        } else {
-          const int t = i / d.N1, n1 = i - t * d.N1;                         // (B_,nH,T',N1,hd) -> (T',B_,N1,C)
-          off = (((int64_t)t * d.B_ + b) * d.N1 + n1) * C + g * HD;
-        }
+        if (!out_offset<MODE>(d, b, g, i, C, off)) continue;                 // a padding token
         d.out[off + l15] = o0[r];
         d.out[off + 16 + l15] = o1[r];
       }
@@ -273,19 +247,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
       }
     }
   };
-  auto norm_q = [&](float (&qr)[8]) __attribute__((always_inline)) {
-    if (MODE == SDF_ATTN_ANN) {                          // F.normalize(q, dim=-1)
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) ss += qr[i] * qr[i];
-      ss += __shfl_xor(ss, 16);
-      ss += __shfl_xor(ss, 32);
-      const float iq = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) qr[i] *= iq;
-    }
-  };
-
   // 11 query tiles over 4 waves leaves one wave a tile short; rotating the start by the workgroup number moves that
   // light wave from SIMD to SIMD across the co-resident workgroups
   const int wv = (wave + L) & 3;
@@ -308,32 +269,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
     for (int it = 0; it < IT; ++it) {
       const int r = (tid >> 3) + 32 * it;
       kq[it] = vq[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < N) {
-        if (MODE == SDF_ATTN_ANN) {
-          const float* base = qkv_row(d, b, r, C) + g * HD + 4 * piece;
-          kq[it] = *reinterpret_cast<const float4*>(base + C);
-          vq[it] = *reinterpret_cast<const float4*>(base + 2 * C);
-        } else {
-          const int64_t off = (((int64_t)b * d.nH + g) * N + r) * HD + 4 * piece;
-          const uint32_t wk = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(d.k) + off);
-          const uint32_t wv = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(d.v) + off);
-          kq[it] = make_float4((float)(wk & 0xff), (float)((wk >> 8) & 0xff), (float)((wk >> 16) & 0xff), (float)(wk >> 24));
-          vq[it] = make_float4((float)(wv & 0xff), (float)((wv >> 8) & 0xff), (float)((wv >> 16) & 0xff), (float)(wv >> 24));
-        }
-      }
+      if (r < N) kv_piece<MODE>(d, b, g, r, piece, C, kq[it], vq[it]);
     }
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
       const int r = (tid >> 3) + 32 * it;
       float4 kv = kq[it];
-      if (MODE == SDF_ATTN_ANN) {                        // F.normalize(k, dim=-1): the row's 8 lanes are neighbours
-        float sk = kv.x * kv.x + kv.y * kv.y + kv.z * kv.z + kv.w * kv.w;
-        sk += __shfl_xor(sk, 1);
-        sk += __shfl_xor(sk, 2);
-        sk += __shfl_xor(sk, 4);
-        const float ik = 1.f / fmaxf(sqrtf(sk), 1e-12f);
-        kv.x *= ik; kv.y *= ik; kv.z *= ik; kv.w *= ik;
-      }
+      if (MODE == SDF_ATTN_ANN) norm_row8(kv);           // F.normalize(k, dim=-1)
       if (r < NP) {
         *reinterpret_cast<float4*>(&Ks[r * LDW + 4 * piece]) = kv;
         Vt[(4 * piece + 0) * LDT + r] = vq[it].x;
@@ -348,11 +290,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
 
   const float ls = (MODE == SDF_ATTN_ANN) ? d.scale[g] : 1.f;
   const uint32_t tbytes = (uint32_t)N * (uint32_t)N * 4u;
-  const __amdgpu_buffer_rsrc_t bias_rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.bias + (int64_t)g * N * N), 0, (int)tbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t mask_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(HAS_MASK ? d.mask + (int64_t)(b % d.nW) * N * N : d.bias), 0, HAS_MASK ? (int)tbytes : 0, 0x00020000);
-  const float NEG = (MODE == SDF_ATTN_ANN) ? -INFINITY : 0.f;
+  const __amdgpu_buffer_rsrc_t bias_rs = make_rsrc_bounded(d.bias + (int64_t)g * N * N, tbytes);
+  const __amdgpu_buffer_rsrc_t mask_rs = make_rsrc_bounded(HAS_MASK ? d.mask + (int64_t)(b % d.nW) * N * N : d.bias, HAS_MASK ? tbytes : 0u);
 
   for (int qt = wv; qt < NTC; qt += 4) {
     if (qt * 16 >= N) break;
@@ -360,7 +299,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
     float qreg[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) qreg[i] = qnext[i];
-    norm_q(qreg);
+    if (MODE == SDF_ATTN_ANN) norm_q_frag(qreg);
     if (qt + 4 < NTC) load_q(qt + 4, qnext);
     // ---- request bias / mask of the strip: lane needs [qi][16 jt + 4 lg .. + 3]; whole tiles with one 16-byte load
     //      (rows are only 8-byte aligned - fine for buffer loads), the ragged last tile with two 8-byte loads ----
@@ -392,38 +331,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
     // ---- S^T = K Q^T ----
     f32x4 st[NTC];
 #pragma unroll
-    for (int jt = 0; jt < NTC; ++jt) {
-      const int kj = jt * 16 + l15;
-      const float4 a = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg]);
-      const float4 c = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg + 4]);
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, qreg[0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, qreg[1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, qreg[2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, qreg[3], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.x, qreg[4], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.y, qreg[5], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.z, qreg[6], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.w, qreg[7], acc, 0, 0, 0);
-      st[jt] = acc;
-    }
-    // ---- attn = qk * logit_scale + bias (+ mask), separately rounded as the reference computes it ----
+    for (int jt = 0; jt < NTC; ++jt) st[jt] = mfma_row8(&Ks[(jt * 16 + l15) * LDW + 8 * lg], qreg);
+    // ---- the scores (win_attn_common.h attn_score); only the last tile can be ragged ----
 #pragma unroll
-    for (int jt = 0; jt < NTC; ++jt) {
-      const int kb = jt * 16 + 4 * lg;
-      const uint32_t b0 = bb[jt].x, b1 = bb[jt].y, b2 = bb[jt].z, b3 = bb[jt].w;
-      float s0 = st[jt][0] * ls + __uint_as_float(b0), s1 = st[jt][1] * ls + __uint_as_float(b1);
-      float s2 = st[jt][2] * ls + __uint_as_float(b2), s3 = st[jt][3] * ls + __uint_as_float(b3);
-      if (HAS_MASK) {
-        const uint32_t m0 = mm[jt].x, m1 = mm[jt].y, m2 = mm[jt].z, m3 = mm[jt].w;
-        s0 += __uint_as_float(m0); s1 += __uint_as_float(m1); s2 += __uint_as_float(m2); s3 += __uint_as_float(m3);
-      }
-      if (jt == NTC - 1) {                                         // only the last tile can be ragged
-        s0 = (kb + 0 < N) ? s0 : NEG; s1 = (kb + 1 < N) ? s1 : NEG;
-        s2 = (kb + 2 < N) ? s2 : NEG; s3 = (kb + 3 < N) ? s3 : NEG;
-      }
-      st[jt][0] = s0; st[jt][1] = s1; st[jt][2] = s2; st[jt][3] = s3;
-    }
+    for (int jt = 0; jt < NTC; ++jt)
+      st[jt] = attn_score4<HAS_MASK>(st[jt], ls, bb[jt], HAS_MASK ? mm[jt] : u32x4{0u, 0u, 0u, 0u}, jt == NTC - 1, jt * 16 + 4 * lg, N, key_past_n<MODE>());
     if (MODE == SDF_ATTN_ANN) {
       float m = -INFINITY;
 #pragma unroll
@@ -432,7 +344,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
       m = fmaxf(m, __shfl_xor(m, 32));
       // exp(x - m) = 2^(x log2e - m log2e): one fma + the hardware exp2 (1 ulp) instead of the ~14-instruction expf;
       // the argument rounding adds <= |x - m| * 2^-24 relative error - far inside the 1e-3 flow tolerance
-      const float L2E = 1.4426950408889634f, mneg = -m * L2E;
+      const float mneg = -m * L2E;
       float sum = 0.f;
 #pragma unroll
       for (int jt = 0; jt < NTC; ++jt) {
@@ -472,14 +384,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
       const int i = qt * 16 + 4 * lg + r;
       if (i < N) {
         int64_t off;
-        if (MODE == SDF_ATTN_ANN) {
-          const int64_t orow = d.row_map ? d.row_map[(int64_t)b * N + i] : (int64_t)b * N + i;   // window reverse + roll back + crop
-          if (orow < 0) continue;
-          off = orow * C + g * HD;
-        } else {
-          const int t = i / d.N1, n1 = i - t * d.N1;
-          off = (((int64_t)t * d.B_ + b) * d.N1 + n1) * C + g * HD;
-        }
+        if (!out_offset<MODE>(d, b, g, i, C, off)) continue;                 // a padding token
         d.out[off + l15] = o0[r];
         d.out[off + 16 + l15] = o1[r];
       }
@@ -548,26 +453,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
   const int l15 = lane & 15, lg = lane >> 4;
   const int C = d.nH * HD;
 
-  auto load_q = [&](int qt, float (&qr)[8]) __attribute__((always_inline)) {
-    const int qi = qt * 16 + l15;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qr[i] = 0.f;
-    if (qi < N) {
-      if (MODE == SDF_ATTN_ANN) {
-        const float* base = qkv_row(d, b, qi, C) + g * HD + 8 * lg;
-        const float4 a = *reinterpret_cast<const float4*>(base), c = *reinterpret_cast<const float4*>(base + 4);
-        qr[0] = a.x; qr[1] = a.y; qr[2] = a.z; qr[3] = a.w; qr[4] = c.x; qr[5] = c.y; qr[6] = c.z; qr[7] = c.w;
-      } else {                                                     // binary q: 0 / 1 (the scale multiplies the exact count afterwards)
-        const uint8_t* qp = reinterpret_cast<const uint8_t*>(d.q) + (((int64_t)b * d.nH + g) * N + qi) * HD + 8 * lg;
-        const uint32_t w0 = *reinterpret_cast<const uint32_t*>(qp), w1 = *reinterpret_cast<const uint32_t*>(qp + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          qr[i] = ((w0 >> (8 * i)) & 0xff) ? 1.f : 0.f;
-          qr[4 + i] = ((w1 >> (8 * i)) & 0xff) ? 1.f : 0.f;
-        }
-      }
-    }
-  };
+  // binary q: 0 / 1 (the scale multiplies the exact count afterwards)
+  auto load_q = [&](int qt, float (&qr)[8]) __attribute__((always_inline)) { load_q_frag<MODE>(d, b, g, qt * 16 + l15, lg, N, C, 1.f, qr); };
   const int wv = (wave + L) & 3;
   float qnext[8];
   load_q(wv, qnext);
@@ -588,19 +475,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
       for (int j = 0; j < 4; ++j) {
         const int r = 4 * kgp + j;
         kq[it][j] = vq[it][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (u < UNITS && r < N) {
-          if (MODE == SDF_ATTN_ANN) {
-            const float* base = qkv_row(d, b, r, C) + g * HD + 4 * piece;
-            kq[it][j] = *reinterpret_cast<const float4*>(base + C);
-            vq[it][j] = *reinterpret_cast<const float4*>(base + 2 * C);
-          } else {
-            const int64_t off = (((int64_t)b * d.nH + g) * N + r) * HD + 4 * piece;
-            const uint32_t wk = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(d.k) + off);
-            const uint32_t wv = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(d.v) + off);
-            kq[it][j] = make_float4((float)(wk & 0xff), (float)((wk >> 8) & 0xff), (float)((wk >> 16) & 0xff), (float)(wk >> 24));
-            vq[it][j] = make_float4((float)(wv & 0xff), (float)((wv >> 8) & 0xff), (float)((wv >> 16) & 0xff), (float)(wv >> 24));
-          }
-        }
+        if (u < UNITS && r < N) kv_piece<MODE>(d, b, g, r, piece, C, kq[it][j], vq[it][j]);
       }
     }
 #pragma unroll
@@ -609,16 +484,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float4 kv = kq[it][j];
-        float ik = 1.f;
-        if (MODE == SDF_ATTN_ANN) {                                // F.normalize(k, dim=-1): the key's 8 units are neighbouring lanes
-          float sk = kv.x * kv.x + kv.y * kv.y + kv.z * kv.z + kv.w * kv.w;
-          sk += __shfl_xor(sk, 1);
-          sk += __shfl_xor(sk, 2);
-          sk += __shfl_xor(sk, 4);
-          ik = 1.f / fmaxf(sqrtf(sk), 1e-12f);
-        }
+        if (MODE == SDF_ATTN_ANN) norm_row8(kv);                   // F.normalize(k, dim=-1)
         uint2 hi, lo;
-        split4_f16(kv.x * ik, kv.y * ik, kv.z * ik, kv.w * ik, hi, lo);
+        split4_f16(kv.x, kv.y, kv.z, kv.w, hi, lo);
         if (u < UNITS) {
           const int kr = 4 * kgp + j, ko = kr * KRS + 16 * ((piece >> 1) ^ kswz(kr)) + 8 * (piece & 1);
           *reinterpret_cast<uint2*>(Khi + ko) = hi;
@@ -642,10 +510,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
 
   const float ls = d.scale[g];                          // ANN: logit scale on cosines; SEW: q's scale on the exact spike count
   const uint32_t tbytes = (uint32_t)N * (uint32_t)N * 4u;
-  const __amdgpu_buffer_rsrc_t bias_rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.bias + (int64_t)g * N * N), 0, (int)tbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t mask_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(HAS_MASK ? d.mask + (int64_t)(b % d.nW) * N * N : d.bias), 0, HAS_MASK ? (int)tbytes : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t bias_rs = make_rsrc_bounded(d.bias + (int64_t)g * N * N, tbytes);
+  const __amdgpu_buffer_rsrc_t mask_rs = make_rsrc_bounded(HAS_MASK ? d.mask + (int64_t)(b % d.nW) * N * N : d.bias, HAS_MASK ? tbytes : 0u);
 
   const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(d.out, 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t map_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(d.row_map ? d.row_map : reinterpret_cast<const int*>(d.out)), 0,
@@ -659,12 +525,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
     if (MODE == SDF_ATTN_ANN) {
       // F.normalize(q, dim=-1), with the head's logit scale and log2(e) folded into the same multiplier: the scores leave the
       // matrix pipe in the log2 domain of the softmax (K Q^T * ls * log2 e), 8 multiplications per lane instead of 4 NTC
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) ss += qreg[i] * qreg[i];
-      ss += __shfl_xor(ss, 16);
-      ss += __shfl_xor(ss, 32);
-      const float iq = (ls * 1.4426950408889634f) / fmaxf(sqrtf(ss), 1e-12f);
+      const float nq = q_frag_norm(qreg), iq = (ls * L2E) / nq;
 #pragma unroll
       for (int i = 0; i < 8; ++i) qreg[i] *= iq;
     }
@@ -701,7 +562,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
     // ANN: the accumulator STARTS as (bias + mask) * log2 e - the additions of the score come out of the matrix pipe for free and
     // the strip is in the softmax's log2 domain when it lands; keys beyond N start at -inf (their K rows are zero: -inf + 0)
     f32x4 st[NTC];
-    constexpr float L2E = 1.4426950408889634f;
 #pragma unroll
     for (int jt = 0; jt < NTC; ++jt) {
       const int kj = jt * 16 + l15;
@@ -759,21 +619,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
       for (int r = 0; r < 4; ++r) rinv[r] = __shfl(inv, (lane & 48) | (4 * lg + r));
     } else {
 #pragma unroll
-      for (int jt = 0; jt < NTC; ++jt) {
-        const int kb = jt * 16 + 4 * lg;
-        const uint32_t b0 = bb[jt].x, b1 = bb[jt].y, b2 = bb[jt].z, b3 = bb[jt].w;
-        float s0 = st[jt][0] * ls + __uint_as_float(b0), s1 = st[jt][1] * ls + __uint_as_float(b1);
-        float s2 = st[jt][2] * ls + __uint_as_float(b2), s3 = st[jt][3] * ls + __uint_as_float(b3);
-        if (HAS_MASK) {
-          const uint32_t m0 = mm[jt].x, m1 = mm[jt].y, m2 = mm[jt].z, m3 = mm[jt].w;
-          s0 += __uint_as_float(m0); s1 += __uint_as_float(m1); s2 += __uint_as_float(m2); s3 += __uint_as_float(m3);
-        }
-        if (jt == NTC - 1) {
-          s0 = (kb + 0 < N) ? s0 : 0.f; s1 = (kb + 1 < N) ? s1 : 0.f;
-          s2 = (kb + 2 < N) ? s2 : 0.f; s3 = (kb + 3 < N) ? s3 : 0.f;
-        }
-        st[jt][0] = s0; st[jt][1] = s1; st[jt][2] = s2; st[jt][3] = s3;
-      }
+      for (int jt = 0; jt < NTC; ++jt) st[jt] = attn_score4<HAS_MASK>(st[jt], ls, bb[jt], HAS_MASK ? mm[jt] : u32x4{0u, 0u, 0u, 0u}, jt == NTC - 1, jt * 16 + 4 * lg, N, 0.f);
     }
     // ---- O = P V: the lane's four probabilities of key tile jt are the A operand (keys 16 jt + 4 lg + 0..3) ----
     f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
@@ -805,8 +651,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SDF_ATTN_WP
         if (d.row_map) orow[r] = (int)__builtin_amdgcn_raw_buffer_load_b32(map_rs, i < N ? (uint32_t)(b * N + i) * 4u : INV, 0, 0);
         if (i >= N) orow[r] = -1;
       } else {
-        const int t = i / d.N1, n1 = i - t * d.N1;
-        orow[r] = i < N ? (t * d.B_ + b) * d.N1 + n1 : -1;
+        orow[r] = i < N ? sew_row<int>(i, b, d.B_, d.N1) : -1;
       }
     }
 #pragma unroll
@@ -842,17 +687,8 @@ bool launch_tiled(const AttnParams& P, bool pipe16, int nt, hipStream_t s) {
 }  // namespace
 
 extern "C" int sdf_win_attn_fwd(const SdfWinAttnDesc* d, void* stream) {
-  if (!d) return SDF_E_NULL;
-  if (!d->q || !d->k || !d->v || !d->out || !d->scale || !d->bias) return SDF_E_NULL;
-  if (d->mode != SDF_ATTN_ANN && d->mode != SDF_ATTN_SEW) return SDF_E_DTYPE;
-  if (d->hd != HD || d->B_ < 1 || d->nH < 1 || d->N < 1 || d->N > 16 * NT_MAX) return SDF_E_SHAPE;
-  if (d->mask && (d->nW < 1 || d->B_ % d->nW)) return SDF_E_SHAPE;
-  if (d->mode == SDF_ATTN_SEW && (d->Tq < 1 || d->N1 < 1 || d->Tq * d->N1 != d->N)) return SDF_E_SHAPE;
-  if (d->row_map && (d->mode != SDF_ATTN_ANN || !d->pad_qkv)) return SDF_E_NULL;   // windowing through the map: ANN form, needs the pad row
-  if (!sdf_aligned(d->q, d->mode == SDF_ATTN_ANN ? 16 : 4) || !sdf_aligned(d->out, 4)) return SDF_E_ALIGN;
-  AttnParams P;
-  P.d = *d;
-  if (!d->mask) P.d.nW = 1;
+  if (const int rc = sdf_win_attn_desc_rc(d, 1, 16 * NT_MAX)) return rc;
+  const AttnParams P = sdf_win_attn_params(d);
   const int NP = ((d->N + 15) / 16) * 16;
   const size_t lds = (size_t)3 * NP * LDW * sizeof(float);
   dim3 grid((unsigned)(d->B_ * d->nH)), block(256);

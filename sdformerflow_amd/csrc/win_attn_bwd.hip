@@ -18,20 +18,14 @@
 // Every product is the exact fp32 MFMA.  The cross-window sums (d_bias, d_scale, d_pad = the gradient of the padding tokens'
 // q | k | v, i.e. of the qkv bias they read) are written per (window, head) to the workspace and summed in window order by a
 // second kernel: no float atomics, two calls give bit-equal results.
-#include "common.h"
+// token_row, norm_bwd, sum16, load_row8 / mfma_row8, the score rounding and the workspace helpers are win_attn_common.h's.  Pass 1
+// is not win_attn_large_bwd.hip's score_strip: folded on the tile count, this kernel went from 188 to 200 VGPRs.
+#include "win_attn_common.h"
 
 namespace {
 
-constexpr int HD = 32;
 constexpr int NT_MAX = 12;            // up to 192 tokens per window
-constexpr int LDW = HD + 4;           // padded LDS row (floats)
-constexpr float NEPS = 1e-12f;        // F.normalize eps
 constexpr int RED = 3 * HD + 1;       // per-wave partials: d_pad (q | k | v of one head) + d_scale
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-__host__ __device__ inline int padded_n(int N) { return ((N + 15) / 16) * 16; }
 
 struct BwdParams {
   SdfWinAttnBwdDesc d;
@@ -39,26 +33,6 @@ struct BwdParams {
   float* ws_scale;      // (B_, nH)
   float* ws_pad;        // (B_, nH, 96): dq | dk | dv of the window's padding tokens, this head's 32 dims each
 };
-
-// row of token r of window b in the (rows, 3C) / (rows, C) buffers, or -1 for a padding token
-__device__ __forceinline__ int64_t token_row(const SdfWinAttnBwdDesc& d, int b, int r) {
-  return d.row_map ? (int64_t)d.row_map[(int64_t)b * d.N + r] : (int64_t)b * d.N + r;
-}
-
-// F.normalize backward for one (row, dim pair): y = x / max(n, eps); n >= eps: dx = (dy - y (y . dy)) / n, else dx = dy / eps
-// (the clamp passes no gradient to the norm).  `dot` = y . dy over the row's 32 dims.
-__device__ __forceinline__ float norm_bwd(float dy, float y, float dot, float n) {
-  return n >= NEPS ? (dy - y * dot) / n : dy / NEPS;
-}
-
-// sum over the 16 lanes l15 of one lane group (xor butterfly: the same order on every call)
-__device__ __forceinline__ float sum16(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void win_attn_ann_bwd_kernel(BwdParams P) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -135,40 +109,15 @@ __global__ __launch_bounds__(256) void win_attn_ann_bwd_kernel(BwdParams P) {
   for (int qt = wave; qt < NT; qt += 4) {
     const int qi = qt * 16 + l15;                          // this lane's query (column of the S^T tiles)
     float qreg[8], greg[8];                                // q^[qi][8 lg + s], dO[qi][8 lg + s]
-    {
-      const float4 a = *reinterpret_cast<const float4*>(&Qs[qi * LDW + 8 * lg]);
-      const float4 c = *reinterpret_cast<const float4*>(&Qs[qi * LDW + 8 * lg + 4]);
-      qreg[0] = a.x; qreg[1] = a.y; qreg[2] = a.z; qreg[3] = a.w; qreg[4] = c.x; qreg[5] = c.y; qreg[6] = c.z; qreg[7] = c.w;
-      const float4 e = *reinterpret_cast<const float4*>(&Gs[qi * LDW + 8 * lg]);
-      const float4 f = *reinterpret_cast<const float4*>(&Gs[qi * LDW + 8 * lg + 4]);
-      greg[0] = e.x; greg[1] = e.y; greg[2] = e.z; greg[3] = e.w; greg[4] = f.x; greg[5] = f.y; greg[6] = f.z; greg[7] = f.w;
-    }
+    load_row8(&Qs[qi * LDW + 8 * lg], qreg);
+    load_row8(&Gs[qi * LDW + 8 * lg], greg);
     f32x4 st[NT_MAX], dp[NT_MAX];
 #pragma unroll
     for (int jt = 0; jt < NT_MAX; ++jt) {
       if (jt < NT) {
         const int kj = jt * 16 + l15;                      // A operand row: key
-        const float4 a = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg]);
-        const float4 c = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg + 4]);
-        const float4 va = *reinterpret_cast<const float4*>(&Vs[kj * LDW + 8 * lg]);
-        const float4 vc = *reinterpret_cast<const float4*>(&Vs[kj * LDW + 8 * lg + 4]);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, qreg[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, qreg[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, qreg[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, qreg[3], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.x, qreg[4], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.y, qreg[5], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.z, qreg[6], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.w, qreg[7], acc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(va.x, greg[0], dacc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(va.y, greg[1], dacc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(va.z, greg[2], dacc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(va.w, greg[3], dacc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(vc.x, greg[4], dacc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(vc.y, greg[5], dacc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(vc.z, greg[6], dacc, 0, 0, 0);
-        dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(vc.w, greg[7], dacc, 0, 0, 0);
+        f32x4 acc = mfma_row8(&Ks[kj * LDW + 8 * lg], qreg);
+        const f32x4 dacc = mfma_row8(&Vs[kj * LDW + 8 * lg], greg);
         // lane holds S[qi][kb + r], kb = 16 jt + 4 lg: scale, bias, mask (separately rounded, as the reference computes it)
         const int kb = jt * 16 + 4 * lg;
 #pragma unroll
@@ -176,7 +125,7 @@ __global__ __launch_bounds__(256) void win_attn_ann_bwd_kernel(BwdParams P) {
           const bool ok = qi < N && kb + r < N;
           const float bv = ok ? bias_g[(int64_t)qi * N + kb + r] : 0.f;
           const float mv = (ok && mask_w) ? mask_w[(int64_t)qi * N + kb + r] : 0.f;
-          acc[r] = (kb + r < N) ? (acc[r] * ls + bv) + mv : -INFINITY;
+          acc[r] = attn_score(acc[r], ls, bv, mv, kb + r < N, -INFINITY);
         }
         st[jt] = acc;
         dp[jt] = dacc;
@@ -269,38 +218,13 @@ __global__ __launch_bounds__(256) void win_attn_ann_bwd_kernel(BwdParams P) {
   for (int kt = wave; kt < NT; kt += 4) {
     const int kj = kt * 16 + l15;                          // this lane's key (column of the S / dP blocks)
     float kreg[8], vreg[8];                                // k^[kj][8 lg + s], v[kj][8 lg + s]
-    {
-      const float4 a = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg]);
-      const float4 c = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg + 4]);
-      kreg[0] = a.x; kreg[1] = a.y; kreg[2] = a.z; kreg[3] = a.w; kreg[4] = c.x; kreg[5] = c.y; kreg[6] = c.z; kreg[7] = c.w;
-      const float4 e = *reinterpret_cast<const float4*>(&Vs[kj * LDW + 8 * lg]);
-      const float4 f = *reinterpret_cast<const float4*>(&Vs[kj * LDW + 8 * lg + 4]);
-      vreg[0] = e.x; vreg[1] = e.y; vreg[2] = e.z; vreg[3] = e.w; vreg[4] = f.x; vreg[5] = f.y; vreg[6] = f.z; vreg[7] = f.w;
-    }
+    load_row8(&Ks[kj * LDW + 8 * lg], kreg);
+    load_row8(&Vs[kj * LDW + 8 * lg], vreg);
     f32x4 dv0 = {0.f, 0.f, 0.f, 0.f}, dv1 = {0.f, 0.f, 0.f, 0.f}, dk0 = {0.f, 0.f, 0.f, 0.f}, dk1 = {0.f, 0.f, 0.f, 0.f};
     for (int it = 0; it < NT; ++it) {
       const int qa = it * 16 + l15;                        // A operand row: query
-      const float4 a = *reinterpret_cast<const float4*>(&Qs[qa * LDW + 8 * lg]);
-      const float4 c = *reinterpret_cast<const float4*>(&Qs[qa * LDW + 8 * lg + 4]);
-      const float4 ga = *reinterpret_cast<const float4*>(&Gs[qa * LDW + 8 * lg]);
-      const float4 gc = *reinterpret_cast<const float4*>(&Gs[qa * LDW + 8 * lg + 4]);
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, kreg[0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, kreg[1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, kreg[2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, kreg[3], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.x, kreg[4], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.y, kreg[5], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.z, kreg[6], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.w, kreg[7], acc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ga.x, vreg[0], dacc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ga.y, vreg[1], dacc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ga.z, vreg[2], dacc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ga.w, vreg[3], dacc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(gc.x, vreg[4], dacc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(gc.y, vreg[5], dacc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(gc.z, vreg[6], dacc, 0, 0, 0);
-      dacc = __builtin_amdgcn_mfma_f32_16x16x4f32(gc.w, vreg[7], dacc, 0, 0, 0);
+      const f32x4 acc = mfma_row8(&Qs[qa * LDW + 8 * lg], kreg);
+      const f32x4 dacc = mfma_row8(&Gs[qa * LDW + 8 * lg], vreg);
       // lane holds S / dP [query it*16 + 4 lg + r][key kj]: P from the stored row statistics, dS
       float p[4], ds[4];
 #pragma unroll
@@ -309,7 +233,7 @@ __global__ __launch_bounds__(256) void win_attn_ann_bwd_kernel(BwdParams P) {
         const bool ok = i < N && kj < N;
         const float bv = ok ? bias_g[(int64_t)i * N + kj] : 0.f;
         const float mv = (ok && mask_w) ? mask_w[(int64_t)i * N + kj] : 0.f;
-        const float sc = (acc[r] * ls + bv) + mv;
+        const float sc = attn_score(acc[r], ls, bv, mv, true, 0.f);
         p[r] = ok ? expf(sc - rm[i]) * rl[i] : 0.f;
         ds[r] = p[r] * (dacc[r] - rD[i]);
       }

@@ -10,10 +10,11 @@
 // LDS or register budget depends on N, many workgroups share a compute unit, and no opt-in above 64 KiB is needed.
 //
 // A key past N scores -inf before the maximum (ANN) or 0 (SEW) and its K / V rows are zero.  Every block holds at least one real
-// key and bias and mask are finite, so a block's row maximum is finite and exp(-inf - (-inf)) is never formed: while the running
-// maximum is still -inf (the first block) the scale factor is 0 without an exponential, on accumulators that are still 0.  (A
-// caller's mask of -inf over a whole block is met with a zero reference point for that block instead of its -inf maximum.)
+// key and bias and mask are finite, so a block's row maximum is finite; how the running sum moves from one rounded reference point
+// to the next, the first block and a block masked to -inf are win_attn_common.h's softmax_ref_step.
 // No atomics: every output element has one writer and a fixed summation order.
+// The query fragment, the K / V piece fetch and their F.normalize, the MFMA chain over an LDS row, the score rounding and the output
+// offset are win_attn_common.h's too.
 #include "win_attn_common.h"
 #include "host_launch.h"
 
@@ -40,36 +41,10 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
   const bool active = qt * 16 < N;                       // (a wave without a query tile still stages keys and meets the barriers)
   const int qi = qt * 16 + l15;                          // this lane's query
 
-  // ---- B operand of S^T = K Q^T: Q[qi][8 lg .. 8 lg + 7], normalised (ANN) / scaled (SEW) ----
+  // ---- B operand of S^T = K Q^T: Q[qi][8 lg .. 8 lg + 7], normalised (ANN) / scaled (SEW: q * scale) ----
   float qreg[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) qreg[i] = 0.f;
-  if (qi < N) {
-    if (MODE == SDF_ATTN_ANN) {
-      const float* base = qkv_row(d, b, qi, C) + g * HD + 8 * lg;
-      const float4 a = *reinterpret_cast<const float4*>(base), c = *reinterpret_cast<const float4*>(base + 4);
-      qreg[0] = a.x; qreg[1] = a.y; qreg[2] = a.z; qreg[3] = a.w; qreg[4] = c.x; qreg[5] = c.y; qreg[6] = c.z; qreg[7] = c.w;
-    } else {
-      const uint8_t* qp = reinterpret_cast<const uint8_t*>(d.q) + (((int64_t)b * d.nH + g) * N + qi) * HD + 8 * lg;
-      const uint32_t w0 = *reinterpret_cast<const uint32_t*>(qp), w1 = *reinterpret_cast<const uint32_t*>(qp + 4);
-      const float sc = d.scale[g];                       // q * scale
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        qreg[i] = ((w0 >> (8 * i)) & 0xff) ? sc : 0.f;
-        qreg[4 + i] = ((w1 >> (8 * i)) & 0xff) ? sc : 0.f;
-      }
-    }
-  }
-  if (MODE == SDF_ATTN_ANN) {                            // F.normalize(q, dim=-1): x / max(||x||_2, 1e-12)
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss += qreg[i] * qreg[i];
-    ss += __shfl_xor(ss, 16);
-    ss += __shfl_xor(ss, 32);
-    const float iq = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qreg[i] *= iq;
-  }
+  load_q_frag<MODE>(d, b, g, qi, lg, N, C, d.scale[g], qreg);
+  if (MODE == SDF_ATTN_ANN) norm_q_frag(qreg);
 
   // ---- a key block's K and V rows: 8 lanes per token row (one float4 each), 32 rows per pass ----
   constexpr int IT = KB / 32;
@@ -80,19 +55,7 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
     for (int it = 0; it < IT; ++it) {
       const int r = kb0 + (tid >> 3) + 32 * it;
       kq[it] = vq[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < N) {
-        if (MODE == SDF_ATTN_ANN) {
-          const float* base = qkv_row(d, b, r, C) + g * HD + 4 * piece;
-          kq[it] = *reinterpret_cast<const float4*>(base + C);
-          vq[it] = *reinterpret_cast<const float4*>(base + 2 * C);
-        } else {
-          const int64_t off = (((int64_t)b * d.nH + g) * N + r) * HD + 4 * piece;
-          const uint32_t wk = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(d.k) + off);
-          const uint32_t wv = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(d.v) + off);
-          kq[it] = make_float4((float)(wk & 0xff), (float)((wk >> 8) & 0xff), (float)((wk >> 16) & 0xff), (float)(wk >> 24));
-          vq[it] = make_float4((float)(wv & 0xff), (float)((wv >> 8) & 0xff), (float)((wv >> 16) & 0xff), (float)(wv >> 24));
-        }
-      }
+      if (r < N) kv_piece<MODE>(d, b, g, r, piece, C, kq[it], vq[it]);
     }
   };
   auto stash = [&]() __attribute__((always_inline)) {
@@ -100,14 +63,7 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
     for (int it = 0; it < IT; ++it) {
       const int r = (tid >> 3) + 32 * it;                // row inside the block
       float4 kv = kq[it];
-      if (MODE == SDF_ATTN_ANN) {                        // F.normalize(k, dim=-1): the row's 8 lanes are neighbours
-        float sk = kv.x * kv.x + kv.y * kv.y + kv.z * kv.z + kv.w * kv.w;
-        sk += __shfl_xor(sk, 1);
-        sk += __shfl_xor(sk, 2);
-        sk += __shfl_xor(sk, 4);
-        const float ik = 1.f / fmaxf(sqrtf(sk), 1e-12f);
-        kv.x *= ik; kv.y *= ik; kv.z *= ik; kv.w *= ik;
-      }
+      if (MODE == SDF_ATTN_ANN) norm_row8(kv);           // F.normalize(k, dim=-1)
       *reinterpret_cast<float4*>(&Ks[r * LDW + 4 * piece]) = kv;
       Vt[(4 * piece + 0) * LDT + r] = vq[it].x;
       Vt[(4 * piece + 1) * LDT + r] = vq[it].y;
@@ -122,7 +78,6 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
   const __amdgpu_buffer_rsrc_t bias_rs = make_rsrc_bounded(d.bias + (int64_t)g * N * N, tbytes);
   const __amdgpu_buffer_rsrc_t mask_rs = make_rsrc_bounded(HAS_MASK ? d.mask + (int64_t)(b % d.nW) * N * N : d.bias, HAS_MASK ? tbytes : 0u);
   const uint32_t rowoff = (uint32_t)qi * (uint32_t)N * 4u;
-  constexpr float L2E = 1.4426950408889634f;
 
   f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;                  // ANN: running maximum and sum of this lane's query row
@@ -154,30 +109,14 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
     f32x4 st[KT];
 #pragma unroll
     for (int jt = 0; jt < KT; ++jt) {
-      const int kj = jt * 16 + l15;                      // A operand row: key (inside the block)
-      const float4 a = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg]);
-      const float4 c = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg + 4]);
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, qreg[0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, qreg[1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, qreg[2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, qreg[3], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.x, qreg[4], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.y, qreg[5], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.z, qreg[6], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.w, qreg[7], acc, 0, 0, 0);
-      st[jt] = acc;
+      st[jt] = mfma_row8(&Ks[(jt * 16 + l15) * LDW + 8 * lg], qreg);   // A operand row: key (inside the block)
     }
-    // ---- attn = qk * logit_scale + bias (+ mask), separately rounded as the reference computes it; a key past N: -inf / 0 ----
-    const float NEG = (MODE == SDF_ATTN_ANN) ? -INFINITY : 0.f;
+    // ---- the scores (win_attn_common.h attn_score); a key past N: -inf / 0 ----
 #pragma unroll
     for (int jt = 0; jt < KT; ++jt) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s = st[jt][r] * ls + __uint_as_float(bb[jt][r]);
-        if (HAS_MASK) s += __uint_as_float(mm[jt][r]);
-        st[jt][r] = (kb0 + jt * 16 + 4 * lg + r < N) ? s : NEG;
-      }
+      for (int r = 0; r < 4; ++r)
+        st[jt][r] = attn_score<HAS_MASK>(st[jt][r], ls, bb[jt][r], mm[jt][r], kb0 + jt * 16 + 4 * lg + r < N, key_past_n<MODE>());
     }
     if (MODE == SDF_ATTN_ANN) {
       float bm = st[0][0];
@@ -185,13 +124,8 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
       for (int jt = 0; jt < KT; ++jt) bm = fmaxf(fmaxf(fmaxf(bm, st[jt][0]), fmaxf(st[jt][1], st[jt][2])), st[jt][3]);
       bm = fmaxf(bm, __shfl_xor(bm, 16));
       bm = fmaxf(bm, __shfl_xor(bm, 32));
-      const float m_new = fmaxf(m_run, bm);
-      // exp(x - m) = 2^(x log2e - m log2e): one fma + the hardware exp2, as win_attn_tiled_kernel
-      const float mneg = (m_new == -INFINITY) ? 0.f : -m_new * L2E;
-      // the old terms are 2^(x log2e + r_run) with the ROUNDED reference point r_run = -m log2e that made them: scaling by
-      // 2^(mneg - r_run) moves them to the new rounded reference point exactly, so the rounding of a reference point (up to
-      // 2^-17 in the exponent at logits near 100) cancels in the final division as it does in a one-pass softmax
-      const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mneg - r_run);   // first block: nothing to scale
+      float mneg, alpha;                                 // the new reference point, the old terms' factor (win_attn_common.h)
+      const float m_new = softmax_ref_step(m_run, r_run, bm, mneg, alpha);
       float psum = 0.f;
 #pragma unroll
       for (int jt = 0; jt < KT; ++jt) {
@@ -241,14 +175,7 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
     const int i = qt * 16 + 4 * lg + r;
     if (i < N) {
       int64_t off;
-      if (MODE == SDF_ATTN_ANN) {
-        const int64_t orow = d.row_map ? d.row_map[(int64_t)b * N + i] : (int64_t)b * N + i;   // window reverse + roll back + crop
-        if (orow < 0) continue;                                            // padding token: cropped away by the reference
-        off = orow * C + g * HD;
-      } else {
-        const int t = i / d.N1, n1 = i - t * d.N1;                         // (B_,nH,T',N1,hd) -> (T',B_,N1,C)
-        off = (((int64_t)t * d.B_ + b) * d.N1 + n1) * C + g * HD;
-      }
+      if (!out_offset<MODE>(d, b, g, i, C, off)) continue;                   // a padding token
       d.out[off + l15] = o0[r] * rinv;
       d.out[off + 16 + l15] = o1[r] * rinv;
     }
@@ -258,20 +185,11 @@ __global__ __launch_bounds__(256) void win_attn_large_kernel(AttnParams P) {
 }  // namespace
 
 extern "C" int sdf_win_attn_large_fwd(const SdfWinAttnDesc* d, void* stream) {
-  if (!d) return SDF_E_NULL;
-  if (!d->q || !d->k || !d->v || !d->out || !d->scale || !d->bias) return SDF_E_NULL;
-  if (d->mode != SDF_ATTN_ANN && d->mode != SDF_ATTN_SEW) return SDF_E_DTYPE;
-  if (d->hd != HD || d->B_ < 1 || d->nH < 1 || d->N <= N_ABOVE || d->N > N_MAX) return SDF_E_SHAPE;
-  if (d->mask && (d->nW < 1 || d->B_ % d->nW)) return SDF_E_SHAPE;
-  if (d->mode == SDF_ATTN_SEW && (d->Tq < 1 || d->N1 < 1 || d->Tq * d->N1 != d->N)) return SDF_E_SHAPE;
-  if (d->row_map && (d->mode != SDF_ATTN_ANN || !d->pad_qkv)) return SDF_E_NULL;   // windowing through the map: ANN form, needs the pad row
-  if (!sdf_aligned(d->q, d->mode == SDF_ATTN_ANN ? 16 : 4) || !sdf_aligned(d->out, 4)) return SDF_E_ALIGN;
-  const int64_t groups = ((d->N + 15) / 16 + 3) / 4;                // workgroups of 64 queries per (window, head)
-  if ((int64_t)d->B_ * d->nH * groups >= (1LL << 31)) return SDF_E_SHAPE;
-  AttnParams P;
-  P.d = *d;
-  if (!d->mask) P.d.nW = 1;
-  const dim3 grid((unsigned)((int64_t)d->B_ * d->nH * groups)), block(256);
+  if (const int rc = sdf_win_attn_desc_rc(d, N_ABOVE + 1, N_MAX)) return rc;
+  const int64_t wgs = sdf_win_attn_group_grid(d);
+  if (!wgs) return SDF_E_SHAPE;
+  const AttnParams P = sdf_win_attn_params(d);
+  const dim3 grid((unsigned)wgs), block(256);
   hipStream_t s = sdf_stream(stream);
   sdf_dispatch(SdfList<SDF_ATTN_ANN, SDF_ATTN_SEW>{}, d->mode, [&](auto mode) {
     if (d->mask) {

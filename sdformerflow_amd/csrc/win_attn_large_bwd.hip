@@ -25,19 +25,18 @@
 //   win_attn_large_sew_bwd_dv_kernel     workgroup = (window, head, 64 keys): dV from Q^T dO and the (bias + mask)^T dO walk, with
 //     (bias + mask) and dO streamed in 64-query blocks.
 //   win_attn_large_sew_dbias_kernel      split-K over runs of windows as sew_bwd_dbias_kernel, V staged per 256-key block.
+// token_row, norm_bwd, sum16, norm_row8, load_row8 / mfma_row8, the score rounding, u8x4_f, dout_row and the workspace helpers are
+// win_attn_common.h's.
 #include "win_attn_common.h"
 
 namespace {
 
 constexpr int N_ABOVE = 192, N_MAX = 1024;   // served: N_ABOVE < N <= N_MAX (up to N_ABOVE: sdf_win_attn_ann_bwd / sdf_win_attn_sew_bwd)
 constexpr int TB = 64;                       // tokens per staged block = tokens a workgroup owns
-constexpr float NEPS = 1e-12f;               // F.normalize eps
 constexpr int RQ = HD + 1;                   // query kernel's partials per workgroup: d_pad (q of one head) + d_scale
 constexpr int RK = 2 * HD;                   // key kernel's: d_pad (k | v of one head)
 constexpr int DBIAS_TARGET_WG = 2048;        // grid the d_bias splits aim for
 
-__host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-__host__ __device__ inline int padded_n(int N) { return ((N + 15) / 16) * 16; }
 __host__ __device__ inline int groups_of(int N) { return (N + TB - 1) / TB; }
 
 // windows per d_bias run and the number of runs: functions of the shape only, so the summation order is too
@@ -75,25 +74,6 @@ struct AnnBwdParams {
   int wrun;             // windows per run
 };
 
-// row of token r of window b in the (rows, 3C) / (rows, C) buffers, or -1 for a padding token
-__device__ __forceinline__ int64_t token_row(const SdfWinAttnBwdDesc& d, int b, int r) {
-  return d.row_map ? (int64_t)d.row_map[(int64_t)b * d.N + r] : (int64_t)b * d.N + r;
-}
-
-// F.normalize backward for one (row, dim pair), as win_attn_bwd.hip: n >= eps: dx = (dy - y (y . dy)) / n, else dx = dy / eps
-__device__ __forceinline__ float norm_bwd(float dy, float y, float dot, float n) {
-  return n >= NEPS ? (dy - y * dot) / n : dy / NEPS;
-}
-
-// sum over the 16 lanes l15 of one lane group (xor butterfly: the same order on every call)
-__device__ __forceinline__ float sum16(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  return v;
-}
-
 // Stage tokens t0 .. t0 + 63 of (window b, head g) as dst[64][LDW]: PART 0 / 1 / 2 = q / k / v of the token's qkv row (a padding
 // token reads pad_qkv), PART 3 = dO (zero for a padding token: its output is cropped).  NORM: the row L2-normalised as the forward
 // does, its raw norm to nrm[64] where the caller keeps it (nrm may be null).  Tokens past N are zero rows.  All 256 threads: 8 lanes per row (one float4 each), 32 rows per pass.
@@ -113,39 +93,12 @@ __device__ __forceinline__ void stage_rows(const SdfWinAttnBwdDesc& d, int b, in
         x = *reinterpret_cast<const float4*>(d.dout + row * C + g * HD + 4 * piece);
       }
     }
-    if (NORM) {                                          // the row's 8 lanes are neighbours
-      float ss = x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
-      ss += __shfl_xor(ss, 1);
-      ss += __shfl_xor(ss, 2);
-      ss += __shfl_xor(ss, 4);
-      const float n = sqrtf(ss), inv = 1.f / fmaxf(n, NEPS);
-      x.x *= inv; x.y *= inv; x.z *= inv; x.w *= inv;
+    if (NORM) {                                          // (win_attn_common.h norm_row8)
+      const float n = norm_row8(x);
       if (nrm && piece == 0) nrm[r] = n;
     }
     *reinterpret_cast<float4*>(&dst[r * LDW + 4 * piece]) = x;
   }
-}
-
-// eight k-steps of the 16 x 16 x 4 fp32 MFMA: A = this lane's row (dims 8 lg .. 8 lg + 7 as a | c), B = b[0..7]
-__device__ __forceinline__ f32x4 mfma_row8(const float* arow, const float (&b)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(arow);
-  const float4 c = *reinterpret_cast<const float4*>(arow + 4);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[3], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.x, b[4], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.y, b[5], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.z, b[6], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(c.w, b[7], acc, 0, 0, 0);
-  return acc;
-}
-
-__device__ __forceinline__ void load_row8(const float* row, float (&o)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(row);
-  const float4 c = *reinterpret_cast<const float4*>(row + 4);
-  o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = c.x; o[5] = c.y; o[6] = c.z; o[7] = c.w;
 }
 
 // Score and dP strip of one 16-query tile against the staged 64-key block: st[jt][r] = S[qi][kb0 + 16 jt + 4 lg + r] (scaled, bias and
@@ -164,7 +117,7 @@ __device__ __forceinline__ void score_strip(const float* Ks, const float* Vs, co
       const bool ok = qi < N && kb + r < N;
       const float bv = ok ? bias_g[(int64_t)qi * N + kb + r] : 0.f;
       const float mv = (ok && mask_w) ? mask_w[(int64_t)qi * N + kb + r] : 0.f;
-      acc[r] = (kb + r < N) ? (acc[r] * ls + bv) + mv : -INFINITY;
+      acc[r] = attn_score(acc[r], ls, bv, mv, kb + r < N, -INFINITY);
     }
     st[jt] = acc;
   }
@@ -379,7 +332,7 @@ __global__ __launch_bounds__(256) void win_attn_large_ann_bwd_key_kernel(AnnBwdP
         const bool ok = i < N && kj < N;
         const float bv = ok ? bias_g[(int64_t)i * N + kj] : 0.f;
         const float mv = (ok && mask_w) ? mask_w[(int64_t)i * N + kj] : 0.f;
-        const float sc = (acc[r] * ls + bv) + mv;
+        const float sc = attn_score(acc[r], ls, bv, mv, true, 0.f);
         p[r] = ok ? expf(sc - rm[il]) * rl[il] : 0.f;
         ds[r] = p[r] * (dacc[r] - rD[il]);
       }
@@ -529,16 +482,6 @@ constexpr int KBD = 256;              // keys per d_bias workgroup (one per thre
 constexpr int LDV = HD + 4;           // fp32 row of V in the d_bias kernel (float4 reads)
 
 __host__ __device__ inline int sew_dbias_tiles(int nH, int N) { return nH * ((N + RT - 1) / RT) * ((N + KBD - 1) / KBD); }
-
-// row n of window b, head g of the scrambled (T', B_, N1, C) layout
-__device__ inline const float* dout_row(const SdfWinAttnSewBwdDesc& d, int b, int g, int n) {
-  const int t = n / d.N1, n1 = n - t * d.N1;
-  return d.dout + (((int64_t)t * d.B_ + b) * d.N1 + n1) * (int64_t)(d.nH * HD) + g * HD;
-}
-
-__device__ inline float4 u8x4_f(uint32_t w) {
-  return make_float4((float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24));
-}
 
 // tokens n0 .. n0 + 63 of one head's contiguous N x 32 byte block -> dst[64 * 32] (zeros past N)
 __device__ __forceinline__ void stage_bytes(const uint8_t* head, int n0, int N, unsigned char* dst, int tid) {

@@ -16,6 +16,8 @@
 // the same bits - and stores exp(s - max) / sum.  SEW walks once and stores the score.
 // A key or query at or past N contributes nothing (a key: -inf before the maximum, no term in the sum) and is never stored.
 // No atomics: every element has one writer and every row sum one order, two calls give bit-equal results.
+// The query fragment, the K piece fetch and their F.normalize, the MFMA chain (the row as B operand: mfma_row8_b), the score rounding
+// and the reference-point step of the online softmax are win_attn_common.h's.
 #include "win_attn_common.h"
 #include "host_launch.h"
 
@@ -43,33 +45,8 @@ __global__ __launch_bounds__(256) void win_attn_scores_kernel(AttnParams P, floa
 
   // ---- A operand of S = Q K^T: Q[qi][8 lg .. 8 lg + 7], normalised (ANN) / the spikes as 0 or 1 (SEW) ----
   float qreg[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) qreg[i] = 0.f;
-  if (qi < N) {
-    if (MODE == SDF_ATTN_ANN) {
-      const float* base = qkv_row(d, b, qi, C) + g * HD + 8 * lg;
-      const float4 a = *reinterpret_cast<const float4*>(base), c = *reinterpret_cast<const float4*>(base + 4);
-      qreg[0] = a.x; qreg[1] = a.y; qreg[2] = a.z; qreg[3] = a.w; qreg[4] = c.x; qreg[5] = c.y; qreg[6] = c.z; qreg[7] = c.w;
-    } else {
-      const uint8_t* qp = reinterpret_cast<const uint8_t*>(d.q) + (((int64_t)b * d.nH + g) * N + qi) * HD + 8 * lg;
-      const uint32_t w0 = *reinterpret_cast<const uint32_t*>(qp), w1 = *reinterpret_cast<const uint32_t*>(qp + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        qreg[i] = ((w0 >> (8 * i)) & 0xff) ? 1.f : 0.f;
-        qreg[4 + i] = ((w1 >> (8 * i)) & 0xff) ? 1.f : 0.f;
-      }
-    }
-  }
-  if (MODE == SDF_ATTN_ANN) {                            // F.normalize(q, dim=-1): x / max(||x||_2, 1e-12)
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss += qreg[i] * qreg[i];
-    ss += __shfl_xor(ss, 16);
-    ss += __shfl_xor(ss, 32);
-    const float iq = 1.f / fmaxf(sqrtf(ss), 1e-12f);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) qreg[i] *= iq;
-  }
+  load_q_frag<MODE>(d, b, g, qi, lg, N, C, 1.f, qreg);
+  if (MODE == SDF_ATTN_ANN) norm_q_frag(qreg);
 
   // ---- a key block's K rows: 8 lanes per token row (one float4 each), 32 rows per pass ----
   constexpr int IT = KB / 32;
@@ -80,15 +57,8 @@ __global__ __launch_bounds__(256) void win_attn_scores_kernel(AttnParams P, floa
     for (int it = 0; it < IT; ++it) {
       const int r = kb0 + (tid >> 3) + 32 * it;
       kq[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < N) {
-        if (MODE == SDF_ATTN_ANN) {
-          kq[it] = *reinterpret_cast<const float4*>(qkv_row(d, b, r, C) + C + g * HD + 4 * piece);
-        } else {
-          const int64_t off = (((int64_t)b * d.nH + g) * N + r) * HD + 4 * piece;
-          const uint32_t wk = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(d.k) + off);
-          kq[it] = make_float4((float)(wk & 0xff), (float)((wk >> 8) & 0xff), (float)((wk >> 16) & 0xff), (float)(wk >> 24));
-        }
-      }
+      float4 unused;                                     // (no V here)
+      if (r < N) kv_piece<MODE, false>(d, b, g, r, piece, C, kq[it], unused);
     }
   };
   auto stash = [&]() __attribute__((always_inline)) {
@@ -96,14 +66,7 @@ __global__ __launch_bounds__(256) void win_attn_scores_kernel(AttnParams P, floa
     for (int it = 0; it < IT; ++it) {
       const int r = (tid >> 3) + 32 * it;                // row inside the block
       float4 kv = kq[it];
-      if (MODE == SDF_ATTN_ANN) {                        // F.normalize(k, dim=-1): the row's 8 lanes are neighbours
-        float sk = kv.x * kv.x + kv.y * kv.y + kv.z * kv.z + kv.w * kv.w;
-        sk += __shfl_xor(sk, 1);
-        sk += __shfl_xor(sk, 2);
-        sk += __shfl_xor(sk, 4);
-        const float ik = 1.f / fmaxf(sqrtf(sk), 1e-12f);
-        kv.x *= ik; kv.y *= ik; kv.z *= ik; kv.w *= ik;
-      }
+      if (MODE == SDF_ATTN_ANN) norm_row8(kv);           // F.normalize(k, dim=-1)
       *reinterpret_cast<float4*>(&Ks[r * LDW + 4 * piece]) = kv;
     }
   };
@@ -114,7 +77,6 @@ __global__ __launch_bounds__(256) void win_attn_scores_kernel(AttnParams P, floa
   const __amdgpu_buffer_rsrc_t bias_rs = make_rsrc_bounded(d.bias + (int64_t)g * N * N, tbytes);
   const __amdgpu_buffer_rsrc_t mask_rs = make_rsrc_bounded(HAS_MASK ? d.mask + (int64_t)(b % d.nW) * N * N : d.bias, HAS_MASK ? tbytes : 0u);
   float* const tile = scores + (int64_t)bg * N * N;      // this (window, head)'s N x N map
-  constexpr float L2E = 1.4426950408889634f;
 
   // ANN, per accumulator row r (query q0 + r): running maximum, sum, and the reference point -m log2e the sum's terms were made with
   float m_run[4], l_run[4], r_run[4];
@@ -149,30 +111,14 @@ __global__ __launch_bounds__(256) void win_attn_scores_kernel(AttnParams P, floa
     f32x4 st[KT];
 #pragma unroll
     for (int jt = 0; jt < KT; ++jt) {
-      const int kj = jt * 16 + l15;                      // B operand column: key (inside the block)
-      const float4 a = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg]);
-      const float4 c = *reinterpret_cast<const float4*>(&Ks[kj * LDW + 8 * lg + 4]);
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[0], a.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[1], a.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[2], a.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[3], a.w, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[4], c.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[5], c.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[6], c.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qreg[7], c.w, acc, 0, 0, 0);
-      st[jt] = acc;
+      st[jt] = mfma_row8_b(qreg, &Ks[(jt * 16 + l15) * LDW + 8 * lg]);   // B operand column: key (inside the block)
     }
     // ---- attn = qk * scale + bias (+ mask), separately rounded as the reference computes it; ANN: a key past N is -inf ----
 #pragma unroll
     for (int jt = 0; jt < KT; ++jt) {
       const bool kin = kb0 + jt * 16 + l15 < N;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s = st[jt][r] * ls + __uint_as_float(bb[jt][r]);
-        if (HAS_MASK) s += __uint_as_float(mm[jt][r]);
-        st[jt][r] = (MODE == SDF_ATTN_ANN && !kin) ? -INFINITY : s;
-      }
+      for (int r = 0; r < 4; ++r) st[jt][r] = attn_score<HAS_MASK>(st[jt][r], ls, bb[jt][r], mm[jt][r], MODE != SDF_ATTN_ANN || kin, -INFINITY);
     }
     if (MODE == SDF_ATTN_ANN && !second) {
       // every block holds at least one real key and bias and mask are finite, so a block's row maximum is finite (a caller's mask
@@ -184,11 +130,8 @@ __global__ __launch_bounds__(256) void win_attn_scores_kernel(AttnParams P, floa
         bm = fmaxf(bm, __shfl_xor(bm, 2));
         bm = fmaxf(bm, __shfl_xor(bm, 4));
         bm = fmaxf(bm, __shfl_xor(bm, 8));
-        const float m_new = fmaxf(m_run[r], bm);
-        // exp(x - m) = 2^(x log2e - m log2e): one fma + the hardware exp2; the old terms move from the ROUNDED reference point
-        // that made them to the new rounded one exactly, so a reference point's rounding cancels in the final division
-        const float mneg = (m_new == -INFINITY) ? 0.f : -m_new * L2E;
-        const float alpha = (m_run[r] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mneg - r_run[r]);   // first block: nothing to scale
+        float mneg, alpha;                               // the new reference point, the old terms' factor (win_attn_common.h)
+        const float m_new = softmax_ref_step(m_run[r], r_run[r], bm, mneg, alpha);
         float psum = 0.f;
 #pragma unroll
         for (int jt = 0; jt < KT; ++jt) psum += __builtin_amdgcn_exp2f(fmaf(st[jt][r], L2E, mneg));
@@ -223,21 +166,16 @@ __global__ __launch_bounds__(256) void win_attn_scores_kernel(AttnParams P, floa
 extern "C" int sdf_win_attn_scores_fwd(const SdfWinAttnDesc* d, float* scores, void* stream) {
   if (!d) return SDF_E_NULL;
   if (!d->q || (d->mode == SDF_ATTN_SEW && !d->k) || !d->scale || !d->bias || (d->row_map && !d->pad_qkv)) return SDF_E_NULL;
-  if (d->mode != SDF_ATTN_ANN && d->mode != SDF_ATTN_SEW) return SDF_E_DTYPE;
-  if (d->hd != HD || d->B_ < 1 || d->nH < 1 || d->N < 1 || d->N > N_MAX) return SDF_E_SHAPE;
-  if (d->mask && (d->nW < 1 || d->B_ % d->nW)) return SDF_E_SHAPE;
-  if (d->mode == SDF_ATTN_SEW && (d->Tq < 1 || d->N1 < 1 || d->Tq * d->N1 != d->N)) return SDF_E_SHAPE;
+  if (const int rc = sdf_win_attn_shape_rc(d, 1, N_MAX)) return rc;
   if (d->mode == SDF_ATTN_SEW && d->row_map) return SDF_E_SHAPE;    // windowing through the map is the ANN form
   if (!scores) return SDF_E_NULL;
   if (!sdf_aligned(scores, 4)) return SDF_E_ALIGN;
   if (!sdf_aligned(d->q, d->mode == SDF_ATTN_ANN ? 16 : 4)) return SDF_E_ALIGN;                    // float4 rows / 4 spikes per load
   if (d->mode == SDF_ATTN_SEW ? !sdf_aligned(d->k, 4) : (d->row_map && !sdf_aligned(d->pad_qkv, 16))) return SDF_E_ALIGN;
-  const int64_t groups = ((d->N + 15) / 16 + 3) / 4;                // workgroups of 64 queries per (window, head)
-  if ((int64_t)d->B_ * d->nH * groups >= (1LL << 31)) return SDF_E_SHAPE;
-  AttnParams P;
-  P.d = *d;
-  if (!d->mask) P.d.nW = 1;
-  const dim3 grid((unsigned)((int64_t)d->B_ * d->nH * groups)), block(256);
+  const int64_t wgs = sdf_win_attn_group_grid(d);
+  if (!wgs) return SDF_E_SHAPE;
+  const AttnParams P = sdf_win_attn_params(d);
+  const dim3 grid((unsigned)wgs), block(256);
   hipStream_t s = sdf_stream(stream);
   sdf_dispatch(SdfList<SDF_ATTN_ANN, SDF_ATTN_SEW>{}, d->mode, [&](auto mode) {
     if (d->mask) {

@@ -15,11 +15,11 @@
 //   float atomics: two calls give bit-equal results.
 // Arithmetic: fp32 FMA on the vector ALU throughout (the spikes are exact 0 / 1, dO and the Grams stay fp32; on gfx950 the fp32 vector
 // rate equals the exact fp32 MFMA rate, MI355X_MICROARCH: 157.3 TFLOPS).
-#include "common.h"
+// The head dimension, the spike unpack u8x4_f and dout_row (the forward's output scramble) are win_attn_common.h's.
+#include "win_attn_common.h"
 
 namespace {
 
-constexpr int HD = 32;
 constexpr int NMAX = 192;             // the forward's limit (12 tiles of 16 tokens)
 constexpr int LDO = HD + 1;           // padded fp32 row of dO (floats)
 constexpr int LDG = HD + 4;           // Gram row (floats; float4 reads)
@@ -28,8 +28,6 @@ constexpr int LDB = MT + 1;
 constexpr int RT = 16;                // query rows per d_bias workgroup
 constexpr int LDV = HD + 4;           // fp32 row of V in the d_bias kernel (float4 reads)
 constexpr int DBIAS_TARGET_WG = 2048; // grid the d_bias split aims for
-
-__host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 // windows per d_bias run: a function of the shape only, so the summation order is too
 __host__ __device__ inline int dbias_run(int B_, int nH, int N) {
@@ -48,16 +46,6 @@ __host__ __device__ inline int dO_floats(int N) { return (N * LDO + 3) & ~3; }  
 
 size_t main_lds_bytes(int N) {
   return (size_t)3 * N * HD + (size_t)(dO_floats(N) + 2 * HD * LDG + N * LDB) * sizeof(float);
-}
-
-// row n of window b, head g of the scrambled (T', B_, N1, C) layout
-__device__ inline const float* dout_row(const SdfWinAttnSewBwdDesc& d, int b, int g, int n) {
-  const int t = n / d.N1, n1 = n - t * d.N1;
-  return d.dout + (((int64_t)t * d.B_ + b) * d.N1 + n1) * (int64_t)(d.nH * HD) + g * HD;
-}
-
-__device__ inline float4 u8x4_f(uint32_t w) {
-  return make_float4((float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24));
 }
 
 __global__ __launch_bounds__(256) void sew_bwd_kernel(SdfWinAttnSewBwdDesc d) {
