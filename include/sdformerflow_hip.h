@@ -1179,6 +1179,62 @@ typedef struct SdfFlowMetricsDesc {
 int64_t sdf_flow_metrics_workspace_bytes(int B, int H, int W);
 int sdf_flow_metrics_fwd(const SdfFlowMetricsDesc* d, void* stream);
 
+/* the largest batch of one sdf_augment_chunk_fwd / sdf_augment_resize_fwd call: their per-sample arrays travel as kernel arguments */
+#define SDF_AUGMENT_MAX_B 64
+
+/* ---------------------------------------------------------------------------------------------
+ * An MDR loader item -> the training step's (input, label, mask): the reference's DenseSparseAugmentor (MDR_dataloader/loader_utils.py:
+ * 244-341; MDR.py:218-241) - bilinear rescale, flow * scale, flips, crop, valid mask - followed by the loop's cat((old, new), dim=1),
+ * polarity split and preparation (train_mdr_supervised_SNN.py:209-276), with the random decisions drawn by the caller.
+ * Added to SDF_VERSION 107 (no existing entry changed).
+ * vox_old, vox_new (B, bins, Hs, Ws) fp32 signed (the loader's d_event_volume_old / _new; vox_old may be NULL when num_chunks is 1 and is
+ * not read then), flow (B, 2, Hs, Ws) fp32.  Per sample b (host arrays, B <= SDF_AUGMENT_MAX_B entries used; scale_x / scale_y point
+ * at B host doubles, read during the call): resized[b]; the scales; the resized size rh[b], rw[b] = rint(Hs scale_y), rint(Ws scale_x)
+ * (half to even), or (Hs, Ws) when not resized; flags[b] bit 0 horizontal, bit 1 vertical flip; the crop origin oy[b], ox[b] in the
+ * flipped, resized image.  Order, as the reference: resize, horizontal flip, vertical flip, crop.
+ *   output pixel (y, x) lies at (oy + y, ox + x) of the flipped image = (vflip ? rh-1-(oy+y) : oy+y, hflip ? rw-1-(ox+x) : ox+x) of the
+ *   resized one.  Each axis maps that index d as cv2.resize(INTER_LINEAR) does for a source of n elements: c = (float)((d + 0.5) / scale
+ *   - 0.5) with 1 / scale, the product and the difference in double; i = floor(c), a = c - i in float; i < 0: i = 0, a = 0;
+ *   i >= n - 1: i = n - 1, a = 0; second tap min(i + 1, n - 1).  value = (S[y0][x0] (1 - ax) + S[y0][x1] ax) (1 - ay) + (S[y1][x0]
+ *   (1 - ax) + S[y1][x1] ax) ay, every product and sum rounded to fp32 on its own: bit for bit the numpy restatement
+ *   (MDR_dataloader.loader_utils.resize_linear).  A real cv2 build may contract the vertical pass: unchecked.  resized[b] == 0: the one
+ *   source pixel, copied.
+ *   label_out (B, 2, h, w) = (float)((double)value * scale * sign), sign -1 for the x component under a horizontal and the y component
+ *   under a vertical flip, scale 1 when not resized;
+ *   mask_out (B, 1, h, w) fp32 = !isinf(u) && !isinf(v) && sqrt(u u + v v) > 0 on those doubles before the rounding (a NaN, and two
+ *   zeros, give 0).  The reference evaluates the norm in fp32 for an item that is neither resized nor flipped, where components below
+ *   about 1e-23 underflow to "invalid"; the double rule is used throughout here;
+ *   out (B, nF, 2, h, w), nF = num_chunks * bins, the old volume's bins first = relu(v) | relu(-v), then norm / per_sample /
+ *   use_spike_th / event_mask as SdfPrepareChunkDesc; mask_events: mask_out is multiplied by the event mask.
+ * Launches: [clear the min / max pairs] | gather + split | [finish]; nothing is allocated, nothing waits for the host.
+ * workspace: sdf_augment_resize_workspace_bytes(B) bytes, 8-byte aligned (0: refused B).
+ * SDF_E_SHAPE: B outside 1 .. SDF_AUGMENT_MAX_B, a dimension or a crop side < 1, a resized sample whose scale is not finite and positive
+ * or whose size is not rint(Hs scale_y) x rint(Ws scale_x), a sample that is not resized with another size than the source's, a size
+ * smaller than the crop, an origin outside [0, rh - h] x [0, rw - w] (all checked for every sample before anything is launched), a
+ * short workspace; SDF_E_DTYPE: norm outside 0 | 1, num_chunks outside 1 | 2, a flags word with other bits; SDF_E_NULL: d, scale_x,
+ * scale_y (the geometry check reads them: refused first), vox_new, flow, out, label_out, mask_out or workspace NULL, vox_old NULL with
+ * num_chunks 2; SDF_E_ALIGN: an fp32 pointer not 4-byte or the workspace not 8-byte aligned. */
+typedef struct SdfAugmentResizeDesc {
+  const float* vox_old;
+  const float* vox_new;
+  const float* flow;
+  const double* scale_x;
+  const double* scale_y;
+  float* out;
+  float* label_out;
+  float* mask_out;
+  float* event_mask;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t B, bins, Hs, Ws, crop_h, crop_w, num_chunks;
+  int32_t norm, per_sample, use_spike_th, mask_events;
+  float spike_th;
+  int32_t resized[64], rh[64], rw[64], oy[64], ox[64], flags[64];
+} SdfAugmentResizeDesc;
+
+int64_t sdf_augment_resize_workspace_bytes(int B);
+int sdf_augment_resize_fwd(const SdfAugmentResizeDesc* d, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * A loader item -> the training step's (input, label, mask): the reference loops' Compose([RandomCrop, Random_horizontal_flip,
  * Random_vertical_flip, Random_event_drop]) (DSEC_dataloader/data_augmentation.py) followed by the preparation below
@@ -1202,8 +1258,6 @@ int sdf_flow_metrics_fwd(const SdfFlowMetricsDesc* d, void* stream);
  * [0, Hs - h] x [0, Ws - w] (checked for every sample before anything is launched), a short workspace; SDF_E_DTYPE: norm outside 0 | 1,
  * a flags word with other bits; SDF_E_NULL: d, voxel, out or workspace NULL, label / valid without its output or the reverse,
  * mask_events without mask_out; SDF_E_ALIGN: an fp32 pointer not 4-byte or the workspace not 8-byte aligned. */
-#define SDF_AUGMENT_MAX_B 64
-
 typedef struct SdfAugmentChunkDesc {
   const float* voxel;
   const float* label;

@@ -10,7 +10,7 @@ restated twice over one set of parameters:
   stream, so after a batch that drops `torch`'s generator stands where the reference's stood BEFORE its `rand_like`.
 
 As in the reference one set of parameters serves the whole batch; the kernel's per-sample arrays are filled with equal values.
-The rotation (`RandomRotationFlip`) is not built, and neither is the MDR loader's `DenseSparseAugmentor`.
+The rotation (`RandomRotationFlip`) is not built.  The MDR loader's `DenseSparseAugmentor` is MDR_dataloader.loader_utils'.
 """
 import numbers
 import random

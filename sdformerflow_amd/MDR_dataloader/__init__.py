@@ -1,3 +1,3 @@
-"""The event front end of the reference's MDR_dataloader (MVSEC / MDR), on the GPU: loader_utils.EventSequence and
-loader_utils.EventSequenceToVoxelGrid_Pytorch.  File readers and the MDR augmentor (DenseSparseAugmentor) are out of scope; the crop,
-flip and event-drop transforms the training loops compose are DSEC_dataloader.data_augmentation's."""
+"""The reference's MDR_dataloader (MVSEC / MDR) for the GPU: loader_utils.EventSequence and loader_utils.EventSequenceToVoxelGrid_Pytorch
+(the event front end), and loader_utils.DenseSparseAugmentor, whose draws hip.augment_resize_chunk applies on the device.  File readers
+are out of scope; the crop, flip and event-drop transforms the DSEC training loops compose are DSEC_dataloader.data_augmentation's."""

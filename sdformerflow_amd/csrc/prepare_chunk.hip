@@ -11,7 +11,14 @@
 // sdf_augment_chunk_fwd is the training loops' front of the same preparation (reference train_flow_parallel_supervised_SNN.py:155-171,
 // :241-308; DSEC_dataloader/data_augmentation.py): its first kernel gathers a per-sample crop window with flips and the event drop - of
 // the voxel, the flow and the valid mask - before the split; the finish kernel is shared.
+//
+// sdf_augment_resize_fwd is the MDR training items' front (reference MDR_dataloader/loader_utils.py DenseSparseAugmentor, MDR.py:218-241,
+// train_mdr_supervised_SNN.py:209-276): its first kernel gathers through a per-sample bilinear rescale (cv2.resize INTER_LINEAR restated,
+// four taps), the flips and the crop - of the old and new dense event volumes and of the flow, which it scales and from which it derives
+// the valid mask - before the same split; the finish kernel is shared.  The split's store and min / max code (pc_split_store,
+// pc_minmax_commit) and the clear / finish launches (pc_clear_pairs, pc_finish) are stated once for the three entry points.
 #include "common.h"
+#include <cmath>
 
 namespace {
 
@@ -22,11 +29,50 @@ struct PcGeom {
 // relu as ATen's device clamp_min forms it: NaN stays, else fmaxf(v, 0) = v_max_f32, which orders -0 below +0: relu(-0) = +0
 __device__ __forceinline__ float pc_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
 
+// the polarity split of one signed value: relu(v) | relu(-v) into the pixel's pair of planes (`pair` = the pixel in the first of them),
+// and the non-zeros into the lane's (~min, max) of bit patterns
+__device__ __forceinline__ void pc_split_store(float v, float* __restrict__ pair, int hw, unsigned& nlo, unsigned& hi) {
+  const float o1 = pc_relu(v), o2 = pc_relu(-v);
+  pair[0] = o1;
+  pair[hw] = o2;
+  if (o1 != 0.f) {
+    nlo = max(nlo, ~__float_as_uint(o1));
+    hi = max(hi, __float_as_uint(o1));
+  }
+  if (o2 != 0.f) {
+    nlo = max(nlo, ~__float_as_uint(o2));
+    hi = max(hi, __float_as_uint(o2));
+  }
+}
+
+// the lanes' (~min, max) -> wave -> workgroup (256 threads, every one of them arrives) -> one pair of atomics on `q`: same-address
+// atomics serialise in L2, and a pair per wave cost more than the pass itself
+__device__ __forceinline__ void pc_minmax_commit(unsigned nlo, unsigned hi, unsigned* __restrict__ q) {
+  for (int off = 32; off > 0; off >>= 1) {
+    nlo = max(nlo, (unsigned)__shfl_xor((int)nlo, off));
+    hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
+  }
+  __shared__ unsigned red[4][2];
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6][0] = nlo;
+    red[threadIdx.x >> 6][1] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    nlo = max(max(red[0][0], red[1][0]), max(red[2][0], red[3][0]));
+    hi = max(max(red[0][1], red[1][1]), max(red[2][1], red[3][1]));
+    if (hi != 0u) {
+      atomicMax(&q[0], nlo);
+      atomicMax(&q[1], hi);
+    }
+  }
+}
+
 // sample blockIdx.y, cells strided over the sample's gridDim.x workgroups: out = relu(v) | relu(-v) on the crop window, and the pair
 // {~min, max} of the bit patterns of the non-zeros into mm[2 g], g = the sample (per_sample) or 0 (the whole batch tensor)
 __global__ __launch_bounds__(256) void prepare_split_kernel(const float* __restrict__ voxel, float* __restrict__ out, PcGeom g,
                                                             unsigned* __restrict__ mm, int want_minmax, int per_sample) {
-  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int b = blockIdx.y;
   const int hw = g.h * g.w;
   const int cells = g.bins * hw;                                           // (< 2^31: pc_geom)
   const float* src = voxel + (int64_t)b * g.bins * g.Hs * g.Ws;
@@ -36,39 +82,9 @@ __global__ __launch_bounds__(256) void prepare_split_kernel(const float* __restr
     const int i = (int)i64, c = i / hw, p = i - c * hw;
     const int y = p / g.w, x = p % g.w;
     const float v = src[((int64_t)c * g.Hs + g.oy + y) * g.Ws + g.ox + x];
-    const float o1 = pc_relu(v), o2 = pc_relu(-v);
-    dst[(int64_t)c * 2 * hw + p] = o1;
-    dst[(int64_t)c * 2 * hw + hw + p] = o2;
-    if (o1 != 0.f) {
-      nlo = max(nlo, ~__float_as_uint(o1));
-      hi = max(hi, __float_as_uint(o1));
-    }
-    if (o2 != 0.f) {
-      nlo = max(nlo, ~__float_as_uint(o2));
-      hi = max(hi, __float_as_uint(o2));
-    }
+    pc_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
   }
-  if (!want_minmax) return;
-  for (int off = 32; off > 0; off >>= 1) {
-    nlo = max(nlo, (unsigned)__shfl_xor((int)nlo, off));
-    hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-  }
-  // one pair of atomics per workgroup: same-address atomics serialise in L2, and a pair per wave cost more than the pass itself
-  __shared__ unsigned red[4][2];
-  if (lane == 0) {
-    red[threadIdx.x >> 6][0] = nlo;
-    red[threadIdx.x >> 6][1] = hi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    nlo = max(max(red[0][0], red[1][0]), max(red[2][0], red[3][0]));
-    hi = max(max(red[0][1], red[1][1]), max(red[2][1], red[3][1]));
-    if (hi != 0u) {
-      unsigned* q = mm + 2 * (per_sample ? b : 0);
-      atomicMax(&q[0], nlo);
-      atomicMax(&q[1], hi);
-    }
-  }
+  if (want_minmax) pc_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
 }
 
 // the per-sample parameters of sdf_augment_chunk_fwd, copied from the descriptor's host arrays into the kernel arguments (832 bytes)
@@ -109,7 +125,7 @@ __global__ __launch_bounds__(256) void augment_split_kernel(const float* __restr
                                                             float* __restrict__ out, float* __restrict__ label_out,
                                                             float* __restrict__ mask_out, PcGeom g, AugParams a, unsigned* __restrict__ mm,
                                                             int want_minmax, int per_sample, int valid_is_u8, uint64_t seed, uint64_t offset) {
-  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int b = blockIdx.y;
   const int hw = g.h * g.w;
   const int cells = g.bins * hw;                                           // (< 2^30: aug_geom)
   const int oy = a.oy[b], ox = a.ox[b];
@@ -130,17 +146,7 @@ __global__ __launch_bounds__(256) void augment_split_kernel(const float* __restr
       const float u = drop_u ? drop_u[cell] : aug_philox_u((uint64_t)cell, seed, offset);
       v = v * (u > q ? 1.f : 0.f);
     }
-    const float o1 = pc_relu(v), o2 = pc_relu(-v);
-    dst[(int64_t)c * 2 * hw + p] = o1;
-    dst[(int64_t)c * 2 * hw + hw + p] = o2;
-    if (o1 != 0.f) {
-      nlo = max(nlo, ~__float_as_uint(o1));
-      hi = max(hi, __float_as_uint(o1));
-    }
-    if (o2 != 0.f) {
-      nlo = max(nlo, ~__float_as_uint(o2));
-      hi = max(hi, __float_as_uint(o2));
-    }
+    pc_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
   }
   if (label || valid) {
     for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {
@@ -158,26 +164,92 @@ __global__ __launch_bounds__(256) void augment_split_kernel(const float* __restr
       }
     }
   }
-  if (!want_minmax) return;
-  for (int off = 32; off > 0; off >>= 1) {
-    nlo = max(nlo, (unsigned)__shfl_xor((int)nlo, off));
-    hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
+  if (want_minmax) pc_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
+}
+
+// the per-sample parameters of sdf_augment_resize_fwd in the kernel arguments (2624 bytes): the position in the resized image of output
+// pixel (y, x) is (by + sy y, bx + sx x), sy / sx = -1 under a flip (flags bit 1 / bit 0), by / bx = the origin in the flipped image
+// taken back through the flips; inv = 1 / scale and mul = the flow's factor, scale * sign (1 or -1 for a sample that is not resized:
+// flags bit 2 clear)
+struct RzParams {
+  double inv_x[SDF_AUGMENT_MAX_B], inv_y[SDF_AUGMENT_MAX_B], mul_x[SDF_AUGMENT_MAX_B], mul_y[SDF_AUGMENT_MAX_B];
+  int32_t by[SDF_AUGMENT_MAX_B], bx[SDF_AUGMENT_MAX_B];
+  uint8_t flags[SDF_AUGMENT_MAX_B];
+};
+
+// one axis of cv2.resize(INTER_LINEAR) as OpenCV forms it: destination index d of a source of n elements at inverse scale `inv` ->
+// taps i0, i1 = min(i0 + 1, n - 1) and the weight a of the second; c = (float)((d + 0.5) inv - 0.5) with the product and the difference
+// in double, i0 = floor(c), a = c - i0 in float; below the first element and from the last one on, the one border element at weight 0.
+// Whatever `inv` is, 0 <= i0 <= i1 <= n - 1.
+__device__ __forceinline__ void rz_axis(int d, double inv, int n, int& i0, int& i1, float& a) {
+  const float c = (float)__dsub_rn(__dmul_rn((double)d + 0.5, inv), 0.5);
+  const float fl = floorf(c);
+  int i = (int)fminf(fmaxf(fl, -1.f), (float)n);                          // (converted inside the int range; a NaN becomes -1)
+  a = __fsub_rn(c, fl);
+  if (i < 0) {
+    i = 0;
+    a = 0.f;
   }
-  __shared__ unsigned red[4][2];                                           // one pair of atomics per workgroup, as prepare_split_kernel
-  if (lane == 0) {
-    red[threadIdx.x >> 6][0] = nlo;
-    red[threadIdx.x >> 6][1] = hi;
+  if (i >= n - 1) {
+    i = n - 1;
+    a = 0.f;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    nlo = max(max(red[0][0], red[1][0]), max(red[2][0], red[3][0]));
-    hi = max(max(red[0][1], red[1][1]), max(red[2][1], red[3][1]));
-    if (hi != 0u) {
-      unsigned* r = mm + 2 * (per_sample ? b : 0);
-      atomicMax(&r[0], nlo);
-      atomicMax(&r[1], hi);
+  i0 = i;
+  i1 = min(i + 1, n - 1);
+}
+
+// the four taps of one plane in OpenCV's order - the horizontal pass on both rows, then the vertical one - every product and sum
+// rounded to float on its own
+__device__ __forceinline__ float rz_taps(const float* __restrict__ r0, const float* __restrict__ r1, int x0, int x1, float ax0, float ax1,
+                                         float ay0, float ay1) {
+  const float top = __fadd_rn(__fmul_rn(r0[x0], ax0), __fmul_rn(r0[x1], ax1));
+  const float bot = __fadd_rn(__fmul_rn(r1[x0], ax0), __fmul_rn(r1[x1], ax1));
+  return __fadd_rn(__fmul_rn(top, ay0), __fmul_rn(bot, ay1));
+}
+
+// The MDR loader's DenseSparseAugmentor - bilinear rescale, flow * scale, flips, crop, valid mask - and the training loop's
+// cat((old, new), dim=1) and polarity split in one pass: sample blockIdx.y, one lane per output pixel (x fastest, strided over the
+// sample's workgroups) over the nF voxel planes and the two flow planes.  A pixel's taps and weights are formed once; a sample that is
+// not resized copies its one source pixel.  The flow is (float)((double)value * mul); the mask is decided on the two doubles.
+__global__ __launch_bounds__(256) void augment_resize_kernel(const float* __restrict__ vox_old, const float* __restrict__ vox_new,
+                                                             const float* __restrict__ flow, float* __restrict__ out,
+                                                             float* __restrict__ label_out, float* __restrict__ mask_out, PcGeom g,
+                                                             int nF, RzParams a, unsigned* __restrict__ mm, int want_minmax,
+                                                             int per_sample) {
+  const int b = blockIdx.y;
+  const int hw = g.h * g.w;
+  const int sy = a.flags[b] & 2 ? -1 : 1, sx = a.flags[b] & 1 ? -1 : 1;
+  const bool resized = a.flags[b] & 4;
+  const int64_t plane = (int64_t)g.Hs * g.Ws;
+  const int n_old = nF - g.bins;                                           // (0 or bins: the old volume's planes come first)
+  float* dst = out + (int64_t)b * nF * 2 * hw;
+  unsigned nlo = 0u, hi = 0u;                                              // (~min, max) over nothing
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {
+    const int y = p / g.w, x = p % g.w;
+    int y0 = a.by[b] + sy * y, x0 = a.bx[b] + sx * x, y1 = y0, x1 = x0;
+    float ay = 0.f, ax = 0.f;
+    if (resized) {
+      rz_axis(y0, a.inv_y[b], g.Hs, y0, y1, ay);
+      rz_axis(x0, a.inv_x[b], g.Ws, x0, x1, ax);
     }
+    const float ay0 = __fsub_rn(1.f, ay), ax0 = __fsub_rn(1.f, ax);
+    const int64_t o0 = (int64_t)y0 * g.Ws, o1 = (int64_t)y1 * g.Ws;
+    for (int c = 0; c < nF; ++c) {
+      const float* src = c < n_old ? vox_old + ((int64_t)b * g.bins + c) * plane : vox_new + ((int64_t)b * g.bins + c - n_old) * plane;
+      const float v = resized ? rz_taps(src + o0, src + o1, x0, x1, ax0, ax, ay0, ay) : src[o0 + x0];
+      pc_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
+    }
+    const float* fu = flow + (int64_t)b * 2 * plane;
+    const float u = resized ? rz_taps(fu + o0, fu + o1, x0, x1, ax0, ax, ay0, ay) : fu[o0 + x0];
+    const float v = resized ? rz_taps(fu + plane + o0, fu + plane + o1, x0, x1, ax0, ax, ay0, ay) : fu[plane + o0 + x0];
+    const double du = __dmul_rn((double)u, a.mul_x[b]), dv = __dmul_rn((double)v, a.mul_y[b]);
+    label_out[(int64_t)b * 2 * hw + p] = (float)du;
+    label_out[(int64_t)b * 2 * hw + hw + p] = (float)dv;
+    // ~isinf(u) & ~isinf(v) & (norm > 0): a NaN fails the comparison, and so do two zeros
+    const bool on = !isinf(du) && !isinf(dv) && __dadd_rn(__dmul_rn(du, du), __dmul_rn(dv, dv)) > 0.0;
+    mask_out[(int64_t)b * hw + p] = on ? 1.f : 0.f;
   }
+  if (want_minmax) pc_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
 }
 
 // prepare_chunk's tail, one lane per pixel of a sample over its 2 bins planes: (v - lo) / (hi - lo) on the non-zeros when there are any
@@ -255,6 +327,65 @@ bool aug_geom(const SdfAugmentChunkDesc* d, PcGeom& g, AugParams& a) {
   return true;
 }
 
+// Geometry check of sdf_augment_resize_fwd and the kernel's per-sample arguments; false = SDF_E_SHAPE.  Per sample: a scale that is
+// finite and positive and a resized size (rh, rw) = rint(Hs scale_y), rint(Ws scale_x) (half to even, as cvRound) - or, not resized,
+// the source's own size -, no smaller than the crop, and an origin inside [0, rh - h] x [0, rw - w].  The kernel then addresses rows
+// 0 .. rh - 1 of the resized image, and rz_axis keeps every tap inside the source.
+bool rz_geom(const SdfAugmentResizeDesc* d, PcGeom& g, RzParams& a) {
+  const int lim = 1 << 20;
+  if (d->B < 1 || d->B > SDF_AUGMENT_MAX_B || d->bins < 1 || d->Hs < 1 || d->Ws < 1 || d->Hs > lim || d->Ws > lim) return false;
+  if (d->crop_h < 1 || d->crop_w < 1) return false;
+  g.B = d->B;
+  g.bins = d->bins;
+  g.Hs = d->Hs;
+  g.Ws = d->Ws;
+  g.oy = g.ox = 0;                                                         // (per sample: RzParams)
+  g.h = d->crop_h;
+  g.w = d->crop_w;
+  if ((int64_t)2 * g.bins * g.h * g.w >= (1ll << 30) || (int64_t)g.bins * g.Hs * g.Ws >= (1ll << 34)) return false;
+  for (int b = 0; b < SDF_AUGMENT_MAX_B; ++b) {
+    a.inv_x[b] = a.inv_y[b] = a.mul_x[b] = a.mul_y[b] = 1.0;
+    a.by[b] = a.bx[b] = 0;
+    a.flags[b] = 0;
+    if (b >= g.B) continue;
+    const int rh = d->rh[b], rw = d->rw[b];
+    const bool hflip = d->flags[b] & 1, vflip = d->flags[b] & 2;
+    if (d->resized[b]) {
+      const double sx = d->scale_x[b], sy = d->scale_y[b];
+      if (!(sx > 0.0) || !(sy > 0.0) || std::isinf(sx) || std::isinf(sy)) return false;
+      if ((double)rh != std::nearbyint(g.Hs * sy) || (double)rw != std::nearbyint(g.Ws * sx)) return false;
+      a.inv_x[b] = 1.0 / sx;
+      a.inv_y[b] = 1.0 / sy;
+      a.mul_x[b] = sx;
+      a.mul_y[b] = sy;
+    } else if (rh != g.Hs || rw != g.Ws) {
+      return false;
+    }
+    if (rh < g.h || rw < g.w || rh > lim || rw > lim) return false;
+    if (d->oy[b] < 0 || d->ox[b] < 0 || d->oy[b] > rh - g.h || d->ox[b] > rw - g.w) return false;
+    if (hflip) a.mul_x[b] = -a.mul_x[b];
+    if (vflip) a.mul_y[b] = -a.mul_y[b];
+    a.by[b] = vflip ? rh - 1 - d->oy[b] : d->oy[b];
+    a.bx[b] = hflip ? rw - 1 - d->ox[b] : d->ox[b];
+    a.flags[b] = (uint8_t)((d->flags[b] & 3) | (d->resized[b] ? 4 : 0));
+  }
+  return true;
+}
+
+// every pair {~min, max} the call uses: no non-zero element
+int pc_clear_pairs(unsigned* mm, int pairs, hipStream_t s) { return (int)hipMemsetAsync(mm, 0, (size_t)8 * pairs, s); }
+
+// the launch of prepare_finish_kernel when something is left to do: min-max, threshold, event mask, mask * event mask
+int pc_finish(float* out, float* event_mask, float* mul, int B, int hw, int planes, const unsigned* mm, int want_minmax, int per_sample,
+              int use_th, float th, hipStream_t s) {
+  if (!want_minmax && !use_th && !event_mask && !mul) return 0;
+  const int64_t pixels = (int64_t)B * hw;
+  SDF_LAUNCH(prepare_finish_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, out, event_mask, pixels, hw, planes, mm,
+             want_minmax, per_sample, use_th, th, mul);
+  SDF_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t sdf_prepare_chunk_workspace_bytes(int B) { return B >= 1 && B <= 65535 ? (int64_t)8 * B : 0; }
@@ -270,11 +401,9 @@ extern "C" int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream)
     return SDF_E_ALIGN;
   hipStream_t s = sdf_stream(stream);
   unsigned* mm = static_cast<unsigned*>(d->workspace);
+  int rc = 0;
   const int per_sample = d->per_sample != 0, want_minmax = d->norm == 1;
-  if (want_minmax) {
-    const hipError_t e = hipMemsetAsync(mm, 0, (size_t)8 * (per_sample ? g.B : 1), s);     // every pair: no non-zero element
-    if (e != hipSuccess) return (int)e;
-  }
+  if (want_minmax && (rc = pc_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
   const int hw = g.h * g.w;
   const int64_t cells = (int64_t)g.bins * hw;
   // at most 1024 workgroups in all (one atomic pair each), at least one per sample
@@ -282,13 +411,7 @@ extern "C" int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream)
   const dim3 block(256), sgrid((unsigned)(need < cap ? need : cap), g.B);
   SDF_LAUNCH(prepare_split_kernel, sgrid, block, 0, s, d->voxel, d->out, g, mm, want_minmax, per_sample);
   SDF_LAUNCH_CHECK();
-  if (want_minmax || d->use_spike_th || d->event_mask) {
-    const int64_t pixels = (int64_t)g.B * hw;
-    SDF_LAUNCH(prepare_finish_kernel, dim3((unsigned)((pixels + 255) / 256)), block, 0, s, d->out, d->event_mask, pixels, hw, 2 * g.bins, mm,
-               want_minmax, per_sample, d->use_spike_th, d->spike_th, (float*)nullptr);
-    SDF_LAUNCH_CHECK();
-  }
-  return 0;
+  return pc_finish(d->out, d->event_mask, nullptr, g.B, hw, 2 * g.bins, mm, want_minmax, per_sample, d->use_spike_th, d->spike_th, s);
 }
 
 extern "C" int64_t sdf_augment_chunk_workspace_bytes(int B) { return B >= 1 && B <= SDF_AUGMENT_MAX_B ? (int64_t)8 * B : 0; }
@@ -311,11 +434,9 @@ extern "C" int sdf_augment_chunk_fwd(const SdfAugmentChunkDesc* d, void* stream)
     return SDF_E_ALIGN;
   hipStream_t s = sdf_stream(stream);
   unsigned* mm = static_cast<unsigned*>(d->workspace);
+  int rc = 0;
   const int per_sample = d->per_sample != 0, want_minmax = d->norm == 1;
-  if (want_minmax) {
-    const hipError_t e = hipMemsetAsync(mm, 0, (size_t)8 * (per_sample ? g.B : 1), s);     // every pair: no non-zero element
-    if (e != hipSuccess) return (int)e;
-  }
+  if (want_minmax && (rc = pc_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
   const int hw = g.h * g.w;
   const int64_t cells = (int64_t)g.bins * hw;
   // the grid of sdf_prepare_chunk_fwd: at most 1024 workgroups in all (one atomic pair each), at least one per sample
@@ -324,12 +445,38 @@ extern "C" int sdf_augment_chunk_fwd(const SdfAugmentChunkDesc* d, void* stream)
   SDF_LAUNCH(augment_split_kernel, sgrid, block, 0, s, d->voxel, d->label, d->valid, d->drop_u, d->out, d->label_out, d->mask_out, g, a, mm,
              want_minmax, per_sample, d->valid_is_u8 != 0, (uint64_t)d->seed, (uint64_t)d->offset);
   SDF_LAUNCH_CHECK();
-  float* mul = d->mask_events ? d->mask_out : nullptr;
-  if (want_minmax || d->use_spike_th || d->event_mask || mul) {
-    const int64_t pixels = (int64_t)g.B * hw;
-    SDF_LAUNCH(prepare_finish_kernel, dim3((unsigned)((pixels + 255) / 256)), block, 0, s, d->out, d->event_mask, pixels, hw, 2 * g.bins, mm,
-               want_minmax, per_sample, d->use_spike_th, d->spike_th, mul);
-    SDF_LAUNCH_CHECK();
-  }
-  return 0;
+  return pc_finish(d->out, d->event_mask, d->mask_events ? d->mask_out : nullptr, g.B, hw, 2 * g.bins, mm, want_minmax, per_sample,
+                   d->use_spike_th, d->spike_th, s);
+}
+
+extern "C" int64_t sdf_augment_resize_workspace_bytes(int B) { return sdf_augment_chunk_workspace_bytes(B); }
+
+extern "C" int sdf_augment_resize_fwd(const SdfAugmentResizeDesc* d, void* stream) {
+  if (!d || !d->scale_x || !d->scale_y) return SDF_E_NULL;                 // (the geometry check reads the scales)
+  PcGeom g;
+  RzParams a;
+  if (!rz_geom(d, g, a)) return SDF_E_SHAPE;                               // every sample's window lies inside its resized image
+  if (d->norm < 0 || d->norm > 1) return SDF_E_DTYPE;                      // 0 none | 1 min-max ("std" stays the torch function's)
+  if (d->num_chunks < 1 || d->num_chunks > 2) return SDF_E_DTYPE;          // data.num_chunks: the new volume, or old | new
+  for (int b = 0; b < g.B; ++b)
+    if (d->flags[b] & ~3) return SDF_E_DTYPE;                              // bit 0 horizontal, bit 1 vertical
+  if (!d->vox_new || !d->flow || !d->out || !d->label_out || !d->mask_out || !d->workspace) return SDF_E_NULL;
+  if (d->num_chunks == 2 && !d->vox_old) return SDF_E_NULL;
+  if (d->workspace_bytes < (int64_t)8 * d->B) return SDF_E_SHAPE;
+  if (!sdf_aligned(d->vox_old, 4) || !sdf_aligned(d->vox_new, 4) || !sdf_aligned(d->flow, 4) || !sdf_aligned(d->out, 4) ||
+      !sdf_aligned(d->label_out, 4) || !sdf_aligned(d->mask_out, 4) || !sdf_aligned(d->event_mask, 4) || !sdf_aligned(d->workspace, 8))
+    return SDF_E_ALIGN;
+  hipStream_t s = sdf_stream(stream);
+  unsigned* mm = static_cast<unsigned*>(d->workspace);
+  int rc = 0;
+  const int per_sample = d->per_sample != 0, want_minmax = d->norm == 1;
+  if (want_minmax && (rc = pc_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
+  const int hw = g.h * g.w, nF = d->num_chunks * g.bins;
+  // a lane per output pixel; as its siblings at most 1024 workgroups in all (one atomic pair each), at least one per sample
+  const int cap = 1024 / g.B > 1 ? 1024 / g.B : 1, need = (hw + 255) / 256;
+  SDF_LAUNCH(augment_resize_kernel, dim3((unsigned)(need < cap ? need : cap), g.B), dim3(256), 0, s, d->vox_old, d->vox_new, d->flow, d->out,
+             d->label_out, d->mask_out, g, nF, a, mm, want_minmax, per_sample);
+  SDF_LAUNCH_CHECK();
+  return pc_finish(d->out, d->event_mask, d->mask_events ? d->mask_out : nullptr, g.B, hw, 2 * nF, mm, want_minmax, per_sample,
+                   d->use_spike_th, d->spike_th, s);
 }

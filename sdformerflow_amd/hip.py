@@ -285,6 +285,17 @@ class PrepareChunkDesc(C.Structure):
 AUGMENT_MAX_B = 64                       # SDF_AUGMENT_MAX_B
 
 
+class AugmentResizeDesc(C.Structure):
+    _fields_ = [("vox_old", C.c_void_p), ("vox_new", C.c_void_p), ("flow", C.c_void_p), ("scale_x", C.c_void_p), ("scale_y", C.c_void_p),
+                ("out", C.c_void_p), ("label_out", C.c_void_p), ("mask_out", C.c_void_p), ("event_mask", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("B", C.c_int32), ("bins", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32),
+                ("num_chunks", C.c_int32), ("norm", C.c_int32), ("per_sample", C.c_int32), ("use_spike_th", C.c_int32),
+                ("mask_events", C.c_int32), ("spike_th", C.c_float),
+                ("resized", C.c_int32 * 64), ("rh", C.c_int32 * 64), ("rw", C.c_int32 * 64), ("oy", C.c_int32 * 64), ("ox", C.c_int32 * 64),
+                ("flags", C.c_int32 * 64)]
+
+
 class AugmentChunkDesc(C.Structure):
     _fields_ = [("voxel", C.c_void_p), ("label", C.c_void_p), ("valid", C.c_void_p), ("drop_u", C.c_void_p), ("out", C.c_void_p),
                 ("label_out", C.c_void_p), ("mask_out", C.c_void_p), ("event_mask", C.c_void_p), ("workspace", C.c_void_p),
@@ -423,6 +434,7 @@ SIGNATURES = {
     "sdf_event_voxel_tb_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i, _i, _i, _i)),
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
     "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
+    "sdf_augment_resize_workspace_bytes": (_i64, (_i,)), "sdf_augment_resize_fwd": (_i, (_P(AugmentResizeDesc), _p)),
     "sdf_augment_chunk_workspace_bytes": (_i64, (_i,)), "sdf_augment_chunk_fwd": (_i, (_P(AugmentChunkDesc), _p)),
     "sdf_prepare_chunk_workspace_bytes": (_i64, (_i,)), "sdf_prepare_chunk_fwd": (_i, (_P(PrepareChunkDesc), _p)),
     "sdf_flow_image_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_image_fwd": (_i, (_P(FlowImageDesc), _p)),
@@ -2437,6 +2449,74 @@ def augment_chunk(voxel, label, valid, crop, origins, flips, drop_q=None, drop_u
     planes = bins * (3 + (drop_u is not None)) + 4 * (label is not None) + (valid is not None) + 4 * bins * (d.norm == 1 or spike_th is not None)
     _note(bytes=B * h * w * (4 * planes + (valid.element_size() if valid is not None else 0)), shape=(B, bins, 2, h, w))
     _check(lib().sdf_augment_chunk_fwd(C.byref(d), _stream()), "sdf_augment_chunk_fwd")
+    return out, label_out, mask_out
+
+
+def augment_resize_chunk(vox_old, vox_new, flow, crop, params, norm_input="minmax", spike_th=None, per_sample=False, mask_events=False,
+                         out=None, label_out=None, mask_out=None, event_mask=None):
+    """An MDR loader item -> the training step's (input, label, mask) on the GPU without a host round trip (sdf_augment_resize_fwd): the
+    reference's DenseSparseAugmentor (MDR_dataloader.loader_utils) - bilinear rescale, flow * scale, flips, crop, valid mask - then the
+    loop's cat((old, new), dim=1), harness.prepare_chunk and, with `mask_events`, mask * event_mask.  vox_old (or None: data.num_chunks
+    1) and vox_new (B, bins, Hs, Ws) fp32 signed, flow (B, 2, Hs, Ws) fp32; `crop` (h, w); `params`: one parameter record for every
+    sample or a sequence of B (what DenseSparseAugmentor.sample / sample_batch return: resized, scale_x, scale_y, size, hflip, vflip,
+    y0, x0).  norm_input / spike_th / per_sample / event_mask as hip.prepare_chunk.  Returns (out (B, nF, 2, h, w) with nF = bins or
+    2 bins, old first; label_out (B, 2, h, w); mask_out (B, 1, h, w) fp32); `out`, `label_out`, `mask_out`: contiguous tensors of those
+    shapes to write into."""
+    _ptr(vox_new, torch.float32)
+    if vox_new.dim() != 4:
+        raise SdfError(f"augment_resize_chunk: vox_new is (B, bins, H, W), got {tuple(vox_new.shape)}")
+    vox_new = vox_new.contiguous()
+    B, bins, Hs, Ws = vox_new.shape
+    if B > AUGMENT_MAX_B:
+        raise SdfError(f"augment_resize_chunk: batch of {B} refused (at most {AUGMENT_MAX_B} per call)", rc=E_SHAPE)
+    if vox_old is not None:
+        _ptr(vox_old, torch.float32)
+        if vox_old.shape != vox_new.shape:
+            raise SdfError(f"augment_resize_chunk: vox_old is vox_new's {tuple(vox_new.shape)}, got {tuple(vox_old.shape)}")
+        vox_old = vox_old.contiguous()
+    _ptr(flow, torch.float32)
+    if tuple(flow.shape) != (B, 2, Hs, Ws):
+        raise SdfError(f"augment_resize_chunk: flow is {(B, 2, Hs, Ws)}, got {tuple(flow.shape)}")
+    flow = flow.contiguous()
+    h, w = crop
+    nF = bins * (1 + (vox_old is not None))
+    dev = vox_new.device
+
+    def buffer(t, shape, name):
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise SdfError(f"augment_resize_chunk: {name} must be a contiguous {shape} tensor")
+        return t
+    out = buffer(out, (B, nF, 2, h, w), "out")
+    label_out = buffer(label_out, (B, 2, h, w), "label_out")
+    mask_out = buffer(mask_out, (B, 1, h, w), "mask_out")
+    if event_mask is not None and (tuple(event_mask.shape) != (B, 1, h, w) or not event_mask.is_contiguous()):
+        raise SdfError(f"augment_resize_chunk: event_mask must be a contiguous {(B, 1, h, w)} tensor")
+    rows = [params] * B if not isinstance(params, (list, tuple)) else list(params)
+    if len(rows) != B:
+        raise SdfError(f"augment_resize_chunk: params is one record or {B} of them (one per sample), got {len(rows)}")
+    need = lib().sdf_augment_resize_workspace_bytes(B)
+    if need <= 0:
+        raise SdfError(f"augment_resize_chunk: batch of {B} refused", rc=E_SHAPE)
+    ws = _stream_ws(_PC_WS, dev, max(need, 256))
+    d = AugmentResizeDesc()
+    sx, sy = ((C.c_double * B)(*(float(getattr(p, k)) for p in rows)) for k in ("scale_x", "scale_y"))
+    d.vox_old, d.vox_new, d.flow = _ptr(vox_old), vox_new.data_ptr(), flow.data_ptr()
+    d.scale_x, d.scale_y = C.addressof(sx), C.addressof(sy)                # (host arrays, read during the call)
+    d.out, d.label_out, d.mask_out = _ptr(out, torch.float32), _ptr(label_out, torch.float32), _ptr(mask_out, torch.float32)
+    d.event_mask, d.workspace, d.workspace_bytes = _ptr(event_mask, torch.float32), ws.data_ptr(), ws.numel()
+    d.B, d.bins, d.Hs, d.Ws, d.crop_h, d.crop_w, d.num_chunks = B, bins, Hs, Ws, int(h), int(w), 1 + (vox_old is not None)
+    d.norm, d.per_sample = {None: 0, "minmax": 1}.get(norm_input, 2), int(bool(per_sample))   # (anything else is the library's to refuse)
+    d.use_spike_th, d.spike_th, d.mask_events = int(spike_th is not None), float(spike_th or 0.0), int(bool(mask_events))
+    for b, p in enumerate(rows):
+        d.resized[b], (d.rh[b], d.rw[b]), d.oy[b], d.ox[b] = int(bool(p.resized)), (int(v) for v in p.size), int(p.y0), int(p.x0)
+        d.flags[b] = int(bool(p.hflip)) | int(bool(p.vflip)) << 1
+    # four taps (one when not resized) of every plane read, input / label / mask written once, the finish's read-modify-write of the input
+    taps = sum(4 if p.resized else 1 for p in rows) / B
+    planes = (nF + 2) * taps + 2 * nF + 3 + 4 * nF * (d.norm == 1 or spike_th is not None)
+    _note(bytes=int(B * h * w * 4 * planes), shape=(B, nF, 2, h, w))
+    _check(lib().sdf_augment_resize_fwd(C.byref(d), _stream()), "sdf_augment_resize_fwd")
     return out, label_out, mask_out
 
 

@@ -26,6 +26,9 @@ Reference semantics mirrored (file:line under /root/reference):
   step                    train_flow_parallel_supervised_SNN.py:233-336 (reset, forward, loss, backward, clip 100, AdamW)
   loader item -> step     ...:155-171, :241-308 (crop, flips, drop, split, min-max, threshold, mask * event_mask): `prepare_train_item`
                           on csrc/prepare_chunk.hip (hip.augment_chunk), `train_step_from_item`
+  MDR loader item -> step MDR_dataloader/loader_utils.py:244-341, MDR.py:218-241, train_mdr_supervised_SNN.py:209-276 (rescale, flow *
+                          scale, flips, crop, valid, cat, split, min-max, threshold, mask * event_mask): `prepare_mdr_item` on
+                          csrc/prepare_chunk.hip (hip.augment_resize_chunk), `train_step_from_mdr_item`
   data parallelism        the reference wraps the model in DataParallel: replicas, local batch statistics, summed
                           gradients; here one process per GPU and ONE bucketed all-reduce(sum)/world per step (RCCL)
 """
@@ -1082,4 +1085,100 @@ def train_step_from_item(model, optimizer, item, config, transform, step=0, **tr
     """`train_step` on a loader item (chunk, label, mask): `prepare_train_item`, then the step unchanged.  Returns its loss."""
     chunk, label, mask = item
     x, label, mask = prepare_train_item(chunk, label, mask, config, transform, step=step)
+    return train_step(model, optimizer, x, label, mask, **train_step_kwargs)
+
+
+# ---------------------------------------------------------------------------------------------- from an MDR loader item to the step
+def mdr_train_augmentor(config):
+    """The MDR training set's augmentor (MDR_dataloader/MDR.py:65): DenseSparseAugmentor(loader.crop, loader.min_scale,
+    loader.max_scale, do_flip=True)."""
+    from .MDR_dataloader.loader_utils import DenseSparseAugmentor
+    loader = config["loader"]
+    return DenseSparseAugmentor(loader["crop"], min_scale=loader["min_scale"], max_scale=loader["max_scale"], do_flip=True)
+
+
+def _mdr_volumes(sample, config):
+    """(d_event_volume_old or None, d_event_volume_new, flow) of a loader dict: the pair the loop reads (train_mdr_supervised_SNN.py:
+    209-214), the old volume only with data.num_chunks 2."""
+    chunks = int(config["data"].get("num_chunks", 1))
+    if chunks not in (1, 2):
+        raise ValueError(f"data.num_chunks is 1 or 2, got {chunks}")
+    return (sample["d_event_volume_old"] if chunks == 2 else None), sample["d_event_volume_new"], sample["flow"]
+
+
+def _mdr_axis_torch(idx, n_src, f):
+    """loader_utils._linear_axis on a device tensor of destination indices: (first tap, second tap, the second tap's weight fp32)."""
+    c = ((idx.double() + 0.5) * (1.0 / float(f)) - 0.5).float()
+    fl = c.floor()
+    i, a = fl.long(), c - fl
+    low, high = i < 0, i >= n_src - 1
+    i = torch.where(low, torch.zeros_like(i), torch.where(high, torch.full_like(i, n_src - 1), i))
+    return i, (i + 1).clamp(max=n_src - 1), torch.where(low | high, torch.zeros_like(a), a)
+
+
+def prepare_mdr_item_torch(sample, config, augmentor, params=None):
+    """`prepare_mdr_item` as a torch sequence on the tensors' device: per sample the index gathers of DenseSparseAugmentor under its
+    record - the four taps combined in fp32 in cv2's order, one torch operation per product and sum; the flow scaled and the valid
+    mask decided in fp64 - then the loop's cat, harness.prepare_chunk and mask * event_mask.  What the kernel is compared with, and what
+    serves `norm_input: std`, `loader.polarity: false` (volumes (B, bins, 2, Hs, Ws)) and the `cnt` encoding.  Returns (x, label, mask
+    (B, 1, h, w) fp32)."""
+    from . import harness
+    old, new, flow = _mdr_volumes(sample, config)
+    B, (Hs, Ws), (h, w) = new.shape[0], new.shape[-2:], augmentor.crop_size
+    params = augmentor.sample_batch(B, (Hs, Ws)) if params is None else params
+    dev = new.device
+    chunks, labels, masks = [], [], []
+    for b, p in enumerate(params):
+        vols = ([old[b]] if old is not None else []) + [new[b]]
+        planes = torch.cat([v.reshape(-1, Hs, Ws).float() for v in vols] + [flow[b].float()])
+        ys, xs = p.y0 + torch.arange(h, device=dev), p.x0 + torch.arange(w, device=dev)
+        ys, xs = (p.size[0] - 1 - ys if p.vflip else ys), (p.size[1] - 1 - xs if p.hflip else xs)
+        if p.resized:
+            y0, y1, ay = _mdr_axis_torch(ys, Hs, p.scale_y)
+            x0, x1, ax = _mdr_axis_torch(xs, Ws, p.scale_x)
+            top, bot = planes[:, y0], planes[:, y1]
+            top = top[:, :, x0] * (1 - ax) + top[:, :, x1] * ax
+            bot = bot[:, :, x0] * (1 - ax) + bot[:, :, x1] * ax
+            got = top * (1 - ay)[:, None] + bot * ay[:, None]
+        else:
+            got = planes[:, ys][:, :, xs]
+        mul = [(p.scale_x if p.resized else 1.0) * (-1.0 if p.hflip else 1.0), (p.scale_y if p.resized else 1.0) * (-1.0 if p.vflip else 1.0)]
+        f64 = got[-2:].double() * torch.tensor(mul, dtype=torch.float64, device=dev)[:, None, None]
+        masks.append((~torch.isinf(f64[0]) & ~torch.isinf(f64[1]) & ((f64[0] * f64[0] + f64[1] * f64[1]).sqrt() > 0))[None].float())
+        labels.append(f64.float())
+        parts = torch.split(got[:-2], [v.numel() // (Hs * Ws) for v in vols])
+        chunks.append(torch.cat([g.reshape(*v.shape[:-2], h, w) for g, v in zip(parts, vols)]))
+    chunk, label, mask = torch.stack(chunks), torch.stack(labels), torch.stack(masks)
+    voxel = config["model"].get("encoding", "voxel") == "voxel"
+    polarity = bool(config["loader"].get("polarity", True))
+    if not voxel and polarity and chunk.dim() == 5:
+        chunk = chunk.reshape(chunk.shape[0], -1, *chunk.shape[3:])
+    x = harness.prepare_chunk(chunk, config["model"].get("norm_input"), config["data"].get("spike_th"), voxel and polarity)
+    if config.get("metrics", {}).get("mask_events"):
+        mask = mask * x.reshape(x.shape[0], -1, *x.shape[-2:]).sum(1, keepdim=True).bool()
+    return x.contiguous(), label.contiguous(), mask.contiguous()
+
+
+def prepare_mdr_item(sample, config, augmentor, params=None):
+    """An MDR loader item - the loader's dict with `d_event_volume_old`, `d_event_volume_new` (B, bins, Hs, Ws) and `flow`
+    (B, 2, Hs, Ws), un-augmented, on the GPU - to `train_step`'s (x, label, mask): `augmentor.sample_batch` draws every item's scale,
+    flips and crop origin as the reference's DenseSparseAugmentor does in Dataset.__getitem__ (`params`: records drawn already), and
+    hip.augment_resize_chunk (csrc/prepare_chunk.hip) applies them together with the loop's cat, polarity split and preparation in at
+    most three launches, without asking the host; bit for bit `prepare_mdr_item_torch` under the same records.  Read from `config`:
+    data.num_chunks (1: the new volume alone), model.norm_input, data.spike_th, metrics.mask_events.  `norm_input: std`,
+    `loader.polarity: false` and the `cnt` encoding run the torch sequence."""
+    norm = config["model"].get("norm_input")
+    if norm not in (None, "minmax") or not config["loader"].get("polarity", True) or config["model"].get("encoding", "voxel") != "voxel":
+        return prepare_mdr_item_torch(sample, config, augmentor, params)
+    old, new, flow = _mdr_volumes(sample, config)
+    if params is None:
+        params = augmentor.sample_batch(new.shape[0], tuple(new.shape[-2:]))
+    return hip.augment_resize_chunk(old, new, flow, tuple(augmentor.crop_size), params, norm_input=norm,
+                                    spike_th=config["data"].get("spike_th"),
+                                    mask_events=bool(config.get("metrics", {}).get("mask_events")))
+
+
+def train_step_from_mdr_item(model, optimizer, sample, config, augmentor, params=None, **train_step_kwargs):
+    """`train_step` on an MDR loader item: `prepare_mdr_item`, then the step unchanged.  Returns its loss."""
+    x, label, mask = prepare_mdr_item(sample, config, augmentor, params)
     return train_step(model, optimizer, x, label, mask, **train_step_kwargs)
