@@ -1179,6 +1179,48 @@ typedef struct SdfFlowMetricsDesc {
 int64_t sdf_flow_metrics_workspace_bytes(int B, int H, int W);
 int sdf_flow_metrics_fwd(const SdfFlowMetricsDesc* d, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Decoder predictions of every level -> the supervised multi-scale flow loss (reference loss/flow_supervised.py:85-102, gamma None)
+ * and its gradient at each level's own resolution: the training twin of the metrics above.  Added to SDF_VERSION 107 (no existing entry
+ * changed).  `levels` (1 .. SDF_FLOW_LOSS_MAX_LEVELS) predictions; level i: pred[i] (T[i], B, 2, h[i], w[i]) contiguous, of `dtype`
+ * (SDF_FLOW_LOSS_F32 / _BF16 / _F16, one for all levels), T[i] in 1 .. 64, factor s = H / h[i] = W / w[i] in {1, 2, 4, 8, 16} - the
+ * factors at which F.interpolate's nearest index floor(dst * (1 / s)) in fp32 equals dst / s.  label (B, 2, H, W), mask (B, H, W) fp32
+ * (the caller's mask * event_mask); n_valid: one fp32 on the device (the valid-pixel count the errors are divided by, all-reduced or
+ * not).  At full-resolution pixel (Y, X), every step one fp32 operation, constants Python doubles rounded to fp32:
+ *   f = sum_t pred[i][t][b][c][Y / s][X / s]   (t ascending; 16-bit inputs: rounded once to the input type when T > 1)
+ *   d = f * flow_scaling - label;  r = sqrtf(dx dx + dy dy + 1e-8);  err = r * m          (the mask multiplies, it does not select)
+ *   S[i][b] = sum err over the sample, an fp64 sum of the fp32 values -> records[i * B + b] (records may be NULL)
+ *   loss[0] = mean_b sum_i lambda_mod S[i][b] / (n_valid + 1e-9) / levels, in fp64 with n_valid + 1e-9 formed in fp32, rounded once
+ *   grad[i] (B, 2, h[i], w[i]) fp32 = the sum over the s x s block, row-major, of m * d_c / r * k,
+ *     k = fp32(flow_scaling lambda_mod / (levels B)) / (n_valid + 1e-9): d loss / d f at the level's resolution.
+ * grad[i] is given for every level or for none (loss only).  One partial launch over 16 x 64 tiles of the frame and one finish launch,
+ * whatever `levels`; label and mask are read once; no float atomics; every output element is written once; bit-identical from run to
+ * run, and a sample's records depend on that sample alone.
+ * workspace: as many bytes as sdf_flow_loss_workspace_bytes returns for (B, H, W, levels), 8-byte aligned (0: refused geometry - B
+ * outside 1 .. 65535, H W >= 2^30, levels outside 1 .. 8). */
+#define SDF_FLOW_LOSS_MAX_LEVELS 8
+#define SDF_FLOW_LOSS_F32 0
+#define SDF_FLOW_LOSS_BF16 1
+#define SDF_FLOW_LOSS_F16 2
+
+typedef struct SdfFlowLossDesc {
+  const void* pred[8];
+  float* grad[8];
+  int32_t h[8], w[8], T[8];
+  const float* label;
+  const float* mask;
+  const float* n_valid;
+  float* loss;
+  double* records;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t levels, B, H, W, dtype;
+  float flow_scaling, lambda_mod;
+} SdfFlowLossDesc;
+
+int64_t sdf_flow_loss_workspace_bytes(int B, int H, int W, int levels);
+int sdf_flow_loss_fwd(const SdfFlowLossDesc* d, void* stream);
+
 /* the largest batch of one sdf_augment_chunk_fwd / sdf_augment_resize_fwd call: their per-sample arrays travel as kernel arguments */
 #define SDF_AUGMENT_MAX_B 64
 

@@ -430,3 +430,26 @@ class WinAttnSewFunction(torch.autograd.Function):
         bwd = hip.win_attn_sew_bwd if Tq * N1 <= hip.ATTN_BWD_MAX_N else hip.win_attn_sew_bwd_large
         dq, dk, dv, d_bias = bwd(qu, ku, vu, scale, b, mask, nH, Tq, B_, N1, dout.float().contiguous())
         return dq.to(dtype), dk.to(dtype), dv.to(dtype), d_bias, None, None, None
+
+
+class FlowLossFunction(torch.autograd.Function):
+    """The supervised multi-scale flow loss on the raw decoder predictions (T_i, B, 2, h_i, w_i) (reference loss/flow_supervised.py:
+    85-102 behind the models' sum over time and nearest upsampling): forward `hip.flow_loss` (csrc/flow_loss.hip, two launches), which
+    also leaves d loss / d preds[i].sum(0) as fp32 (B, 2, h_i, w_i) - the only tensors saved.  Backward: per level one multiplication by
+    the incoming scalar, formed in fp32 and stored in the prediction's dtype (so an fp16 gradient is cast with the loss scale already in
+    it), expanded over T as a stride-0 view.  Nothing at full resolution exists in either direction."""
+
+    @staticmethod
+    def forward(ctx, label, mask, n_valid, flow_scaling, lambda_mod, *preds):
+        loss, grads = hip.flow_loss([p.detach() for p in preds], label, mask, n_valid, flow_scaling, lambda_mod, grads=True)
+        ctx.save_for_backward(*grads)
+        ctx.cfg = [(p.shape[0], p.dtype) for p in preds]
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        out = []
+        for g, (T, dtype) in zip(ctx.saved_tensors, ctx.cfg):
+            scaled = torch.mul(g, grad_loss.float(), out=torch.empty(g.shape, dtype=dtype, device=g.device))   # fp32 product, one store
+            out.append(scaled.unsqueeze(0).expand(T, *g.shape))
+        return (None, None, None, None, None, *out)

@@ -275,6 +275,16 @@ class FlowMetricsDesc(C.Structure):
                 ("row0", C.c_int32), ("rows", C.c_int32), ("flow_scaling", C.c_float)]
 
 
+FLOW_LOSS_MAX_LEVELS = 8                 # SDF_FLOW_LOSS_MAX_LEVELS
+
+
+class FlowLossDesc(C.Structure):
+    _fields_ = [("pred", C.c_void_p * 8), ("grad", C.c_void_p * 8), ("h", C.c_int32 * 8), ("w", C.c_int32 * 8), ("T", C.c_int32 * 8),
+                ("label", C.c_void_p), ("mask", C.c_void_p), ("n_valid", C.c_void_p), ("loss", C.c_void_p), ("records", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("levels", C.c_int32), ("B", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("dtype", C.c_int32), ("flow_scaling", C.c_float), ("lambda_mod", C.c_float)]
+
+
 class PrepareChunkDesc(C.Structure):
     _fields_ = [("voxel", C.c_void_p), ("out", C.c_void_p), ("event_mask", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_int64), ("B", C.c_int32), ("bins", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32),
@@ -434,6 +444,7 @@ SIGNATURES = {
     "sdf_event_voxel_tb_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i, _i, _i, _i)),
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
     "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
+    "sdf_flow_loss_workspace_bytes": (_i64, (_i, _i, _i, _i)), "sdf_flow_loss_fwd": (_i, (_P(FlowLossDesc), _p)),
     "sdf_augment_resize_workspace_bytes": (_i64, (_i,)), "sdf_augment_resize_fwd": (_i, (_P(AugmentResizeDesc), _p)),
     "sdf_augment_chunk_workspace_bytes": (_i64, (_i,)), "sdf_augment_chunk_fwd": (_i, (_P(AugmentChunkDesc), _p)),
     "sdf_prepare_chunk_workspace_bytes": (_i64, (_i,)), "sdf_prepare_chunk_fwd": (_i, (_P(PrepareChunkDesc), _p)),
@@ -2321,6 +2332,81 @@ def flow_metrics(pred, label, valid, event_mask=None, flow_scaling=1.0, table=No
     _note(bytes=B * H * W * (5 + (event_mask is not None)) * 4, shape=(B, H, W))
     _check(lib().sdf_flow_metrics_fwd(C.byref(d), _stream()), "sdf_flow_metrics_fwd")
     return table
+
+
+FLOW_LOSS_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}          # SDF_FLOW_LOSS_F32 / _BF16 / _F16
+FLOW_LOSS_FACTORS = (1, 2, 4, 8, 16)
+_FL_WS = {}
+
+
+def flow_loss(preds, label, mask, n_valid, flow_scaling=1.0, lambda_mod=1.0, grads=True, records=None, loss=None):
+    """The supervised multi-scale flow loss and its gradient on the GPU (sdf_flow_loss_fwd: two launches whatever the number of levels,
+    no read-back): `preds` a list of up to 8 raw decoder predictions (T_i, B, 2, h_i, w_i), contiguous, all fp32, bf16 or fp16, each a
+    factor 1, 2, 4, 8 or 16 below label (B, 2, H, W) fp32; mask (B, H, W) or (B, 1, H, W) fp32; `n_valid` one fp32 on the device
+    (train.global_valid_count).  What train.flow_loss_supervised computes on forward_train's summed, nearest-upsampled flows - per pixel
+    the same fp32 operations, fp64 sums in a fixed order - without a full-resolution tensor per level.  Returns (loss, grads): loss a
+    0-dim fp32 tensor; grads [d loss / d preds[i].sum(0)] as fp32 (B, 2, h_i, w_i) tensors, or None with `grads` False (loss only).
+    `grads` a list of contiguous fp32 tensors: written into.  `records`: a contiguous (levels, B) float64 tensor receiving each level's
+    per-sample sum of err * mask.  `loss`: a 1-element fp32 tensor to write into."""
+    preds = list(preds)
+    if not 1 <= len(preds) <= FLOW_LOSS_MAX_LEVELS:
+        raise SdfError(f"flow_loss: 1 .. {FLOW_LOSS_MAX_LEVELS} prediction levels, got {len(preds)}", rc=E_SHAPE)
+    for a in (label, mask, n_valid):
+        _ptr(a, torch.float32)
+    if label.dim() != 4 or label.shape[1] != 2:
+        raise SdfError(f"flow_loss: label is (B, 2, H, W), got {tuple(label.shape)}")
+    B, _, H, W = label.shape
+    if mask.numel() != B * H * W or tuple(mask.shape[-2:]) != (H, W):
+        raise SdfError(f"flow_loss: mask is (B, H, W) or (B, 1, H, W) at the label's size, got {tuple(mask.shape)}")
+    if n_valid.numel() != 1:
+        raise SdfError(f"flow_loss: n_valid is one fp32 value on the device, got {tuple(n_valid.shape)}")
+    dtype = preds[0].dtype
+    if dtype not in FLOW_LOSS_DTYPES:
+        raise SdfError(f"flow_loss: predictions are float32, bfloat16 or float16, got {dtype}", rc=E_DTYPE)
+    dev = label.device
+    label, mask = label.contiguous(), mask.contiguous()
+    want = grads is not False and grads is not None
+    given = list(grads) if want and grads is not True else None
+    if given is not None and len(given) != len(preds):
+        raise SdfError(f"flow_loss: {len(given)} gradient tensors for {len(preds)} levels")
+    d = FlowLossDesc()
+    keep, out = [], []
+    for i, p in enumerate(preds):
+        _ptr(p, dtype)
+        if p.dim() != 5 or p.shape[1] != B or p.shape[2] != 2:
+            raise SdfError(f"flow_loss: level {i} is (T, {B}, 2, h, w), got {tuple(p.shape)}")
+        T, h, w = p.shape[0], p.shape[3], p.shape[4]
+        if h < 1 or w < 1 or H % h or W % w or H // h != W // w or H // h not in FLOW_LOSS_FACTORS:
+            raise SdfError(f"flow_loss: level {i} at {h} x {w} is not a factor {FLOW_LOSS_FACTORS} below {H} x {W}", rc=E_SHAPE)
+        if not 1 <= T <= 64:
+            raise SdfError(f"flow_loss: level {i} has {T} time steps (1 .. 64)", rc=E_SHAPE)
+        p = p.contiguous()
+        keep.append(p)
+        d.pred[i], d.h[i], d.w[i], d.T[i] = p.data_ptr(), h, w, T
+        if want:
+            g = torch.empty((B, 2, h, w), dtype=torch.float32, device=dev) if given is None else given[i]
+            if _ptr(g, torch.float32) is None or tuple(g.shape) != (B, 2, h, w) or not g.is_contiguous():
+                raise SdfError(f"flow_loss: the gradient of level {i} is a contiguous {(B, 2, h, w)} float32 tensor")
+            out.append(g)
+            d.grad[i] = g.data_ptr()
+    if records is not None and (_ptr(records, torch.float64) is None or tuple(records.shape) != (len(preds), B)
+                                or not records.is_contiguous()):
+        raise SdfError(f"flow_loss: records is a contiguous {(len(preds), B)} float64 tensor")
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    elif _ptr(loss, torch.float32) is None or loss.numel() != 1:
+        raise SdfError("flow_loss: loss is a 1-element float32 tensor")
+    need = lib().sdf_flow_loss_workspace_bytes(B, H, W, len(preds))
+    if need <= 0:
+        raise SdfError(f"flow_loss: geometry refused (B {B}, {H} x {W}, {len(preds)} levels)", rc=E_SHAPE)
+    ws = _stream_ws(_FL_WS, dev, need)
+    d.label, d.mask, d.n_valid, d.loss, d.records = label.data_ptr(), mask.data_ptr(), n_valid.data_ptr(), loss.data_ptr(), _ptr(records)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    d.levels, d.B, d.H, d.W, d.dtype = len(preds), B, H, W, FLOW_LOSS_DTYPES[dtype]
+    d.flow_scaling, d.lambda_mod = float(flow_scaling), float(lambda_mod)
+    _note(bytes=B * H * W * 12 + sum(p.numel() * p.element_size() for p in keep) + sum(g.numel() * 4 for g in out), shape=(B, H, W))
+    _check(lib().sdf_flow_loss_fwd(C.byref(d), _stream()), "sdf_flow_loss_fwd")
+    return loss.reshape(()), (out if want else None)
 
 
 def prepare_chunk(voxel, crop=None, norm_input="minmax", spike_th=None, per_sample=False, out=None, crop_origin=None, event_mask=None):

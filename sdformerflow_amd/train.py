@@ -11,7 +11,9 @@ same stream (MIOpen); their replacements are the next row.  Behind the backward 
 statistics (`vis.store_grads`), the clip coefficient and the AdamW update on the flat buckets (csrc/grad_step.hip), without a host
 synchronisation - also under fp16 autocast with a `LossScaler` (torch.amp.GradScaler's arithmetic on the device: a step with a
 non-finite gradient is skipped by the kernels) and with gradient accumulation (`num_acc`: the running sum is clipped in place);
-with any other optimiser torch's clip_grad_norm_ and step.  Nothing here touches `oracle/`, and CPU
+with any other optimiser torch's clip_grad_norm_ and step.  Between the two, opt-in (`train_step(head="hip")`): the multi-scale loss
+and its gradient on the decoder levels' raw predictions in two launches (`flow_loss_hip`, csrc/flow_loss.hip); the default head is
+the torch composition `flow_loss_supervised`.  Nothing here touches `oracle/`, and CPU
 tensors are refused by the neuron kernels (`SdfError`).
 
 Reference semantics mirrored (file:line under /root/reference):
@@ -246,11 +248,24 @@ def skip_concat_ch(x1, x2):
     return torch.cat([F.pad(x1, (dX // 2, dX - dX // 2, dY // 2, dY - dY // 2)), x2], dim=2)
 
 
+def _flows_of_preds(preds, H, W):
+    """The models' tail on the raw predictions: sum over time, nearest upsampling to (H, W) - one (B, 2, H, W) map per level."""
+    flows = []
+    for f in preds:
+        f = f.sum(0)
+        flows.append(F.interpolate(f, scale_factor=(H / f.shape[-2], W / f.shape[-1])))
+    return flows
+
+
 def forward_train(model, x):
     """(B, bins, 2, H, W) on the GPU -> list of flow maps (B, 2, H, W), differentiable; BN running stats are updated."""
+    return _flows_of_preds(forward_train_preds(model, x), *x.shape[-2:])
+
+
+def forward_train_preds(model, x):
+    """`forward_train` up to the decoder levels' raw predictions: a list of (T, B, 2, h, w), coarsest first (what `flow_loss_hip` takes)."""
     if not x.is_cuda:
         raise hip.SdfError("the training path runs on the GPU only (no CPU fallback)")
-    H, W = x.shape[-2:]
     unet = model.sttmultires_unet
     sw = unet.encoders.swin3d
     y = patch_embed(x.float(), sw.patch_embed).permute(1, 0, 3, 4, 2).contiguous()          # (B, D, h, w, C)
@@ -277,11 +292,7 @@ def forward_train(model, x):
         z = F.conv_transpose2d(s.flatten(0, 1), dc.weight, dc.bias, stride=2, padding=dc.kernel_size[0] // 2, output_padding=1)
         y = _bn_ch2(z.view(T, B, *z.shape[1:]), dec.norm_layer.norm_layer)
         preds.append(_conv_seq(pr.sn(y), pr.conv[0], padding=0))
-    flows = []
-    for f in preds:
-        f = f.sum(0)
-        flows.append(F.interpolate(f, scale_factor=(H / f.shape[-2], W / f.shape[-1])))
-    return flows
+    return preds
 
 
 # ---------------------------------------------------------------------------------------------- SEW family (SpikingformerFlowNet)
@@ -371,9 +382,13 @@ def forward_train_sew(model, x):
     """`SpikingformerFlowNet.forward` in train mode (Spiking_STSwinNet.py:278-305, :161-182): (B, bins, 2, H, W) on the GPU -> list of
     flow maps (B, 2, H, W), differentiable; BN running statistics are updated.  Same patch embedding as the MS models; SEW blocks,
     SEW patch merging, SEW res-blocks, decoders ConvT 3x3 s2 -> BN -> SN (no neuron in front), plain 1x1 predictions."""
+    return _flows_of_preds(forward_train_sew_preds(model, x), *x.shape[-2:])
+
+
+def forward_train_sew_preds(model, x):
+    """`forward_train_sew` up to the decoder levels' raw predictions: a list of (T, B, 2, h, w), coarsest first."""
     if not x.is_cuda:
         raise hip.SdfError("the training path runs on the GPU only (no CPU fallback)")
-    H, W = x.shape[-2:]
     unet = model.sttmultires_unet
     sw = unet.encoders.swin3d
     ws = sw.layers[0].swin_blocks[0].attn.window_size
@@ -401,11 +416,7 @@ def forward_train_sew(model, x):
         z = F.conv_transpose2d(y.flatten(0, 1), dc.weight, dc.bias, stride=2, padding=dc.kernel_size[0] // 2, output_padding=1)
         y = dec.sn(_bn_ch2(z.view(T, B, *z.shape[1:]), dec.norm_layer.norm_layer))
         preds.append(_conv_seq(y, pr.conv[0], padding=0))
-    flows = []
-    for f in preds:
-        f = f.sum(0)
-        flows.append(F.interpolate(f, scale_factor=(H / f.shape[-2], W / f.shape[-1])))
-    return flows
+    return preds
 
 
 # ---------------------------------------------------------------------------------------------- loss, step, all-reduce
@@ -419,6 +430,20 @@ def flow_loss_supervised(pred_list, gt_flow, mask, flow_scaling=1.0, lambda_mod=
         err = torch.sqrt((flow - gt_flow).pow(2).sum(1) + 1e-8).view(flow.shape[0], -1) * mask.reshape(flow.shape[0], -1)
         cur = cur + lambda_mod * (torch.sum(err, dim=1) / (n + 1e-9))
     return torch.mean(cur / len(pred_list))
+
+
+def flow_loss_hip(preds, label, mask, flow_scaling=1.0, lambda_mod=1.0, n_valid=None):
+    """`flow_loss_supervised` on the RAW predictions `forward_train_preds` returns - a list of (T, B, 2, h, w), each a factor 1, 2, 4, 8
+    or 16 below the label - in two launches of csrc/flow_loss.hip (hip.flow_loss): the sum over time, the nearest upsampling and the
+    loss in one pass over the frame, the gradient delivered at each level's own resolution (autograd.FlowLossFunction).  Opt-in
+    (`train_step(head="hip")`); the values agree with the torch head to rounding, not bit for bit.  Under torch.no_grad(), or when no
+    prediction needs a gradient, the loss alone is computed."""
+    from .autograd import FlowLossFunction
+    n = torch.sum(mask) if n_valid is None else n_valid
+    n, label, mask = n.float().reshape(1), label.float(), mask.float()
+    if not (torch.is_grad_enabled() and any(p.requires_grad for p in preds)):
+        return hip.flow_loss(preds, label, mask, n, flow_scaling, lambda_mod, grads=False)[0]
+    return FlowLossFunction.apply(label, mask, n, float(flow_scaling), float(lambda_mod), *preds)
 
 
 def global_valid_count(mask, dist=None, world=1):
@@ -925,7 +950,8 @@ def save_grads_csv(records, path):
 
 
 def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, world=1, clip_grad=100.0, flow_scaling=1.0,
-               lambda_mod=1.0, amp=False, forward_fn=None, grads_out=None, scaler=None, num_acc=1, step_now=True, clip_unscaled=False):
+               lambda_mod=1.0, amp=False, forward_fn=None, grads_out=None, scaler=None, num_acc=1, step_now=True, clip_unscaled=False,
+               head="torch"):
     """One step of train_flow_parallel_supervised_SNN.py's loop body (:233-336) on this rank's shard of the batch; returns the
     loss tensor (this rank's samples' mean of err / n_global; the mean over ranks is the gathered-batch loss).
     `amp`: the reference trains under `torch.cuda.amp.autocast` with fp16 + GradScaler (`optimizer.use_amp: true`,
@@ -945,7 +971,17 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
     is divided by num_acc, a call with `step_now=False` adds its gradients to the running sum in the buckets and clips that sum IN
     PLACE (statistics, coefficient, hip.grad_scale), and the call with `step_now=True` steps; the call after it zeroes the buckets.
     The caller decides: step_now = (sample + 1) % num_acc == 0 or sample + 1 == len(loader).  The returned loss is the divided,
-    unscaled one."""
+    unscaled one.
+    `head`: "torch" (default) - the flows are summed over time and upsampled, and the loss is `flow_loss_supervised`'s torch
+    composition; "hip" - the forward stops at the raw predictions (`forward_train_preds` / `forward_train_sew_preds`; an STTFlowNet's
+    full-resolution flows count as factor-1 levels of one time step) and `flow_loss_hip` computes the loss and its gradient in two
+    launches of csrc/flow_loss.hip.  Everything else - amp, the scaler, num_acc, n_valid over the ranks, the buckets, the tail - is the
+    same code for both."""
+    if head not in ("torch", "hip"):
+        raise ValueError(f'train_step: head is "torch" or "hip", got {head!r}')
+    if head == "hip" and forward_fn is not None:
+        raise ValueError('train_step: head="hip" takes the raw decoder predictions of the HIP train-mode forward; a forward_fn returns '
+                         'finished flow maps - use head="torch" with it')
     if isinstance(optimizer, BucketAdamW) and buckets is not optimizer.buckets:
         raise ValueError("train_step: a BucketAdamW steps on its GradientBuckets - pass them as buckets=")
     if grads_out is not None and buckets is None:
@@ -985,13 +1021,18 @@ def train_step(model, optimizer, chunk, label, mask, buckets=None, dist=None, wo
             flows = forward_fn(model, chunk)
         elif ann:
             flows = model(chunk, None)["flow"]
+            if head == "hip":
+                flows = [f.unsqueeze(0) for f in flows]
         elif isinstance(model, SpikingformerFlowNet):
-            flows = forward_train_sew(model, chunk)
+            flows = forward_train_sew_preds(model, chunk) if head == "hip" else forward_train_sew(model, chunk)
         else:
-            flows = forward_train(model, chunk)
+            flows = forward_train_preds(model, chunk) if head == "hip" else forward_train(model, chunk)
     n_valid = global_valid_count(mask, dist, world)
     # local mean over B_local of err_i / n_global, times 1 / world from the gradient average = the gathered-batch mean
-    loss = flow_loss_supervised([f.float() for f in flows], label, mask, flow_scaling, lambda_mod, n_valid=n_valid)
+    if head == "hip":
+        loss = flow_loss_hip(flows, label, mask, flow_scaling, lambda_mod, n_valid=n_valid)
+    else:
+        loss = flow_loss_supervised([f.float() for f in flows], label, mask, flow_scaling, lambda_mod, n_valid=n_valid)
     if num_acc > 1:
         loss = loss / num_acc
     (loss if scaler is None else scaler.scale(loss)).backward()      # bucket all-reduces leave from the grad-ready hooks
