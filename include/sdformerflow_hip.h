@@ -1587,6 +1587,36 @@ int sdf_grad_clip_scale_coef(const SdfGradClipScaleDesc* d, void* stream);
 int sdf_adamw_step_scaled(const SdfAdamwDesc* d, const SdfLossScaleState* state, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * u8 spikes -> spike counts per SAMPLE and time step: sdf_spike_count_fwd (below) generalised by the sample axis, for the records of
+ * a replica forward (R independent batch-1 samples in one launch sequence), where one count per step would mix the samples.
+ * Element (so, t, si, r, c) is the byte at spikes + ((((so * T + t) * s_in + si) * rows + r) * row_stride + c; the call computes
+ *   counts[(so * s_in + si) * sample_pitch + t] += sum over r, c     (64-bit integers; the CALLER zeroes them)
+ * for the s_out * s_in samples; sample_pitch (in int64 elements, >= T) lets the T counts of a sample lie inside a larger record, e.g. a
+ * (samples, calls, Tmax) block with sample_pitch = calls * Tmax.  s_in = 1: the samples lie OUTSIDE time - channel-last
+ * (B, D, h, w, C) activations and their channel slices.  s_out = 1: the samples are s_in equal consecutive pieces of every time block -
+ * the (T', R * nW * N1, C) window records of a replica forward, the patch merging's (D, B, H2, W2, 4C), the halves of a stacked q | k
+ * buffer (row_stride 2C).  Every (so, t, si) piece is a run of its own: row_stride == C reads 16 bytes per lane from the first
+ * 16-byte boundary INSIDE the piece and the bytes in front of it and behind the last whole vector one by one, so nothing outside a
+ * piece is read and no byte is added to a neighbouring sample; row_stride > C walks the rows (small tensors).  Integer sums, lane ->
+ * wave -> workgroup, one 64-bit atomic per workgroup: the same bits on every run.  s_out = s_in = 1 equals sdf_spike_count_fwd with
+ * outer 1.  Added to SDF_VERSION 107 (no existing entry changed).
+ * SDF_E_NULL: d, spikes or counts NULL; SDF_E_SHAPE: s_out, s_in, rows or C < 1, T outside 1 .. 64, row_stride < C, sample_pitch < T
+ * (or sizes beyond 2^62 bytes / 2^31 workgroups); SDF_E_ALIGN: counts not 8-byte aligned. */
+typedef struct SdfSpikeCountSegDesc {
+  const uint8_t* spikes;
+  int64_t s_out;
+  int T;
+  int64_t s_in;
+  int64_t rows;
+  int C;
+  int64_t row_stride;
+  int64_t* counts;
+  int64_t sample_pitch;
+} SdfSpikeCountSegDesc;
+
+int sdf_spike_count_seg_fwd(const SdfSpikeCountSegDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * u8 spikes -> spike counts per time step: the numerator of the firing rate the reference's output monitor records for a neuron call,
  * `cal_firing_rate(s_seq) = s_seq.flatten(1).mean(1)` (eval_DSEC_flow_SNN.py:22-24, 140-143, `vis.monitor_fr`).
  * Element (o, t, r, c) is the byte at spikes + ((o * T + t) * rows + r) * row_stride + c; the call computes

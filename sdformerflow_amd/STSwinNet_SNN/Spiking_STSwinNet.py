@@ -8,6 +8,8 @@ models/STSwinNet/STSwinNet.py:323-366, models/STSwinNet_SNN/SNN_models.py:30-164
 
 Forward runs on the HIP engine; there is no CPU fallback (it raises on CPU tensors).
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -244,6 +246,12 @@ class MS_SpikingformerFlowNet(nn.Module):
         if self._fr_monitor is not None:
             raise RuntimeError(f"a {self._fr_monitor.what} is enabled on this model and {what}: {instead}")
 
+    def _replica_monitor(self):
+        """forward_replicas' monitor: None, or the enabled monitor.ReplicaFiringRateMonitor; the one-forward monitors are refused."""
+        if not getattr(self._fr_monitor, "replicas", False):
+            self._no_monitor("forward_replicas was called", "a record set follows ONE reference forward - call model(x[i:i+1]) per sample, or disable() the monitor")
+        return self._fr_monitor
+
     def _engine_forward(self, x, scores=None):
         """The eval forward on the packed plan - through the firing-rate or membrane monitor while one is enabled (monitor.py)."""
         if self._fr_monitor is not None:
@@ -267,20 +275,28 @@ class MS_SpikingformerFlowNet(nn.Module):
         couples the samples through `window_partition_v2`'s raw view.)  Eval mode only."""
         if self.training:
             raise RuntimeError("forward_replicas is an inference entry point: call model.eval()")
-        self._no_monitor("forward_replicas was called", "a record set follows ONE reference forward - call model(x[i:i+1]) per sample, or disable() the monitor")
+        mon = self._replica_monitor()
         from .. import hip
 
+        def serve(xs, row=0, replicas=False):
+            """One launch sequence on the eval plan: the samples xs as replicas, or the one sample xs (row `row` of the call) - through
+            the replica firing-rate monitor while one is enabled, which counts the sequence's records into its rows row .. ."""
+            if mon is not None:
+                return mon.run(self.eval_engine(), xs, row, replicas)
+            return self.eval_engine().forward(xs, None, **({"replicas": True} if replicas else {}))
+
         def one_by_one():
-            outs = [self.eval_engine().forward(x[i:i + 1], None) for i in range(x.shape[0])]
+            outs = [serve(x[i:i + 1], i) for i in range(x.shape[0])]
             return [torch.cat([o[lvl] for o in outs], 0) for lvl in range(len(outs[0]))]
-        with torch.no_grad():
+        # (the monitor's refusals - a capture without a count block - come before the plan is packed)
+        with torch.no_grad(), (mon.group(x) if mon is not None else contextlib.nullcontext()):
             if self.gemm_nsplit != 2 and x.shape[0] > 1:
                 # the 16-bit-plane modes (3 = exact, 1 = bf16) run on the streaming kernels, whose split-K plans and tile families follow
                 # the row count: R-fold rows would change the summation order of a layer - the samples go one by one (same results)
                 flows = one_by_one()
             else:
                 try:
-                    flows = self.eval_engine().forward(x, None, replicas=True)
+                    flows = serve(x, 0, True)
                 except hip.ReplicaGeometryError:
                     # an odd window count per sample at some stage (e.g. 256 x 320: 175 windows at stage 0): the replica tables cannot
                     # keep a sample's head scramble inside one attention step - or a GLIF model, whose plan has no replica form -
@@ -323,7 +339,8 @@ class SpikingformerFlowNet(MS_SpikingformerFlowNet):
         samples go one by one - same contract as the MS models' call, flow[i] == self(x[i:i+1])["flow"]."""
         if self.training:
             raise RuntimeError("forward_replicas is an inference entry point: call model.eval()")
-        self._no_monitor("forward_replicas was called", "a record set follows ONE reference forward - call model(x[i:i+1]) per sample, or disable() the monitor")
-        with torch.no_grad():
-            outs = [self.engine().forward(x[i:i + 1], None) for i in range(x.shape[0])]
+        mon = self._replica_monitor()          # (a replica firing-rate monitor counts the samples one by one too: sample i -> row i)
+        with torch.no_grad(), (mon.group(x) if mon is not None else contextlib.nullcontext()):
+            outs = [self.engine().forward(x[i:i + 1], None) if mon is None else mon.run(self.engine(), x[i:i + 1], i)
+                    for i in range(x.shape[0])]
         return {"flow": [torch.cat([o[lvl] for o in outs], 0) for lvl in range(len(outs[0]))], "attn": None}

@@ -13,7 +13,8 @@ Turns the module tree (state_dict holder) into a flat schedule of C-ABI kernel l
     planes and the weight-resident kernel (csrc/spike_conv_wres.hip); no library kernel is left in the SNN forward
   * `forward(x, replicas=True)`: the B samples are B independent batch-1 forwards in one launch sequence (round 6; the route functions, `_slice_map`)
   * `tape` (tests only) keeps every neuron layer's spikes for the spike-forced oracle replay (tests/replay.py); a firing-rate
-    monitor (monitor.py) takes the same recording route and counts the spikes instead of keeping them
+    monitor (monitor.py) takes the same recording route and counts the spikes instead of keeping them - under replicas per sample
+    (monitor.ReplicaFiringRateMonitor; `_rec` says where a record's samples lie), where the tape stays refused
 
 Reference schedule being replaced: models/STSwinNet_SNN/Spiking_STSwinNet.py:161-182,278-305 and the
 call tree of SURVEY.md 3.2.  No CPU fallback: everything here raises off-GPU.
@@ -73,13 +74,15 @@ def _np(sn_module, device):
     return hip.NeuronParams(n.kind, n.tau, n.v_threshold, n.v_reset)
 
 
-def attention_score(e, sn, nH, Tq, B_, N1, launch=None):
+def attention_score(e, sn, nH, Tq, B_, N1, launch=None, rep=1):
     """`attn = self.attn_sn(x)` of `Spiking_QK_WindowAttention3D.forward` (reference Spiking_swin_transformer3D.py:709-711) from the
     gated spikes e (T', B_*N1, C) u8 of one block: the head scramble Z[t,b,n,g,d] = E_flat[((((b nH + g) T' + t) N1 + n) hd + d] as a
     re-layout (diagnostic path: the score is dead on the forward path, :715-716), then the neuron kernel over T' (`launch`: the
-    engine's neuron launch).  -> (T', B_, N1, C) fp32 spikes."""
-    Cc = e.shape[-1]
-    z = e.reshape(B_, nH, Tq, N1, Cc // nH).permute(2, 0, 3, 1, 4).reshape(Tq, B_ * N1 * Cc).float().contiguous()
+    engine's neuron launch).  -> (T', B_, N1, C) fp32 spikes.  `rep` > 1: the B_ windows are `rep` independent batch-1 problems
+    (hip.replica_slice_map): every sample's E_flat is the sub-block [:, r * nW : (r + 1) * nW] and is scrambled on its own."""
+    Cc, nW = e.shape[-1], B_ // rep
+    z = e.reshape(Tq, rep, nW * N1 * Cc).transpose(0, 1).reshape(rep, nW, nH, Tq, N1, Cc // nH).permute(3, 0, 1, 4, 2, 5)
+    z = z.reshape(Tq, B_ * N1 * Cc).float().contiguous()
     out = torch.empty_like(z)
     n = z.shape[1]
     (launch or hip.neuron_fwd)(z, out, Tq, 1, n, 0, n, 0, n, sn)
@@ -455,7 +458,8 @@ class MSFlowEngine:
             raise hip.SdfError(f"expected a contiguous fp32 (B,D,h,w,C) tensor, got shape {tuple(x.shape)} strides {x.stride()} "
                                f"{x.dtype}; call .contiguous() (the update is in place)")
 
-    # A firing-rate monitor (monitor.FiringRateMonitor) while one of its forwards runs, else None: the model's forward sets and clears it.
+    # A firing-rate monitor (monitor.FiringRateMonitor / ReplicaFiringRateMonitor) while one of its forwards runs, else None: the
+    # monitor's forward sets and clears it.
     monitor = None
 
     @property
@@ -470,11 +474,20 @@ class MSFlowEngine:
         they map onto the reference's tensor at that call: "flat" = same memory order (reshape; the time steps are the leading
         blocks - dim 0, or `steps` of them where the record is a (steps * rows, C) matrix), "BDHWC->TBCHW" / "BDHWC->TBHWC" =
         permute (time steps on dim 1).  The parity tape (tests only; `self.tape = []` switches it on, never during graph capture)
-        keeps a copy; a firing-rate monitor counts them where they lie and keeps nothing."""
+        keeps a copy; a firing-rate monitor counts them where they lie and keeps nothing.  Under replicas the record holds
+        `_rec_samples` samples and the layout says on which side of the time axis they lie: "flat" = INSIDE (the samples are that many
+        equal consecutive pieces of every time block: replica_slice_map puts sample r's windows at [r * nW, (r + 1) * nW) of every
+        attention step, and the merge's rows are (t, b, h2, w2)), "BDHWC->..." = OUTSIDE (dim 0)."""
         if self.tape is not None:
             self.tape.append((name, spikes.clone(), layout))
         if self.monitor is not None:
-            self.monitor.record(name, spikes if steps is None else spikes.view(steps, -1, spikes.shape[-1]), layout)
+            self._to_monitor(name, spikes if steps is None else spikes.view(steps, -1, spikes.shape[-1]), layout)
+
+    _rec_samples = 1        # samples a record holds: the batch of forward(x, replicas=True) while it runs, else 1
+
+    def _to_monitor(self, name, spikes, layout):
+        # (only monitor.ReplicaFiringRateMonitor is let through to a replica forward: the others' record() takes no sample count)
+        self.monitor.record(name, spikes, layout, **({"samples": self._rec_samples} if self._rec_samples > 1 else {}))
 
     def _rec_gates(self, blk, q, e, Tq, B_, N1):
         """Firing-rate monitor only: the two neuron calls of Spiking_QK_WindowAttention3D.forward whose spikes no kernel stores.
@@ -482,21 +495,23 @@ class MSFlowEngine:
         here from the recorded q spikes - the head sums are exact small integers, the block's sn2_q runs over T' in the neuron kernel
         - and is not a read-out of the fused kernel's gate; that the two agree is what the replay suite establishes through the gated
         spikes.  `attn.attn_sn`, the dead attention score (:709-711), is `attention_score` on the gated spikes e."""
-        Cc, nH = q.shape[-1], blk.nH
+        Cc, nH, R = q.shape[-1], blk.nH, self._rec_samples
         rows = B_ * N1
-        n = rows * nH
+        n = rows * nH // R                              # per sample (replicas: its rows are the r-th of R pieces of every step)
         n4 = (n + 3) // 4 * 4                           # (the neuron kernel moves 4 neurons per lane; the padding is not counted)
-        a = torch.zeros((Tq, n4), dtype=torch.float32, device=q.device)
-        a[:, :n] = q.reshape(Tq, rows, nH, Cc // nH).sum(-1, dtype=torch.float32).view(Tq, n)
-        g = torch.empty((Tq, n4), dtype=torch.uint8, device=q.device)
-        self._neuron_fwd(a, g, Tq, 1, n4, 0, n4, 0, n4, blk.sn2_q)
-        self._rec_monitor(blk.name + "attn.sn2_q.spiking_neuron.", g[:, :n], "flat")
-        s = attention_score(e, blk.attn_sn, nH, Tq, B_, N1, self._neuron_fwd)
+        # padded PER SAMPLE: the record (T', R, n) of the (T', R, n4) buffer keeps the count kernel's addressing form - R pieces per
+        # step, one row of n bytes each, n4 apart
+        a = torch.zeros((Tq, R, n4), dtype=torch.float32, device=q.device)
+        a[:, :, :n] = q.reshape(Tq, rows, nH, Cc // nH).sum(-1, dtype=torch.float32).view(Tq, R, n)
+        g = torch.empty((Tq, R, n4), dtype=torch.uint8, device=q.device)
+        self._neuron_fwd(a, g, Tq, 1, R * n4, 0, R * n4, 0, R * n4, blk.sn2_q)
+        self._rec_monitor(blk.name + "attn.sn2_q.spiking_neuron.", g[:, :, :n], "flat")
+        s = attention_score(e, blk.attn_sn, nH, Tq, B_, N1, self._neuron_fwd, rep=R)
         self._rec_monitor(blk.name + "attn.attn_sn.spiking_neuron.", s, "flat")
 
     def _rec_monitor(self, name, spikes, layout):
         """A record that goes to the monitor alone (the parity tape does not hold it): u8 spikes, or fp32 ones that are counted as u8."""
-        self.monitor.record(name, spikes if spikes.dtype == torch.uint8 else spikes.to(torch.uint8), layout)
+        self._to_monitor(name, spikes if spikes.dtype == torch.uint8 else spikes.to(torch.uint8), layout)
 
     def _neuron_bd(self, x, p, bn=None, out_dtype=torch.uint8, out=None):
         """Neuron over D of a channel-last (B,D,h,w,C) activation, BN fused when given."""
@@ -665,7 +680,7 @@ class MSFlowEngine:
         rowmap, B_ = self._slice_map(B, D, H, W, ws, ss)
         Tq, N1 = ws[0], ws[1] * ws[2]
         rep_windows = B_ // B if self.replicas and B > 1 else 0
-        if rep_windows and (self.taped or score_out is not None):
+        if rep_windows and (self.tape is not None or score_out is not None):     # (a monitor counts per sample: _rec)
             raise hip.SdfError("the parity tape and log=True follow one forward: run them without replicas")
         # one C-ABI call: neuron over the gathered slices -> q|k spike GEMM (+BN, +PE, neurons fused) -> token gate ->
         # projection spike GEMM through the head scramble with bias + BN + scatter + residual (csrc/qk_attn.hip)
@@ -745,11 +760,17 @@ class MSFlowEngine:
         if spikes is not None:
             out = hip.ms_patch_merge(spikes, lin)
             if out is not None:
-                if self.taped:                   # the tape holds the reference's (T, B, H/2, W/2, 4C) concatenation
+                if self.tape is not None:        # the tape holds the reference's (T, B, H/2, W/2, 4C) concatenation
                     src, H2, W2 = merge_row_map(B, D, H, W)
                     idx = torch.from_numpy(src.reshape(-1).astype("int64")).to(x.device)
                     flat = torch.cat([spikes.view(-1, Cc), spikes.new_zeros(1, Cc)], 0)
-                    self._rec(name, flat[idx].view(D, B, H2, W2, 4 * Cc), "flat")
+                    self.tape.append((name, flat[idx].view(D, B, H2, W2, 4 * Cc), "flat"))
+                if self.monitor is not None:
+                    # the concatenation moves every row of a (sample, step) once and adds zero rows where a size is odd: the spikes of
+                    # a sample and step are those of `spikes`, counted where they lie (nothing gathered, nothing allocated); the
+                    # denominator is the concatenation's (elements per step of the whole record)
+                    self.monitor.record(name, spikes, "BDHWC->TBHWC", elements=B * out.shape[2] * out.shape[3] * 4 * Cc,
+                                        **({"samples": self._rec_samples} if self._rec_samples > 1 else {}))
                 return out
         return self._patch_merge_gathered(x, lin, sn, name)
 
@@ -1000,6 +1021,7 @@ class MSFlowEngine:
             # row count - the caller (forward_replicas) serves those models one sample at a time
             raise hip.ReplicaGeometryError(f"replicas are built for T = 10 / 20 (digit kernels throughout), not T = {self.num_steps}")
         self.replicas = bool(replicas)
+        self._rec_samples = x.shape[0] if replicas else 1
         try:
             feats = self.encoder(x, **self._tail_kwargs())
             self.scores = None
@@ -1007,6 +1029,7 @@ class MSFlowEngine:
         finally:
             self.scores = None
             self.replicas = False
+            self._rec_samples = 1
         self.tail_spikes = None
         # sum over time + nearest upsampling to the input size: done by the prediction head's launch, else one small kernel per scale
         return [f if f is not None else hip.flow_out(p, H, W, H / p.shape[2], W / p.shape[3]) for p, f in zip(preds, self._flows)]

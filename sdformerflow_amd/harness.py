@@ -343,14 +343,24 @@ class StreamEvaluator:
     through ONE launch sequence (model.forward_replicas: bit-equal to separate batch-1 forwards), captured as a HIP graph per stream
     and replayed on `streams` streams; input preparation, metrics (loss.flow_supervised.FlowMetrics) and the optional copy of the flow
     map are enqueued on the group's stream, and the host synchronises once, when run() forms the result.  An instance keeps its static
-    buffers and graphs between run() calls; `metrics` is the FlowMetrics of the last run (counts(): the raw per-sample table)."""
+    buffers and graphs between run() calls; `metrics` is the FlowMetrics of the last run (counts(): the raw per-sample table).
+    `monitor`: a monitor.ReplicaFiringRateMonitor of the model - the launch sequences then take the recording route and every sample's
+    spike counts go to the monitor's table, row = the sample's index (behind the rows the monitor held before the run)."""
 
-    def __init__(self, model, config, device="cuda", replicas=10, streams=2, graphs=True):
+    def __init__(self, model, config, device="cuda", replicas=10, streams=2, graphs=True, monitor=None):
         if replicas < 1 or streams < 1:
             raise ValueError("replicas and streams are at least 1")
-        if (config.get("vis") or {}).get("monitor_fr"):
-            raise RuntimeError("vis.monitor_fr is set: firing rates are counted on single eager forwards, not under replicas and captured "
-                               "graphs - use harness.evaluate / evaluate_mv for the rates, or clear the key for the throughput scheme")
+        if monitor is not None:
+            from .monitor import ReplicaFiringRateMonitor
+            if not isinstance(monitor, ReplicaFiringRateMonitor):
+                raise TypeError(f"monitor= is a {type(monitor).__name__}: it records single eager forwards (harness.evaluate / evaluate_mv) - "
+                                "the streamed evaluation counts per sample under replicas: pass a monitor.ReplicaFiringRateMonitor")
+            if monitor.model is not model:
+                raise ValueError("monitor= belongs to another model: it would record nothing here - pass a ReplicaFiringRateMonitor of this model")
+        elif (config.get("vis") or {}).get("monitor_fr"):
+            raise RuntimeError("vis.monitor_fr is set: that key's monitor counts single eager forwards, not replicas and captured graphs - "
+                               "use harness.evaluate / evaluate_mv for it, or clear the key and pass monitor=ReplicaFiringRateMonitor(model) "
+                               "for the rates at the throughput scheme's rate")
         if (config.get("vis") or {}).get("store"):
             raise RuntimeError("vis.store is set: files are written by harness.evaluate / evaluate_mv (store_dir=) - under the throughput "
                                "scheme pass renders_out= to run() for the rendered bytes on the device, and clear the key")
@@ -362,6 +372,7 @@ class StreamEvaluator:
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(self.F)]
         self.slots = [None] * self.F                             # per stream: static buffers and {samples: [graph, flow]}
         self.metrics = None
+        self.monitor = monitor                                   # a monitor.ReplicaFiringRateMonitor, or None
         self.polarity = config["loader"].get("polarity", True)
         self.norm_input, self.spike_th = config["model"].get("norm_input"), config["data"].get("spike_th")
         self.mask_events = bool(config["metrics"].get("mask_events"))
@@ -464,7 +475,7 @@ class StreamEvaluator:
         if s is None or s["x"].shape[1:] != in_shape or s["lab"].shape[-2:] != hw:
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
             s = self.slots[j] = {"x": z(self.R, *in_shape), "lab": z(self.R, 2, *hw), "msk": z(self.R, 1, *hw),
-                                 "em": z(self.R, 1, *hw) if self.mask_events else None, "fwd": {}}
+                                 "em": z(self.R, 1, *hw) if self.mask_events else None, "fwd": {}, "counts": {}}
         return s
 
     def _render(self, k, units, s, flow, renders_out):
@@ -506,19 +517,33 @@ class StreamEvaluator:
                 self._prepare(kind, payload, s["x"][i:i + 1], s["em"][i:i + 1] if self.mask_events else None)
             x = s["x"][:n]
             functional.reset_net(self.model)
+            mon = self.monitor
+            if mon is not None and n not in s["counts"]:
+                # the slot's static count block of this group size: the sequence zeroes it and adds every record's counts into it
+                s["counts"][n] = torch.zeros((n, len(mon.names), mon.Tmax), dtype=torch.int64, device=self.device)
+            block = s["counts"][n] if mon is not None else None
+
+            def fwd():
+                if mon is None:
+                    return self._fwd(x)
+                block.zero_()
+                with mon.into(block):
+                    return self._fwd(x)
             if not self.graphs:
-                flow = self._fwd(x)
+                flow = fwd()
             else:
                 if n not in s["fwd"]:
                     for _ in range(2):
-                        self._fwd(x)                                     # (also creates this stream's workspaces and plan caches)
+                        fwd()                                            # (also creates this stream's workspaces and plan caches)
                     torch.cuda.synchronize(self.device)
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, stream=st):
-                        out = self._fwd(x)
+                        out = fwd()
                     s["fwd"][n] = [g, out]
                 g, flow = s["fwd"][n]
                 g.replay()
+            if mon is not None:
+                mon.take(block, first=self._first + k)                   # (into its table's rows, on this stream: as flows_out below)
             self.metrics.update(flow, s["lab"][:n], s["msk"][:n], s["em"][:n] if self.mask_events else None,
                                 self.config["metrics"]["flow_scaling"], row=k)
             if flows_out is not None:
@@ -540,21 +565,40 @@ class StreamEvaluator:
         if hasattr(samples, "__len__"):
             rows = max(len(samples), 1)
         self.metrics = FlowMetrics(rows, self.device)
-        with torch.no_grad():
-            for j, k, units in deal(self._units(samples), self.F, self.R):
-                if names is None:
-                    default = ["AEE", "AAE"] if units[0][0] in ("volume", "pairs") else ["AEE"]
-                    names = self.config["metrics"].get("name", default)
-                if k + len(units) > self.metrics.table.shape[0]:
-                    self.metrics.reserve(max(k + len(units), 2 * self.metrics.table.shape[0]))
-                self._issue(j, k, units, flows_out, renders_out)
+        mon = self.monitor
+        if mon is not None:
+            # sample k of this run is row first + k of the monitor's table, sized now where the number of samples is known; when it has
+            # to grow on the way, the growth (a copy on the current stream) waits for every stream's rows first
+            was_on, self._first = mon.enabled, mon.forwards
+            mon.enable()
+            mon.reserve(self._first + rows, self.device)
+        try:
+            with torch.no_grad():
+                for j, k, units in deal(self._units(samples), self.F, self.R):
+                    if names is None:
+                        default = ["AEE", "AAE"] if units[0][0] in ("volume", "pairs") else ["AEE"]
+                        names = self.config["metrics"].get("name", default)
+                    if k + len(units) > self.metrics.table.shape[0]:
+                        self.metrics.reserve(max(k + len(units), 2 * self.metrics.table.shape[0]))
+                    if mon is not None and self._first + k + len(units) > mon.capacity:
+                        for st in self.streams:
+                            torch.cuda.current_stream(self.device).wait_stream(st)
+                        mon.reserve(self._first + k + len(units), self.device)
+                    self._issue(j, k, units, flows_out, renders_out)
+        finally:
+            if mon is not None and not was_on:
+                mon.disable()
         return self.metrics.result(tuple(names or ["AEE"]))
 
 
-def evaluate_stream(model, samples, config, device="cuda", replicas=10, streams=2, graphs=True, flows_out=None, renders_out=None):
+def evaluate_stream(model, samples, config, device="cuda", replicas=10, streams=2, graphs=True, flows_out=None, renders_out=None,
+                    monitor=None):
     """harness.evaluate / evaluate_mv at the throughput scheme's rate (StreamEvaluator): same sample forms, same config keys
     (loader.crop / polarity, model.norm_input, data.spike_th / num_chunks, metrics.mask_events / flow_scaling / name), every sample a
     batch-1 evaluation (a loader batch of B yields B of them), one host synchronisation at the end.  `flows_out` (n, 2, h, w) receives
     the last flow level of every sample in iteration order; `renders_out`: StreamEvaluator.run's dict of device buffers for the rendered
-    images (`vis.store` itself is refused here: no files under this scheme).  graphs=False issues the launch sequences eagerly."""
-    return StreamEvaluator(model, config, device, replicas, streams, graphs).run(samples, flows_out, renders_out)
+    images (`vis.store` itself is refused here: no files under this scheme).  graphs=False issues the launch sequences eagerly.
+    `monitor`: a monitor.ReplicaFiringRateMonitor of the model - every sample's firing-rate record goes to its table in iteration order
+    (monitor.counts(), .mean(), .to_csv(path)): each stream slot owns a static count block per group size that the (captured) sequence
+    zeroes and fills and that is copied into the table on the group's stream, as `flows_out` is; no synchronisation is added."""
+    return StreamEvaluator(model, config, device, replicas, streams, graphs, monitor).run(samples, flows_out, renders_out)

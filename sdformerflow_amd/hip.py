@@ -336,6 +336,11 @@ class SpikeCountDesc(C.Structure):
                 ("row_stride", C.c_int64), ("counts", C.c_void_p)]
 
 
+class SpikeCountSegDesc(C.Structure):
+    _fields_ = [("spikes", C.c_void_p), ("s_out", C.c_int64), ("T", C.c_int), ("s_in", C.c_int64), ("rows", C.c_int64), ("C", C.c_int),
+                ("row_stride", C.c_int64), ("counts", C.c_void_p), ("sample_pitch", C.c_int64)]
+
+
 class MembraneStatsDesc(C.Structure):
     _fields_ = [("v", C.c_void_p), ("outer", C.c_int64), ("T", C.c_int), ("rows", C.c_int64), ("C", C.c_int),
                 ("row_stride", C.c_int64), ("table", C.c_void_p), ("bins", C.c_int), ("lo", C.c_float), ("hi", C.c_float),
@@ -455,6 +460,7 @@ SIGNATURES = {
     "sdf_grad_clip_coef": (_i, (_p, _i, _p, _f, _p, _p, _p)), "sdf_adamw_step": (_i, (_P(AdamwDesc), _p)),
     "sdf_grad_scale_inplace": (_i, (_P(GradScaleDesc), _p)), "sdf_grad_clip_scale_coef": (_i, (_P(GradClipScaleDesc), _p)),
     "sdf_adamw_step_scaled": (_i, (_P(AdamwDesc), _P(LossScaleState), _p)),
+    "sdf_spike_count_seg_fwd": (_i, (_P(SpikeCountSegDesc), _p)),
     "sdf_spike_count_fwd": (_i, (_P(SpikeCountDesc), _p)),
 }
 
@@ -2656,6 +2662,52 @@ def spike_count(spikes, t_dim, counts=None):
     d.outer, d.T, d.rows, d.C, d.row_stride = outer, T, rows, Cc, rs
     _note(bytes=outer * T * rows * Cc, shape=(outer, T, rows, Cc))
     _check(lib().sdf_spike_count_fwd(C.byref(d), _stream()), "sdf_spike_count_fwd")
+    return counts
+
+
+def spike_count_samples_form(spikes, t_dim, samples):
+    """(s_out, T, s_in, rows, C, row_stride) of a u8 tensor or view that holds `samples` independent samples, in
+    sdf_spike_count_seg_fwd's addressing form - element (so, t, si, r, c) at byte (((so T + t) s_in + si) rows + r) row_stride + c behind
+    its first element.  t_dim 1: the samples are dim 0, outside time (s_in = 1; channel-last (B, D, h, w, C) records and their channel
+    slices).  t_dim 0: the samples are `samples` equal consecutive pieces of every time block (s_out = 1; the window records of a replica
+    forward): the rows of a block must divide by `samples`.  Everything else is spike_count_form's, its refusals included; host
+    arithmetic on shapes and strides, no tensor is touched."""
+    if not torch.is_tensor(spikes) or spikes.dtype != torch.uint8:
+        raise SdfError(f"spike_count_samples: spikes are a u8 tensor, got {getattr(spikes, 'dtype', type(spikes).__name__)}", rc=E_DTYPE)
+    samples = int(samples)
+    if samples < 1:
+        raise SdfError(f"spike_count_samples: {samples} samples", rc=E_SHAPE)
+    outer, T, rows, Cc, rs = spike_count_form(spikes, t_dim)
+    if t_dim == 1:
+        if outer != samples:
+            raise SdfError(f"spike_count_samples: the step axis is dim 1, so the samples are dim 0: shape {tuple(spikes.shape)} holds "
+                           f"{outer}, not {samples} (one count over a batch is spike_count's)", rc=E_SHAPE)
+        return outer, T, 1, rows, Cc, rs
+    if rows % samples:
+        raise SdfError(f"spike_count_samples: the {rows} rows of a time block of shape {tuple(spikes.shape)} do not split into {samples} "
+                       "equal consecutive pieces", rc=E_SHAPE)
+    return 1, T, samples, rows // samples, Cc, rs
+
+
+def spike_count_samples(spikes, t_dim, samples, counts):
+    """Spikes per SAMPLE and time step of a u8 tensor or view (sdf_spike_count_seg_fwd): counts[s, t] += the sum over sample s's bytes of
+    step t (spike_count_samples_form says where they lie).  `counts`: an int64 view (samples, T) on the same device, dense along T, its
+    rows any distance >= T apart - e.g. block[:, call, :T] of a (samples, calls, Tmax) block - that is ADDED to.  One launch, counted in
+    place, no torch fallback."""
+    if not torch.is_tensor(spikes) or not spikes.is_cuda:
+        raise SdfError("spike_count_samples: HIP path needs a device tensor (no CPU fallback)")
+    s_out, T, s_in, rows, Cc, rs = spike_count_samples_form(spikes, t_dim, samples)
+    n = s_out * s_in
+    if not (torch.is_tensor(counts) and counts.is_cuda and counts.device == spikes.device and counts.dtype == torch.int64
+            and tuple(counts.shape) == (n, T) and (T == 1 or counts.stride(1) == 1) and (n == 1 or counts.stride(0) >= T)):
+        raise SdfError(f"spike_count_samples: counts must be an int64 view ({n}, {T}) on {spikes.device}, dense along the steps, its "
+                       f"rows at least {T} apart")
+    d = SpikeCountSegDesc()
+    d.spikes, d.counts = spikes.data_ptr(), counts.data_ptr()
+    d.s_out, d.T, d.s_in, d.rows, d.C, d.row_stride = s_out, T, s_in, rows, Cc, rs
+    d.sample_pitch = counts.stride(0) if n > 1 else T
+    _note(bytes=n * T * rows * Cc, shape=(s_out, T, s_in, rows, Cc))
+    _check(lib().sdf_spike_count_seg_fwd(C.byref(d), _stream()), "sdf_spike_count_seg_fwd")
     return counts
 
 

@@ -23,11 +23,17 @@ the recorded q spikes and the gated spikes (engine.MSFlowEngine._rec_gates): the
 the fused kernel.  (A GLIF model runs on the unfused plan, engine_glif.py: there the gate's record IS the gate kernel's own output.)
 Eval mode, eager, one forward at a time: training mode, `forward_replicas` and graph capture are refused.
 
+`ReplicaFiringRateMonitor` is the same record per SAMPLE of `model.forward_replicas(x[R])` - the launch sequence of the streamed
+evaluation (harness.evaluate_stream(..., monitor=)) - counted by one launch per record of the per-sample kernel
+(hip.spike_count_samples, csrc/spike_count.hip: sdf_spike_count_seg_fwd), eagerly into its own table or, under graph capture, into a
+static count block of the caller's.
+
 The reference's other diagnostic, `vis.monitor_v` (eval_DSEC_flow_SNN.py:145-149, 228-230: `v_seq`, the membrane after reset at every
 time step of every neuron call), is `MembraneMonitor` below: the same names, the same switching, the forward on the unfused plan
 (engine_unfused.py), per-step statistics in integers on the device (csrc/membrane_stats.hip, restated here in numpy: membrane_record).
 One monitor of either kind at a time on a model.
 """
+import contextlib
 import csv
 
 import torch
@@ -208,9 +214,8 @@ class FiringRateMonitor:
             table[:self._n] = self._table
             self._table = table
 
-    def record(self, name, spikes, layout):
-        """engine._rec's sink: count the u8 spikes of neuron call `name` where they lie.  `layout` is the tape's tag: "flat" has the
-        time steps on dim 0, "BDHWC->..." on dim 1."""
+    def _call(self, name, spikes, layout):
+        """(index of neuron call `name`, step axis of its record, T), with record()'s refusals."""
         i = self._index.get(name.rstrip("."))
         if i is None:
             raise hip.SdfError(f"firing-rate monitor: the forward recorded {name!r}, which is not a neuron call of this model")
@@ -220,8 +225,15 @@ class FiringRateMonitor:
         T = spikes.shape[t_dim]
         if T > self.Tmax:
             raise hip.SdfError(f"firing-rate monitor: {name!r} has {T} time steps, the table {self.Tmax}")
+        return i, t_dim, T
+
+    def record(self, name, spikes, layout, elements=None):
+        """engine._rec's sink: count the u8 spikes of neuron call `name` where they lie.  `layout` is the tape's tag: "flat" has the
+        time steps on dim 0, "BDHWC->..." on dim 1.  `elements`: the reference tensor's elements per step where the record is not
+        that tensor itself (the patch merging's spikes before the 2x2 concatenation and its zero rows)."""
+        i, t_dim, T = self._call(name, spikes, layout)
         hip.spike_count(spikes, t_dim, counts=self._table[self._n, i, :T])
-        self._seen[i] = (T, spikes.numel() // T)
+        self._seen[i] = (T, spikes.numel() // T if elements is None else int(elements))
 
     # ------------------------------------------------------------------ reading
     def counts(self):
@@ -277,6 +289,199 @@ class FiringRateMonitor:
             for k, fwd in enumerate(host):
                 for name, r in zip(self.names, fwd):
                     w.writerow([k, name] + r)
+
+
+class ReplicaFiringRateMonitor(FiringRateMonitor):
+    """FiringRateMonitor for the streamed rate: one record set per SAMPLE of `model.forward_replicas(x[R])` (and of `model(x[1])`),
+    in sample order, integer for integer what R separate monitored batch-1 forwards count.
+
+        mon = ReplicaFiringRateMonitor(model)
+        with mon:
+            model.forward_replicas(x)                  # eager: R more rows of the monitor's own table (which may grow)
+            with mon.into(block):                      # block (n, calls, Tmax) int64, the caller's and zeroed by the caller
+                model.forward_replicas(x[:n])          # ... ADDS its counts into the block instead: what a graph capture records
+            mon.take(block, first=k)                   # copy of a filled block into rows k .. k + n of the table, on the current stream
+        mon.names, mon.counts(), mon.elements, mon.records, mon.mean(), mon.rates(), mon.to_csv(path)     # as FiringRateMonitor's
+
+    The replica launch sequence takes the engine's recording route with R times the rows; every record is ONE launch of the
+    per-sample count kernel (hip.spike_count_samples) on the tensor where it lies: the samples are dim 0 of a channel-last record and
+    R equal consecutive pieces of every time block of a window record (engine.MSFlowEngine._rec).  Where `forward_replicas` serves
+    its samples one by one (the SEW family, glif, gemm_nsplit != 2, T other than 10 / 20, an odd window count) the monitor does the
+    same and sample i's records go to row i.  Under graph capture nothing may be allocated or grown by the monitor and no
+    destination may depend on the replay: a capture without a block is refused before the engine is packed; the step counts and
+    denominators are host-known at capture and serve every replay of that graph (take).  A reference batch - `model(x[B > 1])` -
+    couples its samples and is refused: that is FiringRateMonitor's.  Eval mode, one monitor at a time."""
+    what = "replica firing-rate monitor"
+    replicas = True                   # what forward_replicas asks an enabled monitor
+
+    def __init__(self, model, forwards=16):
+        self._block, self._cur = None, None
+        # filled count block -> per sample (steps, elements per step) of every call: host-known when the block was filled, and a
+        # property of the (captured) sequence that fills it, not of the records - reset() keeps it
+        self._meta = {}
+        super().__init__(model, forwards)
+
+    # ------------------------------------------------------------------ the table
+    def reserve(self, rows, device=None):
+        """Room for `rows` samples in the table.  It grows by a copy on the current stream: a caller whose other streams still write
+        into the table (take) lets the current stream wait for them first (harness.StreamEvaluator.run)."""
+        shape = (len(self.names), self.Tmax)
+        if device is None:
+            device = self._table.device if self._table is not None else next(self.model.parameters()).device
+        device = torch.device(device)
+        if device.index is None and device.type == "cuda":
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._table is not None and self._table.device != device:
+            if self._n:
+                raise hip.SdfError(f"firing-rate monitor: records so far are on {self._table.device}, these on {device}; reset() first")
+            self._table = None
+        if self._table is None:
+            self._table = torch.zeros((max(int(rows), self._reserve),) + shape, dtype=torch.int64, device=device)
+        elif rows > self._table.shape[0]:
+            table = torch.zeros((max(int(rows), 2 * self._table.shape[0]),) + shape, dtype=torch.int64, device=device)
+            table[:self._table.shape[0]] = self._table
+            self._table = table
+        return self
+
+    @property
+    def capacity(self):
+        """Samples the table holds without growing."""
+        return 0 if self._table is None else self._table.shape[0]
+
+    def _set_row(self, row, steps, elements):
+        while len(self._steps) <= row:
+            self._steps.append(None)
+            self._elements.append(None)
+        self._steps[row], self._elements[row] = steps, elements
+
+    def _check_block(self, block):
+        shape = (len(self.names), self.Tmax)
+        if not (torch.is_tensor(block) and block.is_cuda and block.dtype == torch.int64 and block.dim() == 3 and block.shape[0] >= 1
+                and tuple(block.shape[1:]) == shape and block.is_contiguous()):
+            raise hip.SdfError(f"replica firing-rate monitor: a count block is a contiguous int64 device tensor (n, {shape[0]}, {shape[1]}) "
+                               "- (samples, calls, Tmax)")
+        return block
+
+    @contextlib.contextmanager
+    def into(self, block):
+        """While inside: the monitored forwards ADD their counts into the caller's `block` (n, calls, Tmax) int64 - n = the samples of
+        the forward - and leave the table alone; take(block) puts a filled block into the table.  (A launch sequence that
+        forward_replicas abandons for the one-by-one route zeroes the rows it had begun: zero the block yourself before the forward.)"""
+        prev, self._block = self._block, self._check_block(block)
+        try:
+            yield self
+        finally:
+            self._block = prev
+
+    def take(self, block, first=None):
+        """Enqueue, on the current stream, the copy of a block filled under into() into rows first .. first + n of the table (default:
+        behind the last row); the rows' step counts and denominators are those of the forward that filled the block - of the
+        capture, for every replay of a graph.  No synchronisation."""
+        meta = self._meta.get((self._check_block(block).data_ptr(), block.shape[0]))
+        if meta is None:
+            raise hip.SdfError("replica firing-rate monitor: take() of a block that no forward has filled under into()")
+        n, k = len(meta), self._n if first is None else int(first)
+        if k < 0:
+            raise hip.SdfError(f"replica firing-rate monitor: take(first={first})")
+        self.reserve(k + n, block.device)
+        self._table[k:k + n].copy_(block, non_blocking=True)
+        for r, (steps, elements) in enumerate(meta):
+            self._set_row(k + r, steps, elements)
+        self._n = max(self._n, k + n)
+        return self
+
+    # ------------------------------------------------------------------ the forwards (called by the model)
+    @contextlib.contextmanager
+    def group(self, x):
+        """One `forward_replicas(x)` / `model(x[1])`: the refusals first - nothing is packed or launched for a call that is refused -
+        then the destination of its x.shape[0] record sets; run() fills them, sample by sample or all at once."""
+        if not x.is_cuda:
+            raise hip.SdfError("input must be a GPU tensor (no CPU fallback)")
+        if self._cur is not None:
+            raise RuntimeError("replica firing-rate monitor: a monitored forward is already running on this model")
+        R = x.shape[0]
+        if self._block is not None:
+            if self._block.shape[0] != R or self._block.device != x.device:
+                raise hip.SdfError(f"replica firing-rate monitor: the count block holds {self._block.shape[0]} samples on "
+                                   f"{self._block.device}, the forward {R} on {x.device}")
+            dest = self._block
+        elif torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a replica firing-rate monitor is enabled during graph capture without a count block: a captured sequence "
+                               "may grow no table and add to no place that depends on the replay - capture under `with mon.into(block)` "
+                               "with a static (n, calls, Tmax) int64 block and take() it after every replay, or disable() the monitor")
+        else:
+            self.reserve(self._n + R, x.device)
+            dest = self._table[self._n:self._n + R]
+        self._cur = {"dest": dest, "meta": [None] * R}
+        try:
+            yield self
+            meta = self._cur["meta"]
+            if any(m is None for m in meta):
+                raise hip.SdfError(f"replica firing-rate monitor: {sum(m is None for m in meta)} of {R} samples were not served")
+            if self._block is not None:
+                self._meta[(dest.data_ptr(), R)] = meta
+            else:
+                for r, (steps, elements) in enumerate(meta):
+                    self._set_row(self._n + r, steps, elements)
+                self._n += R
+        except BaseException:
+            if self._block is None:
+                dest.zero_()                             # (a forward that failed leaves no record)
+            raise
+        finally:
+            self._cur = None
+
+    def run(self, engine, x, row=0, replicas=False, scores=None):
+        """Inside group(): `engine.forward(x)` on the recording route with its records counted into rows row .. of the group -
+        x.shape[0] samples in one launch sequence (`replicas`), else the one sample x (1, ...)."""
+        n = x.shape[0]
+        if self._cur is None or (not replicas and n != 1) or row + n > len(self._cur["meta"]):
+            raise hip.SdfError("replica firing-rate monitor: run() serves the samples of the group() it is called in")
+        self._seen, self._row, self._samples = [None] * len(self.names), row, n
+        engine.monitor = self
+        try:
+            flows = engine.forward(x, None, replicas=True) if replicas else engine.forward(x, scores)
+            missing = [m for m, s in zip(self.names, self._seen) if s is None]
+            if missing:
+                raise hip.SdfError(f"firing-rate monitor: {len(missing)} neuron calls were not recorded by this forward, e.g. {missing[:3]}")
+        except BaseException:
+            self._cur["dest"][row:row + n].zero_()       # (a launch sequence that is abandoned leaves nothing in its rows)
+            raise
+        finally:
+            engine.monitor = None
+            seen, self._seen = self._seen, None
+        steps, elements = [s[0] for s in seen], [s[1] for s in seen]
+        self._cur["meta"][row:row + n] = [(steps, elements)] * n
+        return flows
+
+    def forward(self, x, scores=None):
+        """`model(x)`: one sample.  A reference batch is refused - its samples are coupled, there is no per-sample record of it."""
+        if x.dim() < 1 or x.shape[0] != 1:
+            raise RuntimeError(f"a replica firing-rate monitor is enabled and model(x) was called on a batch of {x.shape[0] if x.dim() else 0}: "
+                               "a reference batch couples its samples through the window view and has no per-sample record - use "
+                               "FiringRateMonitor for a reference batch, or model.forward_replicas(x) for independent samples")
+        with self.group(x):
+            return self.run(self.model.eval_engine(), x, 0, False, scores)
+
+    def record(self, name, spikes, layout, elements=None, samples=1):
+        """engine._rec's sink.  `samples` > 1: the record of a replica launch sequence - one launch of the per-sample kernel, the
+        samples outside time ("BDHWC->...": dim 0) or inside it ("flat": equal consecutive pieces of every time block)."""
+        i, t_dim, T = self._call(name, spikes, layout)
+        if samples != self._samples:
+            raise hip.SdfError(f"firing-rate monitor: {name!r} holds {samples} samples, the forward {self._samples}")
+        dst = self._cur["dest"][self._row:self._row + samples, i, :T]
+        if samples == 1:
+            hip.spike_count(spikes, t_dim, counts=dst[0])
+        else:
+            hip.spike_count_samples(spikes, t_dim, samples, dst)
+        self._seen[i] = (T, (spikes.numel() // T if elements is None else int(elements)) // samples)
+
+    # ------------------------------------------------------------------ reading
+    def _host(self):
+        empty = [k for k in range(self._n) if k >= len(self._steps) or self._steps[k] is None]
+        if empty:
+            raise hip.SdfError(f"replica firing-rate monitor: rows {empty[:5]} of the table were never filled (take(first=) left a gap)")
+        return super()._host()
 
 
 def membrane_summary(records, elements):
