@@ -1151,6 +1151,73 @@ int sdf_event_voxel_tb_keys_fwd(const SdfEventVoxelTbDesc* d, void* stream);
 int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Raw event lists + an estimated flow -> the image of warped events (IWE): every event is moved along the flow of its pixel to a common
+ * time and accumulated per polarity.  The ground-truth-free view of a flow's quality (the reference's Visualization_DSEC has `iwe`
+ * slots its loops leave None: there is no reference implementation; this text is the definition).
+ * Per event, in fp32, every operation rounded on its own:
+ *   tn = (t - t_first) / (t_last - t_first) of its list; skipped unless win_a <= tn <= win_b (NaN fails); tau = (tn - win_a) / (win_b - win_a);
+ *   lookup pixel xi = (int)floorf(x + 0.5f) - ox, yi likewise; skipped outside [0, w) x [0, h);
+ *   u = scale * flow[b, 0, yi, xi], v = scale * flow[b, 1, yi, xi]; skipped if either is not finite;
+ *   d = t_ref - tau;  xw = (x - ox) + d * u;  yw = (y - oy) + d * v;  channel 0 if p > 0, else 1;
+ *   mode 0 (bilinear): x0 = floorf(xw), y0 = floorf(yw); corner (x0 + dx, y0 + dy) gets (1 - |xc - xw|) * (1 - |yc - yw|), corners
+ *     outside the window are dropped; a cell's sum is formed in the order: passes dx outer, dy inner, list order within a pass;
+ *   mode 1 (nearest): weight 1 at (rintf(xw), rintf(yw)), halves to even, -0 = 0, dropped outside: the image holds integers.
+ * out (B, 2, h, w) fp32; flow (B, 2, h, w) fp32 on the same window: (crop_h, crop_w) at (crop_oy, crop_ox) of the (H, W) sensor, or the
+ * whole sensor (all four 0).  An empty list gives zeros.  No float atomics: bit-identical from run to run, and a list's image does not
+ * depend on its batch.  Event arrays, offsets (HOST), t_range (HOST), xy_dtype and rectify_map: as SdfEventVoxelDesc.
+ * Two calls with the caller's stable sort between them, as for sdf_event_voxel_*; workspace: sdf_event_iwe_workspace_bytes(...) bytes,
+ * 16-byte aligned, the same for both calls (0: refused geometry or mode).
+ * Checks, before any launch: SDF_E_NULL: d, flow, out, workspace (x, y, t, p, keys / keys_sorted, order with events; offsets with
+ * B > 1; an integer xy_dtype without its map); SDF_E_SHAPE: a refused geometry, not win_a < win_b, a value that is not finite, a short
+ * workspace, offsets that do not cut n_events, a list with t_last == t_first in t_range; SDF_E_DTYPE: mode outside 0 | 1, xy_dtype
+ * outside 0 .. 2, a map with fp32 coordinates - and, last, a pointer the kernels would read or write that is not device memory;
+ * SDF_E_ALIGN: workspace not 16-byte, an fp32 / int32 pointer not 4-byte, a uint16 pointer not 2-byte, order not 8-byte aligned.
+ * Added to SDF_VERSION 107 (no existing entry changed). */
+typedef struct SdfEventIweDesc {
+  const void* x;
+  const void* y;
+  const float* t;
+  const float* p;
+  const float* flow;
+  const float* rectify_map;
+  const int64_t* offsets;
+  const float* t_range;
+  int32_t* keys;
+  const int32_t* keys_sorted;
+  const int64_t* order;
+  void* out;
+  void* workspace;
+  int64_t workspace_bytes, n_events;
+  int32_t B, H, W, crop_h, crop_w, crop_oy, crop_ox, map_h, map_w;
+  int32_t xy_dtype, mode;
+  float scale, t_ref, win_a, win_b;
+} SdfEventIweDesc;
+
+int64_t sdf_event_iwe_workspace_bytes(int64_t n_events, int B, int H, int W, int crop_h, int crop_w, int crop_oy, int crop_ox, int mode);
+int sdf_event_iwe_keys_fwd(const SdfEventIweDesc* d, void* stream);
+int sdf_event_iwe_gather_fwd(const SdfEventIweDesc* d, void* stream);
+
+/* sdf_iwe_stats_fwd: sample b of iwe (B, 2, H, W) fp32 writes row row0 + b of `table` (double[rows][4]; other rows stay):
+ *   {sum c, sum c^2, max c, number of pixels with c != 0},  c = the fp64 sum of the pixel's two channels
+ * fp64 sums formed lane -> wave -> workgroup -> one partial record per workgroup in the workspace, then combined per sample in index
+ * order: no atomics, bit-identical from run to run and independent of B.  On nearest images the sums are integers, exact below 2^53; the
+ * Flow Warp Loss of a sample is var(S) / var(Z), var = (sum c^2 - (sum c)^2 / N) / (N - 1) over the N = H W pixels, S the image warped
+ * by the flow and Z the one with scale 0.
+ * workspace: sdf_iwe_stats_workspace_bytes(B, H, W) bytes, 8-byte aligned (0: refused geometry).
+ * SDF_E_NULL: d, iwe, table or workspace NULL; SDF_E_SHAPE: B, H or W < 1, B > 65535, H W >= 2^30, rows outside the table, a short
+ * workspace; SDF_E_ALIGN: iwe not 4-byte, table or workspace not 8-byte aligned; SDF_E_DTYPE: a pointer that is not device memory. */
+typedef struct SdfIweStatsDesc {
+  const float* iwe;
+  double* table;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t B, H, W, row0, rows;
+} SdfIweStatsDesc;
+
+int64_t sdf_iwe_stats_workspace_bytes(int B, int H, int W);
+int sdf_iwe_stats_fwd(const SdfIweStatsDesc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Flow maps -> the per-sample sums of the evaluation metrics (reference loss/flow_supervised.py: AEE :119-149, AAE :163-175).
  * pred, label (B, 2, H, W), valid (B, H, W), event_mask (B, H, W; may be NULL): fp32, contiguous.  Per pixel, every step one fp32
  * operation in the reference's order, constants Python doubles rounded to fp32:

@@ -8,7 +8,7 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-slp-vec
 mkdir -p obj
 pids=()
 newest_h=$(ls -t *.h ../../include/sdformerflow_hip.h | head -1)   # every header counts: a new one cannot be forgotten
-for f in ms_wide ms_res ms_smallm neuron neuron_bwd glif bn_train qk_attn qk_front ms_mlp_fused pred_head pointwise_conv qk_gate_train spike_gemm spike_splitk switches launch_log spike_mm_pp spike_conv_wres spike_deconv_wres dense_conv_wres dense_linear linear_dw linear_train qk_gate elementwise win_attn win_attn_large win_attn_scores win_attn_bwd win_attn_sew_bwd win_attn_large_bwd ann_block ann_mlp_block head_tail event_voxel event_voxel_tb spike_count membrane_stats flow_metrics flow_loss flow_render grad_step prepare_chunk; do
+for f in ms_wide ms_res ms_smallm neuron neuron_bwd glif bn_train qk_attn qk_front ms_mlp_fused pred_head pointwise_conv qk_gate_train spike_gemm spike_splitk switches launch_log spike_mm_pp spike_conv_wres spike_deconv_wres dense_conv_wres dense_linear linear_dw linear_train qk_gate elementwise win_attn win_attn_large win_attn_scores win_attn_bwd win_attn_sew_bwd win_attn_large_bwd ann_block ann_mlp_block head_tail event_voxel event_voxel_tb event_iwe spike_count membrane_stats flow_metrics flow_loss flow_render grad_step prepare_chunk; do
   if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ "$newest_h" -nt obj/$f.o ]; then
     # (hipcc's own per-kernel resource remarks are kept beside the object: tools/check_spills.py reads them - no second compile)
     ( $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -c $f.hip -o obj/$f.o 2> obj/$f.res || { grep -v "Rpass-analysis\|^ *[0-9]* |\|^ *| *\^" obj/$f.res >&2; exit 1; }

@@ -30,6 +30,16 @@ static inline void sdf_atan_consts(float alpha, float& c_atan, float& half_alpha
   half_alpha = (float)((double)alpha / 2);
 }
 static inline bool sdf_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// Device (or managed) memory, as far as the runtime can tell.  A pointer the runtime does not know - a host allocation, or any
+// pointer where no device is present - is not: the entry points that ask (grad_step.hip, event_iwe.hip) never hand a kernel one.
+static inline bool sdf_on_device(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
 
 // Dynamic LDS above 64 KiB needs an opt-in (hipFuncSetAttribute) per kernel function AND per device.  `done` = one bit per device
 // ordinal, one static instance per kernel: a second GPU driven from the same process, or two host threads at their first call, both end

@@ -362,17 +362,6 @@ __global__ __launch_bounds__(kGsThreads) void grad_scale_kernel(float* __restric
   }
 }
 
-// Device (or managed) memory, as far as the runtime can tell.  A pointer the runtime does not know - a host allocation, or any
-// pointer where no device is present - is not: the kernels must never be handed one.
-inline bool gs_on_device(const void* p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 // segments ascend, do not overlap and lie inside [0, n): `at(i, off, len)` reads row i of the host table
 template <class F>
 inline bool gs_segments_ok(int nseg, int64_t n, F&& at) {
@@ -405,7 +394,7 @@ extern "C" int sdf_grad_stats_fwd(const SdfGradStatsDesc* d, void* stream) {
   if (d->row0 < 0 || (int64_t)d->row0 + d->nseg > d->rows) return SDF_E_SHAPE;     // the records lie inside the table
   if (d->workspace_bytes < sdf_grad_stats_workspace_bytes(d->nseg)) return SDF_E_SHAPE;
   if (!sdf_aligned(d->flat, 4) || !sdf_aligned(d->seg, 8) || !sdf_aligned(d->table, 8) || !sdf_aligned(d->workspace, 8)) return SDF_E_ALIGN;
-  if (!gs_on_device(d->flat) || !gs_on_device(d->seg) || !gs_on_device(d->table) || !gs_on_device(d->workspace)) return SDF_E_DTYPE;
+  if (!sdf_on_device(d->flat) || !sdf_on_device(d->seg) || !sdf_on_device(d->table) || !sdf_on_device(d->workspace)) return SDF_E_DTYPE;
   hipStream_t s = sdf_stream(stream);
   double* part = static_cast<double*>(d->workspace);
   SDF_LAUNCH(grad_stats_partial_kernel, dim3(kGsGroups, d->nseg), dim3(kGsThreads), 0, s, d->flat, d->seg, part);
@@ -419,7 +408,7 @@ extern "C" int sdf_grad_clip_coef(const double* table, int rows, const uint8_t* 
   if (!table || !coef || !record) return SDF_E_NULL;
   if (rows < 1 || rows > (1 << 24) || !(max_norm >= 0.f)) return SDF_E_SHAPE;                  // (+inf: no clip, coef 1)
   if (!sdf_aligned(table, 8) || !sdf_aligned(record, 8) || !sdf_aligned(coef, 4)) return SDF_E_ALIGN;
-  if (!gs_on_device(table) || (mask && !gs_on_device(mask)) || !gs_on_device(coef) || !gs_on_device(record)) return SDF_E_DTYPE;
+  if (!sdf_on_device(table) || (mask && !sdf_on_device(mask)) || !sdf_on_device(coef) || !sdf_on_device(record)) return SDF_E_DTYPE;
   SDF_LAUNCH(grad_clip_coef_kernel, dim3(1), dim3(kGsThreads), 0, sdf_stream(stream), table, rows, mask, (double)max_norm, coef, record);
   return sdf_launch_rc();
 }
@@ -440,11 +429,11 @@ inline int aw_check(const SdfAdamwDesc* d, const SdfLossScaleState* state, bool 
   if (!gs_same_phase(d->grad, d->exp_avg) || !gs_same_phase(d->grad, d->exp_avg_sq)) return SDF_E_ALIGN;
   for (int i = 0; i < d->nseg; ++i)
     if (d->rows_host[i].active && !sdf_aligned(d->rows_host[i].param, 4)) return SDF_E_ALIGN;
-  if (!gs_on_device(d->grad) || !gs_on_device(d->exp_avg) || !gs_on_device(d->exp_avg_sq) || !gs_on_device(d->rows) ||
-      (d->coef && !gs_on_device(d->coef)) || (scaled && !gs_on_device(state)))
+  if (!sdf_on_device(d->grad) || !sdf_on_device(d->exp_avg) || !sdf_on_device(d->exp_avg_sq) || !sdf_on_device(d->rows) ||
+      (d->coef && !sdf_on_device(d->coef)) || (scaled && !sdf_on_device(state)))
     return SDF_E_DTYPE;
   for (int i = 0; i < d->nseg; ++i)
-    if (d->rows_host[i].active && !gs_on_device(d->rows_host[i].param)) return SDF_E_DTYPE;
+    if (d->rows_host[i].active && !sdf_on_device(d->rows_host[i].param)) return SDF_E_DTYPE;
   return 0;
 }
 
@@ -470,7 +459,7 @@ extern "C" int sdf_grad_scale_inplace(const SdfGradScaleDesc* d, void* stream) {
   if (!gs_segments_ok(d->nseg, d->n, [&](int i, int64_t& off, int64_t& len) { off = d->seg_host[2 * i]; len = d->seg_host[2 * i + 1]; }))
     return SDF_E_SHAPE;
   if (!sdf_aligned(d->flat, 4) || !sdf_aligned(d->seg, 8) || !sdf_aligned(d->coef, 4)) return SDF_E_ALIGN;
-  if (!gs_on_device(d->flat) || !gs_on_device(d->seg) || (d->mask && !gs_on_device(d->mask)) || !gs_on_device(d->coef)) return SDF_E_DTYPE;
+  if (!sdf_on_device(d->flat) || !sdf_on_device(d->seg) || (d->mask && !sdf_on_device(d->mask)) || !sdf_on_device(d->coef)) return SDF_E_DTYPE;
   SDF_LAUNCH(grad_scale_kernel, dim3(kGsGroups, d->nseg), dim3(kGsThreads), 0, sdf_stream(stream), d->flat, d->seg, d->mask, d->coef);
   return sdf_launch_rc();
 }
@@ -480,8 +469,8 @@ extern "C" int sdf_grad_clip_scale_coef(const SdfGradClipScaleDesc* d, void* str
   if (d->rows < 1 || d->rows > (1 << 24) || !(d->max_norm >= 0.f)) return SDF_E_SHAPE;            // (+inf: no clip, coef 1)
   if (!(d->growth_factor > 0.f) || !(d->backoff_factor > 0.f) || d->growth_interval < 1) return SDF_E_SHAPE;
   if (!sdf_aligned(d->table, 8) || !sdf_aligned(d->record, 8) || !sdf_aligned(d->coef, 4) || !sdf_aligned(d->state, 8)) return SDF_E_ALIGN;
-  if (!gs_on_device(d->table) || (d->mask && !gs_on_device(d->mask)) || !gs_on_device(d->coef) || !gs_on_device(d->record) ||
-      !gs_on_device(d->state))
+  if (!sdf_on_device(d->table) || (d->mask && !sdf_on_device(d->mask)) || !sdf_on_device(d->coef) || !sdf_on_device(d->record) ||
+      !sdf_on_device(d->state))
     return SDF_E_DTYPE;
   SDF_LAUNCH(grad_clip_scale_coef_kernel, dim3(1), dim3(kGsThreads), 0, sdf_stream(stream), d->table, (int)d->rows, d->mask,
              (double)d->max_norm, d->coef, d->record, d->state, d->growth_factor, d->backoff_factor, (int)d->growth_interval,

@@ -44,12 +44,9 @@ def event_times(ts):
     return t / t[-1]
 
 
-def events_to_chunk(events, bins, sensor_size, crop, norm_input, spike_th, rectify_map=None):
-    """Raw events -> network input (B, bins, 2, h, w) in one HIP launch sequence (hip.event_voxel): voxel grid with the reference's
-    semantics (event_representations.py:248-277), centre crop, polarity split, normalisation and spike threshold as
-    prepare_chunk(center_crop(grid)) gives them, bit for bit.  `events`: a dict of device tensors 'x', 'y', 'p' and 't' (or 'ts'), or a
-    list of B such dicts (one batch; min-max runs over the whole batch tensor, as prepare_chunk does).  x, y: fp32, or integer sensor
-    coordinates with `rectify_map` (H_s, W_s, 2).  norm_input "std" runs prepare_chunk's own code on the un-normalised output."""
+def _event_columns(events, rectify_map, times):
+    """One event dict, or a list of B of them, as the back-to-back arrays the event kernels take: x, y (fp32 - or int32 / uint16 with a
+    `rectify_map`), t (`times` of each list's 't' or 'ts'), p (fp32) and the B + 1 list offsets.  Host tensors are refused."""
     from . import hip
     lists = [events] if isinstance(events, dict) else list(events)
     cols = {k: [] for k in "xytp"}
@@ -64,10 +61,20 @@ def events_to_chunk(events, bins, sensor_size, crop, norm_input, spike_th, recti
             x, y = x.to(torch.int32), y.to(torch.int32)
         elif rectify_map is None:
             x, y = x.to(torch.float32), y.to(torch.float32)
-        for k, a in zip("xytp", (x, y, event_times(t), ev["p"].to(torch.float32))):
+        for k, a in zip("xytp", (x, y, times(t), ev["p"].to(torch.float32))):
             cols[k].append(a.reshape(-1))
         offsets.append(offsets[-1] + cols["t"][-1].numel())
-    x, y, t, p = (c[0] if len(c) == 1 else torch.cat(c) for c in (cols[k] for k in "xytp"))
+    return (*(c[0] if len(c) == 1 else torch.cat(c) for c in (cols[k] for k in "xytp")), offsets)
+
+
+def events_to_chunk(events, bins, sensor_size, crop, norm_input, spike_th, rectify_map=None):
+    """Raw events -> network input (B, bins, 2, h, w) in one HIP launch sequence (hip.event_voxel): voxel grid with the reference's
+    semantics (event_representations.py:248-277), centre crop, polarity split, normalisation and spike threshold as
+    prepare_chunk(center_crop(grid)) gives them, bit for bit.  `events`: a dict of device tensors 'x', 'y', 'p' and 't' (or 'ts'), or a
+    list of B such dicts (one batch; min-max runs over the whole batch tensor, as prepare_chunk does).  x, y: fp32, or integer sensor
+    coordinates with `rectify_map` (H_s, W_s, 2).  norm_input "std" runs prepare_chunk's own code on the un-normalised output."""
+    from . import hip
+    x, y, t, p, offsets = _event_columns(events, rectify_map, event_times)
     fused = norm_input if norm_input == "minmax" else None
     chunk = hip.event_voxel(x, y, t, p, bins, tuple(sensor_size), offsets=offsets, crop=tuple(crop) if crop else None, mode="split",
                             norm=fused, spike_th=spike_th if norm_input != "std" else None, rectify_map=rectify_map)
@@ -118,6 +125,62 @@ def event_pairs_to_chunk(pairs, num_frames, sensor_size, crop, norm_input, spike
         return out
     chunk = prepare_chunk(out, "std", spike_th, polarity=False)
     return (chunk, chunk.sum(1).sum(1, keepdim=True).bool().float()) if want_event_mask else chunk
+
+
+def warp_times(ts):
+    """A list's timestamps -> the fp32 times hip.event_iwe takes.  Integer sensor timestamps and fp32 times: event_times.  The MV
+    loaders' float64 seconds: the normalised time (t - t[0]) / (t[-1] - t[0]) is formed in float64 first, so that the microseconds of
+    a long recording survive the cast (a list whose times are all equal stays all equal, and is refused as such)."""
+    if ts.dtype != torch.float64 or ts.numel() == 0:
+        return event_times(ts)
+    t = ts - ts[0]
+    return torch.where(t[-1] != 0, t / t[-1], t).to(torch.float32)
+
+
+def warp_events(events, flow, sensor_size, crop, scale, crop_origin=None, t_ref=1.0, window=(0.0, 1.0), mode="bilinear",
+                rectify_map=None, check=True):
+    """Raw events + an estimated flow -> the image of warped events (B, 2, h, w) in one HIP launch sequence (hip.event_iwe): every event
+    moved along `scale` * flow to the time `t_ref` of its normalised window and accumulated per polarity (channel 0: p > 0).
+    `events`: a dict of device tensors 'x', 'y', 'p' and 't' (or 'ts'), or a list of B such dicts, as events_to_chunk takes them; flow
+    (B, 2, h, w) on the window `crop` (h, w) of `sensor_size` at `crop_origin` (default center_crop's; the MV loops pass
+    center_crop_origin's).  x, y: fp32 (other dtypes are cast), or integer sensor coordinates with `rectify_map`.  No backward pass."""
+    from . import hip
+    x, y, t, p, offsets = _event_columns(events, rectify_map, warp_times)
+    return hip.event_iwe(x, y, t, p, flow, tuple(sensor_size), offsets=offsets, crop=tuple(crop) if crop else None,
+                         crop_origin=crop_origin, scale=scale, t_ref=t_ref, window=window, mode=mode, rectify_map=rectify_map, check=check)
+
+
+class _FlowWarp:
+    """`fwl=True` of the two loops: every raw-event sample's FWL into a loss.flow_warp.FlowWarpMetrics (read once, at the end) and, when
+    the loop stores (`vis.store`), its bilinear image of warped events as <sequence>/iwe/%09d.png beside the other images."""
+
+    def __init__(self, device, window):
+        from .loss.flow_warp import FlowWarpMetrics
+        self.metrics, self.window = FlowWarpMetrics(64, device), tuple(window)
+
+    @staticmethod
+    def needs_events(sample_has_events):
+        if not sample_has_events:
+            raise ValueError("fwl=True: the warp needs the event list, and this sample came as a voxel tensor - pass the raw events "
+                             "(data.preprocessed: false / 'events_new'), or evaluate without fwl")
+
+    def __call__(self, events, pred, size, crop, scale, store, crop_origin=None):
+        self.metrics.update(pred, events, size, crop, scale, self.window, crop_origin=crop_origin)
+        if store is not None:
+            store.iwe(warp_events(events, pred, size, crop, scale, crop_origin=crop_origin, window=self.window, check=False))
+
+
+def _with_fwl(loop, fwl, fwl_window, device):
+    """`loop` with its `warp=` bound and "FWL" (the mean over the samples) added to its dict when `fwl` is true; else `loop`."""
+    if not fwl:
+        return loop
+
+    def run(model, samples, config, device=device, **kw):
+        warp = _FlowWarp(device, fwl_window)
+        result = loop(model, samples, config, device, warp=warp, **kw)
+        result["FWL"] = warp.metrics.result()["FWL"]
+        return result
+    return run
 
 
 def _with_firing_rates(loop, model, samples, config, device, monitor):
@@ -178,6 +241,18 @@ class _Storer:
                        idx=self.count)
         self.count += pred.shape[0]
 
+    def iwe(self, image):
+        """The image of warped events (B, 2, h, w) of the samples stored last, rendered with the event image's colours, as
+        <sequence>/iwe/%09d.png under their numbers."""
+        import os
+        from . import hip
+        from .utils.png import write_png
+        path_to = os.path.join(self.vis.store_dir, self.sequence, "iwe")
+        os.makedirs(path_to, exist_ok=True)
+        host = hip.event_counts_image(image).cpu().numpy()
+        for b in range(host.shape[0]):
+            write_png(os.path.join(path_to, "%09d.png" % (self.count - host.shape[0] + b)), host[b])
+
 
 def _storing(loop, config, store_dir, sequence, submission):
     """`loop` with its `store=` bound when `vis.store` is true (refused without a `store_dir`, before any forward); else `loop`."""
@@ -189,15 +264,19 @@ def _storing(loop, config, store_dir, sequence, submission):
     return lambda model, samples, config, device: loop(model, samples, config, device, store=store)
 
 
-def evaluate_mv(model, samples, config, device="cuda", monitor=None, store_dir=None, sequence="eval", submission=False):
+def evaluate_mv(model, samples, config, device="cuda", monitor=None, store_dir=None, sequence="eval", submission=False, fwl=False,
+                fwl_window=(0.0, 1.0)):
     """harness.evaluate's counterpart for the MVSEC / MDR sample dicts (`_evaluate_mv`: the loop itself); `vis.monitor_fr` true: the
     forwards run under a FiringRateMonitor (`monitor`, or a new one) and the dict also has "firing_rate" and "firing_rates".
     `vis.store` true: every sample's events, flow * mask and label * mask are stored as harness.evaluate stores them (`store_dir`,
-    `sequence`, `submission`)."""
-    return _with_firing_rates(_storing(_evaluate_mv, config, store_dir, sequence, submission), model, samples, config, device, monitor)
+    `sequence`, `submission`).
+    `fwl` true: every sample that came as raw events also gets its Flow Warp Loss on 'events_new' (loss.flow_warp), the dict gains
+    "FWL", and a storing loop also writes the bilinear image of warped events to <sequence>/iwe/; a voxel sample raises ValueError."""
+    loop = _with_fwl(_evaluate_mv, fwl, fwl_window, device)
+    return _with_firing_rates(_storing(loop, config, store_dir, sequence, submission), model, samples, config, device, monitor)
 
 
-def _evaluate_mv(model, samples, config, device="cuda", store=None):
+def _evaluate_mv(model, samples, config, device="cuda", store=None, warp=None):
     """The model-facing loop of eval_MV_flow_SNN.py:157-249 over an iterable of sample dicts, either the reference loader's
     ('event_volume_old', 'event_volume_new' (B, num_frames, h, w), 'flow' (B, 2, h, w), 'valid' (B, h, w)) or the raw form
     ('events_old', 'events_new': event dicts, or lists of B of them; 'flow', 'valid' at the sensor's or the crop's size, with or without
@@ -221,6 +300,8 @@ def _evaluate_mv(model, samples, config, device="cuda", store=None):
             label, mask = label.unsqueeze(0), mask.unsqueeze(0)
         mask = mask.unsqueeze(1)
         event_mask = None
+        if warp is not None:
+            warp.needs_events("events_new" in data)
         if "events_new" in data:
             if not polarity:
                 raise ValueError("the event path builds the two-polarity input (loader.polarity: true)")
@@ -248,6 +329,9 @@ def _evaluate_mv(model, samples, config, device="cuda", store=None):
             mask = mask * event_mask
         if store is not None:
             store(x if "events_new" in data else chunk, label, pred, mask)
+        if warp is not None:
+            warp([new for _, new in pairs], pred, size, crop, config["metrics"]["flow_scaling"], store,
+                 crop_origin=center_crop_origin(size, crop) if crop else None)
         results = {n: getattr(flow_supervised, n)(pred, label, mask, config["metrics"]["flow_scaling"])() for n in names}
         for b in range(pred.shape[0]):
             it += 1
@@ -261,7 +345,8 @@ def _evaluate_mv(model, samples, config, device="cuda", store=None):
     return {k: v / max(it, 1) for k, v in tot.items()}
 
 
-def evaluate(model, samples, config, device="cuda", monitor=None, store_dir=None, sequence="eval", submission=False):
+def evaluate(model, samples, config, device="cuda", monitor=None, store_dir=None, sequence="eval", submission=False, fwl=False,
+             fwl_window=(0.0, 1.0)):
     """The evaluation loop (`_evaluate`); `vis.monitor_fr` true: its forwards run under a FiringRateMonitor (`monitor`, or a new one) and
     the dict also has "firing_rate" (its mean()) and "firing_rates" (name -> T rates averaged over the forwards); false or absent:
     nothing changes.
@@ -269,11 +354,18 @@ def evaluate(model, samples, config, device="cuda", monitor=None, store_dir=None
     them, are rendered on the GPU and written as PNGs to <store_dir>/results/eval_0/<sequence>/{events, flow, gtflow}/%09d.png, and with
     `submission` the flow in the DSEC benchmark's 16-bit encoding to .../flow_test/<sequence>/%06d.png (utils.visualization); without
     a `store_dir` the key is refused before any forward.  False or absent: nothing changes and no render kernel is launched.
-    `vis.enabled` (the live window) is ignored."""
-    return _with_firing_rates(_storing(_evaluate, config, store_dir, sequence, submission), model, samples, config, device, monitor)
+    `vis.enabled` (the live window) is ignored.
+    `fwl` true: flow quality without ground truth - every sample that came as raw events also gets its Flow Warp Loss
+    (loss.flow_warp: variance of the events warped by the flow over the variance of the unwarped ones, on the events of `fwl_window`
+    of the normalised time) and the dict gains "FWL", their mean; a storing loop also writes the bilinear image of warped events to
+    .../<sequence>/iwe/%09d.png.  A sample that came as a voxel tensor raises ValueError: the warp needs the event list.  False, the
+    default: nothing changes and no warp kernel is launched.  evaluate_stream does not take it: the warp is not built under the
+    throughput scheme."""
+    loop = _with_fwl(_evaluate, fwl, fwl_window, device)
+    return _with_firing_rates(_storing(loop, config, store_dir, sequence, submission), model, samples, config, device, monitor)
 
 
-def _evaluate(model, samples, config, device="cuda", store=None):
+def _evaluate(model, samples, config, device="cuda", store=None, warp=None):
     """Run `model` over an iterable of (chunk (B,bins,H,W), mask (B,H,W), label (B,2,H,W)) like
     valid_test does and return the running-mean metrics dict (AEE, PE1-3, outliers) (:253-271, :283-305).
     `chunk` may also be the raw event dict {'ts', 'x', 'y', 'p'} DSECDatasetLite yields when data.preprocessed is false (one sample;
@@ -284,6 +376,8 @@ def _evaluate(model, samples, config, device="cuda", store=None):
     tot = {"AEE": 0.0, "PE1": 0.0, "PE2": 0.0, "PE3": 0.0, "outliers": 0.0}
     it = 0
     for chunk, mask, label in samples:
+        if warp is not None:
+            warp.needs_events(isinstance(chunk, dict))
         if isinstance(chunk, dict):
             if not config["loader"].get("polarity", True):
                 raise ValueError("the event path builds the two-polarity input (loader.polarity: true)")
@@ -311,6 +405,8 @@ def _evaluate(model, samples, config, device="cuda", store=None):
             mask = mask * x.sum(1).sum(1, keepdim=True).bool()
         if store is not None:
             store(x if chunk is None else chunk, label, pred)
+        if warp is not None:
+            warp(ev, pred, config["loader"]["resolution"], crop, config["metrics"]["flow_scaling"], store)
         m = AEE(pred, label, mask, config["metrics"]["flow_scaling"])()
         for b in range(pred.shape[0]):
             it += 1

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import inspect
+import math
 import os
 
 import torch
@@ -269,6 +270,20 @@ class EventVoxelTbDesc(C.Structure):
                 ("normalize", C.c_int32), ("mode", C.c_int32), ("norm", C.c_int32), ("use_spike_th", C.c_int32), ("spike_th", C.c_float)]
 
 
+class EventIweDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("t", C.c_void_p), ("p", C.c_void_p), ("flow", C.c_void_p), ("rectify_map", C.c_void_p),
+                ("offsets", C.c_void_p), ("t_range", C.c_void_p), ("keys", C.c_void_p), ("keys_sorted", C.c_void_p), ("order", C.c_void_p),
+                ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("n_events", C.c_int64),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32), ("crop_oy", C.c_int32),
+                ("crop_ox", C.c_int32), ("map_h", C.c_int32), ("map_w", C.c_int32), ("xy_dtype", C.c_int32), ("mode", C.c_int32),
+                ("scale", C.c_float), ("t_ref", C.c_float), ("win_a", C.c_float), ("win_b", C.c_float)]
+
+
+class IweStatsDesc(C.Structure):
+    _fields_ = [("iwe", C.c_void_p), ("table", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32)]
+
+
 class FlowMetricsDesc(C.Structure):
     _fields_ = [("pred", C.c_void_p), ("label", C.c_void_p), ("valid", C.c_void_p), ("event_mask", C.c_void_p), ("table", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
@@ -448,6 +463,9 @@ SIGNATURES = {
     "sdf_event_voxel_keys_fwd": (_i, (_P(EventVoxelDesc), _p)), "sdf_event_voxel_gather_fwd": (_i, (_P(EventVoxelDesc), _p)),
     "sdf_event_voxel_tb_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i, _i, _i, _i)),
     "sdf_event_voxel_tb_keys_fwd": (_i, (_P(EventVoxelTbDesc), _p)), "sdf_event_voxel_tb_gather_fwd": (_i, (_P(EventVoxelTbDesc), _p)),
+    "sdf_event_iwe_workspace_bytes": (_i64, (_i64, _i, _i, _i, _i, _i, _i, _i, _i)),
+    "sdf_event_iwe_keys_fwd": (_i, (_P(EventIweDesc), _p)), "sdf_event_iwe_gather_fwd": (_i, (_P(EventIweDesc), _p)),
+    "sdf_iwe_stats_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_iwe_stats_fwd": (_i, (_P(IweStatsDesc), _p)),
     "sdf_flow_metrics_workspace_bytes": (_i64, (_i, _i, _i)), "sdf_flow_metrics_fwd": (_i, (_P(FlowMetricsDesc), _p)),
     "sdf_flow_loss_workspace_bytes": (_i64, (_i, _i, _i, _i)), "sdf_flow_loss_fwd": (_i, (_P(FlowLossDesc), _p)),
     "sdf_augment_resize_workspace_bytes": (_i64, (_i,)), "sdf_augment_resize_fwd": (_i, (_P(AugmentResizeDesc), _p)),
@@ -2188,6 +2206,27 @@ def _event_lists(fn, x, y, t, p, offsets, xy_kinds):
     return x.contiguous(), y.contiguous(), t.contiguous(), p.contiguous(), n, offs, (C.c_int64 * len(offs))(*offs), xy
 
 
+def _event_t_range(fn, t, offs, n):
+    """The descriptor's host array t_range = {t_first, t_last} per list, read back in one small copy: the library refuses a non-empty
+    list whose two times are equal (keep the array alive across the calls)."""
+    B = len(offs) - 1
+    ends = [i for b in range(B) if offs[b + 1] > offs[b] for i in (offs[b], offs[b + 1] - 1)]
+    if any(i < 0 or i >= n for i in ends):
+        raise SdfError(f"{fn}: offsets outside the event arrays")
+    got = iter(t[torch.tensor(ends, device=t.device, dtype=torch.long)].tolist())
+    flat = [v for b in range(B) for v in ((next(got), next(got)) if offs[b + 1] > offs[b] else (0.0, 1.0))]
+    return (C.c_float * (2 * B))(*flat)
+
+
+def _event_rectify_map(fn, d, rectify_map):
+    """`rectify_map` (H_s, W_s, 2) fp32 into the descriptor; returns the contiguous tensor (keep it alive across the calls)."""
+    if rectify_map.dim() != 3 or rectify_map.shape[2] != 2:
+        raise SdfError(f"{fn}: rectify_map is (H_s, W_s, 2)")
+    rectify_map = rectify_map.contiguous()
+    d.rectify_map, d.map_h, d.map_w = _ptr(rectify_map, torch.float32), rectify_map.shape[0], rectify_map.shape[1]
+    return rectify_map
+
+
 def _event_gather(fn, d, cache, need, refused, shape, out, n, dev):
     """The tail the two event front ends share, on a descriptor filled up to the geometry: workspace of `need` bytes (<= 0: the
     library refused the geometry - `refused` says which), `out` (None: a new tensor of `shape`), keys | stable sort | gather.
@@ -2233,21 +2272,13 @@ def event_voxel(x, y, t, p, bins, sensor_size, offsets=None, crop=None, mode="si
     d = EventVoxelDesc()
     d.x, d.y, d.t, d.p, d.xy_dtype = x.data_ptr(), y.data_ptr(), _ptr(t, torch.float32), _ptr(p, torch.float32), xy
     if rectify_map is not None:
-        if rectify_map.dim() != 3 or rectify_map.shape[2] != 2:
-            raise SdfError("event_voxel: rectify_map is (H_s, W_s, 2)")
-        rectify_map = rectify_map.contiguous()
-        d.rectify_map, d.map_h, d.map_w = _ptr(rectify_map, torch.float32), rectify_map.shape[0], rectify_map.shape[1]
+        rectify_map = _event_rectify_map("event_voxel", d, rectify_map)
     d.offsets, d.n_events = C.addressof(host_offs), n
     d.B, d.C, d.H, d.W, d.crop_h, d.crop_w = B, bins, H, W, (h if crop else 0), (w if crop else 0)
     d.mode, d.norm = EVENT_VOXEL_MODES[mode], int(norm == "minmax")
     d.use_spike_th, d.spike_th = int(spike_th is not None), float(spike_th or 0.0)
     if check and n:
-        ends = [i for b in range(B) if offs[b + 1] > offs[b] for i in (offs[b], offs[b + 1] - 1)]
-        if any(i < 0 or i >= n for i in ends):
-            raise SdfError("event_voxel: offsets outside the event arrays")
-        got = iter(t[torch.tensor(ends, device=dev, dtype=torch.long)].tolist())
-        flat = [v for b in range(B) for v in ((next(got), next(got)) if offs[b + 1] > offs[b] else (0.0, 1.0))]
-        host_range = (C.c_float * (2 * B))(*flat)
+        host_range = _event_t_range("event_voxel", t, offs, n)
         d.t_range = C.addressof(host_range)
     need = lib().sdf_event_voxel_workspace_bytes(n, B, bins, H, W, d.crop_h, d.crop_w)
     shape = (B, bins, h, w) if mode == "signed" else (B, bins, 2, h, w)
@@ -2295,6 +2326,87 @@ def event_voxel_tb(x, y, t, p, num_bins, sensor_size, offsets=None, t_scale=1.0,
     out = _event_gather("event_voxel_tb", d, _EV_TB_WS, need,
                         f"{L} lists, bins {num_bins}, sensor {H} x {W}, crop {crop} at {(oy, ox)}, {n} events", shape, out, n, dev)
     return (out, mask) if want_event_mask else out
+
+
+EVENT_IWE_MODES = {"bilinear": 0, "nearest": 1}
+IWE_STATS_FIELDS = ("sum", "sum_sq", "max", "n_nonzero")
+_IWE_WS, _IWE_STATS_WS = {}, {}
+
+
+def event_iwe(x, y, t, p, flow, sensor_size, offsets=None, crop=None, crop_origin=None, scale=1.0, t_ref=1.0, window=(0.0, 1.0),
+              mode="bilinear", rectify_map=None, check=True, out=None):
+    """Raw event lists + a flow -> the image of warped events on the GPU (sdf_event_iwe_keys_fwd | stable sort | sdf_event_iwe_gather_fwd;
+    the definition: csrc/event_iwe.hip): (B, 2, h, w) fp32, channel 0 the p > 0 events and channel 1 the others,
+    every event moved from its normalised time tau to `t_ref` along `scale` * the flow at its pixel.  Bit-identical from run to run and
+    independent of how lists are batched; no float atomics.
+
+    x, y, t, p, `offsets`, `rectify_map`, `check`: as hip.event_voxel takes them (t fp32, each list in time order).  flow (B, 2, h, w)
+    fp32, channel 0 = x, on the output window: `crop` (h, w) of `sensor_size` (H, W) at `crop_origin` (oy, ox), default
+    harness.center_crop's; no crop: the whole sensor.  `window` (a, b): only the events with a <= tn <= b, their time renormalised to
+    the window.  mode "bilinear": four weighted corners, summed per cell in a fixed order | "nearest": 1 at the rounded position - the
+    image holds integers.  The flow is looked up at the event's nearest pixel (a bilinear lookup is not built), and there is no
+    backward pass: contrast-maximisation training is not served."""
+    x, y, t, p, n, offs, host_offs, xy = _event_lists("event_iwe", x, y, t, p, offsets, "fp32, or int32 / uint16 with a rectify_map")
+    if mode not in EVENT_IWE_MODES:
+        raise SdfError(f"event_iwe: unknown mode {mode!r} (bilinear | nearest; a bilinear flow lookup, the average-timestamp image and "
+                       "a backward pass are not built)")
+    B, (H, W) = len(offs) - 1, sensor_size
+    h, w = crop if crop else (H, W)
+    oy, ox = crop_origin if crop_origin is not None else (((H - h) // 2, (W - w) // 2) if crop else (0, 0))
+    if not crop and (oy, ox) != (0, 0):
+        raise SdfError("event_iwe: crop_origin without a crop")
+    a, b = (float(v) for v in window)
+    if not (a < b) or not all(math.isfinite(v) for v in (a, b, float(t_ref))) or float(scale) != float(scale):
+        raise SdfError(f"event_iwe: window {window!r} needs a < b, and finite window / t_ref / scale values", rc=E_SHAPE)
+    _ptr(flow, torch.float32)
+    if tuple(flow.shape) != (B, 2, h, w):
+        raise SdfError(f"event_iwe: flow is {(B, 2, h, w)} on the output window, got {tuple(flow.shape)}")
+    flow = flow.contiguous()
+    dev = t.device
+    d = EventIweDesc()
+    d.x, d.y, d.t, d.p, d.xy_dtype = x.data_ptr(), y.data_ptr(), _ptr(t, torch.float32), _ptr(p, torch.float32), xy
+    d.flow = flow.data_ptr()
+    if rectify_map is not None:
+        rectify_map = _event_rectify_map("event_iwe", d, rectify_map)
+    d.offsets, d.n_events = C.addressof(host_offs), n
+    d.B, d.H, d.W = B, H, W
+    d.crop_h, d.crop_w, d.crop_oy, d.crop_ox = (h if crop else 0), (w if crop else 0), oy, ox
+    d.mode, d.scale, d.t_ref, d.win_a, d.win_b = EVENT_IWE_MODES[mode], float(scale), float(t_ref), a, b
+    if check and n:
+        host_range = _event_t_range("event_iwe", t, offs, n)
+        d.t_range = C.addressof(host_range)
+    need = lib().sdf_event_iwe_workspace_bytes(n, B, H, W, d.crop_h, d.crop_w, oy, ox, d.mode)
+    return _event_gather("event_iwe", d, _IWE_WS, need, f"B {B}, sensor {H} x {W}, crop {crop} at {(oy, ox)}, {n} events", (B, 2, h, w),
+                         out, n, dev)
+
+
+def iwe_stats(iwe, table=None, row=0):
+    """Per-sample statistics of an image of warped events on the GPU (sdf_iwe_stats_fwd: two launches, no read-back): sample b of iwe
+    (B, 2, h, w) fp32 writes row `row` + b of `table` (rows, 4) float64 - IWE_STATS_FIELDS: sum, sum of squares, maximum and number of
+    non-zero pixels of the channel sum - and leaves the other rows as they are.  `table` None: a new zero table of row + B rows.
+    Returns the table.  fp64 sums in a fixed order: bit-identical from run to run and independent of B; exact on nearest images."""
+    _ptr(iwe, torch.float32)
+    if iwe.dim() != 4 or iwe.shape[1] != 2:
+        raise SdfError(f"iwe_stats: iwe is (B, 2, h, w), got {tuple(iwe.shape)}")
+    iwe = iwe.contiguous()
+    B, _, H, W = iwe.shape
+    dev = iwe.device
+    if table is None:
+        table = torch.zeros((row + B, len(IWE_STATS_FIELDS)), dtype=torch.float64, device=dev)
+    if table.dim() != 2 or table.shape[1] != len(IWE_STATS_FIELDS) or not table.is_contiguous():
+        raise SdfError(f"iwe_stats: table must be a contiguous (rows, {len(IWE_STATS_FIELDS)}) float64 tensor")
+    if row < 0 or row + B > table.shape[0]:
+        raise SdfError(f"iwe_stats: rows {row} .. {row + B - 1} lie outside the table's {table.shape[0]}", rc=E_SHAPE)
+    need = lib().sdf_iwe_stats_workspace_bytes(B, H, W)
+    if need <= 0:
+        raise SdfError(f"iwe_stats: geometry refused (B {B}, {H} x {W})", rc=E_SHAPE)
+    ws = _stream_ws(_IWE_STATS_WS, dev, need)
+    d = IweStatsDesc()
+    d.iwe, d.table, d.workspace, d.workspace_bytes = iwe.data_ptr(), _ptr(table, torch.float64), ws.data_ptr(), ws.numel()
+    d.B, d.H, d.W, d.row0, d.rows = B, H, W, row, table.shape[0]
+    _note(bytes=B * H * W * 8, shape=(B, H, W))
+    _check(lib().sdf_iwe_stats_fwd(C.byref(d), _stream()), "sdf_iwe_stats_fwd")
+    return table
 
 
 FLOW_METRICS_FIELDS = ("n_valid", "sum_err", "n_pe1", "n_pe2", "n_pe3", "n_outlier", "sum_ang", "n_pixels")

@@ -3,7 +3,8 @@ the ground-truth flow of every evaluated sample as 8-bit PNGs, and the estimated
 
 Everything is rendered on the GPU (hip.flow_image / flow_submission / event_counts_image, csrc/flow_render.hip) from device tensors; what
 crosses to the host is one copy of the finished bytes per image, and the files are written by utils/png.py.  Not built: the live cv2
-window (`update`), the frames / iwe / `*_window` images (the reference's loops pass None for them) and the gray / blue_red schemes."""
+window (`update`), the frames / `*_window` images (the reference's loops pass None for them; the image of warped events is written by
+the loops themselves with fwl=True, harness.evaluate) and the gray / blue_red schemes."""
 import os
 
 import numpy as np
