@@ -20,6 +20,8 @@
 // Epilogues, operand address modes (rows / tiled hand-over / head scramble / 2x2 merge quadrants) and the tiled hand-over layout are
 // those of wide_pm_kernel (ms_wide.hip): the two kernel families interoperate launch by launch and give bit-equal results (exact
 // integer sums, the same fp32 epilogue expressions).
+// The same kernel takes K = 1 536 (fc2 and the merge of the 384-channel stage: 144 KB of digits) in the forms that fit beside it - without
+// the operand strips, and with the emitted neuron's bytes stored straight from registers (res_pm_lean_kernel): res_pm_form.
 //
 //   res_pm_kernel    : proj (x += BN(Z Wp^T + b) through the head scramble, + the MLP's SN1), fc1 (+ BN1 + SN2), fc2 (+ BN2 +
 //                      shortcut [+ the next layer's first neuron]), patch merging    reference Spiking_swin_transformer3D.py:164-181,
@@ -191,18 +193,22 @@ __device__ __forceinline__ float res_digits_f32(int a0, int a1, int a2) {
 // Position-major product, weight-resident.  EPI / AM as wide_pm_kernel: EPI 1 = neuron (spikes out), 2 = fp32 (+ shortcut), 3 = fp32 and
 // the neuron on the updated stream; AM 0 = rows of a tensor (row-major / tiled / head scramble), 2 = the 2x2 concatenation of patch
 // merging (any C % 16 == 0: the quadrant of every 16-byte k-piece is decoded per lane).  SK: K <= 256 (res_digits_f32).
-template <int T, int EPI, int NK, int AM, bool SK, bool STRIP = false>
-__global__ __launch_bounds__(64 * NWV) void res_pm_kernel(WidePmParams P) {
+// LEAN (K > 1 024, where the digits leave the LDS no room): epilogue 3 stores its spike bytes row-major straight from the transposed
+// quads, four bytes a lane, and has no byte tiles.
+template <int T, int EPI, int NK, int AM, bool SK, bool STRIP, bool LEAN>
+__device__ __forceinline__ void res_pm_body(const WidePmParams P) {
   constexpr int RB = RBW, CB = 2, ROWS = 16 * RB, SLOTS = 4 * RB, PPG = SLOTS / T, PPW = 4 * PPG, BN = 16 * CB;
   constexpr int SP = s_pitch(BN), STILE = ROWS * SP;
   static_assert(SLOTS % T == 0, "T must divide the 20 accumulator slots of a lane");
   static_assert(EPI >= 1 && EPI <= 3 && (AM == 0 || AM == 2 || AM == 3), "epilogue 1 neuron / 2 fp32 / 3 both; operand rows, merge quadrants or the transposed convolution's 2 x 2 neighbourhood");
   static_assert(AM != 3 || EPI == 2, "the transposed convolution has the fp32 epilogue only");
+  static_assert(!LEAN || (EPI == 3 && AM == 0 && !STRIP && !SK), "the lean form is fc2 with the emitted neuron");
+  constexpr bool TILES = (EPI & 1) != 0 && !LEAN;        // the neuron epilogues' byte tiles
   extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
   const int K = P.K, N = P.N, HW = P.HW, KP = res_kp(K);
   uint8_t* Wl = dyn;                                     // resident weights
   uint8_t* Sall = dyn + res_wbytes(K, BN);               // per-wave byte tiles [80][SP]
-  int32_t* rowtab_all = reinterpret_cast<int32_t*>(Sall + ((EPI & 1) ? NWV * STILE : 0));
+  int32_t* rowtab_all = reinterpret_cast<int32_t*>(Sall + (TILES ? NWV * STILE : 0));
   f32x4* coltab = reinterpret_cast<f32x4*>(rowtab_all + NWV * ROWS);           // per column: {alpha x digit scale, beta, digit scale, bias}
   float* psn_tbl = reinterpret_cast<float*>(coltab + BN);
   uint8_t* strips = reinterpret_cast<uint8_t*>(psn_tbl + (NK == 1 ? PSN_TABLE(20) : 0));      // STRIP: RB x 1 KB per wave
@@ -416,12 +422,18 @@ __global__ __launch_bounds__(64 * NWV) void res_pm_kernel(WidePmParams P) {
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
           const uint32_t w = quad_tr_bytes(spread4(bits >> (4 * rb)), sel1, sel2);
-          *reinterpret_cast<uint32_t*>(S + (16 * rb + 4 * q + ci) * SP + 16 * cb + 4 * m4) = w;
+          if constexpr (LEAN) {                            // row 16 rb + 4 q + ci, columns 16 cb + 4 m4 .. + 3 of the row-major output
+            const int32_t g = rowtab[16 * rb + 4 * q + ci];
+            const uint32_t off = (g >= 0 && n0 + 16 * cb < N) ? (uint32_t)g * (uint32_t)P.ldsp + (uint32_t)(n0 + 16 * cb + 4 * m4) : INV;
+            __builtin_amdgcn_raw_buffer_store_b32(w, o_rs, off, 0, 0);
+          } else {
+            *reinterpret_cast<uint32_t*>(S + (16 * rb + 4 * q + ci) * SP + 16 * cb + 4 * m4) = w;
+          }
         }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr ((EPI & 1) != 0) {
+    if constexpr (TILES) {
 #pragma unroll
       for (int it = 0; it < (ROWS * CB + 63) / 64; ++it) {
         const int pc = lane + 64 * it;
@@ -442,6 +454,15 @@ __global__ __launch_bounds__(64 * NWV) void res_pm_kernel(WidePmParams P) {
     RSTAMP(4);
   }
   RSTAMP_OUT(EPI, (u_hi - u_lo + NWV - 1) / NWV);
+}
+
+template <int T, int EPI, int NK, int AM, bool SK, bool STRIP = false>
+__global__ __launch_bounds__(64 * NWV) void res_pm_kernel(WidePmParams P) {
+  res_pm_body<T, EPI, NK, AM, SK, STRIP, false>(P);
+}
+template <int T, int NK>
+__global__ __launch_bounds__(64 * NWV) void res_pm_lean_kernel(WidePmParams P) {
+  res_pm_body<T, 3, NK, 0, false, false, true>(P);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -593,11 +614,14 @@ bool res_env_off() {
   return sdf_sw_is(SW_RES, '0');                     // A/B: 0 = the kernels these replaced (ms_wide.hip / qk_front / ms_mlp_fused / spike_gemm)
 }
 
+constexpr int RES_K_SHORT = 1024;                        // up to here (96 KB of digits) every form fits a compute unit's LDS
+constexpr size_t RES_LDS_MAX = 158 * 1024;               // a workgroup's dynamic LDS: what res_raise opts in to
+
 // dynamic LDS above 64 KB needs the attribute, once per kernel function (process-wide, read-only afterwards)
 template <class KernelT>
 int res_raise(KernelT kern) {
   static std::atomic<uint64_t> done{0};                  // (one instance per kernel type: the template parameter is the function's type; one bit per device)
-  return sdf_lds_opt_in(done, reinterpret_cast<const void*>(kern), 158 * 1024);
+  return sdf_lds_opt_in(done, reinterpret_cast<const void*>(kern), (int)RES_LDS_MAX);
 }
 
 bool res_strip(const WidePmParams& P) {
@@ -605,13 +629,43 @@ bool res_strip(const WidePmParams& P) {
   return P.cv_Cin != 0 || (!P.a_tiled && !P.zsrc);
 }
 
-size_t res_pm_lds(int K, int epi, int T, int nk) {
+// `strip`: the launch runs a STRIP build, `lean`: a LEAN one (no byte tiles).  Up to RES_K_SHORT every fp32-epilogue launch carries the
+// strips' 40 KB, used or not (its size is what it was); a longer K has no room to spare and carries them only where they are used.
+size_t res_pm_lds(int K, int epi, int T, int nk, bool strip, bool lean) {
   constexpr int SP = s_pitch(32);
-  size_t b = (size_t)res_wbytes(K, 32) + ((epi & 1) ? NWV * 80 * SP : 0) + NWV * 80 * 4 + 32 * 16;
+  size_t b = (size_t)res_wbytes(K, 32) + ((epi & 1) && !lean ? NWV * 80 * SP : 0) + NWV * 80 * 4 + 32 * 16;
   if (nk == 1) b += PSN_TABLE(20) * 4;
-  if (epi == 2) b += NWV * RBW * 1024;                  // (the operand strips of the STRIP builds)
+  if (epi == 2 && (strip || K <= RES_K_SHORT)) b += NWV * RBW * 1024;      // (the operand strips of the STRIP builds)
   (void)T;
   return b;
+}
+
+// The build a launch runs and its LDS.  K above RES_K_SHORT (fc2 and the merge of the stages with 4 C > 1 024): the whole K of a column
+// group stays resident where the launch fits beside it - K = 1 536 is 144 KB of digits - so such a launch sheds what it can: the strips
+// (40 KB: row-major operands are then read fragment-shaped) and, with the emitted neuron on row-major spikes, the byte tiles (30 KB:
+// the LEAN build).  What still does not fit (K = 3 072; fc1's tiled spikes at such a K) keeps the K ring: res_pm_takes.
+struct ResPmForm { int nk; bool strip, lean; size_t lds; };
+ResPmForm res_pm_form(const WidePmParams& P, int T, int epi) {
+  ResPmForm f;
+  f.nk = (epi & 1) ? neuron_class(P.sn) : 0;
+  f.lean = P.K > RES_K_SHORT && epi == 3 && !P.cv_Cin && !P.out_tiled;
+  f.strip = epi == 2 && res_strip(P) && (P.K <= RES_K_SHORT || res_pm_lds(P.K, epi, T, f.nk, true, f.lean) <= RES_LDS_MAX);
+  f.lds = res_pm_lds(P.K, epi, T, f.nk, f.strip, f.lean);
+  return f;
+}
+
+// SDF_RES_MAXK: tuning override, 1024 = the routing before the long-K forms (same-build A/B).
+int res_maxk() {
+  if (const char* e = sdf_sw(SW_RES_MAXK)) { const int v = atoi(e); if (v >= RES_K_SHORT && v <= 3072) return v; }
+  return 1536;
+}
+// A long K pays 144 KB of weight loads per workgroup before its first MFMA: worth it where every wave then walks several units (540
+// units - ten samples - of fc2 at 384 channels: 109 -> 75 us), not on one sample's 54 units (19.5 us on the K ring, 25 us here).  Below
+// 64 units (5 120 rows: the bound under which the small-M kernel is offered fc2) the K ring keeps the launch, so the latency of a single
+// forward is what it was.  SDF_RES_LONGK_UNITS: tuning override (tests: 1).
+int res_longk_units() {
+  if (const char* e = sdf_sw(SW_RES_LONGK_UNITS)) { const int v = atoi(e); if (v >= 1) return v; }
+  return 64;
 }
 
 }  // namespace
@@ -620,7 +674,11 @@ size_t res_pm_lds(int K, int epi, int T, int nk) {
 bool res_pm_takes(const WidePmParams& P, int T, int epi) {
   if (res_env_off() || !P.res_stage) return false;
   if (T != 10 && T != 20) return false;
-  if (P.K % 16 || P.K < 32 || P.K > 1024 || P.N % 32 || P.ksplit > 1 || epi < 1 || epi > 3) return false;      // (K <= 1024: 96 KB of resident digits)
+  if (P.K % 16 || P.K < 32 || P.K > res_maxk() || P.N % 32 || P.ksplit > 1 || epi < 1 || epi > 3) return false;
+  if (P.K > RES_K_SHORT) {                                // (K <= 1024: 96 KB of resident digits, any form; beyond: what fits, on enough rows)
+    if (res_pm_form(P, T, epi).lds > RES_LDS_MAX) return false;
+    if (pm_units(P.P, T) < res_longk_units()) return false;
+  }
   if (P.cv_Cin && !(epi == 2 && P.cv_Cin % 16 == 0 && 4 * P.cv_Cin == P.K && !P.zsrc && !P.a_tiled)) return false;      // (patch merging, transposed convolution)
   if (P.dc_cout && !(P.cv_Cin && P.dc_cout % 4 == 0 && P.N == 4 * P.dc_cout && P.no_resid)) return false;
   if (P.zsrc && P.K % 32) return false;
@@ -635,30 +693,41 @@ int launch_res_pm(WidePmParams& P, int T, int epi, hipStream_t s) {
   P.nrg = (int)res_row_ranges(P.ncg, units, P.passes);    // (passes = units per row range)
   dim3 grid;
   if (int rc = grid8((int64_t)P.ncg * P.nrg, grid)) return rc;
-  const int nk = (epi & 1) ? neuron_class(P.sn) : 0;
-  const size_t lds = res_pm_lds(P.K, epi, T, nk);
+  // row-major operands through the full-line loads + LDS strip: patch merging always, the plain fp32 product (the decoders' stacked taps,
+  // fc2 on the parity tape's row-major spikes) where the rows are a plain tensor
+  const ResPmForm f = res_pm_form(P, T, epi);
+  const int nk = f.nk;
+  const bool strip = f.strip;
+  const size_t lds = f.lds;
+  if (lds > RES_LDS_MAX) return SDF_E_SHAPE;
   if (P.cv_Cin) {                                         // patch merging: cv_cpt carries ceil(2^16 / (C / 16)) for the per-piece quadrant decode
     P.cv_cpt = (65536 + (P.cv_Cin >> 4) - 1) / (P.cv_Cin >> 4);
     for (int p = 0; p < (P.K >> 4) + 8; ++p)
       if ((int)(((uint32_t)p * (uint32_t)P.cv_cpt) >> 16) != p / (P.cv_Cin >> 4)) return SDF_E_SHAPE;
   }
-  // row-major operands through the full-line loads + LDS strip: patch merging always, the plain fp32 product (the decoders' stacked taps,
-  // fc2 on the parity tape's row-major spikes) where the rows are a plain tensor
-  const bool strip = epi == 2 && res_strip(P);
   const int am = P.cv_Cin ? (P.dc_cout ? 3 : 2) : 0;      // A addressing: plain rows / patch merging / the 2 x 2 transposed convolution
   int rc = SDF_E_SHAPE;
-  // built: the fp32 epilogue (2) has no neuron and alone reads the merged / transposed operands and the strip; small-K from K <= 256 down
+  // built: the fp32 epilogue (2) has no neuron and alone reads the merged / transposed operands and the strip; small-K from K <= 256 down;
+  // lean: epilogue 3 on plain rows, K > 1 024
   sdf_dispatch(SdfList<10, 20>{}, T, [&](auto t) {
     sdf_dispatch(SdfList<0, 2, 3>{}, am, [&](auto a) {
       sdf_dispatch(SdfList<1, 2, 3>{}, epi, [&](auto e) {
         sdf_dispatch(SdfList<0, 1, 2>{}, nk, [&](auto n) {
           sdf_dispatch(SdfList<0, 1>{}, strip, [&](auto st) {
             sdf_dispatch(SdfList<0, 1>{}, P.K <= 256, [&](auto sk) {
-              if constexpr ((e == 2 || (a == 0 && st == 0)) && (e != 2 || n == 0)) {
-                auto kern = res_pm_kernel<t, e, n, a, sk != 0, st != 0>;
-                rc = res_raise(kern);
-                if (!rc) SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P);
-              }
+              sdf_dispatch(SdfList<0, 1>{}, f.lean, [&](auto ln) {
+                if constexpr (ln != 0) {
+                  if constexpr (e == 3 && a == 0 && st == 0 && sk == 0) {
+                    auto kern = res_pm_lean_kernel<t, n>;
+                    rc = res_raise(kern);
+                    if (!rc) SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P);
+                  }
+                } else if constexpr ((e == 2 || (a == 0 && st == 0)) && (e != 2 || n == 0)) {
+                  auto kern = res_pm_kernel<t, e, n, a, sk != 0, st != 0>;
+                  rc = res_raise(kern);
+                  if (!rc) SDF_LAUNCH(kern, grid, dim3(64 * NWV), lds, s, P);
+                }
+              });
             });
           });
         });

@@ -780,9 +780,19 @@ int launch_pm(WidePmParams& P, int T, int epi, hipStream_t s) {
 // 80-row units (configs[4]'s stage 3 - 24 000 rows - measured +1 % on them: 119.5 against 118.1 samples/s).  Larger problems
 // (configs[4]: 96 000 rows at stage 2) keep the streaming kernels, which they fill: measured 119 -> 109 samples/s with the limit lifted
 // (SDF_WIDE=2: tests, A/B).  Round 5: 131 072 rows - with the row-loop kernels of ms_res.hip taking the front, the projection and fc1
-// of a block at any row count, the limit only decides whether fc2 of the C >= 384 stages (K > 1 024: not theirs) runs here or drags the
-// WHOLE block back to the streaming kernels: configs[4] (96 000 rows at stage 2) 129.7 -> 143.4 samples/s with it lifted
-// (profiles/r5ao_config5_kernel_stats.txt, same box A/B).
+// of a block at any row count, the limit only decides whether fc2 of the C >= 384 stages (K > 1 024: theirs only where the whole K
+// fits the LDS, below) runs here or drags the WHOLE block back to the streaming kernels: configs[4] (96 000 rows at stage 2)
+// 129.7 -> 143.4 samples/s with it lifted (profiles/r5ao_config5_kernel_stats.txt, same box A/B).
+//
+// K > 1 024 (res_pm_takes / res_pm_form, ms_res.hip; SDF_RES_MAXK=1024: all of it here again).  Measured per 10-sample launch sequence
+// (profiles/long_k_launch_table_lif_R10_parent.txt against ..._R10.txt: duration, and chip time = duration x the share of the 256
+// compute units held):
+//   fc2 at 384 channels, K = 1 536, fp32 epilogue     108 - 110 us on 1 624 workgroups here -> 74 - 77 us on 208 there  (chip time 109 -> 61)
+//   the same with the emitted neuron (lean build)     120 us                                -> 83 us                    (120 -> 68)
+//   merge of 384 channels, K = 1 536, no strip        97 us on 216 workgroups               -> 75 us on 216             (82 -> 63)
+// 28 us of chip time per sample in all, and the headline 847 - 853 -> 867 - 875 samples/s (profiles/long_k_routing_ab.txt).
+// They keep this kernel: K = 3 072 (fc2 at 768 channels: 96 / 102 us, chip time 81 / 86 - 288 KB of digits per 32 columns fit no LDS),
+// and any K > 1 024 on fewer than 64 units - one sample's fc2 at 384 channels is 19.5 us here against 25 us there.
 static int64_t wide_max_rows() {                      // (SDF_WIDE_MAXROWS: tuning override)
   if (const char* e = sdf_sw(SW_WIDE_MAXROWS)) { const long v = atol(e); if (v >= 80) return v; }
   return 131072;
@@ -877,7 +887,8 @@ bool wide_merge_supports(const SdfMsMergeDesc* d) {
 int launch_wide_merge(const SdfMsMergeDesc* d, hipStream_t s) {
   WidePmParams P = pm_merge(d);
   const int T = d->D;
-  P.res_stage = res_stage_ok(d->C, true);
+  // (beyond 256 channels, K = 4 C > 1 024, this kernel serves every shape: the row loop only where res_pm_takes finds it fits and pays)
+  P.res_stage = res_stage_ok(d->C, true) || (d->C > 256 && d->C % 64 == 0);
   if (res_pm_takes(P, T, 2)) return launch_res_pm(P, T, 2, s);
   dim3 grid;
   if (int rc = pm_ring_grid(P, T, 2, false, grid)) return rc;

@@ -5,7 +5,8 @@
 #pragma once
 #define SDF_SWITCH_LIST(X)                                                                                                        \
   X(DENSE_TPW) X(DENSE_LINEAR_XCD) X(HEAD_MFMA) X(MLP_FUSED_ANY) X(MLP_FUSED) X(RES) X(RES_STRIP) X(RES_UPW) X(RES_RMUL)            \
-  X(RES_MINC) X(RES_MAXC) X(SMALLM) X(SMALLM_CONV_ROWS) X(SMALLM_CB) X(SMALLM_FC2) X(WIDE) X(WIDE_CB) X(WIDE_PASSES)                \
+  X(RES_MINC) X(RES_MAXC) X(RES_MAXK) X(RES_LONGK_UNITS) X(SMALLM) X(SMALLM_CONV_ROWS) X(SMALLM_CB) X(SMALLM_FC2) X(WIDE) X(WIDE_CB)   \
+  X(WIDE_PASSES)                                                                                                                  \
   X(WIDE_MAXROWS) X(WIDE_CONV) X(QK_FRONT) X(QK_FRONT_ANY) X(CONV_WRES) X(CONV_WRES_RB) X(CONV_WRES_GROUPS) X(CONV_WRES_CB_INNER)   \
   X(CONV_WRES_NOSPK) X(CONV_MULTI) X(DECONV_WRES) X(DECONV_BALANCE) X(DECONV_EPI) X(GEMM_CFG) X(GEMM_WGS) X(PP_PAIR)     \
   X(ATTN_GENERIC) X(ATTN_F32) X(KSPLIT_MULT) X(GEMM_WS)
