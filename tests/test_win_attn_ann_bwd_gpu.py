@@ -1,7 +1,9 @@
 """Backward of the ANN cosine window attention (csrc/win_attn_bwd.hip through autograd.WinAttnAnnFunction) against an fp64 torch
 composition that materialises the reference's pad, roll and window partition (swin_transformer3D_v2.py:286-310, :176-202):
 dqkv, d_pad (the padding tokens' share of the qkv bias gradient), d_logit_scale (through the clamp) and the cpb_mlp gradients,
-each within 2e-5 of the tensor's largest element (the forward's bound); two backward calls bit-equal."""
+each within 2e-5 of the tensor's largest element (the forward's bound) - the q, k and v thirds of dqkv and of d_pad each against
+their own largest element (with a zero pad row the k third of d_pad exceeds 1e6 and would hide the other two); two backward calls
+bit-equal.  Per element and per kernel route: test_win_attn_bwd_routes_gpu.py."""
 import math
 import zlib
 
@@ -24,10 +26,14 @@ CASES = {                    # name: (B, D, H, W, shifted, zero pad row, logit_s
 
 
 def _reference(qkv, pad, attn, B, D, H, W, ws, ss, nH, dout):
-    """fp64, materialised: pad (padding rows read `pad`) -> roll -> partition -> attention -> reverse -> roll back -> crop."""
+    """fp64, materialised: pad (padding rows read `pad`) -> roll -> partition -> attention -> reverse -> roll back -> crop.  The pad row
+    is selected into the padding positions, so its gradient is the sum over those positions alone and its q third is exactly 0 (a
+    padding token's output is cropped: its dO, so its row of dS, is 0), as the kernel's is."""
     Cc = qkv.shape[1] // 3
     Dp, Hp, Wp = D + (-D) % ws[0], H + (-H) % ws[1], W + (-W) % ws[2]
-    x = F.pad(qkv.view(B, D, H, W, -1) - pad, (0, 0, 0, Wp - W, 0, Hp - H, 0, Dp - D)) + pad
+    grow = (0, 0, 0, Wp - W, 0, Hp - H, 0, Dp - D)
+    real = F.pad(torch.ones((B, D, H, W, 1), dtype=qkv.dtype, device=qkv.device), grow) > 0
+    x = torch.where(real, F.pad(qkv.view(B, D, H, W, -1), grow), pad)      # (not pad(qkv - pad) + pad: d_pad would be a cancelling difference)
     shifted = any(ss)
     if shifted:
         x = torch.roll(x, shifts=tuple(-s for s in ss), dims=(1, 2, 3))
@@ -51,6 +57,13 @@ def _close(got, ref, what):
     ref = ref.double()
     err = (got.double() - ref).abs().max().item()
     assert err <= TOL * ref.abs().max().item(), (what, err, ref.abs().max().item())
+
+
+def _close_thirds(got, ref, what):
+    """the q, k and v thirds of a (..., 3C) tensor, each against its own largest element"""
+    Cc = ref.shape[-1] // 3
+    for i, part in enumerate("qkv"):
+        _close(got[..., i * Cc:(i + 1) * Cc], ref[..., i * Cc:(i + 1) * Cc], f"{what}.{part}")
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -91,8 +104,8 @@ def test_attention_backward_matches_fp64_materialised(Cc, nH, ws, case):
     q64, p64 = qkv.double().requires_grad_(True), pad.double().requires_grad_(True)
     _reference(q64, p64, ref_attn, B, D, H, W, ws, ss, nH, dout.double())
 
-    _close(q32.grad, q64.grad, "dqkv")
-    _close(p32.grad, p64.grad, "d_pad")
+    _close_thirds(q32.grad, q64.grad, "dqkv")
+    _close_thirds(p32.grad, p64.grad, "d_pad")
     _close(attn.logit_scale.grad, ref_attn.logit_scale.grad, "d_logit_scale")
     if big:
         assert attn.logit_scale.grad[0].item() == 0.0

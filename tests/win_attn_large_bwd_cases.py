@@ -39,10 +39,13 @@ def _ann_windows(win, attn, nH, mask):
 
 def ann_reference(qkv, pad, attn, B, D, H, W, ws, ss, nH, dout):
     """fp64, materialised: pad (padding rows read `pad`) -> roll -> partition -> attention -> reverse -> roll back -> crop; leaves the
-    gradients in qkv.grad, pad.grad and the module's parameters."""
+    gradients in qkv.grad, pad.grad and the module's parameters.  The pad row is selected into the padding positions: pad.grad is the sum
+    over those positions alone, its q third exactly 0 (a padding token's dO, so its row of dS, is 0)."""
     Cc = qkv.shape[1] // 3
     Dp, Hp, Wp = D + (-D) % ws[0], H + (-H) % ws[1], W + (-W) % ws[2]
-    x = F.pad(qkv.view(B, D, H, W, -1) - pad, (0, 0, 0, Wp - W, 0, Hp - H, 0, Dp - D)) + pad
+    grow = (0, 0, 0, Wp - W, 0, Hp - H, 0, Dp - D)
+    real = F.pad(torch.ones((B, D, H, W, 1), dtype=qkv.dtype, device=qkv.device), grow) > 0
+    x = torch.where(real, F.pad(qkv.view(B, D, H, W, -1), grow), pad)      # (not pad(qkv - pad) + pad: d_pad would be a cancelling difference)
     shifted = any(ss)
     if shifted:
         x = torch.roll(x, shifts=tuple(-s for s in ss), dims=(1, 2, 3))
