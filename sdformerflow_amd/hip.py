@@ -1730,14 +1730,15 @@ def dense_conv_slices(records):
     return [(6 * i, 6) for i in range(six)] + ([(6 * six, 1)] if one else [])
 
 
-def dense_conv3x3_wide(xp, wslices, beta=None, relu=False, out_f32=False):
+def dense_conv3x3_wide(xp, wslices, beta=None, relu=False, out_f32=False, out=None):
     """3x3 convolution over any record count `dense_conv_slices` can cut: link k multiplies records [first, first + count) with its own
-    weight planes and adds the previous link's result (`resid`); the last link adds beta, applies relu and picks the output format."""
-    out = None
+    weight planes and adds the previous link's result (`resid`); the last link adds beta, applies relu and picks the output format
+    (and writes into `out` where one is given)."""
+    res = None
     for k, ((r0, n), wp) in enumerate(wslices):
         last = k == len(wslices) - 1
-        out = dense_conv3x3(xp[:, r0:r0 + n], wp, None, beta if last else None, out, relu and last, out_f32 and last)
-    return out
+        res = dense_conv3x3(xp[:, r0:r0 + n], wp, None, beta if last else None, res, relu and last, out_f32 and last, out if last else None)
+    return res
 
 
 def dense_conv_applicable(imgs, H, W, Cin, Cout):
@@ -1746,9 +1747,10 @@ def dense_conv_applicable(imgs, H, W, Cin, Cout):
     return rec in (1, 6) and Cout % 32 == 0 and imgs * H * W * max(rec * 64, Cout * 4) < 1 << 31
 
 
-def dense_conv3x3(xp, wplanes, alpha=None, beta=None, resid=None, relu=False, out_f32=False):
+def dense_conv3x3(xp, wplanes, alpha=None, beta=None, resid=None, relu=False, out_f32=False, out=None):
     """out = act(alpha * conv3x3(x, w) + beta (+ resid)), stride 1, zero padding 1 (sdf_dense_conv3x3_fwd).  xp / resid / the result
-    are activation planes; out_f32 returns (imgs, H, W, N) fp32 (channels last) instead."""
+    are activation planes; out_f32 returns (imgs, H, W, N) fp32 (channels last) instead.  `out`: a preallocated contiguous tensor of the
+    result's shape and dtype to write into (e.g. a slice of a larger buffer) instead of a fresh one."""
     imgs, rec, H, W, _ = xp.shape
     N = wplanes.shape[1]
     if wplanes.shape[2] != rec * 144:
@@ -1759,8 +1761,11 @@ def dense_conv3x3(xp, wplanes, alpha=None, beta=None, resid=None, relu=False, ou
     x_records = xp.stride(0) // (H * W * 32)
     if resid is not None and tuple(resid.shape) != (imgs, N // 16, H, W, 32):
         raise SdfError("residual planes must have the output's shape")
-    out = (torch.empty((imgs, H, W, N), dtype=torch.float32, device=xp.device) if out_f32 else
-           torch.empty((imgs, N // 16, H, W, 32), dtype=torch.float16, device=xp.device))
+    shape, dtype = ((imgs, H, W, N), torch.float32) if out_f32 else ((imgs, N // 16, H, W, 32), torch.float16)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=xp.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != xp.device:
+        raise SdfError(f"out must be a contiguous {dtype} tensor of shape {shape} on the activations' device")
     d = DenseConvDesc()
     d.x, d.w, d.x_records = _ptr(xp, torch.float16), _ptr(wplanes, torch.float16), x_records
     d.alpha, d.beta = _ptr(alpha, torch.float32), _ptr(beta, torch.float32)
