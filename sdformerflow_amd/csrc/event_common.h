@@ -1,15 +1,50 @@
-// The skeleton the two event front ends share (event_voxel.hip, event_voxel_tb.hip), stated once: the run table of the stably
-// sorted events, the ordered summation of one pass over a cell's run, the ReLU and min / max of the model-input form, and the
-// launchers' checks and run-table preamble.  What differs stays in the files: the keys, the record (float4 | float2), one event's
-// term (ev_add | tb_add) and the passes of a cell.
+// The skeleton the three event front ends share (event_voxel.hip, event_voxel_tb.hip, event_iwe.hip), stated once: the coordinate
+// load through the rectify map, the checks of the lists and of the keys call's inputs, the per-list keys launch with its coordinate
+// dtype dispatch, the run table of the stably sorted events (with or without moving a record), and the ordered summation of one pass
+// over a cell's run.  What differs stays in the files: the keys, the record (float4 | float2 | none), one event's term (ev_add | tb_add
+// | IweTerm) and the passes of a cell.  event_voxel_tb.hip truncates integer pixels and has no map: its coordinate load is its own.
+// The model-input tail behind the two voxel front ends is model_input.h's.
+//
+// An inconsistency that stays: the IWE calls refuse host memory (SDF_E_DTYPE, after NULL and alignment); event_voxel and event_voxel_tb
+// make no device-memory check.
 #pragma once
 #include "common.h"
+#include <initializer_list>
+#include <type_traits>
 
 namespace {
 
 constexpr int kLongRun = 48;     // runs at least this long are summed by their lane with the whole wave fetching and weighting for it
 
-// sorted position i: the event's record moves to its sorted place, and the first / last position of a key's run go to the run table
+struct EventNoRec {};            // the record-free form: a cell's value is the length of its run (event_iwe.hip, nearest mode)
+
+// XY: 0 = fp32 coordinates as given, 1 = int32 sensor coordinates through the rectify map (x, y <- map[y, x]), 2 = uint16 likewise.
+// false: outside the map (the reference asserts this; here such an event adds nothing), x, y then the map's first entry
+template <int XY>
+__device__ __forceinline__ bool event_load_xy(const void* __restrict__ xs, const void* __restrict__ ys, const float* __restrict__ map,
+                                              int map_h, int map_w, int64_t e, float& x, float& y) {
+  if (XY == 0) {
+    x = static_cast<const float*>(xs)[e];
+    y = static_cast<const float*>(ys)[e];
+    return true;
+  }
+  int xi, yi;
+  if (XY == 1) {
+    xi = static_cast<const int32_t*>(xs)[e];
+    yi = static_cast<const int32_t*>(ys)[e];
+  } else {
+    xi = static_cast<const uint16_t*>(xs)[e];
+    yi = static_cast<const uint16_t*>(ys)[e];
+  }
+  const bool ok = xi >= 0 && xi < map_w && yi >= 0 && yi < map_h;
+  const int64_t m = ok ? ((int64_t)yi * map_w + xi) * 2 : 0;
+  x = map[m];
+  y = map[m + 1];
+  return ok;
+}
+
+// sorted position i: the event's record moves to its sorted place (Rec = EventNoRec: there is none, `order` is not read), and the
+// first / last position of a key's run go to the run table
 template <typename Rec>
 __global__ __launch_bounds__(256) void event_runs_kernel(const int* __restrict__ ks, const int64_t* __restrict__ order,
                                                          const Rec* __restrict__ rec, int n, int KT, Rec* __restrict__ rec_s,
@@ -18,9 +53,11 @@ __global__ __launch_bounds__(256) void event_runs_kernel(const int* __restrict__
   if (i >= n) return;
   const int k = ks[i];
   if (k < 0 || k >= KT) return;
-  const int64_t e = order[i];
-  if (e < 0 || e >= n) return;
-  rec_s[i] = rec[e];
+  if constexpr (!std::is_same<Rec, EventNoRec>::value) {
+    const int64_t e = order[i];
+    if (e < 0 || e >= n) return;
+    rec_s[i] = rec[e];
+  }
   if (i == 0 || ks[i - 1] != k) tab[k].x = i;
   if (i == n - 1 || ks[i + 1] != k) tab[k].y = i + 1;
 }
@@ -62,26 +99,6 @@ __device__ __forceinline__ void event_sum_run(const int2 r, const Rec* rec, cons
   acc2_io = acc2;
 }
 
-// relu as ATen's device clamp_min forms it: NaN stays, else fmaxf(v, 0) = v_max_f32, which orders -0 below +0: relu(-0) = +0
-__device__ __forceinline__ float event_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
-
-// min / max of the non-zero outputs.  They are positive floats here, which order as their bit patterns: integer min / max, any arrival
-// order.  Start from lo = 0xffffffff, hi = 0 ("no non-zero element").  The atomics behind the wave's reduction stay in the files:
-// event_voxel.hip's gather kernel issues a pair per wave (one value per lane, no LDS or barrier in that kernel), event_voxel_tb.hip's
-// grid-stride pass a pair per workgroup through LDS (a pair per wave cost more than that pass itself).
-__device__ __forceinline__ void minmax_nonzero(float o, unsigned& lo, unsigned& hi) {
-  if (o != 0.f) {
-    lo = min(lo, __float_as_uint(o));
-    hi = max(hi, __float_as_uint(o));
-  }
-}
-__device__ __forceinline__ void wave_minmax(unsigned& lo, unsigned& hi) {
-  for (int off = 32; off > 0; off >>= 1) {
-    lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
-    hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-  }
-}
-
 inline int64_t pad256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 // `offs` cuts n events into `lists` lists: from 0 to n, never backwards
@@ -92,20 +109,69 @@ inline bool event_offsets_ok(const int64_t* offs, int lists, int64_t n) {
   return true;
 }
 
-// The head of a gather launcher: the caller's sorted keys and permutation are there and aligned; every run empty; min / max over
-// nothing when they are wanted; then the run table and the sorted records.  0 or the error.
+// `offsets` (NULL: the one list of a B = 1 call, written to `own`) and, when given, the lists' {first, last} times: 0 and `offs`, or
+// the error
+inline int event_lists_check(const int64_t* offsets, int B, int64_t n, const float* t_range, const int64_t*& offs, int64_t* own) {
+  offs = offsets;
+  if (!offs) {
+    if (B != 1) return SDF_E_NULL;
+    own[0] = 0;
+    own[1] = n;
+    offs = own;
+  }
+  if (!event_offsets_ok(offs, B, n)) return SDF_E_SHAPE;
+  if (t_range)
+    for (int b = 0; b < B; ++b)                                          // a list whose first and last time are equal has no t_norm
+      if (offs[b + 1] > offs[b] && !(t_range[2 * b + 1] != t_range[2 * b])) return SDF_E_SHAPE;
+  return 0;
+}
+
+// the inputs of a keys call with events: there | the rectify map (`mapped` entry points: required with integer coordinates, refused
+// with fp32 ones, which do not index it) | aligned, t to `t_align` (4: fp32, 8: fp64)
+inline int event_keys_check(const void* x, const void* y, const void* t, const void* p, const void* keys, int xy_dtype, size_t t_align,
+                            bool mapped, const float* map, int map_h, int map_w) {
+  if (!x || !y || !t || !p || !keys) return SDF_E_NULL;
+  if (mapped && xy_dtype != 0 && (!map || map_h < 1 || map_w < 1)) return map ? SDF_E_SHAPE : SDF_E_NULL;
+  if (mapped && xy_dtype == 0 && map) return SDF_E_DTYPE;
+  const size_t xy_align = xy_dtype == 2 ? 2 : 4;
+  if (!sdf_aligned(x, xy_align) || !sdf_aligned(y, xy_align) || !sdf_aligned(t, t_align) || !sdf_aligned(p, 4) || !sdf_aligned(keys, 4) ||
+      (mapped && map && !sdf_aligned(map, 4)))
+    return SDF_E_ALIGN;
+  return 0;
+}
+
+template <int XY>
+using EventXY = std::integral_constant<int, XY>;
+
+// one keys launch per non-empty list: launch(EventXY<xy_dtype>, grid, first event, events, list) with 256 threads per workgroup
+template <typename Launch>
+inline int event_keys_launch(const int64_t* offs, int lists, int xy_dtype, Launch launch) {
+  for (int b = 0; b < lists; ++b) {
+    const int64_t i0 = offs[b];
+    const int n = (int)(offs[b + 1] - i0);
+    if (n == 0) continue;
+    const dim3 grid((n + 255) / 256);
+    if (xy_dtype == 0) launch(EventXY<0>{}, grid, i0, n, b);
+    else if (xy_dtype == 1) launch(EventXY<1>{}, grid, i0, n, b);
+    else launch(EventXY<2>{}, grid, i0, n, b);
+    SDF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// The head of a gather launcher: the caller's sorted keys and permutation are there and aligned - and, for an entry point that refuses
+// host memory, on the device together with its other buffers `device` -; every run empty; then the run table and the sorted records
+// (Rec = EventNoRec: the run table alone).  0 or the error.
 template <typename Rec>
-inline int event_runs_launch(const int32_t* keys_sorted, const int64_t* order, const Rec* rec, Rec* rec_s, int2* tab, unsigned* mm, int n,
-                             int KT, int want_minmax, hipStream_t s) {
+inline int event_runs_launch(const int32_t* keys_sorted, const int64_t* order, const Rec* rec, Rec* rec_s, int2* tab, int n, int KT,
+                             hipStream_t s, std::initializer_list<const void*> device = {}) {
   if (n && (!keys_sorted || !order)) return SDF_E_NULL;
   if (n && (!sdf_aligned(keys_sorted, 4) || !sdf_aligned(order, 8))) return SDF_E_ALIGN;
-  hipError_t e = hipMemsetAsync(tab, 0, (size_t)KT * 8, s);             // every run empty
+  for (const void* p : device)
+    if (!sdf_on_device(p)) return SDF_E_DTYPE;
+  if (device.size() && n && (!sdf_on_device(keys_sorted) || !sdf_on_device(order))) return SDF_E_DTYPE;
+  const hipError_t e = hipMemsetAsync(tab, 0, (size_t)KT * 8, s);       // every run empty
   if (e != hipSuccess) return (int)e;
-  if (want_minmax) {
-    e = hipMemsetAsync(mm, 0xff, 4, s);                                  // min over nothing
-    if (e == hipSuccess) e = hipMemsetAsync(mm + 1, 0, 4, s);            // max over nothing: "no non-zero element"
-    if (e != hipSuccess) return (int)e;
-  }
   if (n) {
     SDF_LAUNCH(event_runs_kernel<Rec>, dim3((n + 255) / 256), dim3(256), 0, s, keys_sorted, order, rec, n, KT, rec_s, tab);
     SDF_LAUNCH_CHECK();

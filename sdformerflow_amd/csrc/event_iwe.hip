@@ -22,13 +22,15 @@
 // (xw, yw).  In nearest mode the base cell is the cell itself and its value is the length of its run: no record is stored or moved.
 // Nothing depends on how the events are split over workgroups or lists over a batch: two runs, or two batchings, give the same bits.
 //
-// Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | runs (+ permute) | gather.
+// Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | event_runs_kernel (bilinear: + permute;
+// nearest: its record-free form) | gather.
 //
-// sdf_iwe_stats_fwd: per sample {sum c, sum c^2, max c, pixels with c != 0} of c = the fp64 sum of a pixel's two channels, as
-// flow_metrics.hip forms its sums: lane -> wave -> workgroup -> one fp64 partial record per workgroup, then added in index order.
+// sdf_iwe_stats_fwd: per sample {sum c, sum c^2, max c, pixels with c != 0} of c = the fp64 sum of a pixel's two channels, in
+// record_table.h's form: lane -> wave -> workgroup -> one fp64 partial record per workgroup, then combined in index order.
 // The Flow Warp Loss (Stoffregen et al. 2020) of a sample is var(S) / var(Z) on nearest images, S warped by the flow and Z by none, with
 // var = (sum c^2 - (sum c)^2 / N) / (N - 1) in fp64 over the N = h w pixels: the sums are integers, exact while below 2^53.
 #include "event_common.h"
+#include "record_table.h"
 
 namespace {
 
@@ -46,7 +48,7 @@ struct IweParams {
   float scale, t_ref, a, b;
 };
 
-// XY: 0 = fp32 coordinates as given, 1 = int32 sensor coordinates through the rectify map, 2 = uint16 likewise.  NEAREST: no record.
+// XY: the coordinates' form (event_common.h event_load_xy).  NEAREST: no record.
 template <int XY, bool NEAREST>
 __global__ __launch_bounds__(256) void iwe_keys_kernel(const void* __restrict__ xs, const void* __restrict__ ys, const float* __restrict__ t,
                                                        const float* __restrict__ p, const float* __restrict__ flow,
@@ -56,24 +58,7 @@ __global__ __launch_bounds__(256) void iwe_keys_kernel(const void* __restrict__ 
   if (i >= n) return;
   const int64_t e = i0 + i;
   float x, y;
-  bool ok = true;
-  if (XY == 0) {
-    x = static_cast<const float*>(xs)[e];
-    y = static_cast<const float*>(ys)[e];
-  } else {
-    int xi, yi;
-    if (XY == 1) {
-      xi = static_cast<const int32_t*>(xs)[e];
-      yi = static_cast<const int32_t*>(ys)[e];
-    } else {
-      xi = static_cast<const uint16_t*>(xs)[e];
-      yi = static_cast<const uint16_t*>(ys)[e];
-    }
-    ok = xi >= 0 && xi < map_w && yi >= 0 && yi < map_h;        // (as event_voxel.hip: such an event adds nothing)
-    const int64_t m = ok ? ((int64_t)yi * map_w + xi) * 2 : 0;
-    x = map[m];
-    y = map[m + 1];
-  }
+  bool ok = event_load_xy<XY>(xs, ys, map, map_h, map_w, e, x, y);
   const float t_first = t[i0], t_last = t[i0 + n - 1];
   const float tn = (t[e] - t_first) / (t_last - t_first);
   ok = ok && tn >= q.a && tn <= q.b;                             // (NaN fails)
@@ -97,16 +82,6 @@ __global__ __launch_bounds__(256) void iwe_keys_kernel(const void* __restrict__ 
   }
   keys[e] = key;
   if (!NEAREST) rec[e] = make_float2(xw, yw);
-}
-
-// the run table alone (nearest mode: a cell's value is its run's length, no record moves)
-__global__ __launch_bounds__(256) void iwe_runs_kernel(const int* __restrict__ ks, int n, int KT, int2* __restrict__ tab) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int k = ks[i];
-  if (k < 0 || k >= KT) return;
-  if (i == 0 || ks[i - 1] != k) tab[k].x = i;
-  if (i == n - 1 || ks[i + 1] != k) tab[k].y = i + 1;
 }
 
 // an event's weight at the corner (xc, yc), as the lane of that cell applies it (event_common.h event_sum_run)
@@ -185,34 +160,21 @@ int iwe_check(const SdfEventIweDesc* d, IwePlan& pl, const int64_t*& offs, int64
   if (!d->workspace || !d->out || !d->flow) return SDF_E_NULL;
   if (d->workspace_bytes < pl.bytes) return SDF_E_SHAPE;
   if (!sdf_aligned(d->workspace, 16) || !sdf_aligned(d->out, 4) || !sdf_aligned(d->flow, 4)) return SDF_E_ALIGN;
-  offs = d->offsets;
-  if (!offs) {
-    if (d->B != 1) return SDF_E_NULL;
-    own[0] = 0;
-    own[1] = d->n_events;
-    offs = own;
-  }
-  if (!event_offsets_ok(offs, d->B, d->n_events)) return SDF_E_SHAPE;
-  if (d->t_range)
-    for (int b = 0; b < d->B; ++b)                                       // a list whose first and last time are equal has no tn
-      if (offs[b + 1] > offs[b] && !(d->t_range[2 * b + 1] != d->t_range[2 * b])) return SDF_E_SHAPE;
-  return 0;
+  return event_lists_check(d->offsets, d->B, d->n_events, d->t_range, offs, own);
 }
 
-constexpr int kIsThreads = 256;
-constexpr int kIsPerLane = 4;                           // pixels per lane, kIsThreads apart (coalesced)
-constexpr int kIsTile = kIsThreads * kIsPerLane;        // pixels per workgroup
 constexpr int kIsFields = 4;
+constexpr unsigned kIsMaxes = 1u << 2;                  // field 2 is a maximum
 
-__global__ __launch_bounds__(kIsThreads) void iwe_stats_partial_kernel(const float* __restrict__ iwe, int hw, int nblk,
+__global__ __launch_bounds__(kRtThreads) void iwe_stats_partial_kernel(const float* __restrict__ iwe, int hw, int nblk,
                                                                        double* __restrict__ part) {
-  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int b = blockIdx.y;
   const float* c0 = iwe + (int64_t)b * 2 * hw;
   double s1 = 0.0, s2 = 0.0, mx = 0.0;
   unsigned nz = 0u;
 #pragma unroll
-  for (int k = 0; k < kIsPerLane; ++k) {
-    const int i = blockIdx.x * kIsTile + k * kIsThreads + threadIdx.x;
+  for (int k = 0; k < kRtPerLane; ++k) {
+    const int i = blockIdx.x * kRtTile + k * kRtThreads + threadIdx.x;
     if (i >= hw) continue;
     const double c = (double)c0[i] + (double)c0[hw + i];
     s1 += c;
@@ -220,48 +182,15 @@ __global__ __launch_bounds__(kIsThreads) void iwe_stats_partial_kernel(const flo
     mx = fmax(mx, c);
     nz += c != 0.0;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    s1 += __shfl_xor(s1, off);
-    s2 += __shfl_xor(s2, off);
-    mx = fmax(mx, __shfl_xor(mx, off));
-    nz += (unsigned)__shfl_xor((int)nz, off);
-  }
-  __shared__ double red[kIsThreads / 64][kIsFields];
-  if (lane == 0) {
-    double* r = red[threadIdx.x >> 6];
-    r[0] = s1;
-    r[1] = s2;
-    r[2] = mx;
-    r[3] = (double)nz;
-  }
-  __syncthreads();
-  if (threadIdx.x < kIsFields) {
-    const int k = threadIdx.x;
-    const double v = k == 2 ? fmax(fmax(red[0][k], red[1][k]), fmax(red[2][k], red[3][k]))
-                            : ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    part[((int64_t)b * nblk + blockIdx.x) * kIsFields + k] = v;
-  }
+  const double rec[kIsFields] = {rt_wave_sum(s1), rt_wave_sum(s2), rt_wave_max(mx), (double)rt_wave_sum(nz)};
+  rt_block_store<kIsFields, kIsMaxes>(rec, part + ((int64_t)b * nblk + blockIdx.x) * kIsFields);
 }
 
 // sample blockIdx.x: lane k combines field k of the sample's partial records in index order
 __global__ __launch_bounds__(64) void iwe_stats_finish_kernel(const double* __restrict__ part, int nblk, double* __restrict__ rows) {
   const int b = blockIdx.x, k = threadIdx.x;
   if (k >= kIsFields) return;
-  const double* p = part + (int64_t)b * nblk * kIsFields + k;
-  double s = 0.0;
-  for (int i = 0; i < nblk; ++i) {
-    const double v = p[(int64_t)i * kIsFields];
-    s = k == 2 ? fmax(s, v) : s + v;
-  }
-  rows[(int64_t)b * kIsFields + k] = s;
-}
-
-// tiles per sample; 0 = refused geometry
-inline int64_t iwe_stats_tiles(int B, int H, int W) {
-  if (B < 1 || B > 65535 || H < 1 || W < 1) return 0;
-  const int64_t hw = (int64_t)H * W;
-  if (hw >= (1ll << 30)) return 0;
-  return (hw + kIsTile - 1) / kIsTile;
+  rows[(int64_t)b * kIsFields + k] = rt_finish_field<kIsFields, kIsMaxes>(part + (int64_t)b * nblk * kIsFields, nblk, k);
 }
 
 }  // namespace
@@ -279,12 +208,7 @@ extern "C" int sdf_event_iwe_keys_fwd(const SdfEventIweDesc* d, void* stream) {
   int64_t own[2];
   if (int rc = iwe_check(d, pl, offs, own)) return rc;
   if (d->n_events == 0) return 0;
-  if (!d->x || !d->y || !d->t || !d->p || !d->keys) return SDF_E_NULL;
-  if (d->xy_dtype != 0 && (!d->rectify_map || d->map_h < 1 || d->map_w < 1)) return d->rectify_map ? SDF_E_SHAPE : SDF_E_NULL;
-  if (d->xy_dtype == 0 && d->rectify_map) return SDF_E_DTYPE;            // the map is indexed by integer sensor coordinates
-  if (!sdf_aligned(d->x, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->y, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->t, 4) ||
-      !sdf_aligned(d->p, 4) || !sdf_aligned(d->keys, 4) || (d->rectify_map && !sdf_aligned(d->rectify_map, 4)))
-    return SDF_E_ALIGN;
+  if (int rc = event_keys_check(d->x, d->y, d->t, d->p, d->keys, d->xy_dtype, 4, true, d->rectify_map, d->map_h, d->map_w)) return rc;
   for (const void* ptr : {d->x, d->y, (const void*)d->t, (const void*)d->p, (const void*)d->flow, (const void*)d->keys,
                           (const void*)d->workspace})
     if (!sdf_on_device(ptr)) return SDF_E_DTYPE;
@@ -292,27 +216,12 @@ extern "C" int sdf_event_iwe_keys_fwd(const SdfEventIweDesc* d, void* stream) {
   hipStream_t s = sdf_stream(stream);
   float2* rec = reinterpret_cast<float2*>(static_cast<char*>(d->workspace) + pl.off_rec);
   const IweParams q = {d->scale, d->t_ref, d->win_a, d->win_b};
-  for (int b = 0; b < d->B; ++b) {
-    const int64_t i0 = offs[b];
-    const int n = (int)(offs[b + 1] - i0);
-    if (n == 0) continue;
-    const dim3 grid((n + 255) / 256), block(256);
-#define IWE_KEYS(XY, NEAREST)                                                                                                          \
-  SDF_LAUNCH((iwe_keys_kernel<XY, NEAREST>), grid, block, 0, s, d->x, d->y, d->t, d->p, d->flow, d->rectify_map, d->map_h, d->map_w, i0, \
-             n, b, pl.g, q, d->keys, rec)
-    if (d->mode == 0) {
-      if (d->xy_dtype == 0) IWE_KEYS(0, false);
-      else if (d->xy_dtype == 1) IWE_KEYS(1, false);
-      else IWE_KEYS(2, false);
-    } else {
-      if (d->xy_dtype == 0) IWE_KEYS(0, true);
-      else if (d->xy_dtype == 1) IWE_KEYS(1, true);
-      else IWE_KEYS(2, true);
-    }
-#undef IWE_KEYS
-    SDF_LAUNCH_CHECK();
-  }
-  return 0;
+  return event_keys_launch(offs, d->B, d->xy_dtype, [&](auto xy, dim3 grid, int64_t i0, int n, int b) {
+    constexpr int XY = decltype(xy)::value;
+    const auto kernel = d->mode == 0 ? iwe_keys_kernel<XY, false> : iwe_keys_kernel<XY, true>;
+    SDF_LAUNCH(kernel, grid, dim3(256), 0, s, d->x, d->y, d->t, d->p, d->flow, d->rectify_map, d->map_h, d->map_w, i0, n, b, pl.g, q, d->keys,
+               rec);
+  });
 }
 
 extern "C" int sdf_event_iwe_gather_fwd(const SdfEventIweDesc* d, void* stream) {
@@ -321,26 +230,16 @@ extern "C" int sdf_event_iwe_gather_fwd(const SdfEventIweDesc* d, void* stream) 
   int64_t own[2];
   if (int rc = iwe_check(d, pl, offs, own)) return rc;
   const int n = (int)d->n_events;
-  if (n && (!d->keys_sorted || !d->order)) return SDF_E_NULL;
-  if (n && (!sdf_aligned(d->keys_sorted, 4) || !sdf_aligned(d->order, 8))) return SDF_E_ALIGN;
-  if (!sdf_on_device(d->out) || !sdf_on_device(d->workspace) || (n && (!sdf_on_device(d->keys_sorted) || !sdf_on_device(d->order))))
-    return SDF_E_DTYPE;
   hipStream_t s = sdf_stream(stream);
   char* ws = static_cast<char*>(d->workspace);
   const float2* rec = reinterpret_cast<const float2*>(ws + pl.off_rec);
   float2* rec_s = reinterpret_cast<float2*>(ws + pl.off_rec_s);
   int2* tab = reinterpret_cast<int2*>(ws + pl.off_tab);
   const IweGeom& g = pl.g;
-  if (d->mode == 0) {
-    if (int rc = event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, (unsigned*)nullptr, n, g.KT, 0, s)) return rc;
-  } else {
-    hipError_t e = hipMemsetAsync(tab, 0, (size_t)g.KT * 8, s);          // every run empty
-    if (e != hipSuccess) return (int)e;
-    if (n) {
-      SDF_LAUNCH(iwe_runs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d->keys_sorted, n, g.KT, tab);
-      SDF_LAUNCH_CHECK();
-    }
-  }
+  const int rc = d->mode == 0 ? event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, n, g.KT, s, {d->out, d->workspace})
+                              : event_runs_launch<EventNoRec>(d->keys_sorted, d->order, nullptr, nullptr, tab, n, g.KT, s,
+                                                              {d->out, d->workspace});
+  if (rc) return rc;
   const int64_t cells = (int64_t)g.B * 2 * g.h * g.w;
   const dim3 grid((unsigned)((cells + 255) / 256)), block(256);
   float* out = static_cast<float*>(d->out);
@@ -351,23 +250,19 @@ extern "C" int sdf_event_iwe_gather_fwd(const SdfEventIweDesc* d, void* stream) 
 }
 
 extern "C" int64_t sdf_iwe_stats_workspace_bytes(int B, int H, int W) {
-  const int64_t t = iwe_stats_tiles(B, H, W);
+  const int64_t t = rt_tiles(B, H, W);
   return t ? (int64_t)B * t * kIsFields * 8 : 0;
 }
 
 extern "C" int sdf_iwe_stats_fwd(const SdfIweStatsDesc* d, void* stream) {
   if (!d) return SDF_E_NULL;
-  const int64_t tiles = iwe_stats_tiles(d->B, d->H, d->W);
-  if (!tiles) return SDF_E_SHAPE;
-  if (d->row0 < 0 || (int64_t)d->row0 + d->B > d->rows) return SDF_E_SHAPE;       // the records lie inside the table
-  if (!d->iwe || !d->table || !d->workspace) return SDF_E_NULL;
-  if (d->workspace_bytes < (int64_t)d->B * tiles * kIsFields * 8) return SDF_E_SHAPE;
-  if (!sdf_aligned(d->iwe, 4) || !sdf_aligned(d->table, 8) || !sdf_aligned(d->workspace, 8)) return SDF_E_ALIGN;
+  int64_t tiles;
+  if (int rc = rt_check(d->B, d->H, d->W, d->row0, d->rows, kIsFields, {d->iwe}, d->table, d->workspace, d->workspace_bytes, tiles)) return rc;
   if (!sdf_on_device(d->iwe) || !sdf_on_device(d->table) || !sdf_on_device(d->workspace)) return SDF_E_DTYPE;
   hipStream_t s = sdf_stream(stream);
   double* part = static_cast<double*>(d->workspace);
   const int hw = d->H * d->W, nblk = (int)tiles;
-  SDF_LAUNCH(iwe_stats_partial_kernel, dim3(nblk, d->B), dim3(kIsThreads), 0, s, d->iwe, hw, nblk, part);
+  SDF_LAUNCH(iwe_stats_partial_kernel, dim3(nblk, d->B), dim3(kRtThreads), 0, s, d->iwe, hw, nblk, part);
   SDF_LAUNCH_CHECK();
   SDF_LAUNCH(iwe_stats_finish_kernel, dim3(d->B), dim3(64), 0, s, part, nblk, d->table + (int64_t)d->row0 * kIsFields);
   SDF_LAUNCH_CHECK();

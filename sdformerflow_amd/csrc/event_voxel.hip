@@ -11,8 +11,10 @@
 // writes the keys, the caller sorts them stably, sdf_event_voxel_gather_fwd takes the sorted keys and the permutation); nothing here
 // depends on how the events are split over workgroups, so two runs - or two different batchings - give the same bits.
 //
-// Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | runs + permute | gather | [finish].
+// Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | runs + permute | [clear the min / max
+// pair] | gather (+ min / max) | [finish: min-max, threshold].
 #include "event_common.h"
+#include "model_input.h"
 
 namespace {
 
@@ -25,7 +27,7 @@ __device__ __forceinline__ int ev_key(const EvGeom& g, int b, int kt, int ky, in
   return ((b * (g.C + 1) + kt) * (g.h + 1) + ky) * (g.w + 1) + kx;
 }
 
-// XY: 0 = fp32 coordinates as given, 1 = int32 sensor coordinates through the rectify map, 2 = uint16 likewise
+// XY: the coordinates' form (event_common.h event_load_xy)
 template <int XY>
 __global__ __launch_bounds__(256) void ev_keys_kernel(const void* __restrict__ xs, const void* __restrict__ ys, const float* __restrict__ t,
                                                       const float* __restrict__ p, const float* __restrict__ map, int map_h, int map_w,
@@ -34,24 +36,7 @@ __global__ __launch_bounds__(256) void ev_keys_kernel(const void* __restrict__ x
   if (i >= n) return;
   const int64_t e = i0 + i;
   float x, y;
-  bool ok = true;
-  if (XY == 0) {
-    x = static_cast<const float*>(xs)[e];
-    y = static_cast<const float*>(ys)[e];
-  } else {
-    int xi, yi;
-    if (XY == 1) {
-      xi = static_cast<const int32_t*>(xs)[e];
-      yi = static_cast<const int32_t*>(ys)[e];
-    } else {
-      xi = static_cast<const uint16_t*>(xs)[e];
-      yi = static_cast<const uint16_t*>(ys)[e];
-    }
-    ok = xi >= 0 && xi < map_w && yi >= 0 && yi < map_h;        // (the reference asserts this; here such an event adds nothing)
-    const int64_t m = ok ? ((int64_t)yi * map_w + xi) * 2 : 0;
-    x = map[m];
-    y = map[m + 1];
-  }
+  bool ok = event_load_xy<XY>(xs, ys, map, map_h, map_w, e, x, y);
   // t_norm = (C - 1) (t - t[0]) / (t[N-1] - t[0]): multiply, then divide, each rounded to fp32 (event_representations.py:255)
   const float t_first = t[i0], t_last = t[i0 + n - 1];
   const float tn = ((float)(g.C - 1) * (t[e] - t_first)) / (t_last - t_first);
@@ -114,41 +99,28 @@ __global__ __launch_bounds__(256) void ev_gather_kernel(const int2* __restrict__
     if (active) out[idx] = acc;
     return;
   }
-  float o1 = acc, o2 = acc2;
-  if (MODE == 1) {
-    o1 = event_relu(acc);
-    o2 = event_relu(-acc);
-  }
-  if (active) {
-    out[(bc * 2) * hw + plane] = o1;
-    out[(bc * 2 + 1) * hw + plane] = o2;
-  }
-  if (MODE == 1 && want_minmax) {
-    unsigned lo = 0xffffffffu, hi = 0u;
+  float* pair = out + (bc * 2) * hw + plane;
+  if (MODE == 2) {
     if (active) {
-      minmax_nonzero(o1, lo, hi);
-      minmax_nonzero(o2, lo, hi);
+      pair[0] = acc;
+      pair[hw] = acc2;
     }
-    wave_minmax(lo, hi);
-    if (lane == 0 && hi != 0u) {
-      atomicMin(&mm[0], lo);
-      atomicMax(&mm[1], hi);
-    }
+    return;
   }
+  unsigned nlo = 0u, hi = 0u;                                            // (~min, max) over nothing
+  if (active) mi_split_store(acc, pair, hw, nlo, hi);
+  if (want_minmax) mi_minmax_commit_wave(nlo, hi, mm);                   // (no LDS or barrier in this kernel: a pair per wave)
 }
 
-// harness.prepare_chunk's tail on output 1, in place: (v - lo) / (hi - lo) on the non-zeros when there are any and lo != hi; then the
-// spike threshold (> th: 1, < th: 0, == th: kept)
+// harness.prepare_chunk's tail on output 1, in place (model_input.h mi_finish_value), as a grid-stride pass over the elements: there is
+// no event mask to form here, so the pass needs no lane per pixel (prepare_finish_kernel's shape: profiles/data_path_shared_code.txt)
 __global__ __launch_bounds__(256) void ev_finish_kernel(float* __restrict__ out, int64_t n, const unsigned* __restrict__ mm, int want_minmax,
                                                         int want_th, float th) {
-  const unsigned lob = mm[0], hib = mm[1];
-  const float lo = __uint_as_float(lob), hi = __uint_as_float(hib);
-  const bool norm = want_minmax && hib != 0u && lob != hib;
-  const float span = hi - lo;
+  float lo, span;
+  const bool norm = mi_norm_of(mm, want_minmax, lo, span);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float v = out[i];
-    if (norm && v != 0.f) v = (v - lo) / span;
-    if (want_th) v = v > th ? 1.f : (v < th ? 0.f : v);
+    mi_finish_value(v, norm, lo, span, want_th, th);
     out[i] = v;
   }
 }
@@ -188,18 +160,7 @@ int ev_check(const SdfEventVoxelDesc* d, EvPlan& pl, const int64_t*& offs, int64
   if (!d->workspace || !d->out) return SDF_E_NULL;
   if (d->workspace_bytes < pl.bytes) return SDF_E_SHAPE;
   if (!sdf_aligned(d->workspace, 16) || !sdf_aligned(d->out, 4)) return SDF_E_ALIGN;
-  offs = d->offsets;
-  if (!offs) {
-    if (d->B != 1) return SDF_E_NULL;
-    own[0] = 0;
-    own[1] = d->n_events;
-    offs = own;
-  }
-  if (!event_offsets_ok(offs, d->B, d->n_events)) return SDF_E_SHAPE;
-  if (d->t_range)
-    for (int b = 0; b < d->B; ++b)                                       // a list whose first and last time are equal has no t_norm
-      if (offs[b + 1] > offs[b] && !(d->t_range[2 * b + 1] != d->t_range[2 * b])) return SDF_E_SHAPE;
-  return 0;
+  return event_lists_check(d->offsets, d->B, d->n_events, d->t_range, offs, own);
 }
 
 }  // namespace
@@ -215,28 +176,13 @@ extern "C" int sdf_event_voxel_keys_fwd(const SdfEventVoxelDesc* d, void* stream
   int64_t own[2];
   if (int rc = ev_check(d, pl, offs, own)) return rc;
   if (d->n_events == 0) return 0;
-  if (!d->x || !d->y || !d->t || !d->p || !d->keys) return SDF_E_NULL;
-  if (d->xy_dtype != 0 && (!d->rectify_map || d->map_h < 1 || d->map_w < 1)) return d->rectify_map ? SDF_E_SHAPE : SDF_E_NULL;
-  if (d->xy_dtype == 0 && d->rectify_map) return SDF_E_DTYPE;            // the map is indexed by integer sensor coordinates
-  if (!sdf_aligned(d->x, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->y, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->t, 4) ||
-      !sdf_aligned(d->p, 4) || !sdf_aligned(d->keys, 4) || (d->rectify_map && !sdf_aligned(d->rectify_map, 4)))
-    return SDF_E_ALIGN;
+  if (int rc = event_keys_check(d->x, d->y, d->t, d->p, d->keys, d->xy_dtype, 4, true, d->rectify_map, d->map_h, d->map_w)) return rc;
   hipStream_t s = sdf_stream(stream);
   float4* rec = reinterpret_cast<float4*>(static_cast<char*>(d->workspace) + pl.off_rec);
-  for (int b = 0; b < d->B; ++b) {
-    const int64_t i0 = offs[b];
-    const int n = (int)(offs[b + 1] - i0);
-    if (n == 0) continue;
-    const dim3 grid((n + 255) / 256), block(256);
-#define EV_KEYS(XY) \
-  SDF_LAUNCH(ev_keys_kernel<XY>, grid, block, 0, s, d->x, d->y, d->t, d->p, d->rectify_map, d->map_h, d->map_w, i0, n, b, pl.g, d->keys, rec)
-    if (d->xy_dtype == 0) EV_KEYS(0);
-    else if (d->xy_dtype == 1) EV_KEYS(1);
-    else EV_KEYS(2);
-#undef EV_KEYS
-    SDF_LAUNCH_CHECK();
-  }
-  return 0;
+  return event_keys_launch(offs, d->B, d->xy_dtype, [&](auto xy, dim3 grid, int64_t i0, int n, int b) {
+    SDF_LAUNCH(ev_keys_kernel<decltype(xy)::value>, grid, dim3(256), 0, s, d->x, d->y, d->t, d->p, d->rectify_map, d->map_h, d->map_w, i0, n,
+               b, pl.g, d->keys, rec);
+  });
 }
 
 extern "C" int sdf_event_voxel_gather_fwd(const SdfEventVoxelDesc* d, void* stream) {
@@ -252,7 +198,9 @@ extern "C" int sdf_event_voxel_gather_fwd(const SdfEventVoxelDesc* d, void* stre
   int2* tab = reinterpret_cast<int2*>(ws + pl.off_tab);
   unsigned* mm = reinterpret_cast<unsigned*>(ws + pl.off_mm);
   const EvGeom& g = pl.g;
-  if (int rc = event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, mm, n, g.KT, d->norm, s)) return rc;
+  if (int rc = event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, n, g.KT, s)) return rc;
+  if (d->norm)
+    if (int rc = mi_clear_pairs(mm, 1, s)) return rc;
   const int64_t cells = (int64_t)g.B * g.C * g.h * g.w;
   const dim3 grid((unsigned)((cells + 255) / 256)), block(256);
   float* out = static_cast<float*>(d->out);

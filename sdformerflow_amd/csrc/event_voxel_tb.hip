@@ -9,12 +9,14 @@
 // forms it - the left pass (events whose bin is the cell's) in list order, then the right pass (events of the bin before) in list
 // order.  The order comes from a stable sort of the events by the key of their base cell (list, bin, y, x), which is the caller's
 // (sdf_event_voxel_tb_keys_fwd writes the keys, sdf_event_voxel_tb_gather_fwd takes the sorted keys and the permutation).  The
-// statistics of a list are fp64 sums over per-workgroup partials combined in a fixed order; min / max are integer atomics on bit
-// patterns.  Nothing depends on arrival order: two runs, or two batchings, give the same bits.
+// statistics of a list are fp64 sums over per-workgroup partials combined in a fixed order (record_table.h); min / max are integer
+// atomics on bit patterns (model_input.h).  Nothing depends on arrival order: two runs, or two batchings, give the same bits.
 //
 // Launch sequence: keys (one launch per list) | [caller: stable sort] | clear the run table | runs + permute | gather (+ partial
-// statistics) | [statistics] | [normalise / split / min-max] | [finish: min-max, threshold, event mask].
+// statistics) | [statistics] | [normalise / split / min-max] | [model_input.h's finish: min-max, threshold, event mask].
 #include "event_common.h"
+#include "model_input.h"
+#include "record_table.h"
 
 namespace {
 
@@ -132,22 +134,8 @@ __global__ __launch_bounds__(256) void tb_gather_kernel(const int2* __restrict__
     sm += (double)acc2;
     sq += (double)acc2 * (double)acc2;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    cn += __shfl_xor(cn, off);
-    sm += __shfl_xor(sm, off);
-    sq += __shfl_xor(sq, off);
-  }
-  __shared__ double red[4][3];
-  if (lane == 0) {
-    red[threadIdx.x >> 6][0] = cn;
-    red[threadIdx.x >> 6][1] = sm;
-    red[threadIdx.x >> 6][2] = sq;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    part[((int64_t)l * g.nblk + blockIdx.x) * 3 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
+  const double sums[3] = {rt_wave_sum(cn), rt_wave_sum(sm), rt_wave_sum(sq)};
+  rt_block_store<3>(sums, part + ((int64_t)l * g.nblk + blockIdx.x) * 3);
 }
 
 // list blockIdx.x: its workgroups' partials summed in a fixed order -> st = {mean, std}; std = 1 where the reference only subtracts
@@ -180,70 +168,20 @@ __global__ __launch_bounds__(256) void tb_stats_kernel(const double* __restrict_
 
 // The pass over the written cells behind the gather.  SPLIT false: the per-list normalisation in place (n values).  SPLIT true: n =
 // L nb h w cells; the raw sum lies in the first of the cell's two planes; normalise when asked, write relu(v) | relu(-v), and collect
-// min / max of the non-zeros (positive floats order as their bit patterns: integer min / max, any arrival order).
+// min / max of the non-zeros (model_input.h), one pair of atomics per workgroup.
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void tb_norm_kernel(float* __restrict__ out, int64_t n, int64_t per_list, int64_t hw,
                                                       const double* __restrict__ stats, int normalize, unsigned* __restrict__ mm,
                                                       int want_minmax) {
-  const int lane = threadIdx.x & 63;
-  unsigned lo = 0xffffffffu, hi = 0u;
+  unsigned nlo = 0u, hi = 0u;                                            // (~min, max) over nothing
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int64_t at = SPLIT ? (i / hw) * 2 * hw + i % hw : i;
     float v = out[at];
     if (normalize) v = tb_normalise(v, stats + 2 * (i / per_list));
-    if (!SPLIT) {
-      out[at] = v;
-      continue;
-    }
-    const float o1 = event_relu(v), o2 = event_relu(-v);
-    out[at] = o1;
-    out[at + hw] = o2;
-    minmax_nonzero(o1, lo, hi);
-    minmax_nonzero(o2, lo, hi);
+    if (SPLIT) mi_split_store(v, out + at, hw, nlo, hi);
+    else out[at] = v;
   }
-  if (SPLIT && want_minmax) {
-    wave_minmax(lo, hi);
-    // one pair of atomics per workgroup: same-address atomics serialise in L2, and a pair per wave cost more than the pass itself
-    __shared__ unsigned red[4][2];
-    if (lane == 0) {
-      red[threadIdx.x >> 6][0] = lo;
-      red[threadIdx.x >> 6][1] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      lo = min(min(red[0][0], red[1][0]), min(red[2][0], red[3][0]));
-      hi = max(max(red[0][1], red[1][1]), max(red[2][1], red[3][1]));
-      if (hi != 0u) {
-        atomicMin(&mm[0], lo);
-        atomicMax(&mm[1], hi);
-      }
-    }
-  }
-}
-
-// harness.prepare_chunk's tail, one lane per pixel of a sample over its `planes` = 2 S nb planes: (v - lo) / (hi - lo) on the non-zeros
-// when there are any and lo != hi; the spike threshold (> th: 1, < th: 0, == th: kept); and the event mask, chunk.sum(1).sum(1).bool():
-// the values are non-negative here, so their sum is non-zero exactly when one of them is
-__global__ __launch_bounds__(256) void tb_finish_kernel(float* __restrict__ out, float* __restrict__ mask, int64_t pixels, int64_t hw,
-                                                        int planes, const unsigned* __restrict__ mm, int want_minmax, int want_th,
-                                                        float th) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= pixels) return;
-  const unsigned lob = mm[0], hib = mm[1];
-  const float lo = __uint_as_float(lob), hi = __uint_as_float(hib);
-  const bool norm = want_minmax && hib != 0u && lob != hib;
-  const float span = hi - lo;
-  float* q = out + (i / hw) * planes * hw + i % hw;
-  bool any = false;
-  const bool write = norm || want_th;
-  for (int j = 0; j < planes; ++j) {
-    float v = q[(int64_t)j * hw];
-    if (norm && v != 0.f) v = (v - lo) / span;
-    if (want_th) v = v > th ? 1.f : (v < th ? 0.f : v);
-    if (write) q[(int64_t)j * hw] = v;
-    any = any || v != 0.f;
-  }
-  if (mask) mask[i] = any ? 1.f : 0.f;
+  if (SPLIT && want_minmax) mi_minmax_commit(nlo, hi, mm);
 }
 
 struct TbPlan {
@@ -314,26 +252,13 @@ extern "C" int sdf_event_voxel_tb_keys_fwd(const SdfEventVoxelTbDesc* d, void* s
   TbPlan pl;
   if (int rc = tb_check(d, pl)) return rc;
   if (d->n_events == 0) return 0;
-  if (!d->x || !d->y || !d->t || !d->p || !d->keys) return SDF_E_NULL;
-  if (!sdf_aligned(d->x, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->y, d->xy_dtype == 2 ? 2 : 4) || !sdf_aligned(d->t, 8) ||
-      !sdf_aligned(d->p, 4) || !sdf_aligned(d->keys, 4))
-    return SDF_E_ALIGN;
+  if (int rc = event_keys_check(d->x, d->y, d->t, d->p, d->keys, d->xy_dtype, 8, false, nullptr, 0, 0)) return rc;
   const double t_scale = d->t_scale ? *d->t_scale : 1.0;
   hipStream_t s = sdf_stream(stream);
   float2* rec = reinterpret_cast<float2*>(static_cast<char*>(d->workspace) + pl.off_rec);
-  for (int l = 0; l < d->n_lists; ++l) {
-    const int64_t i0 = d->offsets[l];
-    const int n = (int)(d->offsets[l + 1] - i0);
-    if (n == 0) continue;
-    const dim3 grid((n + 255) / 256), block(256);
-#define TB_KEYS(XY) SDF_LAUNCH(tb_keys_kernel<XY>, grid, block, 0, s, d->x, d->y, d->t, d->p, t_scale, i0, n, l, pl.g, d->keys, rec)
-    if (d->xy_dtype == 0) TB_KEYS(0);
-    else if (d->xy_dtype == 1) TB_KEYS(1);
-    else TB_KEYS(2);
-#undef TB_KEYS
-    SDF_LAUNCH_CHECK();
-  }
-  return 0;
+  return event_keys_launch(d->offsets, d->n_lists, d->xy_dtype, [&](auto xy, dim3 grid, int64_t i0, int n, int l) {
+    SDF_LAUNCH(tb_keys_kernel<decltype(xy)::value>, grid, dim3(256), 0, s, d->x, d->y, d->t, d->p, t_scale, i0, n, l, pl.g, d->keys, rec);
+  });
 }
 
 extern "C" int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void* stream) {
@@ -349,7 +274,9 @@ extern "C" int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void*
   double* stats = reinterpret_cast<double*>(ws + pl.off_stats);
   unsigned* mm = reinterpret_cast<unsigned*>(ws + pl.off_mm);
   const TbGeom& g = pl.g;
-  if (int rc = event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, mm, n, g.KT, d->norm, s)) return rc;
+  if (int rc = event_runs_launch(d->keys_sorted, d->order, rec, rec_s, tab, n, g.KT, s)) return rc;
+  if (d->norm)
+    if (int rc = mi_clear_pairs(mm, 1, s)) return rc;
   const dim3 block(256), ggrid(g.nblk, g.L);
   float* out = static_cast<float*>(d->out);
   if (d->mode == 2) SDF_LAUNCH(tb_gather_kernel<true>, ggrid, block, 0, s, tab, rec_s, out, part, g, 2, d->normalize);
@@ -364,12 +291,9 @@ extern "C" int sdf_event_voxel_tb_gather_fwd(const SdfEventVoxelTbDesc* d, void*
   if (d->mode == 1) {
     SDF_LAUNCH(tb_norm_kernel<true>, blocks(cells), block, 0, s, out, cells, (int64_t)g.nb * hw, hw, stats, d->normalize, mm, d->norm);
     SDF_LAUNCH_CHECK();
-    if (d->norm || d->use_spike_th || d->event_mask) {
-      const int64_t pixels = (int64_t)(g.L / g.S) * hw;
-      SDF_LAUNCH(tb_finish_kernel, dim3((unsigned)((pixels + 255) / 256)), block, 0, s, out, static_cast<float*>(d->event_mask), pixels, hw,
-                 2 * g.S * g.nb, mm, d->norm, d->use_spike_th, d->spike_th);
-      SDF_LAUNCH_CHECK();
-    }
+    if (int rc = mi_finish(out, static_cast<float*>(d->event_mask), nullptr, g.L / g.S, (int)hw, 2 * g.S * g.nb, mm, d->norm, 0,
+                           d->use_spike_th, d->spike_th, s))
+      return rc;
   } else if (d->normalize) {
     const int64_t per_list = (int64_t)g.nb * hw * (d->mode == 2 ? 2 : 1);
     SDF_LAUNCH(tb_norm_kernel<false>, blocks(g.L * per_list), block, 0, s, out, g.L * per_list, per_list, hw, stats, 1, mm, 0);

@@ -2,9 +2,8 @@
 // (reference eval_DSEC_flow_SNN.py:179-217) without a host round trip.
 //
 // The torch composition asks the host three times (nz.any(), chunk[nz], lo != hi); here the decisions stay on the device.  Every
-// operation is IEEE fp32 in both, so the output equals the composition bit for bit.  min / max of the non-zeros are integer atomics on
-// bit patterns (the values are positive floats, which order as their bit patterns: any arrival order gives the same pair), one pair per
-// workgroup; the minimum is kept as the maximum of the complemented pattern, so that "no non-zero element" is all-zero for both words.
+// operation is IEEE fp32 in both, so the output equals the composition bit for bit.  The split's store, the min / max pairs (one pair of
+// integer atomics per workgroup), their clear and the finish kernel are model_input.h's, shared with the voxel front ends.
 //
 // Launch sequence: [clear the pairs] | split (+ min / max) | [finish: min-max, threshold, event mask].
 //
@@ -15,9 +14,8 @@
 // sdf_augment_resize_fwd is the MDR training items' front (reference MDR_dataloader/loader_utils.py DenseSparseAugmentor, MDR.py:218-241,
 // train_mdr_supervised_SNN.py:209-276): its first kernel gathers through a per-sample bilinear rescale (cv2.resize INTER_LINEAR restated,
 // four taps), the flips and the crop - of the old and new dense event volumes and of the flow, which it scales and from which it derives
-// the valid mask - before the same split; the finish kernel is shared.  The split's store and min / max code (pc_split_store,
-// pc_minmax_commit) and the clear / finish launches (pc_clear_pairs, pc_finish) are stated once for the three entry points.
-#include "common.h"
+// the valid mask - before the same split; the finish kernel is shared.
+#include "model_input.h"
 #include <cmath>
 
 namespace {
@@ -25,48 +23,6 @@ namespace {
 struct PcGeom {
   int32_t B, bins, Hs, Ws, oy, ox, h, w;
 };
-
-// relu as ATen's device clamp_min forms it: NaN stays, else fmaxf(v, 0) = v_max_f32, which orders -0 below +0: relu(-0) = +0
-__device__ __forceinline__ float pc_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
-
-// the polarity split of one signed value: relu(v) | relu(-v) into the pixel's pair of planes (`pair` = the pixel in the first of them),
-// and the non-zeros into the lane's (~min, max) of bit patterns
-__device__ __forceinline__ void pc_split_store(float v, float* __restrict__ pair, int hw, unsigned& nlo, unsigned& hi) {
-  const float o1 = pc_relu(v), o2 = pc_relu(-v);
-  pair[0] = o1;
-  pair[hw] = o2;
-  if (o1 != 0.f) {
-    nlo = max(nlo, ~__float_as_uint(o1));
-    hi = max(hi, __float_as_uint(o1));
-  }
-  if (o2 != 0.f) {
-    nlo = max(nlo, ~__float_as_uint(o2));
-    hi = max(hi, __float_as_uint(o2));
-  }
-}
-
-// the lanes' (~min, max) -> wave -> workgroup (256 threads, every one of them arrives) -> one pair of atomics on `q`: same-address
-// atomics serialise in L2, and a pair per wave cost more than the pass itself
-__device__ __forceinline__ void pc_minmax_commit(unsigned nlo, unsigned hi, unsigned* __restrict__ q) {
-  for (int off = 32; off > 0; off >>= 1) {
-    nlo = max(nlo, (unsigned)__shfl_xor((int)nlo, off));
-    hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-  }
-  __shared__ unsigned red[4][2];
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6][0] = nlo;
-    red[threadIdx.x >> 6][1] = hi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    nlo = max(max(red[0][0], red[1][0]), max(red[2][0], red[3][0]));
-    hi = max(max(red[0][1], red[1][1]), max(red[2][1], red[3][1]));
-    if (hi != 0u) {
-      atomicMax(&q[0], nlo);
-      atomicMax(&q[1], hi);
-    }
-  }
-}
 
 // sample blockIdx.y, cells strided over the sample's gridDim.x workgroups: out = relu(v) | relu(-v) on the crop window, and the pair
 // {~min, max} of the bit patterns of the non-zeros into mm[2 g], g = the sample (per_sample) or 0 (the whole batch tensor)
@@ -82,9 +38,9 @@ __global__ __launch_bounds__(256) void prepare_split_kernel(const float* __restr
     const int i = (int)i64, c = i / hw, p = i - c * hw;
     const int y = p / g.w, x = p % g.w;
     const float v = src[((int64_t)c * g.Hs + g.oy + y) * g.Ws + g.ox + x];
-    pc_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
+    mi_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
   }
-  if (want_minmax) pc_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
+  if (want_minmax) mi_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
 }
 
 // the per-sample parameters of sdf_augment_chunk_fwd, copied from the descriptor's host arrays into the kernel arguments (832 bytes)
@@ -146,7 +102,7 @@ __global__ __launch_bounds__(256) void augment_split_kernel(const float* __restr
       const float u = drop_u ? drop_u[cell] : aug_philox_u((uint64_t)cell, seed, offset);
       v = v * (u > q ? 1.f : 0.f);
     }
-    pc_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
+    mi_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
   }
   if (label || valid) {
     for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {
@@ -164,7 +120,7 @@ __global__ __launch_bounds__(256) void augment_split_kernel(const float* __restr
       }
     }
   }
-  if (want_minmax) pc_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
+  if (want_minmax) mi_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
 }
 
 // the per-sample parameters of sdf_augment_resize_fwd in the kernel arguments (2624 bytes): the position in the resized image of output
@@ -237,7 +193,7 @@ __global__ __launch_bounds__(256) void augment_resize_kernel(const float* __rest
     for (int c = 0; c < nF; ++c) {
       const float* src = c < n_old ? vox_old + ((int64_t)b * g.bins + c) * plane : vox_new + ((int64_t)b * g.bins + c - n_old) * plane;
       const float v = resized ? rz_taps(src + o0, src + o1, x0, x1, ax0, ax, ay0, ay) : src[o0 + x0];
-      pc_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
+      mi_split_store(v, dst + (int64_t)c * 2 * hw + p, hw, nlo, hi);
     }
     const float* fu = flow + (int64_t)b * 2 * plane;
     const float u = resized ? rz_taps(fu + o0, fu + o1, x0, x1, ax0, ax, ay0, ay) : fu[o0 + x0];
@@ -249,40 +205,7 @@ __global__ __launch_bounds__(256) void augment_resize_kernel(const float* __rest
     const bool on = !isinf(du) && !isinf(dv) && __dadd_rn(__dmul_rn(du, du), __dmul_rn(dv, dv)) > 0.0;
     mask_out[(int64_t)b * hw + p] = on ? 1.f : 0.f;
   }
-  if (want_minmax) pc_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
-}
-
-// prepare_chunk's tail, one lane per pixel of a sample over its 2 bins planes: (v - lo) / (hi - lo) on the non-zeros when there are any
-// and lo != hi; the spike threshold (> th: 1, < th: 0, == th: kept); and the event mask, chunk.sum(1).sum(1).bool(): the values are
-// non-negative here, so their sum is non-zero exactly when one of them is.  `mul` (the training loop's mask * event_mask; may be NULL):
-// (B, 1, h, w) fp32, multiplied by the event mask in place
-__global__ __launch_bounds__(256) void prepare_finish_kernel(float* __restrict__ out, float* __restrict__ mask, int64_t pixels, int hw,
-                                                             int planes, const unsigned* __restrict__ mm, int want_minmax, int per_sample,
-                                                             int want_th, float th, float* __restrict__ mul) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= pixels) return;
-  const int64_t b = i / hw;
-  bool norm = false;
-  float lo = 0.f, span = 1.f;
-  if (want_minmax) {
-    const unsigned* q = mm + 2 * (per_sample ? b : 0);
-    const unsigned lob = ~q[0], hib = q[1];
-    lo = __uint_as_float(lob);
-    span = __uint_as_float(hib) - lo;
-    norm = hib != 0u && lob != hib;
-  }
-  float* q = out + b * planes * hw + i % hw;
-  bool any = false;
-  const bool write = norm || want_th;
-  for (int j = 0; j < planes; ++j) {
-    float v = q[(int64_t)j * hw];
-    if (norm && v != 0.f) v = (v - lo) / span;
-    if (want_th) v = v > th ? 1.f : (v < th ? 0.f : v);
-    if (write) q[(int64_t)j * hw] = v;
-    any = any || v != 0.f;
-  }
-  if (mask) mask[i] = any ? 1.f : 0.f;
-  if (mul) mul[i] = mul[i] * (any ? 1.f : 0.f);
+  if (want_minmax) mi_minmax_commit(nlo, hi, mm + 2 * (per_sample ? b : 0));
 }
 
 // geometry check; false = SDF_E_SHAPE
@@ -372,20 +295,6 @@ bool rz_geom(const SdfAugmentResizeDesc* d, PcGeom& g, RzParams& a) {
   return true;
 }
 
-// every pair {~min, max} the call uses: no non-zero element
-int pc_clear_pairs(unsigned* mm, int pairs, hipStream_t s) { return (int)hipMemsetAsync(mm, 0, (size_t)8 * pairs, s); }
-
-// the launch of prepare_finish_kernel when something is left to do: min-max, threshold, event mask, mask * event mask
-int pc_finish(float* out, float* event_mask, float* mul, int B, int hw, int planes, const unsigned* mm, int want_minmax, int per_sample,
-              int use_th, float th, hipStream_t s) {
-  if (!want_minmax && !use_th && !event_mask && !mul) return 0;
-  const int64_t pixels = (int64_t)B * hw;
-  SDF_LAUNCH(prepare_finish_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, out, event_mask, pixels, hw, planes, mm,
-             want_minmax, per_sample, use_th, th, mul);
-  SDF_LAUNCH_CHECK();
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int64_t sdf_prepare_chunk_workspace_bytes(int B) { return B >= 1 && B <= 65535 ? (int64_t)8 * B : 0; }
@@ -403,7 +312,7 @@ extern "C" int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream)
   unsigned* mm = static_cast<unsigned*>(d->workspace);
   int rc = 0;
   const int per_sample = d->per_sample != 0, want_minmax = d->norm == 1;
-  if (want_minmax && (rc = pc_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
+  if (want_minmax && (rc = mi_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
   const int hw = g.h * g.w;
   const int64_t cells = (int64_t)g.bins * hw;
   // at most 1024 workgroups in all (one atomic pair each), at least one per sample
@@ -411,7 +320,7 @@ extern "C" int sdf_prepare_chunk_fwd(const SdfPrepareChunkDesc* d, void* stream)
   const dim3 block(256), sgrid((unsigned)(need < cap ? need : cap), g.B);
   SDF_LAUNCH(prepare_split_kernel, sgrid, block, 0, s, d->voxel, d->out, g, mm, want_minmax, per_sample);
   SDF_LAUNCH_CHECK();
-  return pc_finish(d->out, d->event_mask, nullptr, g.B, hw, 2 * g.bins, mm, want_minmax, per_sample, d->use_spike_th, d->spike_th, s);
+  return mi_finish(d->out, d->event_mask, nullptr, g.B, hw, 2 * g.bins, mm, want_minmax, per_sample, d->use_spike_th, d->spike_th, s);
 }
 
 extern "C" int64_t sdf_augment_chunk_workspace_bytes(int B) { return B >= 1 && B <= SDF_AUGMENT_MAX_B ? (int64_t)8 * B : 0; }
@@ -436,7 +345,7 @@ extern "C" int sdf_augment_chunk_fwd(const SdfAugmentChunkDesc* d, void* stream)
   unsigned* mm = static_cast<unsigned*>(d->workspace);
   int rc = 0;
   const int per_sample = d->per_sample != 0, want_minmax = d->norm == 1;
-  if (want_minmax && (rc = pc_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
+  if (want_minmax && (rc = mi_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
   const int hw = g.h * g.w;
   const int64_t cells = (int64_t)g.bins * hw;
   // the grid of sdf_prepare_chunk_fwd: at most 1024 workgroups in all (one atomic pair each), at least one per sample
@@ -445,7 +354,7 @@ extern "C" int sdf_augment_chunk_fwd(const SdfAugmentChunkDesc* d, void* stream)
   SDF_LAUNCH(augment_split_kernel, sgrid, block, 0, s, d->voxel, d->label, d->valid, d->drop_u, d->out, d->label_out, d->mask_out, g, a, mm,
              want_minmax, per_sample, d->valid_is_u8 != 0, (uint64_t)d->seed, (uint64_t)d->offset);
   SDF_LAUNCH_CHECK();
-  return pc_finish(d->out, d->event_mask, d->mask_events ? d->mask_out : nullptr, g.B, hw, 2 * g.bins, mm, want_minmax, per_sample,
+  return mi_finish(d->out, d->event_mask, d->mask_events ? d->mask_out : nullptr, g.B, hw, 2 * g.bins, mm, want_minmax, per_sample,
                    d->use_spike_th, d->spike_th, s);
 }
 
@@ -470,13 +379,13 @@ extern "C" int sdf_augment_resize_fwd(const SdfAugmentResizeDesc* d, void* strea
   unsigned* mm = static_cast<unsigned*>(d->workspace);
   int rc = 0;
   const int per_sample = d->per_sample != 0, want_minmax = d->norm == 1;
-  if (want_minmax && (rc = pc_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
+  if (want_minmax && (rc = mi_clear_pairs(mm, per_sample ? g.B : 1, s))) return rc;
   const int hw = g.h * g.w, nF = d->num_chunks * g.bins;
   // a lane per output pixel; as its siblings at most 1024 workgroups in all (one atomic pair each), at least one per sample
   const int cap = 1024 / g.B > 1 ? 1024 / g.B : 1, need = (hw + 255) / 256;
   SDF_LAUNCH(augment_resize_kernel, dim3((unsigned)(need < cap ? need : cap), g.B), dim3(256), 0, s, d->vox_old, d->vox_new, d->flow, d->out,
              d->label_out, d->mask_out, g, nF, a, mm, want_minmax, per_sample);
   SDF_LAUNCH_CHECK();
-  return pc_finish(d->out, d->event_mask, d->mask_events ? d->mask_out : nullptr, g.B, hw, 2 * nF, mm, want_minmax, per_sample,
+  return mi_finish(d->out, d->event_mask, d->mask_events ? d->mask_out : nullptr, g.B, hw, 2 * nF, mm, want_minmax, per_sample,
                    d->use_spike_th, d->spike_th, s);
 }

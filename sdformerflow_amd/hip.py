@@ -2194,9 +2194,9 @@ def _stream_ws(cache, dev, need):
 
 
 def _event_lists(fn, x, y, t, p, offsets, xy_kinds):
-    """What the two event front ends check alike: x, y, t, p are 1-D GPU arrays of one length, x and y of one dtype the entry point takes
-    (`xy_kinds` words them; `fn` prefixes every message).  Returns the arrays contiguous, n, the list offsets as ints and as the
-    descriptor's host array (keep it alive across the calls), and the descriptor's xy_dtype."""
+    """What the three event front ends (event_voxel, event_voxel_tb, event_iwe) check alike: x, y, t, p are 1-D GPU arrays of one
+    length, x and y of one dtype the entry point takes (`xy_kinds` words them; `fn` prefixes every message).  Returns the arrays
+    contiguous, n, the list offsets as ints and as the descriptor's host array (keep it alive), and the descriptor's xy_dtype."""
     for a in (x, y, t, p):
         _ptr(a)                                                          # (CPU tensors are refused, as everywhere)
     n = int(t.numel())
@@ -2233,7 +2233,7 @@ def _event_rectify_map(fn, d, rectify_map):
 
 
 def _event_gather(fn, d, cache, need, refused, shape, out, n, dev):
-    """The tail the two event front ends share, on a descriptor filled up to the geometry: workspace of `need` bytes (<= 0: the
+    """The tail the three event front ends share, on a descriptor filled up to the geometry: workspace of `need` bytes (<= 0: the
     library refused the geometry - `refused` says which), `out` (None: a new tensor of `shape`), keys | stable sort | gather.
     `fn` names the entry-point pair sdf_<fn>_keys_fwd / sdf_<fn>_gather_fwd and prefixes the messages."""
     if need <= 0:
@@ -2385,6 +2385,19 @@ def event_iwe(x, y, t, p, flow, sensor_size, offsets=None, crop=None, crop_origi
                          out, n, dev)
 
 
+def _record_table(fn, table, row, n, fields, dev):
+    """The caller's table of per-sample fp64 records for a call that writes rows `row` .. `row` + n - 1: (rows, len(fields)) float64,
+    contiguous, the rows inside it; None: a new zero table of row + n rows on `dev`.  Returns the table."""
+    if table is None:
+        table = torch.zeros((row + n, len(fields)), dtype=torch.float64, device=dev)
+    _ptr(table, torch.float64)
+    if table.dim() != 2 or table.shape[1] != len(fields) or not table.is_contiguous():
+        raise SdfError(f"{fn}: table must be a contiguous (rows, {len(fields)}) float64 tensor")
+    if row < 0 or row + n > table.shape[0]:
+        raise SdfError(f"{fn}: rows {row} .. {row + n - 1} lie outside the table's {table.shape[0]}", rc=E_SHAPE)
+    return table
+
+
 def iwe_stats(iwe, table=None, row=0):
     """Per-sample statistics of an image of warped events on the GPU (sdf_iwe_stats_fwd: two launches, no read-back): sample b of iwe
     (B, 2, h, w) fp32 writes row `row` + b of `table` (rows, 4) float64 - IWE_STATS_FIELDS: sum, sum of squares, maximum and number of
@@ -2396,18 +2409,13 @@ def iwe_stats(iwe, table=None, row=0):
     iwe = iwe.contiguous()
     B, _, H, W = iwe.shape
     dev = iwe.device
-    if table is None:
-        table = torch.zeros((row + B, len(IWE_STATS_FIELDS)), dtype=torch.float64, device=dev)
-    if table.dim() != 2 or table.shape[1] != len(IWE_STATS_FIELDS) or not table.is_contiguous():
-        raise SdfError(f"iwe_stats: table must be a contiguous (rows, {len(IWE_STATS_FIELDS)}) float64 tensor")
-    if row < 0 or row + B > table.shape[0]:
-        raise SdfError(f"iwe_stats: rows {row} .. {row + B - 1} lie outside the table's {table.shape[0]}", rc=E_SHAPE)
+    table = _record_table("iwe_stats", table, row, B, IWE_STATS_FIELDS, dev)
     need = lib().sdf_iwe_stats_workspace_bytes(B, H, W)
     if need <= 0:
         raise SdfError(f"iwe_stats: geometry refused (B {B}, {H} x {W})", rc=E_SHAPE)
     ws = _stream_ws(_IWE_STATS_WS, dev, need)
     d = IweStatsDesc()
-    d.iwe, d.table, d.workspace, d.workspace_bytes = iwe.data_ptr(), _ptr(table, torch.float64), ws.data_ptr(), ws.numel()
+    d.iwe, d.table, d.workspace, d.workspace_bytes = iwe.data_ptr(), table.data_ptr(), ws.data_ptr(), ws.numel()
     d.B, d.H, d.W, d.row0, d.rows = B, H, W, row, table.shape[0]
     _note(bytes=B * H * W * 8, shape=(B, H, W))
     _check(lib().sdf_iwe_stats_fwd(C.byref(d), _stream()), "sdf_iwe_stats_fwd")
@@ -2438,19 +2446,14 @@ def flow_metrics(pred, label, valid, event_mask=None, flow_scaling=1.0, table=No
     if event_mask is not None:
         event_mask = plane(event_mask, "event_mask")
     dev = pred.device
-    if table is None:
-        table = torch.zeros((row + B, len(FLOW_METRICS_FIELDS)), dtype=torch.float64, device=dev)
-    if table.dim() != 2 or table.shape[1] != len(FLOW_METRICS_FIELDS) or not table.is_contiguous():
-        raise SdfError(f"flow_metrics: table must be a contiguous (rows, {len(FLOW_METRICS_FIELDS)}) float64 tensor")
-    if row < 0 or row + B > table.shape[0]:
-        raise SdfError(f"flow_metrics: rows {row} .. {row + B - 1} lie outside the table's {table.shape[0]}", rc=E_SHAPE)
+    table = _record_table("flow_metrics", table, row, B, FLOW_METRICS_FIELDS, dev)
     need = lib().sdf_flow_metrics_workspace_bytes(B, H, W)
     if need <= 0:
         raise SdfError(f"flow_metrics: geometry refused (B {B}, {H} x {W})", rc=E_SHAPE)
     ws = _stream_ws(_FM_WS, dev, need)
     d = FlowMetricsDesc()
     d.pred, d.label, d.valid, d.event_mask = pred.data_ptr(), label.data_ptr(), valid.data_ptr(), _ptr(event_mask, torch.float32)
-    d.table, d.workspace, d.workspace_bytes = _ptr(table, torch.float64), ws.data_ptr(), ws.numel()
+    d.table, d.workspace, d.workspace_bytes = table.data_ptr(), ws.data_ptr(), ws.numel()
     d.B, d.H, d.W, d.row0, d.rows, d.flow_scaling = B, H, W, row, table.shape[0], float(flow_scaling)
     _note(bytes=B * H * W * (5 + (event_mask is not None)) * 4, shape=(B, H, W))
     _check(lib().sdf_flow_metrics_fwd(C.byref(d), _stream()), "sdf_flow_metrics_fwd")
@@ -2914,11 +2917,7 @@ def grad_stats(flat, segments, table=None, row=0):
     dev = flat.device
     if not isinstance(segments, GradSegments):
         segments = GradSegments(segments, dev)
-    if table is None:
-        table = torch.zeros((row + segments.n, len(GRAD_STATS_FIELDS)), dtype=torch.float64, device=dev)
-    _ptr(table, torch.float64)
-    if table.dim() != 2 or table.shape[1] != len(GRAD_STATS_FIELDS) or not table.is_contiguous():
-        raise SdfError(f"grad_stats: table must be a contiguous (rows, {len(GRAD_STATS_FIELDS)}) float64 tensor")
+    table = _record_table("grad_stats", table, row, segments.n, GRAD_STATS_FIELDS, dev)
     need = lib().sdf_grad_stats_workspace_bytes(segments.n)
     if need <= 0:
         raise SdfError(f"grad_stats: {segments.n} segments; the entry point takes 1 to 65535", rc=E_SHAPE)

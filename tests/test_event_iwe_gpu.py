@@ -198,7 +198,7 @@ def test_launch_log_names_the_new_kernels(parity_case):
     # (a keys launch per non-empty list, then the run table with the permutation, then the gather)
     assert [r.split(" ", 3)[3].split("<")[0] for r in rows] == ["iwe_keys_kernel", "iwe_keys_kernel", "event_runs_kernel", "iwe_gather_kernel"], rows
     rows, near = logged(lambda: call("nearest"))
-    assert [r.split(" ", 3)[3].split("<")[0] for r in rows] == ["iwe_keys_kernel", "iwe_keys_kernel", "iwe_runs_kernel", "iwe_gather_kernel"], rows
+    assert [r.split(" ", 3)[3].split("<")[0] for r in rows] == ["iwe_keys_kernel", "iwe_keys_kernel", "event_runs_kernel", "iwe_gather_kernel"], rows
     rows, _ = logged(lambda: hip.iwe_stats(near))
     assert [r.split(" ", 3)[3].split("<")[0] for r in rows] == ["iwe_stats_partial_kernel", "iwe_stats_finish_kernel"], rows
     rows, _ = logged(lambda: hip.event_iwe(d["x"], d["y"], d["t"], d["p"], flows_d, K.PARITY_SENSOR, offsets=offs, crop=K.PARITY_CROP,

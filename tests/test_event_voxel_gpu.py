@@ -140,6 +140,43 @@ def test_no_events_and_degenerate_time():
                         10, SENSOR, offsets=[0, 1000, 2000])
 
 
+TINY = (8, 12)
+
+
+def tiny_lists():
+    """name -> one list on the 8 x 12 sensor at 2 bins: three events at half-pixel x, integer y and t_norm 0 | 0 | 1, so that every
+    non-zero cell of the split is the one float 0.5 (min == max: nothing is normalised); and the empty list (no non-zero at all)."""
+    three = {"x": [2.5, 6.5, 9.5], "y": [3.0, 5.0, 1.0], "t": [0.0, 0.0, 1.0], "p": [1.0, 0.0, 1.0]}
+    return {"one value": {k: torch.tensor(v, dtype=torch.float32, device=DEV) for k, v in three.items()},
+            "empty": {k: torch.empty(0, device=DEV) for k in "xytp"}}
+
+
+@pytest.mark.parametrize("spike_th", [None, 0.25, 0.5])
+@pytest.mark.parametrize("name", ["one value", "empty"])
+def test_minmax_over_one_value_and_over_nothing(name, spike_th):
+    """The min / max pair's two edge states - min == max, and no non-zero element - leave the split un-normalised, as
+    harness.prepare_chunk of the signed grid does (0.5 against the thresholds: above 0.25 -> 1, equal to 0.5 -> kept)."""
+    from sdformerflow_amd import harness, hip
+    e = tiny_lists()[name]
+    grid = hip.event_voxel(e["x"], e["y"], e["t"], e["p"], 2, TINY)
+    split = harness.prepare_chunk(grid, None, None)
+    assert grid.shape == (1, 2) + TINY and set(split[split != 0].tolist()) == ({0.5} if name == "one value" else set())
+    assert int((split != 0).sum()) == (6 if name == "one value" else 0) and (name == "empty" or (split[:, :, 1] != 0).any())
+    got = hip.event_voxel(e["x"], e["y"], e["t"], e["p"], 2, TINY, mode="split", norm="minmax", spike_th=spike_th)
+    assert same_bits(got, harness.prepare_chunk(grid, "minmax", spike_th)), (name, spike_th)
+
+
+def test_launch_log_names_the_kernels_of_a_call():
+    from routes_common import logged
+    from sdformerflow_amd import hip
+    e = tiny_lists()["one value"]
+    names = lambda rows: [r.split(" ", 3)[3].split("<")[0] for r in rows]
+    rows, _ = logged(lambda: hip.event_voxel(e["x"], e["y"], e["t"], e["p"], 2, TINY, mode="split", norm="minmax", check=False))
+    assert names(rows) == ["ev_keys_kernel", "event_runs_kernel", "ev_gather_kernel", "ev_finish_kernel"], rows
+    rows, _ = logged(lambda: hip.event_voxel(e["x"], e["y"], e["t"], e["p"], 2, TINY, check=False))
+    assert names(rows) == ["ev_keys_kernel", "event_runs_kernel", "ev_gather_kernel"], rows
+
+
 def lif_model():
     from sdformerflow_amd.STSwinNet_SNN.Spiking_STSwinNet import MS_SpikingformerFlowNet_en4
     from sdformerflow_amd.synthetic import synth_state_dict

@@ -145,6 +145,54 @@ def test_model_input_and_event_mask(lists, bound):
     assert same_bits(one, harness.prepare_chunk(voxel(new, size), "minmax", None, True))
 
 
+TINY = (8, 12)
+
+
+def tiny_pair(name):
+    """(x, y, t, p, offsets) of an (old, new) pair on the 8 x 12 sensor at 2 bins.  "one value": three events on three pixels at
+    t_norm 0 | 0 | 1 and an empty new list - every non-zero cell of the split is the one float 1 (min == max: nothing is normalised);
+    "empty": two empty lists (no non-zero at all)."""
+    n = 3 if name == "one value" else 0
+    x, y = torch.tensor([2, 6, 9][:n], dtype=torch.int32, device=DEV), torch.tensor([3, 5, 1][:n], dtype=torch.int32, device=DEV)
+    t = torch.tensor([0.0, 0.0, 1.0][:n], dtype=torch.float64, device=DEV)
+    return x, y, t, torch.tensor([1.0, 0.0, 1.0][:n], dtype=torch.float32, device=DEV), [0, n, n]
+
+
+@pytest.mark.parametrize("spike_th", [None, 1.0, 2.0])
+@pytest.mark.parametrize("name", ["one value", "empty"])
+def test_minmax_over_one_value_and_over_nothing(name, spike_th):
+    """The min / max pair's two edge states - min == max, and no non-zero element - leave the split un-normalised, as
+    harness.prepare_chunk of the signed volumes does (1 against the thresholds: equal to 1 -> kept, below 2 -> 0), and the event mask
+    is chunk.sum(1).sum(1).bool()."""
+    from sdformerflow_amd import harness, hip
+    x, y, t, p, offs = tiny_pair(name)
+    vols = hip.event_voxel_tb(x, y, t, p, 2, TINY, offsets=offs, normalize=False)
+    vols = vols.reshape(1, 4, *TINY)                                                       # old | new along the bins
+    split = harness.prepare_chunk(vols, None, None)
+    assert set(split[split != 0].tolist()) == ({1.0} if name == "one value" else set())
+    assert int((split != 0).sum()) == (3 if name == "one value" else 0) and (name == "empty" or (split[:, :, 1] != 0).any())
+    got, mask = hip.event_voxel_tb(x, y, t, p, 2, TINY, offsets=offs, normalize=False, mode="split", lists_per_sample=2, norm="minmax",
+                                   spike_th=spike_th, want_event_mask=True)
+    want = harness.prepare_chunk(vols, "minmax", spike_th)
+    assert got.shape == (1, 4, 2) + TINY and same_bits(got, want), (name, spike_th)
+    assert mask.shape == (1, 1) + TINY and torch.equal(mask != 0, want.sum(1).sum(1, keepdim=True).bool()), (name, spike_th)
+    assert bool(mask.any()) == (name == "one value" and spike_th != 2.0)
+
+
+def test_launch_log_names_the_kernels_of_a_call():
+    from routes_common import logged
+    from sdformerflow_amd import hip
+    x, y, t, p, offs = tiny_pair("one value")
+    names = lambda rows: [r.split(" ", 3)[3].split("<")[0] for r in rows]
+    rows, _ = logged(lambda: hip.event_voxel_tb(x, y, t, p, 2, TINY, offsets=offs, normalize=False, mode="split", lists_per_sample=2,
+                                                norm="minmax", want_event_mask=True))
+    # (a keys launch per non-empty list, the run table with the permutation, the gather, the split with min / max, the shared finish)
+    assert names(rows) == ["tb_keys_kernel", "event_runs_kernel", "tb_gather_kernel", "tb_norm_kernel", "prepare_finish_kernel"], rows
+    rows, _ = logged(lambda: hip.event_voxel_tb(x, y, t, p, 2, TINY, offsets=offs))
+    # (signed volumes, normalised per list: the lists' statistics between the gather and the normalisation)
+    assert names(rows) == ["tb_keys_kernel", "event_runs_kernel", "tb_gather_kernel", "tb_stats_kernel", "tb_norm_kernel"], rows
+
+
 def test_batching_does_not_change_a_sample(lists):
     """Pairs one by one and as one batch of 4 give the same bits per sample before the batch-wide min-max; with it, the batch equals
     prepare_chunk on the concatenated per-sample outputs.  The crop (default centre origin) and the event mask ride along."""
